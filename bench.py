@@ -10,15 +10,26 @@ A "step" is one pass of the hot path over one synthetic batch that is already re
            clip 1.0 + Adam(6e-5), encoder frozen (configs/dofa_config_RGB.yaml:11,57-65), bf16
            autocast, per-GPU batch fixed (weak scaling), DDP over RCCL with SyncBatchNorm;
   infer  = forward + softmax->argmax mask under no_grad.
-`value` is the TRAINING throughput of the whole job (tiles/s over all ranks); the inference
-throughput measured the same way is reported alongside.  Rank 0 prints ONE JSON line.
+`value` is the TRAINING throughput of the whole job (tiles/s over all ranks).  Rank 0 prints ONE JSON line.
+
+A plain run (no --full) does only what `value` needs: set up, W warm-up steps, exactly K timed steps of the headline step
+(--mode both: the training step), the outputs of the last timed step when --dump-outputs DIR is given, and the line.
+Everything else below -- the inference step timed beside the training step, the per-kernel timer, `sustained`,
+`step_roofline`, the PCIe-inclusive leg (also: --with-input-stage), the DDP diagnostics, the side tables and `cpu_baseline` --
+runs with --full only.
+
+--dump-outputs DIR writes what the headline step(s) computed in the last timed step as DIR/<name>.npy (float32 / float64,
+under 64 MB in all): train_loss (the loss training_step returned), train_param_sample / train_grad_sample (the trainable
+parameters and their gradients as that step left them, flattened in named_parameters order), infer_mask_sample (the mask
+validation_step returned).  A `_sample` is the whole tensor when it has at most DUMP_SAMPLE elements, else the elements
+at DUMP_SAMPLE fixed, seeded, sorted indices.  Inputs and initial weights are seeded: the same arguments give the same inputs.
 
 The stdout line is the SHORT form (< ~3 KB: contract keys, `roofline`, `cpu_baseline`, then one number per extra, the most
-important ones last -- see compact_line); the LONG form with every table below goes to bench_details.json beside this file
+important ones last -- see compact_line); with --full the LONG form with every table below goes to bench_details.json beside this file
 (and to gpurun_out/bench_details.json when that directory exists).  `value` always covers exactly --steps steps; when those
-take less than --min-seconds (3 s) the same steps are timed again over a longer run and reported under `sustained`.
+take less than --min-seconds (3 s) the same steps are timed again over a longer run and reported under `sustained` (--full).
 
-Besides the contract fields the long form carries (N = 1 only, all measured in this same process):
+Besides the contract fields the long form carries (--full, N = 1 only, all measured in this same process):
   roofline      dominant MFMA kernel by HIP events on the launch stream; `traffic` = HBM bytes per launch from the
                 committed rocprofv3 PMC passes (FETCH_SIZE doubled per MI355X_MICROARCH.md + WRITE_SIZE), see --help
   hbm_kernels   the HBM-bound kernels of the step at their DOFA shapes: algorithmic GB/s vs the 8 TB/s peak
@@ -44,6 +55,7 @@ for p in (ROOT, ROOT / "geo-deep-learning_amd"):
     if str(p) not in sys.path:
         sys.path.insert(0, str(p))
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -98,6 +110,12 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip hbm_kernels / by_batch / other_models (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside `value` (inference beside training, kernel timer, sustained, step_roofline, "
+                         "PCIe-inclusive leg, DDP diagnostics, side tables, cpu_baseline) and write the long form; the --no-* "
+                         "options above and --min-seconds / --details act on these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (see the module docstring)")
     return ap.parse_args()
 
 
@@ -187,12 +205,39 @@ def make_steps(task, optimizer, get_batch, use_bf16: bool):
             loss.backward()
         with rng("optimizer"):
             optimizer.step()
+        return loss
 
     def infer_step():
         task.eval()
         with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_bf16):
-            task.validation_step(get_batch(), 0)
+            return task.validation_step(get_batch(), 0)
     return train_step, infer_step
+
+
+DUMP_SAMPLE = 1 << 22     # elements per dumped sample: three float32 samples + the loss stay under 64 MB
+DUMP_SEED = 20240601
+
+
+def dump_sample(t: torch.Tensor) -> np.ndarray:
+    """`t` flattened to float32 on the host: whole when it has at most DUMP_SAMPLE elements, else at DUMP_SAMPLE fixed
+    indices (seeded by DUMP_SEED and the element count, sorted)."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        g = torch.Generator(device="cpu").manual_seed(DUMP_SEED + flat.numel())
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def snapshot_outputs(key: str, ret, task) -> dict:
+    """Host copies of what the last timed step of `key` handed back (see the module docstring, --dump-outputs)."""
+    if key == "infer":
+        return {"infer_mask_sample": dump_sample(ret)}
+    params = [p for _, p in task.named_parameters() if p.requires_grad]
+    grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    return {"train_loss": np.asarray([ret.item()], dtype=np.float64),
+            "train_param_sample": dump_sample(torch.cat([p.detach().reshape(-1).float() for p in params])),
+            "train_grad_sample": dump_sample(torch.cat([g.detach().reshape(-1).float() for g in grads]))}
 
 
 class OpAccounting:
@@ -609,32 +654,49 @@ def main() -> None:
     use_bf16 = args.dtype == "bf16"
     train_step, infer_step = make_steps(task, optimizer, lambda: batch, use_bf16)
 
+    # the outputs of the last timed step of each leg (--dump-outputs), copied to the host right after its timed region
+    dumps = {}
+    dumping = args.dump_outputs is not None and rank == 0
+    last = {}
+
+    def keeping(key, fn):
+        def step():
+            last[key] = fn()
+        return step if dumping else fn
+
     timer = None
     res = {}
-    if args.mode in ("both", "train"):
-        if not args.no_kernel_timer:
+    # a plain run times the headline step only (--mode both: training); --full times inference beside it
+    time_train = args.mode in ("both", "train")
+    time_infer = args.mode == "infer" or (args.mode == "both" and args.full)
+    if time_train:
+        if args.full and not args.no_kernel_timer:
             for _ in range(args.warmup):   # warm up untimed, then time WITH the kernel events on
                 train_step()
             timer = ops.KernelTimer()
             ops.TIMER = timer
-            dt = timed(train_step, args.steps, 0, world, device)
+            dt = timed(keeping("train", train_step), args.steps, 0, world, device)
             ops.TIMER = None
         else:
-            dt = timed(train_step, args.steps, args.warmup, world, device)
+            dt = timed(keeping("train", train_step), args.steps, args.warmup, world, device)
         res["train"] = dt
-    if args.mode in ("both", "infer"):
-        res["infer"] = timed(infer_step, args.steps, args.warmup, world, device)
+        if dumping:
+            dumps.update(snapshot_outputs("train", last.pop("train"), task))
+    if time_infer:
+        res["infer"] = timed(keeping("infer", infer_step), args.steps, args.warmup, world, device)
+        if dumping:
+            dumps.update(snapshot_outputs("infer", last.pop("infer"), task))
     # `value` times EXACTLY --steps steps (the driver's contract).  A caller that passes a small K (the driver: 20 steps = 0.7 s)
     # gets a second, longer measurement of the same steps beside it: as many steps as make the timed region >= 3 s
     sustained = {}
-    if args.min_seconds > 0 and not args.no_extras:      # (profiling / A-B runs pass --no-extras: exactly their --steps, nothing else)
+    if args.full and args.min_seconds > 0 and not args.no_extras:      # (profiling / A-B runs pass --no-extras: exactly their --steps, nothing else)
         for key, fn in (("train", train_step), ("infer", infer_step)):
             if key in res and res[key] < args.min_seconds:
                 k_long = int(math.ceil(args.min_seconds / (res[key] / args.steps)))
                 sustained[key] = (k_long, timed(fn, k_long, 0, world, device))
 
     step_roofline = None
-    if not args.no_extras and world == 1:
+    if args.full and not args.no_extras and world == 1:
         # op-level accounting of the headline steps (see OpAccounting): what the whole step looks like against the HBM / MFMA
         # bounds of its ops, beside the dominant-kernel roofline below
         step_roofline = {}
@@ -645,7 +707,7 @@ def main() -> None:
                 step_roofline[key] = acct.summary(1e3 * res[key] / args.steps, top=5)
 
     ddp_info = None
-    if dist_on and "train" in res:
+    if args.full and dist_on and "train" in res:
         from gdlhip import nn as gnn
         # the exchange step on its own: one all-reduce of the trainable gradients' bytes (what DDP's buckets move per step)
         nparam = sum(p.numel() for p in task.parameters() if p.requires_grad)
@@ -743,7 +805,7 @@ def main() -> None:
             ddp_info["graphed"] = {"error": failure}
 
     pcie = None
-    if not args.no_input_stage and "train" in res:
+    if (args.full or args.with_input_stage) and not args.no_input_stage and "train" in res:
         # host batches exactly as the dataset workers hand them over: raw uint8 tiles + int64 masks + sensor stats
         from geo_deep_learning.datamodules.device_input import DeviceInputStage
         g = torch.Generator(device="cpu").manual_seed(7 + rank)
@@ -853,7 +915,7 @@ def main() -> None:
         out["pcie_inclusive"] = pcie
     if ddp_info is not None:
         out["ddp"] = ddp_info
-    if world == 1 and not args.no_extras and args.model == "dofa" and use_bf16:
+    if args.full and world == 1 and not args.no_extras and args.model == "dofa" and use_bf16:
         del task, optimizer
         torch.cuda.empty_cache()
         side_batch = min(args.batch, SIDE_BATCH)      # the side tables stay at the batch of rounds 1-5 (comparable across rounds)
@@ -870,7 +932,7 @@ def main() -> None:
         out["other_models"]["dofa_base_6band"] = side_measurement("dofa6", side_batch, side_steps, args.warmup, device, True, roofline=True)
         out["other_models"]["dofa_large_1024_10band"] = side_measurement("dofa_large", max(1, side_batch // 4), max(3, side_steps // 2),
                                                                           min(2, args.warmup), device, True, roofline=True)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline()
     if sustained:
         out["sustained"] = {("train" if k == "train" else "inference") + "_tiles_per_s": round(args.batch * world * n / dt, 3)
@@ -881,6 +943,8 @@ def main() -> None:
                                          f"{args.min_seconds:g} s (barrier + synchronize on both sides, max over ranks)"})
     details_paths = [Path(args.details)] if args.details else [ROOT / "bench_details.json"] + (
         [ROOT / "gpurun_out" / "bench_details.json"] if (ROOT / "gpurun_out").is_dir() else [])
+    if not (args.full or args.details):
+        details_paths = []      # a plain run writes its line (and --dump-outputs) only
     written = []
     for dp in details_paths:
         try:
@@ -888,6 +952,11 @@ def main() -> None:
             written.append(str(dp.relative_to(ROOT)) if dp.is_relative_to(ROOT) else str(dp))
         except OSError as exc:
             print(f"bench.py: could not write {dp}: {exc}", file=sys.stderr)
+    if dumping:
+        dump_dir = Path(args.dump_outputs)
+        dump_dir.mkdir(parents=True, exist_ok=True)
+        for name, arr in dumps.items():
+            np.save(dump_dir / f"{name}.npy", arr)
     line = compact_line(out, written)
     json_out.write(json.dumps(line, separators=(",", ":")) + "\n")
     json_out.flush()

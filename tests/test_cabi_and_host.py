@@ -393,6 +393,43 @@ def test_bench_stdout_line_is_short_and_ends_with_the_headline_extras():
     assert {"value", "unit", "cores", "kind", "sample"} <= set(line["cpu_baseline"])
 
 
+def test_bench_plain_run_options_and_output_dump():
+    """bench.py: --full is off by default, --dump-outputs DIR is optional; the dumped outputs of a training step (loss, trainable
+    parameters and gradients) and of an inference step (mask) are float32 / float64, the same on every call, whole when small and
+    a fixed sample when large, and the three samples + the loss stay under 64 MB."""
+    import importlib.util
+    import numpy as np
+    root = Path(__file__).resolve().parents[1]
+    spec = importlib.util.spec_from_file_location("bench_for_test", root / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        spec.loader.exec_module(bench)
+        args = bench.parse()
+        assert args.full is False and args.dump_outputs is None
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out_dir", "--steps", "7"]
+        args = bench.parse()
+        assert args.full is True and args.dump_outputs == "out_dir" and args.steps == 7
+    finally:
+        sys.argv = argv
+    assert 3 * bench.DUMP_SAMPLE * 4 + 8 <= 64e6
+    net = torch.nn.Sequential(torch.nn.Linear(8, 4), torch.nn.Linear(4, 3))
+    net[1].bias.requires_grad_(False)
+    loss = net(torch.randn(5, 8)).square().mean()
+    loss.backward()
+    got = bench.snapshot_outputs("train", loss, net)
+    assert set(got) == {"train_loss", "train_param_sample", "train_grad_sample"}
+    assert got["train_loss"].dtype == np.float64 and got["train_loss"][0] == loss.item()
+    assert got["train_param_sample"].dtype == np.float32 and got["train_param_sample"].shape == (8 * 4 + 4 + 4 * 3,)
+    assert np.array_equal(got["train_grad_sample"][:32], net[0].weight.grad.reshape(-1).numpy())
+    big = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.int64)
+    a, b = bench.snapshot_outputs("infer", big, None), bench.snapshot_outputs("infer", big, None)
+    s = a["infer_mask_sample"]
+    assert s.dtype == np.float32 and s.shape == (bench.DUMP_SAMPLE,) and np.array_equal(s, b["infer_mask_sample"])
+    assert (np.diff(s) >= 0).all() and s.min() >= 0 and s.max() < big.numel()
+
+
 def test_dofa_training_step_asks_for_low_resolution_logits_only_where_the_loss_can_use_them(monkeypatch):
     """Host logic of tasks_with_models/segmentation_dofa.py: ``training_step`` (round 5) and ``validation_step`` / ``test_step``
     (round 6: the mask comes from ``gnn.predict_mask`` on the same low-resolution map) hand the heads' not-yet-resized maps

@@ -104,28 +104,38 @@ def test_tiny_eval(tiny):
     assert (mask == g["eval_mask"]).mean() > 0.9999
 
 
-def test_tiny_train_step(tiny):
+def test_tiny_train_step(tiny, golden_dir):
+    """The oracle runs this step in float64: in float32 the gradients behind the batch-2 BatchNorm of the 1x1 pyramid bin move by
+    up to 2e-3 with the host's BLAS path (thread count, AVX2 vs AVX-512), beyond the 1e-3 bound below.  Outputs, loss and
+    BatchNorm buffers are held to the reference's float32 step (dofa_tiny.npz); the gradients to its float64 step
+    (dofa_tiny_grads_f64.npz, same weights, batch and masks), since a float64 step also flips a few near-zero ReLU decisions of
+    the float32 one."""
+    import copy
     g, meta, m, batch = tiny
+    gg = np.load(golden_dir / "dofa_tiny_grads_f64.npz")
+    m = copy.deepcopy(m).double()
+    batch = {k: v.double() if torch.is_tensor(v) and v.is_floating_point() else v for k, v in batch.items()}
     m.train()
     for n, p in m.named_parameters():
         p.requires_grad = "encoder" not in n
         p.grad = None
     b = meta["batch"]
-    masks = _drop_masks(meta["tiny"]["depth"], 0.1, b, meta["seed"])
-    r = m(batch["image"], batch["wavelengths"], masks, _aux_mask(b, 256, meta["seed"]))
+    masks = [tuple(t.double() for t in pair) for pair in _drop_masks(meta["tiny"]["depth"], 0.1, b, meta["seed"])]
+    r = m(batch["image"], batch["wavelengths"], masks, _aux_mask(b, 256, meta["seed"]).double())
     np.testing.assert_allclose(r.out.detach().numpy(), g["train_out"], atol=TOL, rtol=0)
     np.testing.assert_allclose(r.aux.detach().numpy(), g["train_aux"], atol=TOL, rtol=0)
     loss = oracle.model.training_loss(r, batch["mask"])
     assert abs(loss.item() - float(g["train_loss"])) < 1e-5
     loss.backward()
+    assert json.loads(str(gg["meta"]))["grad_names"] == meta["grad_names"]
     for n in meta["grad_names"]:
         p = dict(m.named_parameters())[n]
-        ref_norm = float(g["gradnorm/" + n])
+        ref_norm = float(gg["gradnorm/" + n])
         # conv biases feeding a train-mode BN have an analytically ZERO gradient: what is
         # stored there is rounding noise, so tolerances carry an absolute floor.
         assert abs(p.grad.double().norm().item() - ref_norm) <= 1e-3 * ref_norm + 1e-5, n
-        np.testing.assert_allclose(_grad_sample(p.grad, 2048), g["grad/" + n],
-                                   atol=0.02 * float(np.abs(g["grad/" + n]).max()) + 2e-6,
+        np.testing.assert_allclose(_grad_sample(p.grad, 2048), gg["grad/" + n],
+                                   atol=0.02 * float(np.abs(gg["grad/" + n]).max()) + 2e-6,
                                    rtol=1e-3, err_msg=n)
     bufs = dict(m.named_buffers())
     for k in g.files:

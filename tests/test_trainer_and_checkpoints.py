@@ -146,6 +146,13 @@ def test_dofa_pretrained_key_remap_and_pos_embed_resize(tmp_path, monkeypatch):
     assert torch.equal(hot.state_dict()["blocks.1.mlp.fc2.weight"], src["blocks.1.mlp.fc2.weight"])
 
 
+def _cpu_ranks(monkeypatch):
+    """The spawned ranks of these gloo tests are CPU processes, as on a machine without a GPU: hide the GPUs from them (an
+    invalid ordinal ends the device list).  Otherwise MiniTrainer puts rank r on cuda:r, which a box with one GPU lacks."""
+    for k in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
+        monkeypatch.setenv(k, "-1")
+
+
 def _ddp_worker(rank, world, port, tmp, ret):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -164,6 +171,15 @@ def _ddp_worker(rank, world, port, tmp, ret):
         dist.destroy_process_group()
 
 
+def _single_process_worker(tmp, ret):
+    import _toy_task as toy
+    torch.manual_seed(0)
+    task = toy.ToyTask(3, torch.nn.CrossEntropyLoss(), optimizer=lambda p: torch.optim.SGD(p, lr=0.1), batchnorm=False)
+    tr = MiniTrainer(max_epochs=2, default_root_dir=tmp)
+    tr.fit(task, train_dataloaders=toy.make_batches(4, 8, 3, 1), val_dataloaders=toy.make_batches(2, 8, 3, 2))
+    ret["single"] = {"w": task.model.encoder.weight.detach().clone(), "val": tr.callback_metrics["val_loss"]}
+
+
 def _empty_val_rank_worker(rank, world, port, tmp, ret):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -180,11 +196,12 @@ def _empty_val_rank_worker(rank, world, port, tmp, ret):
         dist.destroy_process_group()
 
 
-def test_minitrainer_rank_without_validation_batches_does_not_hang(tmp_path):
+def test_minitrainer_rank_without_validation_batches_does_not_hang(tmp_path, monkeypatch):
     """Round-3 advisor finding: a rank that logged nothing in validation skipped the epoch-mean all-reduce its peers were in
     (hang) and never saw the monitored metric.  The reduction is now shape-stable (union of the ranks' metric names, zeros for
     what a rank did not log): both ranks finish, hold the same val_loss (= rank 0's) and agree on the checkpoint."""
     world, port = 2, 33700 + os.getpid() % 2000
+    _cpu_ranks(monkeypatch)
     ctx = mp.get_context("spawn")
     ret = ctx.Manager().dict()
     procs = [ctx.Process(target=_empty_val_rank_worker, args=(r, world, port, str(tmp_path), ret)) for r in range(world)]
@@ -197,10 +214,11 @@ def test_minitrainer_rank_without_validation_batches_does_not_hang(tmp_path):
     assert ret[0]["best"] == ret[1]["best"] and Path(ret[0]["best"]).is_file()
 
 
-def test_minitrainer_ddp_world2_matches_single_process(tmp_path):
+def test_minitrainer_ddp_world2_matches_single_process(tmp_path, monkeypatch):
     """Two gloo ranks, each on half of every batch, under DDP == one process on the full batches (mean-reduced loss =>
     averaged gradients), metrics averaged over ranks, one checkpoint written by rank 0 and known to both."""
     world, port = 2, 29700 + os.getpid() % 2000
+    _cpu_ranks(monkeypatch)
     ctx = mp.get_context("spawn")
     ret = ctx.Manager().dict()
     procs = [ctx.Process(target=_ddp_worker, args=(r, world, port, str(tmp_path), ret)) for r in range(world)]
@@ -209,14 +227,15 @@ def test_minitrainer_ddp_world2_matches_single_process(tmp_path):
     for p in procs:
         p.join(240)
         assert p.exitcode == 0
-    torch.manual_seed(0)
-    task = toy.ToyTask(3, torch.nn.CrossEntropyLoss(), optimizer=lambda p: torch.optim.SGD(p, lr=0.1), batchnorm=False)
-    tr = MiniTrainer(max_epochs=2, default_root_dir=str(tmp_path / "single"))
-    tr.fit(task, train_dataloaders=toy.make_batches(4, 8, 3, 1), val_dataloaders=toy.make_batches(2, 8, 3, 2))
-    r0, r1 = ret[0], ret[1]
+    # the single-process reference: a CPU process of its own too (this one may have a GPU open)
+    single = ctx.Process(target=_single_process_worker, args=(str(tmp_path / "single"), ret))
+    single.start()
+    single.join(240)
+    assert single.exitcode == 0
+    r0, r1, one = ret[0], ret[1], ret["single"]
     assert torch.equal(r0["w"], r1["w"]) and r0["best"] == r1["best"] and Path(r0["best"]).is_file()
-    assert torch.allclose(r0["w"], task.model.encoder.weight, atol=1e-5)
-    assert abs(r0["val"] - tr.callback_metrics["val_loss"]) < 1e-5 and abs(r0["val"] - r1["val"]) < 1e-12
+    assert torch.allclose(r0["w"], one["w"], atol=1e-5)
+    assert abs(r0["val"] - one["val"]) < 1e-5 and abs(r0["val"] - r1["val"]) < 1e-12
     sd = torch.load(r0["best"])["state_dict"]
     assert "model.encoder.weight" in sd and not any("module." in k for k in sd)
 
@@ -237,7 +256,7 @@ def _torchrun_worker(rank, world, port, cfg_path, tmp, ret):
     ret[rank] = {"seen": seen, "best": out["best_model_path"], "tested": "test" in out, "alive": d.is_initialized()}
 
 
-def test_train_py_under_torchrun_initialises_the_process_group(tmp_path):
+def test_train_py_under_torchrun_initialises_the_process_group(tmp_path, monkeypatch):
     """`python -m torch.distributed.run --nproc-per-node 2 -m geo_deep_learning.train fit ...`: with only the
     launcher's environment set, train.main creates the process group itself (gloo here, nccl = RCCL on GPUs), the trainer
     sees world size 2, ONE checkpoint is written (by rank 0) and known to both ranks, only rank 0 runs the post-fit test,
@@ -245,6 +264,7 @@ def test_train_py_under_torchrun_initialises_the_process_group(tmp_path):
     cfg_path = tmp_path / "cfg.yaml"
     cfg_path.write_text(yaml.safe_dump(CONFIG))
     world, port = 2, 31700 + os.getpid() % 2000
+    _cpu_ranks(monkeypatch)
     ctx = mp.get_context("spawn")
     ret = ctx.Manager().dict()
     procs = [ctx.Process(target=_torchrun_worker, args=(r, world, port, str(cfg_path), str(tmp_path), ret)) for r in range(world)]

@@ -6,6 +6,6 @@ AB=$GRAFT_REPO_ROOT/geo-deep-learning_amd/gdlhip/libgdlhip_ab.so
 for r in $(seq $REP); do
   for lib in $AB ""; do
     echo "== ${lib:-product build}"
-    env GDL_LIB_PATH=$lib python bench.py --steps 40 --warmup 8 --no-extras --no-cpu-baseline --no-input-stage 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print(d['value'], d.get('inference_tiles_per_s'), d['ms_per_step'])"
+    env GDL_LIB_PATH=$lib python bench.py --full --steps 40 --warmup 8 --no-extras --no-cpu-baseline --no-input-stage 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.readline()); print(d['value'], d.get('inference_tiles_per_s'), d['ms_per_step'])"
   done
 done

@@ -17,7 +17,7 @@ if [[ " $* " != *" nopmc "* ]]; then      # first: bench.py reads the refreshed 
   cp gpurun_out/pmc_traffic/pmc_dominant_kernel_traffic.json $O/pmc_dominant_kernel_traffic.json 2>/dev/null
 fi
 T0=$(date +%s)
-timeout 1500 python bench.py 2>$O/bench.err | tail -1 > $O/bench.json
+timeout 1500 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench.json
 echo "default bench.py wall clock: $(( $(date +%s) - T0 )) s" | tee $O/bench_wall_clock.txt
 cp $R/gpurun_out/bench_details.json $O/bench_details.json
 cut -c1-700 $O/bench.json; echo; python -c "
@@ -27,7 +27,7 @@ print({k:(v['train_tiles_per_s'],v['inference_tiles_per_s']) for k,v in d['other
 print({k:(v['train_tiles_per_s'],v['inference_tiles_per_s']) for k,v in d['by_batch'].items()})
 print('step_roofline', {k:v.get('frac_of_bound') for k,v in d.get('step_roofline',{}).items()})"
 T0=$(date +%s)
-timeout 900 python bench.py --steps 20 --warmup 5 2>$O/bench_driver_flags.err | tail -1 > $O/bench_driver_flags.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 2>$O/bench_driver_flags.err | tail -1 > $O/bench_driver_flags.json
 echo "bench.py --steps 20 --warmup 5 (the driver's flags) wall clock: $(( $(date +%s) - T0 )) s" | tee -a $O/bench_wall_clock.txt
 python -c "
 import json; d=json.loads(open('$O/bench_driver_flags.json').read()); print('driver flags: train', d['value'], 'infer', d['inference_tiles_per_s'], 'sustained', d.get('sustained'), 'line bytes', len(json.dumps(d, separators=(',',':'))))"

@@ -35,7 +35,7 @@ PY
 }
 rocm-smi --showmaxpower 2>/dev/null | grep -i "max\|power" | head -3
 sample idle sleep 2
-sample bench python bench.py --steps 60 --warmup 5 --no-extras --no-cpu-baseline --no-input-stage
+sample bench python bench.py --full --steps 60 --warmup 5 --no-extras --no-cpu-baseline --no-input-stage
 sample gemm_random python tools/probe_power_gemm.py random
 sample gemm_zero python tools/probe_power_gemm.py zero
 sample hbm_stream python tools/probe_power_gemm.py stream
