@@ -415,6 +415,166 @@ __global__ __launch_bounds__(256) void bn_bwd_dx(const void* __restrict__ x, con
   }
 }
 
+// ---------------------------------------------------------------- BatchNorm -> GELU (erf), NHWC [P][C]
+// UperNet scale_modules fpn1.1 / fpn1.2 (models/decoders/upernet.py:40-42: BatchNorm2d -> GELU between the two transposed
+// convolutions).  Same split as the ReLU kernels above -- apply | backward reduce -> [all-reduce] -> backward dx -- and the same
+// per-element expressions with gelu(u) / gelu'(u), u = bn(x), in place of the mask: g = dy * gelu'(u) is recomputed from the saved
+// convolution output x in both backward passes, nothing else is saved.  All three kernels use the 16-byte mapping of
+// bn_bwd_partial8 for both dtypes: thread t owns the V = 8 (bf16) / 4 (f32) channels V (t % G) of pixel row t / G, G = C / V lanes
+// cover one pixel, a block of 256 threads covers R = 256 / G whole pixels per step and a contiguous pixel range overall (threads
+// beyond R G idle: 16 of 256 at C = 384 bf16); the per-channel constants stay in registers.
+template <typename T> struct V16;
+template <> struct V16<uint16_t> {
+  static constexpr int N = 8;
+  static __device__ __forceinline__ void load(const void* p, int64_t i, float (&v)[8]) { unpack8(*(const uint4*)((const uint16_t*)p + i), v); }
+  static __device__ __forceinline__ void store(void* p, int64_t i, const float (&v)[8]) {
+    *(uint4*)((uint16_t*)p + i) = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+  }
+};
+template <> struct V16<float> {
+  static constexpr int N = 4;
+  static __device__ __forceinline__ void load(const void* p, int64_t i, float (&v)[4]) { load4<float>(p, i, v); }
+  static __device__ __forceinline__ void store(void* p, int64_t i, const float (&v)[4]) { store4<float>(p, i, v); }
+};
+
+constexpr int BNG_T = 256;
+
+template <typename T>
+__global__ __launch_bounds__(BNG_T) void bn_gelu_apply_kernel(const void* __restrict__ x, void* y, int64_t P, int C, int64_t x_sP,
+                                                              int64_t y_sP, const float* __restrict__ mean, const float* __restrict__ var,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta, float eps) {
+  constexpr int V = V16<T>::N;
+  const int G = C / V, R = BNG_T / G;
+  const int t = threadIdx.x, g = t % G, prow = t / G;
+  if (prow >= R) return;
+  const int c = V * g;
+  float mu[V], sc[V], be[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) { mu[j] = mean[c + j]; sc[j] = rsqrtf(var[c + j] + eps) * gamma[c + j]; be[j] = beta[c + j]; }
+  const int64_t per = (P + gridDim.x - 1) / gridDim.x;
+  const int64_t p0 = per * blockIdx.x, p1 = p0 + per < P ? p0 + per : P;
+  int64_t p = p0 + prow;
+  for (; p + R < p1; p += 2 * R) {        // two pixel rows in flight
+    float v[2][V];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) V16<T>::load(x, (p + (int64_t)u * R) * x_sP + c, v[u]);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) v[u][j] = gelu_erf((v[u][j] - mu[j]) * sc[j] + be[j]);
+      V16<T>::store(y, (p + (int64_t)u * R) * y_sP + c, v[u]);
+    }
+  }
+  for (; p < p1; p += R) {
+    float v[V];
+    V16<T>::load(x, p * x_sP + c, v);
+#pragma unroll
+    for (int j = 0; j < V; ++j) v[j] = gelu_erf((v[j] - mu[j]) * sc[j] + be[j]);
+    V16<T>::store(y, p * y_sP + c, v);
+  }
+}
+
+// backward pass 1: dbeta = sum g, dgamma = sum g * xhat with g = dy * gelu'(bn(x)); partials ws[block][2][C] -> bn_bwd_final
+template <typename T>
+__global__ __launch_bounds__(BNG_T) void bn_gelu_bwd_partial(const void* __restrict__ x, const void* __restrict__ dy, int64_t P, int C,
+                                                             int64_t x_sP, int64_t dy_sP, const float* __restrict__ mean,
+                                                             const float* __restrict__ var, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, float eps, float* __restrict__ ws) {
+  constexpr int V = V16<T>::N;
+  __shared__ float red[2][BNG_T][V + 1];          // (+1: bank spread)
+  const int G = C / V, R = BNG_T / G;
+  const int t = threadIdx.x, g = t % G, prow = t / G;
+  const int c = V * g;
+  const int64_t per = (P + gridDim.x - 1) / gridDim.x;
+  const int64_t p0 = per * blockIdx.x, p1 = p0 + per < P ? p0 + per : P;
+  float s[V], q[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) { s[j] = 0.f; q[j] = 0.f; }
+  if (prow < R) {
+    float mu[V], rs[V], ga[V], be[V];
+#pragma unroll
+    for (int j = 0; j < V; ++j) { mu[j] = mean[c + j]; rs[j] = rsqrtf(var[c + j] + eps); ga[j] = gamma[c + j]; be[j] = beta[c + j]; }
+    auto add = [&](const float (&v)[V], const float (&d)[V]) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const float xh = (v[j] - mu[j]) * rs[j];
+        const float gg = d[j] * gelu_erf_grad(xh * ga[j] + be[j]);
+        s[j] += gg; q[j] += gg * xh;
+      }
+    };
+    int64_t p = p0 + prow;
+    for (; p + R < p1; p += 2 * R) {      // two pixel rows (four 16-byte loads) in flight per lane
+      float v[2][V], d[2][V];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) { V16<T>::load(x, (p + (int64_t)u * R) * x_sP + c, v[u]); V16<T>::load(dy, (p + (int64_t)u * R) * dy_sP + c, d[u]); }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) add(v[u], d[u]);
+    }
+    for (; p < p1; p += R) {
+      float v[V], d[V];
+      V16<T>::load(x, p * x_sP + c, v);
+      V16<T>::load(dy, p * dy_sP + c, d);
+      add(v, d);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < V; ++j) { red[0][t][j] = s[j]; red[1][t][j] = q[j]; }
+  __syncthreads();
+  for (int cc = t; cc < C; cc += BNG_T) {
+    float ss = 0.f, qq = 0.f;
+    for (int r = 0; r < R; ++r) { ss += red[0][r * G + cc / V][cc % V]; qq += red[1][r * G + cc / V][cc % V]; }
+    ws[((int64_t)blockIdx.x * 2 + 0) * C + cc] = ss;
+    ws[((int64_t)blockIdx.x * 2 + 1) * C + cc] = qq;
+  }
+}
+
+// backward pass 2: dx = gamma rstd (g - dbeta_sum / P_total - xhat dgamma_sum / P_total); total_dev as in bn_bwd_dx
+template <typename T>
+__global__ __launch_bounds__(BNG_T) void bn_gelu_bwd_dx_kernel(const void* __restrict__ x, const void* __restrict__ dy, void* dx, int64_t P,
+                                                               int64_t P_total, int C, int64_t x_sP, int64_t dy_sP, int64_t dx_sP,
+                                                               const float* __restrict__ mean, const float* __restrict__ var,
+                                                               const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                               const float* __restrict__ dgamma, const float* __restrict__ dbeta,
+                                                               const float* __restrict__ total_dev) {
+  constexpr int V = V16<T>::N;
+  const float invP = total_dev ? 1.0f / total_dev[0] : 1.0f / (float)P_total;
+  const int G = C / V, R = BNG_T / G;
+  const int t = threadIdx.x, g = t % G, prow = t / G;
+  if (prow >= R) return;
+  const int c = V * g;
+  float mu[V], rs[V], ga[V], be[V], k1[V], k2[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    mu[j] = mean[c + j]; rs[j] = rsqrtf(var[c + j] + eps); ga[j] = gamma[c + j]; be[j] = beta[c + j];
+    k1[j] = dbeta[c + j] * invP; k2[j] = dgamma[c + j] * invP;
+  }
+  const int64_t per = (P + gridDim.x - 1) / gridDim.x;
+  const int64_t p0 = per * blockIdx.x, p1 = p0 + per < P ? p0 + per : P;
+  auto one = [&](float (&v)[V], const float (&d)[V]) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+      const float xh = (v[j] - mu[j]) * rs[j];
+      const float gg = d[j] * gelu_erf_grad(xh * ga[j] + be[j]);
+      v[j] = ga[j] * rs[j] * (gg - k1[j] - xh * k2[j]);
+    }
+  };
+  int64_t p = p0 + prow;
+  for (; p + R < p1; p += 2 * R) {
+    float v[2][V], d[2][V];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) { V16<T>::load(x, (p + (int64_t)u * R) * x_sP + c, v[u]); V16<T>::load(dy, (p + (int64_t)u * R) * dy_sP + c, d[u]); }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) { one(v[u], d[u]); V16<T>::store(dx, (p + (int64_t)u * R) * dx_sP + c, v[u]); }
+  }
+  for (; p < p1; p += R) {
+    float v[V], d[V];
+    V16<T>::load(x, p * x_sP + c, v);
+    V16<T>::load(dy, p * dy_sP + c, d);
+    one(v, d);
+    V16<T>::store(dx, p * dx_sP + c, v);
+  }
+}
+
 // ---------------------------------------------------------------- small maps: the whole BatchNorm in ONE launch per direction
 // Round 5.  At the reference's own per-GPU batch of 4 (configs/dofa_config_RGB.yaml:85) fourteen of the 21 train-mode
 // ConvModules of DOFA + UperNet have at most 36 x 36 x 4 = 5184 pixels: their BatchNorm is five launches forward (partial
@@ -658,6 +818,21 @@ int bn_nsplit(int64_t P, int C) {
   return (int)n;
 }
 
+// pixel-range blocks of the elementwise BatchNorm -> GELU kernels: at least four steps of R pixels per block, at most 4096 blocks
+int bn_gelu_blocks(int64_t P, int C, int dtype) {
+  const int G = C / (dtype == GDL_BF16 ? 8 : 4), R = BNG_T / G;
+  int64_t n = P / (4 * R);
+  if (n > 4096) n = 4096;
+  if (n < 1) n = 1;
+  return (int)n;
+}
+
+bool bn_gelu_shape_ok(int dtype, int C, int64_t a, int64_t b, int64_t c, const void* p0, const void* p1, const void* p2) {
+  const int v = dtype == GDL_BF16 ? 8 : 4;
+  return (dtype == GDL_F32 || dtype == GDL_BF16) && C > 0 && C % v == 0 && C / v <= BNG_T && a % v == 0 && b % v == 0 && c % v == 0 &&
+         (uintptr_t)p0 % 16 == 0 && (uintptr_t)p1 % 16 == 0 && (uintptr_t)p2 % 16 == 0;
+}
+
 }  // namespace
 
 extern "C" void gdl_debug_set_bn_wide(int on) { g_bn_wide = on; }
@@ -844,5 +1019,58 @@ extern "C" int gdl_bn_bwd_dx_sync(const void* x, const void* dy, void* dx, int d
   else
     hipLaunchKernelGGL(bn_bwd_dx<float>, g2, dim3(256), 0, s, x, dy, dx, P, (int64_t)1, C, x_sP, dy_sP, dx_sP, mean, var, gamma, beta, eps, relu, dgamma_sum, dbeta_sum, total_count);
   GDL_CHECK_LAUNCH("gdl_bn_bwd_dx_sync");
+  return GDL_OK;
+}
+
+#define GDL_BN_GELU_SHAPE_MSG "C must be a multiple of 8 (bf16) / 4 (f32) and at most 2048 / 1024, strides and pointers 16-byte aligned"
+
+// y = gelu(bn(x)) with the given statistics (batch statistics in training, running estimates in eval); y may alias x
+extern "C" int gdl_bn_gelu_apply(const void* x, void* y, int dtype, int64_t P, int C, int64_t x_sP, int64_t y_sP, const float* mean,
+                                 const float* var, const float* gamma, const float* beta, float eps, gdl_stream_t stream) {
+  GDL_CHECK_ARG(x && y && mean && var && gamma && beta && P > 0, "gdl_bn_gelu_apply: null pointer or no pixels");
+  GDL_CHECK_ARG(bn_gelu_shape_ok(dtype, C, x_sP, y_sP, 0, x, y, nullptr), "gdl_bn_gelu_apply: " GDL_BN_GELU_SHAPE_MSG);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(bn_gelu_blocks(P, C, dtype));
+  if (dtype == GDL_BF16)
+    hipLaunchKernelGGL(bn_gelu_apply_kernel<uint16_t>, grid, dim3(BNG_T), 0, s, x, y, P, C, x_sP, y_sP, mean, var, gamma, beta, eps);
+  else
+    hipLaunchKernelGGL(bn_gelu_apply_kernel<float>, grid, dim3(BNG_T), 0, s, x, y, P, C, x_sP, y_sP, mean, var, gamma, beta, eps);
+  GDL_CHECK_LAUNCH("gdl_bn_gelu_apply");
+  return GDL_OK;
+}
+
+// workspace: gdl_bn_stats_workspace(P, C) bytes, as gdl_bn_bwd_reduce
+extern "C" int gdl_bn_gelu_bwd_reduce(const void* x, const void* dy, int dtype, int64_t P, int C, int64_t x_sP, int64_t dy_sP,
+                                      const float* mean, const float* var, const float* gamma, const float* beta, float eps,
+                                      float* dgamma, float* dbeta, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
+  GDL_CHECK_ARG(x && dy && mean && var && gamma && beta && dgamma && dbeta && ws && P > 0, "gdl_bn_gelu_bwd_reduce: null pointer or no pixels");
+  GDL_CHECK_ARG(bn_gelu_shape_ok(dtype, C, x_sP, dy_sP, 0, x, dy, nullptr), "gdl_bn_gelu_bwd_reduce: " GDL_BN_GELU_SHAPE_MSG);
+  GDL_CHECK_ARG(ws_bytes >= gdl_bn_stats_workspace(P, C), "gdl_bn_gelu_bwd_reduce: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int nsplit = bn_nsplit(P, C);
+  if (dtype == GDL_BF16)
+    hipLaunchKernelGGL(bn_gelu_bwd_partial<uint16_t>, dim3(nsplit), dim3(BNG_T), 0, s, x, dy, P, C, x_sP, dy_sP, mean, var, gamma, beta, eps, ws);
+  else
+    hipLaunchKernelGGL(bn_gelu_bwd_partial<float>, dim3(nsplit), dim3(BNG_T), 0, s, x, dy, P, C, x_sP, dy_sP, mean, var, gamma, beta, eps, ws);
+  hipLaunchKernelGGL(bn_bwd_final, dim3((C + 3) / 4), dim3(BN_FINAL_T), 0, s, ws, nsplit, C, dgamma, dbeta);
+  GDL_CHECK_LAUNCH("gdl_bn_gelu_bwd_reduce");
+  return GDL_OK;
+}
+
+// total_count (optional): the global pixel count in device memory (SyncBatchNorm, as gdl_bn_bwd_dx_sync); NULL -> P_total
+extern "C" int gdl_bn_gelu_bwd_dx(const void* x, const void* dy, void* dx, int dtype, int64_t P, int C, int64_t x_sP, int64_t dy_sP,
+                                  int64_t dx_sP, const float* mean, const float* var, const float* gamma, const float* beta, float eps,
+                                  const float* dgamma_sum, const float* dbeta_sum, int64_t P_total, const float* total_count,
+                                  gdl_stream_t stream) {
+  GDL_CHECK_ARG(x && dy && dx && mean && var && gamma && beta && dgamma_sum && dbeta_sum && P > 0, "gdl_bn_gelu_bwd_dx: null pointer or no pixels");
+  GDL_CHECK_ARG(total_count || P_total > 0, "gdl_bn_gelu_bwd_dx: P_total must be positive when total_count is NULL");
+  GDL_CHECK_ARG(bn_gelu_shape_ok(dtype, C, x_sP, dy_sP, dx_sP, x, dy, dx), "gdl_bn_gelu_bwd_dx: " GDL_BN_GELU_SHAPE_MSG);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid(bn_gelu_blocks(P, C, dtype));
+  if (dtype == GDL_BF16)
+    hipLaunchKernelGGL(bn_gelu_bwd_dx_kernel<uint16_t>, grid, dim3(BNG_T), 0, s, x, dy, dx, P, P_total, C, x_sP, dy_sP, dx_sP, mean, var, gamma, beta, eps, dgamma_sum, dbeta_sum, total_count);
+  else
+    hipLaunchKernelGGL(bn_gelu_bwd_dx_kernel<float>, grid, dim3(BNG_T), 0, s, x, dy, dx, P, P_total, C, x_sP, dy_sP, dx_sP, mean, var, gamma, beta, eps, dgamma_sum, dbeta_sum, total_count);
+  GDL_CHECK_LAUNCH("gdl_bn_gelu_bwd_dx");
   return GDL_OK;
 }

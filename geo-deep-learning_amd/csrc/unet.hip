@@ -202,6 +202,84 @@ __global__ __launch_bounds__(256) void add_relu_kernel(const void* __restrict__ 
   }
 }
 
+// ---------------------------------------------------------------- max-pool 2x2 / stride 2 / no padding
+// nn.MaxPool2d(kernel_size=2, stride=2) (UperNet scale_modules fpn4, models/decoders/upernet.py:54): floor output size, an odd
+// last row / column belongs to no window.  Same scan order and strict '>' as above, so ties go to the first maximum.
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool2_fwd_kernel(const void* __restrict__ in, int B, int C, Strides is, void* out, int Ho,
+                                                           int Wo, Strides os) {
+  constexpr int V = Vec<T>::N;
+  const int cv = C / V;
+  const int64_t total = (int64_t)B * Ho * Wo * cv;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % cv) * V;
+    int64_t t = i / cv;
+    const int ox = (int)(t % Wo); t /= Wo;
+    const int oy = (int)(t % Ho);
+    const int b = (int)(t / Ho);
+    const int64_t base = (int64_t)b * is.sB + (int64_t)(2 * oy) * is.sH + (int64_t)(2 * ox) * is.sW + c;
+    float v[4][V], m[V];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) Vec<T>::load(in, base + (k >> 1) * is.sH + (k & 1) * is.sW, v[k]);
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      m[e] = v[0][e];
+#pragma unroll
+      for (int k = 1; k < 4; ++k) m[e] = v[k][e] > m[e] ? v[k][e] : m[e];
+    }
+    Vec<T>::store(out, (int64_t)b * os.sB + (int64_t)oy * os.sH + (int64_t)ox * os.sW + c, m);
+  }
+}
+
+// One thread per window position (the output grid rounded UP, so the odd last row / column is visited too): the arg-max is
+// recomputed from the input and the four (or fewer) input pixels of the window get dout or zero -- windows do not overlap,
+// every din element is written exactly once, no atomics.
+template <typename T>
+__global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const void* __restrict__ in, int B, int H, int W, int C, Strides is,
+                                                           const void* __restrict__ dout, Strides ds, void* din, Strides gs) {
+  constexpr int V = Vec<T>::N;
+  const int cv = C / V, Ho = H >> 1, Wo = W >> 1, Hc = (H + 1) >> 1, Wc = (W + 1) >> 1;
+  const int64_t total = (int64_t)B * Hc * Wc * cv;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int c = (int)(i % cv) * V;
+    int64_t t = i / cv;
+    const int ox = (int)(t % Wc); t /= Wc;
+    const int oy = (int)(t % Hc);
+    const int b = (int)(t / Hc);
+    const int64_t gbase = (int64_t)b * gs.sB + (int64_t)(2 * oy) * gs.sH + (int64_t)(2 * ox) * gs.sW + c;
+    float z[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) z[e] = 0.f;
+    if (oy >= Ho || ox >= Wo) {     // the dropped odd row / column: zero gradient
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (2 * oy + (k >> 1) < H && 2 * ox + (k & 1) < W) Vec<T>::store(din, gbase + (k >> 1) * gs.sH + (k & 1) * gs.sW, z);
+      continue;
+    }
+    const int64_t base = (int64_t)b * is.sB + (int64_t)(2 * oy) * is.sH + (int64_t)(2 * ox) * is.sW + c;
+    float v[4][V], g[V];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) Vec<T>::load(in, base + (k >> 1) * is.sH + (k & 1) * is.sW, v[k]);
+    Vec<T>::load(dout, (int64_t)b * ds.sB + (int64_t)oy * ds.sH + (int64_t)ox * ds.sW + c, g);
+    int pos[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      float m = v[0][e];
+      pos[e] = 0;
+#pragma unroll
+      for (int k = 1; k < 4; ++k)
+        if (v[k][e] > m) { m = v[k][e]; pos[e] = k; }     // strict '>': the first maximum wins
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      float o[V];
+#pragma unroll
+      for (int e = 0; e < V; ++e) o[e] = pos[e] == k ? g[e] : 0.f;
+      Vec<T>::store(din, gbase + (k >> 1) * gs.sH + (k & 1) * gs.sW, o);
+    }
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void relu_bwd_kernel(const void* __restrict__ y, const void* __restrict__ dy, void* dx,
                                                        int64_t nvec) {
@@ -278,6 +356,43 @@ extern "C" int gdl_maxpool3x3s2_bwd(const void* in, const void* dout, void* din,
     hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(tiles_x * tiles_y, B, (C / 4 + 7) / 8), dim3(256), 0, s, in, B, H, W, C, is, dout, Ho, Wo, ds, din, gs, tiles_x);
   }
   GDL_CHECK_LAUNCH("gdl_maxpool3x3s2_bwd");
+  return GDL_OK;
+}
+
+extern "C" int gdl_maxpool2x2s2_fwd(const void* in, int dtype, int B, int H, int W, int C, int64_t in_sB, int64_t in_sH,
+                                    int64_t in_sW, void* out, int64_t out_sB, int64_t out_sH, int64_t out_sW,
+                                    gdl_stream_t stream) {
+  GDL_CHECK_ARG(in && out && B > 0 && H >= 2 && W >= 2, "gdl_maxpool2x2s2_fwd: bad args (the map must be at least 2 x 2)");
+  GDL_CHECK_ARG(dtype == GDL_F32 || dtype == GDL_BF16, "gdl_maxpool2x2s2_fwd: bad dtype");
+  GDL_CHECK_ARG(aligned(in, dtype, in_sB, in_sH, in_sW, C) && aligned(out, dtype, out_sB, out_sH, out_sW, C),
+                "gdl_maxpool2x2s2_fwd: channels / strides / pointers must keep 16-byte alignment");
+  const int Ho = H / 2, Wo = W / 2;
+  const Strides is{in_sB, in_sH, in_sW}, os{out_sB, out_sH, out_sW};
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == GDL_BF16)
+    hipLaunchKernelGGL(maxpool2_fwd_kernel<bf16_tag>, dim3(blocks_for((int64_t)B * Ho * Wo * (C / 8))), dim3(256), 0, s, in, B, C, is, out, Ho, Wo, os);
+  else
+    hipLaunchKernelGGL(maxpool2_fwd_kernel<float>, dim3(blocks_for((int64_t)B * Ho * Wo * (C / 4))), dim3(256), 0, s, in, B, C, is, out, Ho, Wo, os);
+  GDL_CHECK_LAUNCH("gdl_maxpool2x2s2_fwd");
+  return GDL_OK;
+}
+
+extern "C" int gdl_maxpool2x2s2_bwd(const void* in, const void* dout, void* din, int dtype, int B, int H, int W, int C,
+                                    int64_t in_sB, int64_t in_sH, int64_t in_sW, int64_t d_sB, int64_t d_sH,
+                                    int64_t d_sW, int64_t g_sB, int64_t g_sH, int64_t g_sW, gdl_stream_t stream) {
+  GDL_CHECK_ARG(in && dout && din && B > 0 && H >= 2 && W >= 2, "gdl_maxpool2x2s2_bwd: bad args (the map must be at least 2 x 2)");
+  GDL_CHECK_ARG(dtype == GDL_F32 || dtype == GDL_BF16, "gdl_maxpool2x2s2_bwd: bad dtype");
+  GDL_CHECK_ARG(aligned(in, dtype, in_sB, in_sH, in_sW, C) && aligned(dout, dtype, d_sB, d_sH, d_sW, C) &&
+                    aligned(din, dtype, g_sB, g_sH, g_sW, C),
+                "gdl_maxpool2x2s2_bwd: channels / strides / pointers must keep 16-byte alignment");
+  const Strides is{in_sB, in_sH, in_sW}, ds{d_sB, d_sH, d_sW}, gs{g_sB, g_sH, g_sW};
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t windows = (int64_t)B * ((H + 1) / 2) * ((W + 1) / 2);
+  if (dtype == GDL_BF16)
+    hipLaunchKernelGGL(maxpool2_bwd_kernel<bf16_tag>, dim3(blocks_for(windows * (C / 8))), dim3(256), 0, s, in, B, H, W, C, is, dout, ds, din, gs);
+  else
+    hipLaunchKernelGGL(maxpool2_bwd_kernel<float>, dim3(blocks_for(windows * (C / 4))), dim3(256), 0, s, in, B, H, W, C, is, dout, ds, din, gs);
+  GDL_CHECK_LAUNCH("gdl_maxpool2x2s2_bwd");
   return GDL_OK;
 }
 

@@ -164,6 +164,14 @@ SIGNATURES = {
     "gdl_dice_loss_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_f, c_p, c_p, c_l, c_p]),
     "gdl_pad_nhwc": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_p, c_i, c_i, c_i, c_p]),
     "gdl_subpix4_weights": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "gdl_convt2x2_pack": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
+    "gdl_convt2x2_unpack_grad": (c_i, [c_p, c_i, c_i, c_p, c_i, c_p]),
+    "gdl_bn_gelu_apply": (c_i, [c_p, c_p, c_i, c_l, c_i, c_l, c_l, c_p, c_p, c_p, c_p, c_f, c_p]),
+    "gdl_bn_gelu_bwd_reduce": (c_i, [c_p, c_p, c_i, c_l, c_i, c_l, c_l, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_bn_gelu_bwd_dx": (c_i, [c_p, c_p, c_p, c_i, c_l, c_i, c_l, c_l, c_l, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_l, c_p, c_p]),
+    "gdl_maxpool2x2s2_fwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_p, c_l, c_l, c_l, c_p]),
+    "gdl_maxpool2x2s2_bwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_l,
+                                   c_p]),
     "gdl_dice_binary_loss_fwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_l, c_p]),
     "gdl_dice_binary_loss_bwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_f, c_p, c_i, c_p]),
     "gdl_sumsq": (c_i, [c_p, c_l, c_p, c_p]),

@@ -934,6 +934,156 @@ def conv_bn_act(x: Tensor, conv: nn.Conv2d, norm: nn.Module, *, relu: bool = Tru
                          shift=shift, act=ACT_RELU if relu else ACT_NONE)
 
 
+# ------------------------------------------------------------------ UperNet scale_modules (upernet.py:37-54,113-119)
+_EVAL_BN_GRAD_MSG = ("gdlhip: autograd through eval-mode BatchNorm is not implemented; call under "
+                     "torch.no_grad() for inference or model.train() for training")
+
+
+def _nhwc_grad(g: Tensor, dtype: torch.dtype) -> Tensor:
+    """Incoming gradient as an NHWC tensor of the node's compute dtype with unit channel stride."""
+    if g.dtype != dtype:
+        return to_compute(g if g.stride(-1) == 1 else g.contiguous(), dtype)
+    return g if g.stride(-1) == 1 else ops.copy_cast(g.contiguous())
+
+
+def _check_convt2x2(convt: nn.ConvTranspose2d) -> None:
+    if not (isinstance(convt, nn.ConvTranspose2d) and tuple(convt.kernel_size) == (2, 2) and tuple(convt.stride) == (2, 2)
+            and tuple(convt.padding) == (0, 0) and tuple(convt.output_padding) == (0, 0) and tuple(convt.dilation) == (1, 1)
+            and convt.groups == 1):
+        raise NotImplementedError(f"gdlhip: only nn.ConvTranspose2d(kernel_size=2, stride=2) without padding / groups / dilation "
+                                  f"has a HIP path, got {convt}")
+
+
+def convt2x2_operands(convt: nn.ConvTranspose2d, cd: torch.dtype) -> tuple[Tensor, Tensor]:
+    """(forward, data-gradient) GEMM operands of a ConvTranspose2d(2, 2) parameter in the compute dtype.  A weight that is being
+    trained is packed inside EVERY forward (one small launch): the operands can never be one optimizer update behind, whoever
+    rewrote the parameter and through whatever pointer, and a captured step is correct by construction.  Frozen weights and eval
+    go through the version-keyed cache."""
+    w = convt.weight
+    if w.requires_grad and convt.training and torch.is_grad_enabled():
+        return ops.convt2x2_pack(w.detach(), cd)
+    return cached((w,), f"convt2x2:{cd}", lambda: ops.convt2x2_pack(w.detach(), cd))
+
+
+def _convt2x2_backward(x, gout, w_dgrad, need_dx, need_dw):
+    dx = ops.convt2x2_dgrad(gout, w_dgrad) if need_dx else None
+    dw = ops.convt2x2_wgrad(x, gout) if need_dw else None
+    return dx, dw
+
+
+class _ConvT2x2(Function):
+    """nn.ConvTranspose2d(kernel 2, stride 2) on NHWC (upernet.py:39,42,45)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, w_fwd, w_dgrad):
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        ctx.save_for_backward(x if need_dw else None, w_dgrad if need_dx else None)
+        return ops.convt2x2(x, w_fwd, None if bias is None else bias.detach())
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, w_dgrad = ctx.saved_tensors
+        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
+        gout = _nhwc_grad(gout, (x if x is not None else w_dgrad).dtype) if (need_dx or need_dw) else gout
+        dx, dw = _convt2x2_backward(x, gout, w_dgrad, need_dx, need_dw)
+        db = ops.colsum(gout if gout.stride(-1) == 1 else gout.contiguous()) if need_db else None
+        return dx, dw, db, None, None
+
+
+def conv_transpose2x2(x: Tensor, convt: nn.ConvTranspose2d) -> Tensor:
+    """ConvTranspose2d(kernel 2, stride 2) forward on an NHWC tensor in the compute dtype: [B,H,W,Cin] -> [B,2H,2W,Cout]."""
+    _check_convt2x2(convt)
+    w_fwd, w_dgrad = convt2x2_operands(convt, x.dtype)
+    bias = convt.bias
+    if torch.is_grad_enabled() and (x.requires_grad or convt.weight.requires_grad or (bias is not None and bias.requires_grad)):
+        return _ConvT2x2.apply(x, convt.weight, bias, w_fwd, w_dgrad)
+    return ops.convt2x2(x, w_fwd, None if bias is None else bias.detach())
+
+
+class _ConvT2x2BNGeluTrain(Function):
+    """Training-mode ConvTranspose2d(2, 2) -> BatchNorm(batch statistics) -> GELU (upernet.py:39-41), nn.BatchNorm2d /
+    nn.SyncBatchNorm semantics as _ConvBNActTrain.  Saved for the backward: the input, the convolution output (overwritten by its
+    gradient there) and the statistics; gelu'(bn(.)) is recomputed."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, momentum, eps, sync_group, w_fwd, w_dgrad):
+        n = w_fwd.shape[1]
+        y = ops.convt2x2(x, w_fwd, None if bias is None else bias.detach())
+        world = _world(sync_group) if sync_group is not False else 1
+        p_local, total = y.numel() // n, None
+        if world > 1:
+            mean, var = ops.bn_stats(y)
+            mean, var, total = sync_batch_stats(mean, var, sync_group or None, count=p_local)
+            if running_mean is not None:
+                update_running_stats(running_mean, running_var, mean, var, momentum, total)
+        else:
+            mean, var = ops.bn_stats(y, running_mean, running_var, momentum)
+            if running_mean is not None:     # written through raw pointers
+                mark_updated(running_mean)
+                mark_updated(running_var)
+        out = ops.bn_gelu_apply(y, mean, var, gamma.detach(), beta.detach(), eps)
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        ctx.save_for_backward(x if need_dw else None, w_dgrad if need_dx else None, y, mean, var, gamma, beta, total)
+        ctx.cfg = (eps, bias is not None, sync_group, world, p_local)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, w_dgrad, y, mean, var, gamma, beta, total = ctx.saved_tensors
+        eps, has_bias, sync_group, world, p_local = ctx.cfg
+        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gout = _nhwc_grad(gout, y.dtype)
+        g, b = gamma.detach(), beta.detach()
+        dgamma, dbeta = ops.bn_gelu_bwd_reduce(y, gout, mean, var, g, b, eps)
+        sg, sb = dgamma, dbeta
+        if world > 1:
+            sg, sb = sync_sum_pair(dgamma, dbeta, sync_group or None)
+        dx = dw = None
+        if need_dx or need_dw:
+            dy = ops.bn_gelu_bwd_dx(y, gout, mean, var, g, b, eps, sg, sb, p_local, total_count=total, out=y)
+            dx, dw = _convt2x2_backward(x, dy, w_dgrad, need_dx, need_dw)
+        # a bias feeding train-mode BatchNorm has an analytically zero gradient
+        db = torch.zeros(y.shape[-1], device=y.device, dtype=torch.float32) if has_bias and ctx.needs_input_grad[2] else None
+        return (dx, dw, db, dgamma if ctx.needs_input_grad[3] else None, dbeta if ctx.needs_input_grad[4] else None,
+                None, None, None, None, None, None, None)
+
+
+def conv_transpose2x2_bn_gelu(x: Tensor, convt: nn.ConvTranspose2d, norm: nn.Module) -> Tensor:
+    """ConvTranspose2d(2, 2) -> BatchNorm2d -> GELU (erf) on an NHWC tensor in the compute dtype (UperNet scale_modules fpn1[0:3])."""
+    _check_convt2x2(convt)
+    w_fwd, w_dgrad = convt2x2_operands(convt, x.dtype)
+    if norm.training:
+        sync_group = norm.process_group if isinstance(norm, nn.SyncBatchNorm) else False
+        momentum = 0.1 if norm.momentum is None else norm.momentum
+        out = _ConvT2x2BNGeluTrain.apply(x, convt.weight, convt.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var,
+                                         momentum, norm.eps, sync_group, w_fwd, w_dgrad)
+        bump(norm.num_batches_tracked)
+        return out
+    if torch.is_grad_enabled() and (x.requires_grad or convt.weight.requires_grad):
+        raise NotImplementedError(_EVAL_BN_GRAD_MSG)
+    y = ops.convt2x2(x, w_fwd, None if convt.bias is None else convt.bias.detach())
+    return ops.bn_gelu_apply(y, norm.running_mean, norm.running_var, norm.weight.detach(), norm.bias.detach(), norm.eps, out=y)
+
+
+class _MaxPool2x2(Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return ops.maxpool2x2s2(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        return ops.maxpool2x2s2_bwd(x, _nhwc_grad(g, x.dtype))
+
+
+def maxpool2x2(x: Tensor) -> Tensor:
+    """nn.MaxPool2d(kernel_size=2, stride=2) on NHWC (upernet.py:48)."""
+    if x.requires_grad and torch.is_grad_enabled():
+        return _MaxPool2x2.apply(x)
+    return ops.maxpool2x2s2(x)
+
+
 # ------------------------------------------------------------------ resampling
 class _Bilinear(Function):
     @staticmethod

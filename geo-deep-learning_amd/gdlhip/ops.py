@@ -526,6 +526,131 @@ def bn_bwd_dx(x, dy, mean, var, gamma, beta, eps, relu, dgamma_sum, dbeta_sum, p
     return dx
 
 
+# ------------------------------------------------------------------ BatchNorm -> GELU (UperNet scale_modules, fpn1.1 / fpn1.2)
+def bn_gelu_apply(x: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, beta: Tensor, eps: float, out: Tensor | None = None) -> Tensor:
+    """gelu(batch_norm(x)) (erf GELU) with the given per-channel statistics: batch statistics in training (bn_stats), running
+    estimates in eval.  ``out`` may be x."""
+    _need_cuda(x)
+    P, Cc, sP = _pix(x, "bn_gelu_apply x")
+    if out is None:
+        out = torch.empty(x.shape, device=x.device, dtype=x.dtype)
+    _, _, sPo = _pix(out, "bn_gelu_apply out")
+    check(_lib.load().gdl_bn_gelu_apply(_p(x), _p(out), dt(x), P, Cc, sP, sPo, _p(_f32vec(mean, Cc, "mean")), _p(_f32vec(var, Cc, "var")),
+                                        _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")), eps, _stream()), "gdl_bn_gelu_apply")
+    return out
+
+
+def bn_gelu_bwd_reduce(x: Tensor, dy: Tensor, mean, var, gamma, beta, eps):
+    """(dgamma, dbeta) = (sum g * xhat, sum g), g = dy * gelu'(bn(x)), from the saved convolution output x."""
+    _need_cuda(x, dy)
+    P, Cc, sP = _pix(x, "bn_gelu_bwd x")
+    _, _, sPd = _pix(dy, "bn_gelu_bwd dy")
+    if dy.dtype != x.dtype or dy.shape != x.shape:
+        raise ValueError("bn_gelu_bwd: dy must match x in shape and dtype")
+    dgamma = torch.empty(Cc, device=x.device, dtype=torch.float32)
+    dbeta = torch.empty_like(dgamma)
+    lib = _lib.load()
+    nbytes = lib.gdl_bn_stats_workspace(P, Cc)
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
+    check(lib.gdl_bn_gelu_bwd_reduce(_p(x), _p(dy), dt(x), P, Cc, sP, sPd, _p(mean), _p(var), _p(gamma), _p(beta), eps, _p(dgamma),
+                                     _p(dbeta), _p(ws), nbytes, _stream()), "gdl_bn_gelu_bwd_reduce")
+    return dgamma, dbeta
+
+
+def bn_gelu_bwd_dx(x: Tensor, dy: Tensor, mean, var, gamma, beta, eps, dgamma_sum, dbeta_sum, p_total: int,
+                   total_count: Tensor | None = None, out: Tensor | None = None) -> Tensor:
+    """dx of gelu(batch_norm(x)) from the (all-reduced) sums; ``total_count``: the global pixel count as one f32 element on the
+    device (SyncBatchNorm), else ``p_total``.  ``out`` may be x."""
+    _need_cuda(x, dy)
+    P, Cc, sP = _pix(x, "bn_gelu_bwd x")
+    _, _, sPd = _pix(dy, "bn_gelu_bwd dy")
+    if dy.dtype != x.dtype or dy.shape != x.shape:
+        raise ValueError("bn_gelu_bwd: dy must match x in shape and dtype")
+    dx = out if out is not None else torch.empty(x.shape, device=x.device, dtype=x.dtype)
+    _, _, sPx = _pix(dx, "bn_gelu_bwd dx")
+    if total_count is not None and (total_count.dtype != torch.float32 or total_count.numel() != 1):
+        raise ValueError("bn_gelu_bwd_dx: total_count must be one f32 element on the device")
+    check(_lib.load().gdl_bn_gelu_bwd_dx(_p(x), _p(dy), _p(dx), dt(x), P, Cc, sP, sPd, sPx, _p(mean), _p(var), _p(gamma), _p(beta), eps,
+                                         _p(dgamma_sum), _p(dbeta_sum), int(p_total), _p(total_count), _stream()), "gdl_bn_gelu_bwd_dx")
+    return dx
+
+
+# ------------------------------------------------------------------ ConvTranspose2d(kernel 2, stride 2) (UperNet scale_modules)
+def _convt_channels(cin: int, cout: int, dtype: torch.dtype) -> None:
+    al = 8 if dtype == torch.bfloat16 else 4
+    if cin % al or cout % al:
+        raise ValueError(f"convt2x2: in / out channels ({cin}, {cout}) must be multiples of {al} for {dtype} "
+                         f"(16-byte pieces of the MFMA GEMM operands)")
+
+
+def convt2x2_pack(weight: Tensor, dtype: torch.dtype) -> tuple[Tensor, Tensor]:
+    """nn.ConvTranspose2d(k=2, s=2) parameter [Cin, Cout, 2, 2] f32 -> (forward operand [4, Cout, Cin] phase-major, data-gradient
+    operand [Cin, 4 * Cout]) in ``dtype``, one launch."""
+    _need_cuda(weight)
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (2, 2) or weight.dtype != torch.float32 or not weight.is_contiguous():
+        raise ValueError(f"convt2x2_pack: contiguous f32 [Cin, Cout, 2, 2] parameter expected, got {tuple(weight.shape)} {weight.dtype}")
+    cin, cout = weight.shape[0], weight.shape[1]
+    _convt_channels(cin, cout, dtype)
+    fwd = torch.empty((4, cout, cin), device=weight.device, dtype=dtype)
+    dgrad = torch.empty((cin, 4 * cout), device=weight.device, dtype=dtype)
+    check(_lib.load().gdl_convt2x2_pack(_p(weight), cin, cout, dt(dtype), _p(fwd), _p(dgrad), _stream()), "gdl_convt2x2_pack")
+    return fwd, dgrad
+
+
+def convt2x2(x: Tensor, w_fwd: Tensor, bias: Tensor | None = None) -> Tensor:
+    """F.conv_transpose2d(x, w, bias, stride=2) for a 2x2 kernel on NHWC x [B,H,W,Cin] -> [B,2H,2W,Cout]: the four output phases
+    are one batched 1x1 GEMM launch writing the strided phase positions; w_fwd from convt2x2_pack."""
+    _need_cuda(x, w_fwd)
+    x4 = _nhwc4(x, "convt2x2 x")
+    B, H, W, Cc = x4.shape
+    if w_fwd.dim() != 3 or w_fwd.shape[0] != 4 or w_fwd.shape[2] != Cc or w_fwd.dtype != x.dtype or not w_fwd.is_contiguous():
+        raise ValueError(f"convt2x2: operand must be contiguous [4, Cout, {Cc}] {x.dtype}, got {tuple(w_fwd.shape)} {w_fwd.dtype}")
+    N = w_fwd.shape[1]
+    _convt_channels(Cc, N, x.dtype)
+    y = torch.empty((B, 2 * H, 2 * W, N), device=x.device, dtype=x.dtype)
+    a = ConvArgs()
+    a.inp, a.dtype = x4.data_ptr(), dt(x4)
+    a.B, a.H, a.W, a.C = B, H, W, Cc
+    a.in_sB, a.in_sH, a.in_sW = x4.stride(0), x4.stride(1), x4.stride(2)
+    a.Ho, a.Wo, a.R, a.S, a.stride, a.pad = H, W, 1, 1, 1, 0
+    a.w, a.w_sN, a.N = w_fwd.data_ptr(), Cc, N
+    a.out, a.out_dtype = y.data_ptr(), dt(y)
+    a.out_sB, a.out_sH, a.out_sW = y.stride(0), 2 * y.stride(1), 2 * y.stride(2)
+    a.alpha, a.act = 1.0, ACT_NONE
+    a.bias = None if bias is None else _f32vec(bias, N, "bias").data_ptr()
+    a.nz, a.nz_inner = 4, 2                                   # z = (row phase, column phase)
+    a.w_sZ0, a.w_sZ1 = 2 * N * Cc, N * Cc
+    a.out_sZ0, a.out_sZ1 = y.stride(1), y.stride(2)
+    batched_gemm_raw(a)
+    return y
+
+
+def convt2x2_dgrad(dy: Tensor, w_dgrad: Tensor) -> Tensor:
+    """Data gradient of convt2x2: a 2x2 / stride-2 convolution of dy [B,2H,2W,Cout] with w_dgrad [Cin, 4 * Cout] -> [B,H,W,Cin]."""
+    if dy.dim() != 4 or dy.shape[1] % 2 or dy.shape[2] % 2:
+        raise ValueError(f"convt2x2_dgrad: dy must be [B, 2H, 2W, Cout], got {tuple(dy.shape)}")
+    _convt_channels(w_dgrad.shape[0], dy.shape[3], dy.dtype)
+    return conv_gemm(dy, w_dgrad, R=2, S=2, stride=2, pad=0)
+
+
+def convt2x2_wgrad(x: Tensor, dy: Tensor, out: Tensor | None = None, accumulate: bool = False) -> Tensor:
+    """Weight gradient of convt2x2 in the parameter's own layout [Cin, Cout, 2, 2] f32: the weight-gradient GEMM with the roles
+    swapped (in = dy under a 2x2 / stride-2 window, dy = x) gives [Cin, (py, px, n)], one kernel re-orders (and, with
+    ``accumulate``, adds into ``out``)."""
+    _need_cuda(x, dy)
+    cin, cout = x.shape[-1], dy.shape[-1]
+    _convt_channels(cin, cout, x.dtype)
+    if dy.dim() != 4 or x.dim() != 4 or dy.shape[1] != 2 * x.shape[1] or dy.shape[2] != 2 * x.shape[2] or dy.shape[0] != x.shape[0]:
+        raise ValueError(f"convt2x2_wgrad: x {tuple(x.shape)} and dy {tuple(dy.shape)} do not belong to one layer")
+    dw = conv_wgrad(dy, x, R=2, S=2, stride=2, pad=0)         # [Cin, 4 * Cout]
+    if out is None:
+        out, accumulate = torch.empty((cin, cout, 2, 2), device=x.device, dtype=torch.float32), False
+    elif tuple(out.shape) != (cin, cout, 2, 2) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("convt2x2_wgrad: out must be a contiguous f32 [Cin, Cout, 2, 2] tensor")
+    check(_lib.load().gdl_convt2x2_unpack_grad(_p(dw), cin, cout, _p(out), int(accumulate), _stream()), "gdl_convt2x2_unpack_grad")
+    return out
+
+
 # ------------------------------------------------------------------ resampling
 def bilinear(x: Tensor, size: tuple[int, int], out: Tensor | None = None,
              out_dtype: torch.dtype | None = None, accumulate: bool = False) -> Tensor:
@@ -1309,6 +1434,33 @@ def maxpool3x3s2_bwd(x: Tensor, dout: Tensor) -> Tensor:
     check(_lib.load().gdl_maxpool3x3s2_bwd(_p(x4), _p(d4), _p(din), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1),
                                            x4.stride(2), d4.stride(0), d4.stride(1), d4.stride(2), din.stride(0),
                                            din.stride(1), din.stride(2), _stream()), "gdl_maxpool3x3s2_bwd")
+    return din
+
+
+def maxpool2x2s2(x: Tensor) -> Tensor:
+    """F.max_pool2d(kernel 2, stride 2) on NHWC (floor output size: an odd last row / column is dropped)."""
+    _need_cuda(x)
+    x4 = _nhwc4(x, "maxpool2x2 x")
+    B, H, W, Cc = x4.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"maxpool2x2s2: the map must be at least 2 x 2, got {H} x {W}")
+    out = torch.empty((B, H // 2, W // 2, Cc), device=x.device, dtype=x.dtype)
+    check(_lib.load().gdl_maxpool2x2s2_fwd(_p(x4), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1), x4.stride(2), _p(out),
+                                           out.stride(0), out.stride(1), out.stride(2), _stream()), "gdl_maxpool2x2s2_fwd")
+    return out
+
+
+def maxpool2x2s2_bwd(x: Tensor, dout: Tensor) -> Tensor:
+    """Gradient of maxpool2x2s2 wrt x: each window's gradient goes to its first maximum, everything else is zero."""
+    _need_cuda(x, dout)
+    x4, d4 = _nhwc4(x, "maxpool2x2_bwd x"), _nhwc4(dout, "maxpool2x2_bwd dout")
+    B, H, W, Cc = x4.shape
+    if tuple(d4.shape) != (B, H // 2, W // 2, Cc) or d4.dtype != x4.dtype:
+        raise ValueError(f"maxpool2x2s2_bwd: dout {tuple(d4.shape)} {d4.dtype} does not match x {tuple(x4.shape)} {x4.dtype}")
+    din = torch.empty((B, H, W, Cc), device=x.device, dtype=x.dtype)
+    check(_lib.load().gdl_maxpool2x2s2_bwd(_p(x4), _p(d4), _p(din), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1),
+                                           x4.stride(2), d4.stride(0), d4.stride(1), d4.stride(2), din.stride(0),
+                                           din.stride(1), din.stride(2), _stream()), "gdl_maxpool2x2s2_bwd")
     return din
 
 

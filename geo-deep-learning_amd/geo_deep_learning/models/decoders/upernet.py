@@ -11,19 +11,26 @@ from gdlhip import ops
 
 
 class UperNetDecoder(nn.Module):
-    """PPM + FPN decoder (upernet.py:9-152), scale_modules=False path."""
+    """PPM + FPN decoder (upernet.py:9-152), with or without the scale_modules pyramid (upernet.py:37-54)."""
 
     def __init__(self, embed_dim: list[int], pool_scales: tuple[int, ...] = (1, 2, 3, 6), channels: int = 256,
                  *, align_corners: bool = True, scale_modules: bool = False) -> None:
         super().__init__()
-        if scale_modules:
-            msg = "gdlhip UperNetDecoder: scale_modules (ConvTranspose path) is unused by DOFA (dofa.py:68)"
-            raise NotImplementedError(msg)
         if align_corners:
             msg = "gdlhip UperNetDecoder: align_corners=True is not on the hot path (dofa.py:66)"
             raise NotImplementedError(msg)
         self.scale_modules = scale_modules
-        self.embed_dim = embed_dim
+        if scale_modules:
+            # upernet.py:37-54: the pyramid is built inside the decoder from four equal-resolution taps (plain ViT encoders).
+            # Plain torch containers: state-dict keys / shapes of the reference, and convert_sync_batchnorm finds fpn1.1
+            self.fpn1 = nn.Sequential(nn.ConvTranspose2d(embed_dim[0], embed_dim[0] // 2, 2, 2), nn.BatchNorm2d(embed_dim[0] // 2),
+                                      nn.GELU(), nn.ConvTranspose2d(embed_dim[0] // 2, embed_dim[0] // 4, 2, 2))
+            self.fpn2 = nn.Sequential(nn.ConvTranspose2d(embed_dim[1], embed_dim[1] // 2, 2, 2))
+            self.fpn3 = nn.Sequential(nn.Identity())
+            self.fpn4 = nn.Sequential(nn.MaxPool2d(kernel_size=2, stride=2))
+            self.embed_dim = [embed_dim[0] // 4, embed_dim[1] // 2, embed_dim[2], embed_dim[3]]
+        else:
+            self.embed_dim = embed_dim
         self.out_channels = channels
         self.channels = channels
         self.align_corners = align_corners
@@ -45,7 +52,15 @@ class UperNetDecoder(nn.Module):
         cat = gnn.concat_upsample([x, *self.psp_modules.forward_nhwc_lowres(x)], size)
         return self.bottleneck.forward_nhwc(cat)
 
+    def scale_inputs_nhwc(self, inputs: list[torch.Tensor]) -> list[torch.Tensor]:
+        """upernet.py:113-119: x4 (ConvTranspose -> BN -> GELU -> ConvTranspose), x2 (ConvTranspose), x1, x1/2 (2x2 max-pool)."""
+        half = gnn.conv_transpose2x2_bn_gelu(inputs[0], self.fpn1[0], self.fpn1[1])
+        return [gnn.conv_transpose2x2(half, self.fpn1[3]), gnn.conv_transpose2x2(inputs[1], self.fpn2[0]), inputs[2],
+                gnn.maxpool2x2(inputs[3])]
+
     def forward_nhwc(self, inputs: list[torch.Tensor]) -> torch.Tensor:
+        if self.scale_modules:
+            inputs = self.scale_inputs_nhwc(inputs)
         # lateral 1x1 convolutions and the PPM branches are independent: one group (one SyncBatchNorm message per direction)
         lat_items = [dict(x=inputs[i], conv=m.conv, norm=m.norm) for i, m in enumerate(self.lateral_convs)]
         ppm_items = self.psp_modules.items_nhwc(inputs[-1])

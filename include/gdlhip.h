@@ -183,6 +183,22 @@ int gdl_bn_small_bwd(const void* x, const void* dy, void* dx, int dtype, int64_t
                      const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
                      float* dgamma, float* dbeta, gdl_stream_t stream);
 
+/* BatchNorm2d -> GELU (erf) on NHWC [P pixels][C] (UperNet scale_modules fpn1.1 / fpn1.2, models/decoders/upernet.py:40-42;
+ * F.gelu(F.batch_norm(x))).  apply: y = gelu((x-mean)*rsqrt(var+eps)*gamma + beta) with batch statistics (training, from
+ * gdl_bn_stats) or the running estimates (eval); in place allowed.  Backward from the saved convolution output x, in the same two
+ * steps as gdl_bn_bwd_reduce / gdl_bn_bwd_dx with g = dy * gelu'(bn(x)); workspace gdl_bn_stats_workspace(P, C) bytes.
+ * total_count: NULL, or the global pixel count in device memory (SyncBatchNorm, as gdl_bn_bwd_dx_sync; P_total is then unused).
+ * 16-byte vectors: C % 8 == 0 (bf16) / C % 4 == 0 (f32), C <= 2048 / 1024, strides and pointers 16-byte aligned. */
+int gdl_bn_gelu_apply(const void* x, void* y, int dtype, int64_t P, int C, int64_t x_sP, int64_t y_sP, const float* mean,
+                      const float* var, const float* gamma, const float* beta, float eps, gdl_stream_t stream);
+int gdl_bn_gelu_bwd_reduce(const void* x, const void* dy, int dtype, int64_t P, int C, int64_t x_sP, int64_t dy_sP,
+                           const float* mean, const float* var, const float* gamma, const float* beta, float eps,
+                           float* dgamma, float* dbeta, float* workspace, int64_t workspace_bytes, gdl_stream_t stream);
+int gdl_bn_gelu_bwd_dx(const void* x, const void* dy, void* dx, int dtype, int64_t P, int C, int64_t x_sP, int64_t dy_sP,
+                       int64_t dx_sP, const float* mean, const float* var, const float* gamma, const float* beta, float eps,
+                       const float* dgamma_sum, const float* dbeta_sum, int64_t P_total, const float* total_count,
+                       gdl_stream_t stream);
+
 /* ---- transformer-block backward (timm Block dofa_v2.py:248-263, MiT Block mix_transformer.py:160-221) ----
  * Column reductions (parameter gradients) go through per-block partials in `ws`
  * (>= gdl_colreduce_workspace(rows, C, planes) bytes) and a deterministic final pass; no atomics. */
@@ -261,6 +277,14 @@ int gdl_augment(const void* img, int kind, float* out, const int64_t* mask, int6
 int gdl_maxpool3x3s2_fwd(const void* in, int dtype, int B, int H, int W, int C, int64_t in_sB, int64_t in_sH,
                          int64_t in_sW, void* out, int64_t out_sB, int64_t out_sH, int64_t out_sW, gdl_stream_t stream);
 int gdl_maxpool3x3s2_bwd(const void* in, const void* dout, void* din, int dtype, int B, int H, int W, int C,
+                         int64_t in_sB, int64_t in_sH, int64_t in_sW, int64_t d_sB, int64_t d_sH, int64_t d_sW,
+                         int64_t g_sB, int64_t g_sH, int64_t g_sW, gdl_stream_t stream);
+/* nn.MaxPool2d(kernel_size=2, stride=2) (UperNet scale_modules fpn4, models/decoders/upernet.py:54): [B,H,W,C] -> [B,H/2,W/2,C]
+ * (floor: an odd last row / column is dropped).  Backward recomputes each window's FIRST maximum from `in` and writes every
+ * element of din once (the dropped row / column gets zero); no atomics. */
+int gdl_maxpool2x2s2_fwd(const void* in, int dtype, int B, int H, int W, int C, int64_t in_sB, int64_t in_sH,
+                         int64_t in_sW, void* out, int64_t out_sB, int64_t out_sH, int64_t out_sW, gdl_stream_t stream);
+int gdl_maxpool2x2s2_bwd(const void* in, const void* dout, void* din, int dtype, int B, int H, int W, int C,
                          int64_t in_sB, int64_t in_sH, int64_t in_sW, int64_t d_sB, int64_t d_sH, int64_t d_sW,
                          int64_t g_sB, int64_t g_sH, int64_t g_sW, gdl_stream_t stream);
 /* F.interpolate(scale_factor=2, mode="nearest"): [B,H,W,C] -> [B,2H,2W,C]; backward sums each 2x2 block */
@@ -520,6 +544,15 @@ int gdl_pad_nhwc(const void* in, int dtype, int B, int H, int W, int C, int64_t 
                  void* out, int pad_h, int pad_w, int zero_mode, gdl_stream_t stream);
 int gdl_subpix4_weights(const float* w, int N, int C, int out_dtype, void* g22, void* g23, void* g32, void* g33,
                         void* lines, gdl_stream_t stream);
+
+/* ---- nn.ConvTranspose2d(kernel_size=2, stride=2) (UperNet scale_modules, models/decoders/upernet.py:37-54) ----------
+ * out[b,2y+py,2x+px,n] = bias[n] + sum_c in[b,y,x,c] * w[c][n][py][px]: forward, data gradient and weight gradient are
+ * gdl_conv_gemm (nz = 4 phases, strided output) / gdl_conv_gemm (R = S = 2, stride 2 on dy) / gdl_conv_wgrad (in = dy, dy = x);
+ * see csrc/convt.hip.  gdl_convt2x2_pack: the f32 parameter w [Cin][Cout][2][2] -> both GEMM operands in out_dtype in ONE
+ * launch, fwd [4 phases (py,px)][Cout][Cin] and dgrad [Cin][(py,px,n)].  gdl_convt2x2_unpack_grad: the weight-gradient GEMM's
+ * f32 result dw [Cin][(py,px,n)] -> the parameter's gradient grad [Cin][Cout][2][2] (accumulate != 0: grad += ...). */
+int gdl_convt2x2_pack(const float* w, int Cin, int Cout, int out_dtype, void* fwd, void* dgrad, gdl_stream_t stream);
+int gdl_convt2x2_unpack_grad(const float* dw, int Cin, int Cout, float* grad, int accumulate, gdl_stream_t stream);
 
 /* ---- optimizer -------------------------------------------------------------------------
  * torch.optim.Adam step (configs/dofa_config_RGB.yaml:62-65) on one flat f32 tensor, with the
