@@ -964,16 +964,59 @@ __global__ __launch_bounds__(256) void class_probs_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------ Dice loss (smp multiclass)
-// pass 1: per-block partial sums of I_c = sum p_c*[y==c], S_c = sum p_c, N_c = count(y==c)
+// The constructor options of smp's DiceLoss (losses/dice.py) beyond the defaults:
+//   ignore_index -- template flag IGN of the per-pixel kernels: a pixel whose target equals `ignore` (compared as int64, before the
+//                   cast to int) adds nothing to the three sums and gets a zero gradient.  IGN = false is the code as it was.
+//   smooth, log_loss, classes -- DiceCoef: they only change how the per-class sums become the loss (dice_final_kernel) and the two
+//                   per-class gradient coefficients (dice_coeffs); `plain` (smooth == 0, no log, every class) selects the original
+//                   expressions so that the defaults stay bit-identical.
+struct DiceCoef {
+  float smooth;
+  uint32_t cls;     // bit k: class k takes part in the mean
+  int nsel;         // number of set bits (the mean's divisor)
+  int log_loss;
+  int plain;
+};
+
+// dL/dp_c = ca[c]*[y==c] + cb[c] from sums = [I | S | N]:  loss_c = L(score_c), score_c = (2 I_c + smooth) / max(S_c + N_c + smooth, eps),
+// L(s) = 1 - s or -log(max(s, eps)); weight [N_c > 0] * [c selected] / nsel.  `up` = upstream * grad_scale.
 template <int K>
+__device__ __forceinline__ void dice_coeffs(const float* __restrict__ sums, float eps, float up, const DiceCoef o, float (&ca)[K],
+                                            float (&cb)[K]) {
+  if (o.plain) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float I = sums[k], card = sums[K + k] + sums[2 * K + k];
+      const bool on = sums[2 * K + k] > 0.f && card > eps;
+      ca[k] = on ? -2.f / (K * card) * up : 0.f;
+      cb[k] = on ? 2.f * I / (K * card * card) * up : 0.f;
+    }
+  } else {
+    const float w = up / (float)o.nsel;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float num = 2.f * sums[k] + o.smooth, den = sums[K + k] + sums[2 * K + k] + o.smooth;
+      const bool clamped = !(den > eps);
+      const float denc = clamped ? eps : den, score = num / denc;
+      float f = (sums[2 * K + k] > 0.f && ((o.cls >> k) & 1u)) ? -w : 0.f;      // w_c * [N_c > 0] * L'(score) * up
+      if (o.log_loss) f = score > eps ? f / score : 0.f;
+      ca[k] = f * 2.f / denc;
+      cb[k] = clamped ? 0.f : -f * num / (denc * denc);
+    }
+  }
+}
+
+// pass 1: per-block partial sums of I_c = sum p_c*[y==c], S_c = sum p_c, N_c = count(y==c)
+template <int K, bool IGN>
 __global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
-                                                           int B, int64_t HW, float* __restrict__ ws) {
+                                                           int B, int64_t HW, float* __restrict__ ws, int64_t ignore) {
   __shared__ float red[4][3 * K];
   const int64_t total = (int64_t)B * HW;
   float I[K], S[K], Nc[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) I[k] = S[k] = Nc[k] = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    if (IGN && target[i] == ignore) continue;
     const int64_t b = i / HW, p = i - b * HW;
     float x[K], mx = -INFINITY;
 #pragma unroll
@@ -1004,7 +1047,7 @@ __global__ __launch_bounds__(256) void dice_partial_kernel(const float* __restri
 
 template <int K>
 __global__ __launch_bounds__(256) void dice_final_kernel(const float* __restrict__ ws, int nblk, float eps,
-                                                         float* __restrict__ sums, float* __restrict__ loss) {
+                                                         float* __restrict__ sums, float* __restrict__ loss, const DiceCoef o) {
   __shared__ double part[4][64];
   __shared__ double tot[64];
   const int t = threadIdx.x, v = t & 63, grp = t >> 6;   // 4 groups of 64 value slots (3K <= 48)
@@ -1020,7 +1063,7 @@ __global__ __launch_bounds__(256) void dice_final_kernel(const float* __restrict
     sums[t] = (float)r;
   }
   __syncthreads();
-  if (t == 0) {
+  if (t == 0 && o.plain) {
     double l = 0;
     for (int k = 0; k < K; ++k) {
       const double I = tot[k], card = tot[K + k] + tot[2 * K + k];
@@ -1028,24 +1071,28 @@ __global__ __launch_bounds__(256) void dice_final_kernel(const float* __restrict
       if (tot[2 * K + k] > 0) l += 1.0 - dice;
     }
     loss[0] = (float)(l / K);
+  } else if (t == 0) {
+    double l = 0;
+    for (int k = 0; k < K; ++k) {
+      if (!((o.cls >> k) & 1u) || !(tot[2 * K + k] > 0)) continue;
+      const double num = 2.0 * tot[k] + o.smooth, den = tot[K + k] + tot[2 * K + k] + o.smooth;
+      const double score = num / (den > eps ? den : eps);
+      l += o.log_loss ? -log(score > eps ? score : (double)eps) : 1.0 - score;
+    }
+    loss[0] = (float)(l / o.nsel);
   }
 }
 
 // pass 2: dL/dlogits; sums = [I | S | N] as produced above
-template <int K>
+template <int K, bool IGN>
 __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target,
                                                        int B, int64_t HW, const float* __restrict__ sums, float eps,
                                                        const float* __restrict__ upstream, float grad_scale,
-                                                       float* __restrict__ dlogits, int accumulate) {
+                                                       float* __restrict__ dlogits, int accumulate, int64_t ignore,
+                                                       const DiceCoef o) {
   float ca[K], cb[K];  // dL/dp_c = ca[c]*[y==c] + cb[c]
   const float up = (upstream ? upstream[0] : 1.f) * grad_scale;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const float I = sums[k], card = sums[K + k] + sums[2 * K + k];
-    const bool on = sums[2 * K + k] > 0.f && card > eps;
-    ca[k] = on ? -2.f / (K * card) * up : 0.f;
-    cb[k] = on ? 2.f * I / (K * card * card) * up : 0.f;
-  }
+  dice_coeffs<K>(sums, eps, up, o, ca, cb);
   const int64_t total = (int64_t)B * HW;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
     const int64_t b = i / HW, p = i - b * HW;
@@ -1067,7 +1114,8 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const int64_t o = (b * K + k) * HW + p;
-      const float v = x[k] * (g[k] - dot);
+      float v = x[k] * (g[k] - dot);
+      if (IGN && target[i] == ignore) v = 0.f;      // an ignored pixel: exactly zero in every class
       dlogits[o] = accumulate ? dlogits[o] + v : v;
     }
   }
@@ -1124,9 +1172,10 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(const float* __res
   }
 }
 
-template <int K>
+template <int K, bool IGN>
 __global__ __launch_bounds__(256) void dice_lowres_partial_kernel(const float* __restrict__ low, const int64_t* __restrict__ target,
-                                                                  int B, int Hi, int Wi, int Ho, int Wo, float* __restrict__ ws) {
+                                                                  int B, int Hi, int Wi, int Ho, int Wo, float* __restrict__ ws,
+                                                                  int64_t ignore) {
   __shared__ float red[4][3 * K];
   const int64_t total = (int64_t)B * Ho * Wo;
   const float ry = (float)Hi / (float)Ho, rx = (float)Wi / (float)Wo;
@@ -1149,6 +1198,7 @@ __global__ __launch_bounds__(256) void dice_lowres_partial_kernel(const float* _
     for (int k = 0; k < K; ++k) { x[k] = expf(x[k] - mx); s += x[k]; }
     const float inv = 1.f / s;
     const int y = (int)target[i];
+    if (IGN && target[i] == ignore) continue;      // (tested here, not at the top: the target load goes out with the logit loads)
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const float pk = x[k] * inv;
@@ -1171,20 +1221,14 @@ __global__ __launch_bounds__(256) void dice_lowres_partial_kernel(const float* _
 constexpr int DICE_LOWRES_MAX_FACTOR = 64;   // (every loop below is a run-time loop; the bound only keeps the K > 8 gather kernel's
                                              // window -- (2 * factor + 4)^2 softmax evaluations per low-resolution logit -- finite)
 
-template <int K>
+template <int K, bool IGN>
 __global__ __launch_bounds__(256) void dice_lowres_bwd_kernel(const float* __restrict__ low, const int64_t* __restrict__ target, int B,
                                                               int Hi, int Wi, int Ho, int Wo, const float* __restrict__ sums,
                                                               float eps, const float* __restrict__ upstream, float grad_scale,
-                                                              float* __restrict__ dlow) {
+                                                              float* __restrict__ dlow, int64_t ignore, const DiceCoef o) {
   float ca[K], cb[K];  // dL/dp_c = ca[c]*[y==c] + cb[c]   (dice_bwd_kernel)
   const float up = (upstream ? upstream[0] : 1.f) * grad_scale;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const float I = sums[k], card = sums[K + k] + sums[2 * K + k];
-    const bool on = sums[2 * K + k] > 0.f && card > eps;
-    ca[k] = on ? -2.f / (K * card) * up : 0.f;
-    cb[k] = on ? 2.f * I / (K * card * card) * up : 0.f;
-  }
+  dice_coeffs<K>(sums, eps, up, o, ca, cb);
   const int64_t total = (int64_t)B * Hi * Wi;
   const float ry = (float)Hi / (float)Ho, rx = (float)Wi / (float)Wo;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -1219,7 +1263,8 @@ __global__ __launch_bounds__(256) void dice_lowres_bwd_kernel(const float* __res
 #pragma unroll
         for (int k = 0; k < K; ++k) { x[k] = expf(x[k] - mx); s += x[k]; }
         const float inv = 1.f / s;
-        const int y = (int)target[trow + ox];
+        const int64_t t = target[trow + ox];
+        const int y = (int)t;
         float g[K], dot = 0.f;
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -1228,7 +1273,10 @@ __global__ __launch_bounds__(256) void dice_lowres_bwd_kernel(const float* __res
           dot += x[k] * g[k];
         }
 #pragma unroll
-        for (int k = 0; k < K; ++k) acc[k] += w * (x[k] * (g[k] - dot));
+        for (int k = 0; k < K; ++k) {
+          const float sum = acc[k] + w * (x[k] * (g[k] - dot));
+          acc[k] = (IGN && t == ignore) ? acc[k] : sum;      // an ignored pixel adds nothing
+        }
       }
     }
 #pragma unroll
@@ -1253,6 +1301,8 @@ struct DiceTile {
   const float* low; const int64_t* target; const float* sums; const float* upstream; float* ws; float* dlow;
   int B, Hi, Wi, Ho, Wo, tiles_y, tiles_x, ny_max, nx_max;
   float eps, grad_scale;
+  int64_t ignore;
+  DiceCoef o;
 };
 
 // low-resolution index range [lo, hi] that the full-resolution positions [p0, p1] interpolate from
@@ -1263,7 +1313,7 @@ __device__ __forceinline__ void touched_range(float ratio, int p0, int p1, int i
   lo = a0; hi = b1;
 }
 
-template <int K>
+template <int K, bool IGN>
 __global__ __launch_bounds__(DT_T) void dice_lowres_bwd_tile_kernel(const DiceTile a) {
   extern __shared__ __attribute__((aligned(16))) float dsm[];
   float* dl = dsm;                                   // [K][DT_H][DT_W]
@@ -1277,13 +1327,7 @@ __global__ __launch_bounds__(DT_T) void dice_lowres_bwd_tile_kernel(const DiceTi
   const float ry = (float)a.Hi / (float)a.Ho, rx = (float)a.Wi / (float)a.Wo;
   float ca[K], cb[K];
   const float up = (a.upstream ? a.upstream[0] : 1.f) * a.grad_scale;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const float I = a.sums[k], card = a.sums[K + k] + a.sums[2 * K + k];
-    const bool on = a.sums[2 * K + k] > 0.f && card > a.eps;
-    ca[k] = on ? -2.f / (K * card) * up : 0.f;
-    cb[k] = on ? 2.f * I / (K * card * card) * up : 0.f;
-  }
+  dice_coeffs<K>(a.sums, a.eps, up, a.o, ca, cb);
   // ---- 1. dL/dlogit of the tile (zeros outside the image)
   for (int i = tid; i < DT_H * DT_W; i += DT_T) {
     const int r = i / DT_W, c = i - r * DT_W;
@@ -1303,7 +1347,8 @@ __global__ __launch_bounds__(DT_T) void dice_lowres_bwd_tile_kernel(const DiceTi
 #pragma unroll
       for (int k = 0; k < K; ++k) { x[k] = expf(x[k] - mx); sden += x[k]; }
       const float inv = 1.f / sden;
-      const int y = (int)a.target[((int64_t)b * a.Ho + oy) * a.Wo + ox];
+      const int64_t t = a.target[((int64_t)b * a.Ho + oy) * a.Wo + ox];
+      const int y = (int)t;
       float g[K], dot = 0.f;
 #pragma unroll
       for (int k = 0; k < K; ++k) {
@@ -1312,7 +1357,7 @@ __global__ __launch_bounds__(DT_T) void dice_lowres_bwd_tile_kernel(const DiceTi
         dot += x[k] * g[k];
       }
 #pragma unroll
-      for (int k = 0; k < K; ++k) v[k] = x[k] * (g[k] - dot);
+      for (int k = 0; k < K; ++k) v[k] = (IGN && t == a.ignore) ? 0.f : x[k] * (g[k] - dot);      // an ignored pixel: zero
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) dl[(k * DT_H + r) * DT_W + c] = v[k];
@@ -1427,12 +1472,14 @@ __global__ __launch_bounds__(256) void dice_lowres_bwd_reduce_kernel(const DiceT
 // smp DiceLoss(mode="binary") (configs/unetplus_config_RGB.yaml: num_classes 1): p = exp(logsigmoid(x)), one class,
 // sums over dims (batch, pixels); the target is used as a 0/1 weight.  Partials have the multiclass layout with K = 1
 // ([I | S | N]) so dice_final_kernel<1> finishes them (loss * [sum y > 0], mean over the single class).
+template <bool IGN>
 __global__ __launch_bounds__(256) void dice_binary_partial_kernel(const float* __restrict__ logits,
                                                                   const int64_t* __restrict__ target, int64_t total,
-                                                                  float* __restrict__ ws) {
+                                                                  float* __restrict__ ws, int64_t ignore) {
   __shared__ float red[4][3];
   float I = 0.f, S = 0.f, Nc = 0.f;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    if (IGN && target[i] == ignore) continue;
     const float x = logits[i];
     // exp(logsigmoid(x)) with logsigmoid(x) = min(x, 0) - log1p(exp(-|x|)), as torch computes it
     const float p = expf(fminf(x, 0.f) - log1pf(expf(-fabsf(x))));
@@ -1448,17 +1495,30 @@ __global__ __launch_bounds__(256) void dice_binary_partial_kernel(const float* _
         (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
+template <bool IGN>
 __global__ __launch_bounds__(256) void dice_binary_bwd_kernel(const float* __restrict__ logits,
                                                               const int64_t* __restrict__ target, int64_t total,
                                                               const float* __restrict__ sums, float eps,
                                                               const float* __restrict__ upstream, float grad_scale,
-                                                              float* __restrict__ dlogits, int accumulate) {
+                                                              float* __restrict__ dlogits, int accumulate, int64_t ignore,
+                                                              const DiceCoef o) {
   const float up = (upstream ? upstream[0] : 1.f) * grad_scale;
-  const float I = sums[0], card = sums[1] + sums[2];
-  const bool on = sums[2] > 0.f && card > eps;
-  const float ca = on ? -2.f / card * up : 0.f;              // dL/dp = ca * y + cb
-  const float cb = on ? 2.f * I / (card * card) * up : 0.f;
+  float ca, cb;                                              // dL/dp = ca * y + cb
+  if (o.plain) {
+    const float I = sums[0], card = sums[1] + sums[2];
+    const bool on = sums[2] > 0.f && card > eps;
+    ca = on ? -2.f / card * up : 0.f;
+    cb = on ? 2.f * I / (card * card) * up : 0.f;
+  } else {
+    float a1[1], b1[1];
+    dice_coeffs<1>(sums, eps, up, o, a1, b1);
+    ca = a1[0]; cb = b1[0];
+  }
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    if (IGN && target[i] == ignore) {
+      if (!accumulate) dlogits[i] = 0.f;
+      continue;
+    }
     const float x = logits[i];
     const float p = expf(fminf(x, 0.f) - log1pf(expf(-fabsf(x))));
     const float v = (cb + ca * (float)target[i]) * p * (1.f - p);
@@ -1923,16 +1983,57 @@ extern "C" int64_t gdl_dice_loss_workspace(int B, int K, int64_t HW) {
   return (int64_t)dice_blocks((int64_t)B * HW) * 3 * K * sizeof(float);
 }
 
-extern "C" int gdl_dice_loss_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
-                                 float* sums, float* loss, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
+// gdl_dice_options (host) -> the kernels' arguments.  Null = smp's defaults.
+struct DiceHostOpt { bool ign; int64_t ignore; DiceCoef o; };
+static int dice_host_opt(const gdl_dice_options* opt, int K, const char* who, DiceHostOpt& h) {
+  const uint32_t all = K >= 32 ? 0xffffffffu : ((1u << K) - 1u);
+  h.ign = false; h.ignore = 0;
+  h.o.smooth = 0.f; h.o.cls = all; h.o.nsel = K; h.o.log_loss = 0; h.o.plain = 1;
+  if (!opt) return GDL_OK;
+  if (opt->num_classes < 0 || (opt->num_classes > 0 && !opt->classes)) {
+    gdl_set_error("%s: bad class list", who);
+    return GDL_ERR_INVALID;
+  }
+  if (opt->num_classes > 0) {
+    h.o.cls = 0;
+    for (int i = 0; i < opt->num_classes; ++i) {
+      const int c = opt->classes[i];
+      if (c < 0 || c >= K || ((h.o.cls >> c) & 1u)) {
+        gdl_set_error("%s: classes must be distinct indices in 0..%d (got %d)", who, K - 1, c);
+        return GDL_ERR_INVALID;
+      }
+      h.o.cls |= 1u << c;
+    }
+    h.o.nsel = opt->num_classes;
+  }
+  h.ign = opt->has_ignore_index != 0; h.ignore = opt->ignore_index;
+  h.o.smooth = opt->smooth; h.o.log_loss = opt->log_loss != 0;
+  h.o.plain = h.o.smooth == 0.f && !h.o.log_loss && h.o.cls == all;
+  return GDL_OK;
+}
+#define DICE_OPT(who, K)                                                      \
+  DiceHostOpt h;                                                              \
+  { const int st_ = dice_host_opt(opt, K, who, h); if (st_ != GDL_OK) return st_; }
+// launch `kernel<..., IGN>` with IGN = h.ign (two instantiations; IGN = false is the code without the test)
+#define IGN_SWITCH(...)                                                       \
+  if (h.ign) { constexpr bool IG = true; __VA_ARGS__; } else { constexpr bool IG = false; __VA_ARGS__; }
+
+extern "C" int gdl_dice_loss_opt_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
+                                     const gdl_dice_options* opt, float* sums, float* loss, float* ws, int64_t ws_bytes,
+                                     gdl_stream_t stream) {
   GDL_CHECK_ARG(logits && target && sums && loss && ws, "gdl_dice_loss_fwd: null pointer");
   GDL_CHECK_ARG(ws_bytes >= gdl_dice_loss_workspace(B, K, HW), "gdl_dice_loss_fwd: workspace too small");
+  DICE_OPT("gdl_dice_loss_fwd", K);
   const int nblk = dice_blocks((int64_t)B * HW);
   hipStream_t s = (hipStream_t)stream;
-  K_SWITCH(K, hipLaunchKernelGGL((dice_partial_kernel<KK>), dim3(nblk), dim3(256), 0, s, logits, target, B, HW, ws);
-              hipLaunchKernelGGL((dice_final_kernel<KK>), dim3(1), dim3(256), 0, s, ws, nblk, eps, sums, loss));
+  K_SWITCH(K, IGN_SWITCH(hipLaunchKernelGGL((dice_partial_kernel<KK, IG>), dim3(nblk), dim3(256), 0, s, logits, target, B, HW, ws, h.ignore));
+              hipLaunchKernelGGL((dice_final_kernel<KK>), dim3(1), dim3(256), 0, s, ws, nblk, eps, sums, loss, h.o));
   GDL_CHECK_LAUNCH("gdl_dice_loss_fwd");
   return GDL_OK;
+}
+extern "C" int gdl_dice_loss_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
+                                 float* sums, float* loss, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
+  return gdl_dice_loss_opt_fwd(logits, target, B, K, HW, eps, nullptr, sums, loss, ws, ws_bytes, stream);
 }
 
 // (four times the workgroups of dice_partial_kernel: the scattered 4-byte loads of the on-the-fly bilinear logit are a chain of L2
@@ -1948,19 +2049,25 @@ extern "C" int64_t gdl_dice_loss_lowres_workspace(int B, int K, int Ho, int Wo) 
 // Dice loss (multiclass) of bilinear(low -> [Ho, Wo]) against target [B, Ho, Wo] WITHOUT the full-resolution logits: low = the
 // [B, Hi, Wi, K] f32 map gdl_head_1x1 writes.  sums / loss as gdl_dice_loss_fwd; workspace of gdl_dice_loss_lowres_workspace(B, K, Ho,
 // Wo) bytes.  Upsampling factors up to 64 per direction.
-extern "C" int gdl_dice_loss_lowres_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
-                                        float* sums, float* loss, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
+extern "C" int gdl_dice_loss_lowres_opt_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo,
+                                            float eps, const gdl_dice_options* opt, float* sums, float* loss, float* ws,
+                                            int64_t ws_bytes, gdl_stream_t stream) {
   GDL_CHECK_ARG(low && target && sums && loss && ws, "gdl_dice_loss_lowres_fwd: null pointer");
   GDL_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi, "gdl_dice_loss_lowres_fwd: bad sizes (an upsample is expected)");
   GDL_CHECK_ARG((Ho + Hi - 1) / Hi <= DICE_LOWRES_MAX_FACTOR && (Wo + Wi - 1) / Wi <= DICE_LOWRES_MAX_FACTOR,
                 "gdl_dice_loss_lowres_fwd: upsampling factors above 64 are not supported");
   GDL_CHECK_ARG(ws_bytes >= gdl_dice_loss_lowres_workspace(B, K, Ho, Wo), "gdl_dice_loss_lowres_fwd: workspace too small");
+  DICE_OPT("gdl_dice_loss_lowres_fwd", K);
   const int nblk = dice_lowres_blocks((int64_t)B * Ho * Wo);
   hipStream_t s = (hipStream_t)stream;
-  K_SWITCH(K, hipLaunchKernelGGL((dice_lowres_partial_kernel<KK>), dim3(nblk), dim3(256), 0, s, low, target, B, Hi, Wi, Ho, Wo, ws);
-              hipLaunchKernelGGL((dice_final_kernel<KK>), dim3(1), dim3(256), 0, s, ws, nblk, eps, sums, loss));
+  K_SWITCH(K, IGN_SWITCH(hipLaunchKernelGGL((dice_lowres_partial_kernel<KK, IG>), dim3(nblk), dim3(256), 0, s, low, target, B, Hi, Wi, Ho, Wo, ws, h.ignore));
+              hipLaunchKernelGGL((dice_final_kernel<KK>), dim3(1), dim3(256), 0, s, ws, nblk, eps, sums, loss, h.o));
   GDL_CHECK_LAUNCH("gdl_dice_loss_lowres_fwd");
   return GDL_OK;
+}
+extern "C" int gdl_dice_loss_lowres_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
+                                        float* sums, float* loss, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
+  return gdl_dice_loss_lowres_opt_fwd(low, target, B, K, Hi, Wi, Ho, Wo, eps, nullptr, sums, loss, ws, ws_bytes, stream);
 }
 
 static std::atomic<int> g_dice_tiled{1};
@@ -1983,13 +2090,14 @@ extern "C" int64_t gdl_dice_loss_lowres_bwd_workspace(int B, int K, int Hi, int 
 
 // d loss / d low [B, Hi, Wi, K] (f32, overwritten) from the sums of the forward; upstream (device scalar, may be null) * grad_scale
 // multiplies the gradient.  ws: gdl_dice_loss_lowres_bwd_workspace() bytes (may be null when that is 0).
-extern "C" int gdl_dice_loss_lowres_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
-                                        const float* sums, const float* upstream, float grad_scale, float* dlow, float* ws,
-                                        int64_t ws_bytes, gdl_stream_t stream) {
+extern "C" int gdl_dice_loss_lowres_opt_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo,
+                                            float eps, const gdl_dice_options* opt, const float* sums, const float* upstream,
+                                            float grad_scale, float* dlow, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
   GDL_CHECK_ARG(low && target && sums && dlow, "gdl_dice_loss_lowres_bwd: null pointer");
   GDL_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi, "gdl_dice_loss_lowres_bwd: bad sizes");
   GDL_CHECK_ARG((Ho + Hi - 1) / Hi <= DICE_LOWRES_MAX_FACTOR && (Wo + Wi - 1) / Wi <= DICE_LOWRES_MAX_FACTOR,
                 "gdl_dice_loss_lowres_bwd: upsampling factors above 64 are not supported");
+  DICE_OPT("gdl_dice_loss_lowres_bwd", K);
   {
     int ny, nx;
     const int64_t need = gdl_dice_loss_lowres_bwd_workspace(B, K, Hi, Wi, Ho, Wo);
@@ -1998,14 +2106,14 @@ extern "C" int gdl_dice_loss_lowres_bwd(const float* low, const int64_t* target,
       a.low = low; a.target = target; a.sums = sums; a.upstream = upstream; a.ws = ws; a.dlow = dlow;
       a.B = B; a.Hi = Hi; a.Wi = Wi; a.Ho = Ho; a.Wo = Wo;
       a.tiles_y = (Ho + DT_H - 1) / DT_H; a.tiles_x = (Wo + DT_W - 1) / DT_W; a.ny_max = ny; a.nx_max = nx;
-      a.eps = eps; a.grad_scale = grad_scale;
+      a.eps = eps; a.grad_scale = grad_scale; a.ignore = h.ignore; a.o = h.o;
       const unsigned tiles = (unsigned)(B * a.tiles_y * a.tiles_x);
       const int64_t total = (int64_t)B * Hi * Wi;
       hipStream_t st = (hipStream_t)stream;
       K_SWITCH(K, if (KK <= 8) {
                     const size_t lds = ((size_t)KK * DT_H * DT_W + (size_t)KK * ny * (DT_W + 1) + (size_t)ny * DT_H + (size_t)nx * DT_W) * sizeof(float);
-                    GDL_SET_MAX_LDS_ONCE((dice_lowres_bwd_tile_kernel<(KK <= 8 ? KK : 8)>), 160 * 1024);
-                    hipLaunchKernelGGL((dice_lowres_bwd_tile_kernel<(KK <= 8 ? KK : 8)>), dim3(tiles), dim3(DT_T), lds, st, a);
+                    IGN_SWITCH(GDL_SET_MAX_LDS_ONCE((dice_lowres_bwd_tile_kernel<(KK <= 8 ? KK : 8), IG>), 160 * 1024);
+                               hipLaunchKernelGGL((dice_lowres_bwd_tile_kernel<(KK <= 8 ? KK : 8), IG>), dim3(tiles), dim3(DT_T), lds, st, a));
                     hipLaunchKernelGGL((dice_lowres_bwd_reduce_kernel<(KK <= 8 ? KK : 8)>), dim3(grid_for(total)), dim3(256), 0, st, a);
                   });
       GDL_CHECK_LAUNCH("gdl_dice_loss_lowres_bwd");
@@ -2013,42 +2121,66 @@ extern "C" int gdl_dice_loss_lowres_bwd(const float* low, const int64_t* target,
     }
   }
   const int64_t total = (int64_t)B * Hi * Wi;
-  K_SWITCH(K, hipLaunchKernelGGL((dice_lowres_bwd_kernel<KK>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, low,
-                                 target, B, Hi, Wi, Ho, Wo, sums, eps, upstream, grad_scale, dlow));
+  K_SWITCH(K, IGN_SWITCH(hipLaunchKernelGGL((dice_lowres_bwd_kernel<KK, IG>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, low,
+                                            target, B, Hi, Wi, Ho, Wo, sums, eps, upstream, grad_scale, dlow, h.ignore, h.o)));
   GDL_CHECK_LAUNCH("gdl_dice_loss_lowres_bwd");
   return GDL_OK;
 }
+extern "C" int gdl_dice_loss_lowres_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
+                                        const float* sums, const float* upstream, float grad_scale, float* dlow, float* ws,
+                                        int64_t ws_bytes, gdl_stream_t stream) {
+  return gdl_dice_loss_lowres_opt_bwd(low, target, B, K, Hi, Wi, Ho, Wo, eps, nullptr, sums, upstream, grad_scale, dlow, ws, ws_bytes,
+                                      stream);
+}
 
-extern "C" int gdl_dice_loss_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
-                                 const float* sums, const float* upstream, float grad_scale, float* dlogits,
-                                 int accumulate, gdl_stream_t stream) {
+extern "C" int gdl_dice_loss_opt_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
+                                     const gdl_dice_options* opt, const float* sums, const float* upstream, float grad_scale,
+                                     float* dlogits, int accumulate, gdl_stream_t stream) {
   GDL_CHECK_ARG(logits && target && sums && dlogits, "gdl_dice_loss_bwd: null pointer");
+  DICE_OPT("gdl_dice_loss_bwd", K);
   const int64_t total = (int64_t)B * HW;
-  K_SWITCH(K, hipLaunchKernelGGL((dice_bwd_kernel<KK>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, logits, target, B, HW, sums, eps, upstream, grad_scale, dlogits, accumulate));
+  K_SWITCH(K, IGN_SWITCH(hipLaunchKernelGGL((dice_bwd_kernel<KK, IG>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, logits, target, B, HW, sums, eps, upstream, grad_scale, dlogits, accumulate, h.ignore, h.o)));
   GDL_CHECK_LAUNCH("gdl_dice_loss_bwd");
   return GDL_OK;
 }
+extern "C" int gdl_dice_loss_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
+                                 const float* sums, const float* upstream, float grad_scale, float* dlogits,
+                                 int accumulate, gdl_stream_t stream) {
+  return gdl_dice_loss_opt_bwd(logits, target, B, K, HW, eps, nullptr, sums, upstream, grad_scale, dlogits, accumulate, stream);
+}
 
-extern "C" int gdl_dice_binary_loss_fwd(const float* logits, const int64_t* target, int64_t total, float eps,
-                                        float* sums, float* loss, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
+extern "C" int gdl_dice_binary_loss_opt_fwd(const float* logits, const int64_t* target, int64_t total, float eps,
+                                            const gdl_dice_options* opt, float* sums, float* loss, float* ws, int64_t ws_bytes,
+                                            gdl_stream_t stream) {
   GDL_CHECK_ARG(logits && target && sums && loss && ws, "gdl_dice_binary_loss_fwd: null pointer");
   const int nblk = dice_blocks(total);
   GDL_CHECK_ARG(ws_bytes >= (int64_t)nblk * 3 * (int64_t)sizeof(float), "gdl_dice_binary_loss_fwd: workspace too small");
+  DICE_OPT("gdl_dice_binary_loss_fwd", 1);
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(dice_binary_partial_kernel, dim3(nblk), dim3(256), 0, s, logits, target, total, ws);
-  hipLaunchKernelGGL((dice_final_kernel<1>), dim3(1), dim3(256), 0, s, ws, nblk, eps, sums, loss);
+  IGN_SWITCH(hipLaunchKernelGGL((dice_binary_partial_kernel<IG>), dim3(nblk), dim3(256), 0, s, logits, target, total, ws, h.ignore));
+  hipLaunchKernelGGL((dice_final_kernel<1>), dim3(1), dim3(256), 0, s, ws, nblk, eps, sums, loss, h.o);
   GDL_CHECK_LAUNCH("gdl_dice_binary_loss_fwd");
   return GDL_OK;
 }
+extern "C" int gdl_dice_binary_loss_fwd(const float* logits, const int64_t* target, int64_t total, float eps,
+                                        float* sums, float* loss, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
+  return gdl_dice_binary_loss_opt_fwd(logits, target, total, eps, nullptr, sums, loss, ws, ws_bytes, stream);
+}
 
+extern "C" int gdl_dice_binary_loss_opt_bwd(const float* logits, const int64_t* target, int64_t total, float eps,
+                                            const gdl_dice_options* opt, const float* sums, const float* upstream,
+                                            float grad_scale, float* dlogits, int accumulate, gdl_stream_t stream) {
+  GDL_CHECK_ARG(logits && target && sums && dlogits, "gdl_dice_binary_loss_bwd: null pointer");
+  DICE_OPT("gdl_dice_binary_loss_bwd", 1);
+  IGN_SWITCH(hipLaunchKernelGGL((dice_binary_bwd_kernel<IG>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, logits, target,
+                                total, sums, eps, upstream, grad_scale, dlogits, accumulate, h.ignore, h.o));
+  GDL_CHECK_LAUNCH("gdl_dice_binary_loss_bwd");
+  return GDL_OK;
+}
 extern "C" int gdl_dice_binary_loss_bwd(const float* logits, const int64_t* target, int64_t total, float eps,
                                         const float* sums, const float* upstream, float grad_scale, float* dlogits,
                                         int accumulate, gdl_stream_t stream) {
-  GDL_CHECK_ARG(logits && target && sums && dlogits, "gdl_dice_binary_loss_bwd: null pointer");
-  hipLaunchKernelGGL(dice_binary_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, logits, target,
-                     total, sums, eps, upstream, grad_scale, dlogits, accumulate);
-  GDL_CHECK_LAUNCH("gdl_dice_binary_loss_bwd");
-  return GDL_OK;
+  return gdl_dice_binary_loss_opt_bwd(logits, target, total, eps, nullptr, sums, upstream, grad_scale, dlogits, accumulate, stream);
 }
 
 extern "C" int gdl_sumsq(const float* x, int64_t n, float* out_accum, gdl_stream_t stream) {

@@ -54,6 +54,15 @@ class WgradArgs(C.Structure):
     ]
 
 
+class DiceOptions(C.Structure):
+    """Mirror of gdl_dice_options (include/gdlhip.h)."""
+
+    _fields_ = [
+        ("has_ignore_index", c_i), ("ignore_index", c_l), ("smooth", c_f), ("log_loss", c_i),
+        ("classes", C.POINTER(c_i)), ("num_classes", c_i),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/gdlhip.h
 SIGNATURES = {
     "gdl_version": (c_i, []),
@@ -158,10 +167,14 @@ SIGNATURES = {
     "gdl_dice_loss_workspace": (c_l, [c_i, c_i, c_l]),
     "gdl_dice_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_l, c_f, c_p, c_p, c_p, c_l, c_p]),
     "gdl_dice_loss_bwd": (c_i, [c_p, c_p, c_i, c_i, c_l, c_f, c_p, c_p, c_f, c_p, c_i, c_p]),
+    "gdl_dice_loss_opt_fwd": (c_i, [c_p, c_p, c_i, c_i, c_l, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_dice_loss_opt_bwd": (c_i, [c_p, c_p, c_i, c_i, c_l, c_f, c_p, c_p, c_p, c_f, c_p, c_i, c_p]),
     "gdl_dice_loss_lowres_workspace": (c_l, [c_i, c_i, c_i, c_i]),
     "gdl_dice_loss_lowres_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_l, c_p]),
     "gdl_dice_loss_lowres_bwd_workspace": (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),
     "gdl_dice_loss_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_f, c_p, c_p, c_l, c_p]),
+    "gdl_dice_loss_lowres_opt_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_dice_loss_lowres_opt_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_f, c_p, c_p, c_l, c_p]),
     "gdl_pad_nhwc": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_p, c_i, c_i, c_i, c_p]),
     "gdl_subpix4_weights": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     "gdl_convt2x2_pack": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
@@ -174,6 +187,8 @@ SIGNATURES = {
                                    c_p]),
     "gdl_dice_binary_loss_fwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_l, c_p]),
     "gdl_dice_binary_loss_bwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_f, c_p, c_i, c_p]),
+    "gdl_dice_binary_loss_opt_fwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_dice_binary_loss_opt_bwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_f, c_p, c_i, c_p]),
     "gdl_sumsq": (c_i, [c_p, c_l, c_p, c_p]),
     "gdl_clip_coef": (c_i, [c_p, c_f, c_p, c_p]),
     "gdl_multi_sumsq": (c_i, [c_p, c_i, c_p, c_p]),

@@ -8,6 +8,7 @@ reference's ``loss.backward()`` / DDP hooks keep working unchanged.
 from __future__ import annotations
 
 import contextlib
+import math
 import os
 
 import logging
@@ -1247,58 +1248,70 @@ def head_logits(feat: Tensor, conv: nn.Conv2d, size, chan_scale: Tensor | None =
 
 
 class _DiceLoss(Function):
-    """smp DiceLoss(mode='multiclass') (configs/dofa_config_RGB.yaml:58-61)."""
+    """smp DiceLoss(mode='multiclass') (configs/dofa_config_RGB.yaml:58-61); ``options``: ops.DiceOptions or None (defaults)."""
 
     @staticmethod
-    def forward(ctx, logits, target, eps):
-        loss, sums = ops.dice_loss_fwd(logits, target, eps)
+    def forward(ctx, logits, target, eps, options=None):
+        loss, sums = ops.dice_loss_fwd(logits, target, eps, options=options)
         ctx.save_for_backward(logits, target, sums)
-        ctx.eps = eps
+        ctx.eps, ctx.options = eps, options
         return loss
 
     @staticmethod
     def backward(ctx, g):
         logits, target, sums = ctx.saved_tensors
-        return ops.dice_loss_bwd(logits, target, sums, g.contiguous().float(), 1.0, ctx.eps), None, None
+        return ops.dice_loss_bwd(logits, target, sums, g.contiguous().float(), 1.0, ctx.eps, options=ctx.options), None, None, None
 
 
 class _DiceLowres(Function):
     """smp DiceLoss(mode='multiclass') of bilinear(low -> size), forward and backward from the low-resolution map."""
 
     @staticmethod
-    def forward(ctx, low, target, size, eps):
-        loss, sums = ops.dice_loss_lowres_fwd(low, target, size, eps)
+    def forward(ctx, low, target, size, eps, options=None):
+        loss, sums = ops.dice_loss_lowres_fwd(low, target, size, eps, options=options)
         ctx.save_for_backward(low, target, sums)
-        ctx.size, ctx.eps = size, eps
+        ctx.size, ctx.eps, ctx.options = size, eps, options
         return loss
 
     @staticmethod
     def backward(ctx, g):
         low, target, sums = ctx.saved_tensors
-        return ops.dice_loss_lowres_bwd(low, target, ctx.size, sums, g.contiguous().float(), 1.0, ctx.eps), None, None, None
+        dlow = ops.dice_loss_lowres_bwd(low, target, ctx.size, sums, g.contiguous().float(), 1.0, ctx.eps, options=ctx.options)
+        return dlow, None, None, None, None
 
 
 class _DiceBinaryLoss(Function):
     """smp DiceLoss(mode='binary') (configs/unetplus_config_RGB.yaml:40-47, num_classes 1)."""
 
     @staticmethod
-    def forward(ctx, logits, target, eps):
-        loss, sums = ops.dice_binary_loss_fwd(logits, target, eps)
+    def forward(ctx, logits, target, eps, options=None):
+        loss, sums = ops.dice_binary_loss_fwd(logits, target, eps, options=options)
         ctx.save_for_backward(logits, target, sums)
-        ctx.eps = eps
+        ctx.eps, ctx.options = eps, options
         return loss
 
     @staticmethod
     def backward(ctx, g):
         logits, target, sums = ctx.saved_tensors
-        return ops.dice_binary_loss_bwd(logits, target, sums, g.contiguous().float(), 1.0, ctx.eps), None, None
+        return (ops.dice_binary_loss_bwd(logits, target, sums, g.contiguous().float(), 1.0, ctx.eps, options=ctx.options),
+                None, None, None)
 
 
 class DiceLoss(nn.Module):
-    """Drop-in for ``segmentation_models_pytorch.losses.DiceLoss`` in the two modes the reference's configs use:
-    ``mode="multiclass"`` (configs/dofa_config_RGB.yaml:58-61, segformer) and ``mode="binary"``
-    (configs/unetplus_config_RGB.yaml, ``num_classes: 1``); ``smooth=0``, ``ignore_index=None``, ``from_logits=True``,
-    ``log_loss=False``, ``classes=None`` (smp's defaults, which are also what the configs pass)."""
+    """Drop-in for ``segmentation_models_pytorch.losses.DiceLoss`` (smp 0.5.0 losses/dice.py) in the two modes the reference's
+    configs use: ``mode="multiclass"`` (configs/dofa_config_RGB.yaml:58-61, segformer) and ``mode="binary"``
+    (configs/unetplus_config_RGB.yaml, ``num_classes: 1``), with smp's constructor options evaluated inside the HIP kernels:
+
+    - ``ignore_index`` (any int, e.g. 255 or -1): pixels whose target equals it are left out of every sum and get a zero gradient;
+    - ``smooth``: ``score_k = (2 I_k + smooth) / max(P_k + Y_k + smooth, eps)``;
+    - ``log_loss``: ``-log(max(score_k, eps))`` instead of ``1 - score_k``;
+    - ``classes``: the mean runs over the listed classes only (distinct indices in ``0..K-1``, checked at the first forward, when
+      ``K`` is known; binary mode takes ``None`` or ``[0]``).
+
+    A class without a valid (not ignored) pixel in the batch contributes 0.  A target value outside ``0..K-1`` that is not
+    ``ignore_index`` matches no class while its probabilities still count in the denominators (unchanged behaviour).  With every
+    option at its default the plain kernels run and the results are bit-identical to earlier builds.  ``from_logits=False`` is
+    not implemented and raises."""
 
     def __init__(self, mode: str = "multiclass", classes=None, log_loss: bool = False, from_logits: bool = True,
                  smooth: float = 0.0, ignore_index=None, eps: float = 1e-7) -> None:
@@ -1306,11 +1319,31 @@ class DiceLoss(nn.Module):
         if mode not in ("multiclass", "binary"):
             msg = f"gdlhip DiceLoss implements mode='multiclass' and mode='binary' (got {mode!r})"
             raise NotImplementedError(msg)
-        if classes is not None or log_loss or not from_logits or smooth != 0.0 or ignore_index is not None:
-            msg = ("gdlhip DiceLoss implements smp's defaults (classes=None, log_loss=False, from_logits=True, "
-                   "smooth=0, ignore_index=None), which are what the reference's configs use")
-            raise NotImplementedError(msg)
+        if not from_logits:
+            raise NotImplementedError("gdlhip DiceLoss takes logits (from_logits=True); from_logits=False is not implemented")
+        if classes is not None:
+            classes = tuple(int(c) for c in classes)
+            if len(classes) == 0 or len(set(classes)) != len(classes) or min(classes) < 0:
+                raise ValueError(f"DiceLoss: classes must be a non-empty list of distinct class indices >= 0 (got {classes})")
+            if mode == "binary" and classes != (0,):
+                raise ValueError(f"DiceLoss(binary) has the single class 0: classes must be None or [0] (got {list(classes)})")
+        if ignore_index is not None:
+            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
+                raise ValueError(f"DiceLoss: ignore_index must be an int64 value or None (got {ignore_index!r})")
+            ignore_index = int(ignore_index)
+        smooth = float(smooth)
+        if not math.isfinite(smooth):
+            raise ValueError(f"DiceLoss: smooth must be finite (got {smooth})")
         self.mode, self.eps = mode, eps
+        self.classes, self.log_loss, self.smooth, self.ignore_index = classes, bool(log_loss), smooth, ignore_index
+        # None = smp's defaults: the plain entry points
+        self.options = None
+        if classes is not None or self.log_loss or smooth != 0.0 or ignore_index is not None:
+            self.options = ops.DiceOptions(ignore_index, smooth, self.log_loss, classes)
+
+    def _check_classes(self, K: int) -> None:
+        if self.classes is not None and max(self.classes) >= K:
+            raise ValueError(f"DiceLoss: classes {list(self.classes)} out of range for {K} classes")
 
     def forward(self, y_pred, y_true: Tensor) -> Tensor:
         if isinstance(y_pred, LowresLogits):
@@ -1319,7 +1352,8 @@ class DiceLoss(nn.Module):
             yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
             if (self.mode == "multiclass" and FUSE_LOWRES_DICE and ops.dice_lowres_ok(y_pred.low, size)
                     and y_pred.low.dtype == torch.float32 and tuple(yt.shape[1:]) == size):
-                return _DiceLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.eps)
+                self._check_classes(y_pred.low.shape[3])
+                return _DiceLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.eps, self.options)
             y_pred = y_pred.materialise()
         if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
             y_pred = y_pred.float().contiguous()
@@ -1327,10 +1361,11 @@ class DiceLoss(nn.Module):
             if y_pred.shape[0] != y_true.shape[0] or y_pred.numel() != y_true.numel():
                 msg = f"DiceLoss(binary): y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} do not match"
                 raise ValueError(msg)
-            return _DiceBinaryLoss.apply(y_pred, y_true.long().contiguous(), self.eps)
+            return _DiceBinaryLoss.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
         if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
             y_true = y_true[:, 0]          # smp views the target as [B, -1]: an un-squeezed [B,1,H,W] mask is the same
-        return _DiceLoss.apply(y_pred, y_true.long().contiguous(), self.eps)
+        self._check_classes(y_pred.shape[1])
+        return _DiceLoss.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
 
 
 def predict_mask(logits) -> Tensor:

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import torch
 from torch import Tensor
@@ -1781,7 +1782,27 @@ def iou_counts(pred: Tensor, target: Tensor, num_classes: int) -> Tensor:
     return counts
 
 
-def dice_loss_fwd(logits: Tensor, target: Tensor, eps: float = 1e-7):
+class DiceOptions(NamedTuple):
+    """The constructor options of smp's DiceLoss that the gdl_dice_*_opt_* entry points take (gdl_dice_options in
+    include/gdlhip.h): ``ignore_index`` (any int64, or None), ``smooth``, ``log_loss``, ``classes`` (a tuple of distinct class
+    indices, or None for all)."""
+
+    ignore_index: int | None = None
+    smooth: float = 0.0
+    log_loss: bool = False
+    classes: tuple | None = None
+
+    def c_arg(self):
+        """(pointer for the C call, objects that must stay alive during it)"""
+        arr = (C.c_int * len(self.classes))(*self.classes) if self.classes else None
+        o = _lib.DiceOptions(int(self.ignore_index is not None), int(self.ignore_index or 0), float(self.smooth),
+                             int(bool(self.log_loss)), C.cast(arr, C.POINTER(C.c_int)) if arr is not None else None,
+                             len(self.classes) if self.classes else 0)
+        return C.addressof(o), (o, arr)
+
+
+def dice_loss_fwd(logits: Tensor, target: Tensor, eps: float = 1e-7, options: DiceOptions | None = None):
+    """(loss, sums) of smp DiceLoss(mode="multiclass"); ``options`` None = smp's defaults through the plain entry point."""
     _need_cuda(logits, target)
     if logits.dtype != torch.float32 or not logits.is_contiguous():
         raise ValueError("dice_loss: contiguous f32 NCHW logits expected")
@@ -1793,20 +1814,31 @@ def dice_loss_fwd(logits: Tensor, target: Tensor, eps: float = 1e-7):
     lib = _lib.load()
     nbytes = lib.gdl_dice_loss_workspace(B, K, H * W)
     ws = torch.empty(nbytes // 4, device=logits.device, dtype=torch.float32)
-    check(lib.gdl_dice_loss_fwd(_p(logits), _p(target), B, K, H * W, eps, _p(sums), _p(loss), _p(ws),
-                                nbytes, _stream()), "gdl_dice_loss_fwd")
+    if options is None:
+        check(lib.gdl_dice_loss_fwd(_p(logits), _p(target), B, K, H * W, eps, _p(sums), _p(loss), _p(ws),
+                                    nbytes, _stream()), "gdl_dice_loss_fwd")
+    else:
+        opt, keep = options.c_arg()
+        check(lib.gdl_dice_loss_opt_fwd(_p(logits), _p(target), B, K, H * W, eps, opt, _p(sums), _p(loss), _p(ws),
+                                        nbytes, _stream()), "gdl_dice_loss_opt_fwd")
     return loss, sums
 
 
 def dice_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream: Tensor | None,
                   grad_scale: float = 1.0, eps: float = 1e-7, out: Tensor | None = None,
-                  accumulate: bool = False) -> Tensor:
+                  accumulate: bool = False, options: DiceOptions | None = None) -> Tensor:
     B, K, H, W = logits.shape
     if out is None:
         out = torch.empty_like(logits)
-    check(_lib.load().gdl_dice_loss_bwd(_p(logits), _p(target), B, K, H * W, eps, _p(sums),
-                                        _p(upstream), grad_scale, _p(out), int(accumulate),
-                                        _stream()), "gdl_dice_loss_bwd")
+    if options is None:
+        check(_lib.load().gdl_dice_loss_bwd(_p(logits), _p(target), B, K, H * W, eps, _p(sums),
+                                            _p(upstream), grad_scale, _p(out), int(accumulate),
+                                            _stream()), "gdl_dice_loss_bwd")
+    else:
+        opt, keep = options.c_arg()
+        check(_lib.load().gdl_dice_loss_opt_bwd(_p(logits), _p(target), B, K, H * W, eps, opt, _p(sums),
+                                                _p(upstream), grad_scale, _p(out), int(accumulate),
+                                                _stream()), "gdl_dice_loss_opt_bwd")
     return out
 
 
@@ -1819,7 +1851,8 @@ def dice_lowres_ok(low: Tensor, size: tuple[int, int]) -> bool:
     return size[0] >= hi and size[1] >= wi and -(-size[0] // hi) <= 64 and -(-size[1] // wi) <= 64
 
 
-def dice_loss_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], eps: float = 1e-7):
+def dice_loss_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], eps: float = 1e-7,
+                         options: DiceOptions | None = None):
     """Dice(multiclass) of bilinear(low -> size) vs target [B, H, W] without the full-resolution logits: (loss, sums)."""
     _need_cuda(low, target)
     if low.dtype != torch.float32 or not low.is_contiguous() or low.dim() != 4:
@@ -1832,24 +1865,34 @@ def dice_loss_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], eps
     lib = _lib.load()
     nbytes = lib.gdl_dice_loss_lowres_workspace(B, K, size[0], size[1])
     ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32)
-    check(lib.gdl_dice_loss_lowres_fwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, _p(sums), _p(loss), _p(ws), nbytes,
-                                       _stream()), "gdl_dice_loss_lowres_fwd")
+    if options is None:
+        check(lib.gdl_dice_loss_lowres_fwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, _p(sums), _p(loss), _p(ws), nbytes,
+                                           _stream()), "gdl_dice_loss_lowres_fwd")
+    else:
+        opt, keep = options.c_arg()
+        check(lib.gdl_dice_loss_lowres_opt_fwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, opt, _p(sums), _p(loss),
+                                               _p(ws), nbytes, _stream()), "gdl_dice_loss_lowres_opt_fwd")
     return loss, sums
 
 
 def dice_loss_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], sums: Tensor, upstream: Tensor | None,
-                         grad_scale: float = 1.0, eps: float = 1e-7) -> Tensor:
+                         grad_scale: float = 1.0, eps: float = 1e-7, options: DiceOptions | None = None) -> Tensor:
     B, Hi, Wi, K = low.shape
     dlow = torch.empty_like(low)
     lib = _lib.load()
     nbytes = lib.gdl_dice_loss_lowres_bwd_workspace(B, K, Hi, Wi, size[0], size[1])
     ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
-    check(lib.gdl_dice_loss_lowres_bwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, _p(sums), _p(upstream),
-                                       grad_scale, _p(dlow), _p(ws), nbytes, _stream()), "gdl_dice_loss_lowres_bwd")
+    if options is None:
+        check(lib.gdl_dice_loss_lowres_bwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, _p(sums), _p(upstream),
+                                           grad_scale, _p(dlow), _p(ws), nbytes, _stream()), "gdl_dice_loss_lowres_bwd")
+    else:
+        opt, keep = options.c_arg()
+        check(lib.gdl_dice_loss_lowres_opt_bwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, opt, _p(sums), _p(upstream),
+                                               grad_scale, _p(dlow), _p(ws), nbytes, _stream()), "gdl_dice_loss_lowres_opt_bwd")
     return dlow
 
 
-def dice_binary_loss_fwd(logits: Tensor, target: Tensor, eps: float = 1e-7):
+def dice_binary_loss_fwd(logits: Tensor, target: Tensor, eps: float = 1e-7, options: DiceOptions | None = None):
     """smp DiceLoss(mode="binary"): logits [B,1,H,W] (or any shape) f32, target of the same numel, int64 0/1."""
     _need_cuda(logits, target)
     if logits.dtype != torch.float32 or not logits.is_contiguous():
@@ -1862,16 +1905,26 @@ def dice_binary_loss_fwd(logits: Tensor, target: Tensor, eps: float = 1e-7):
     lib = _lib.load()
     nbytes = lib.gdl_dice_loss_workspace(1, 1, total)
     ws = torch.empty(nbytes // 4, device=logits.device, dtype=torch.float32)
-    check(lib.gdl_dice_binary_loss_fwd(_p(logits), _p(target), total, eps, _p(sums), _p(loss), _p(ws), nbytes,
-                                       _stream()), "gdl_dice_binary_loss_fwd")
+    if options is None:
+        check(lib.gdl_dice_binary_loss_fwd(_p(logits), _p(target), total, eps, _p(sums), _p(loss), _p(ws), nbytes,
+                                           _stream()), "gdl_dice_binary_loss_fwd")
+    else:
+        opt, keep = options.c_arg()
+        check(lib.gdl_dice_binary_loss_opt_fwd(_p(logits), _p(target), total, eps, opt, _p(sums), _p(loss), _p(ws), nbytes,
+                                               _stream()), "gdl_dice_binary_loss_opt_fwd")
     return loss, sums
 
 
 def dice_binary_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream: Tensor | None,
-                         grad_scale: float = 1.0, eps: float = 1e-7) -> Tensor:
+                         grad_scale: float = 1.0, eps: float = 1e-7, options: DiceOptions | None = None) -> Tensor:
     out = torch.empty_like(logits)
-    check(_lib.load().gdl_dice_binary_loss_bwd(_p(logits), _p(target), logits.numel(), eps, _p(sums), _p(upstream),
-                                               grad_scale, _p(out), 0, _stream()), "gdl_dice_binary_loss_bwd")
+    if options is None:
+        check(_lib.load().gdl_dice_binary_loss_bwd(_p(logits), _p(target), logits.numel(), eps, _p(sums), _p(upstream),
+                                                   grad_scale, _p(out), 0, _stream()), "gdl_dice_binary_loss_bwd")
+    else:
+        opt, keep = options.c_arg()
+        check(_lib.load().gdl_dice_binary_loss_opt_bwd(_p(logits), _p(target), logits.numel(), eps, opt, _p(sums), _p(upstream),
+                                                       grad_scale, _p(out), 0, _stream()), "gdl_dice_binary_loss_opt_bwd")
     return out
 
 

@@ -499,6 +499,24 @@ int gdl_upsample_argmax(const float* low, int B, int Hi, int Wi, int K, int64_t*
                         gdl_stream_t stream);
 /* f.softmax(output, dim=1) (K > 1) / f.sigmoid (K == 1) of the exported inference model (tools/script_model.py:55-59) */
 int gdl_class_probs(const float* logits, int B, int K, int64_t HW, float* probs, gdl_stream_t stream);
+/* The constructor options of smp 0.5.0 DiceLoss (losses/dice.py) for the gdl_dice_*_opt_* entry points below; a null pointer
+ * means smp's defaults (the plain gdl_dice_* entry points).  Read on the host when the call is made.  With `valid` = (target !=
+ * ignore_index), compared as int64 (any value, negative ones included; all true without has_ignore_index):
+ *   I_k = sum valid p_k [y==k], P_k = sum valid p_k, Y_k = sum valid [y==k] over batch and pixels (binary: [y==k] is y itself);
+ *   score_k = (2 I_k + smooth) / max(P_k + Y_k + smooth, eps);  loss_k = 1 - score_k, or -log(max(score_k, eps)) with log_loss;
+ *   loss_k *= [Y_k > 0];  loss = mean of loss_k over `classes` (num_classes distinct indices in 0..K-1; num_classes == 0: all K).
+ * sums [3*K] = (I, P, Y) hold the masked sums; an ignored pixel's gradient is exactly 0 in every class.  A target outside 0..K-1
+ * that is not ignore_index matches no class but its p still counts in P (as without options).  With every field at its default
+ * the results are bit-identical to the plain entry points. */
+typedef struct {
+  int has_ignore_index;
+  int64_t ignore_index;
+  float smooth;
+  int log_loss;
+  const int* classes; /* host pointer; may be null when num_classes == 0 */
+  int num_classes;
+} gdl_dice_options;
+
 /* smp DiceLoss(mode="multiclass", smooth=0, eps=1e-7) forward+backward on NCHW f32 logits
  * (configs/dofa_config_RGB.yaml:58-61).  sums [3*K] = (intersection, sum p, count y)
  * is produced by fwd and consumed by bwd.  dlogits = upstream[0]*grad_scale*dL/dlogits. */
@@ -509,6 +527,14 @@ int gdl_dice_loss_fwd(const float* logits, const int64_t* target, int B, int K, 
 int gdl_dice_loss_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
                       const float* sums, const float* upstream, float grad_scale, float* dlogits,
                       int accumulate, gdl_stream_t stream);
+/* The same two calls with smp's constructor options (gdl_dice_options above: ignore_index, smooth, log_loss, classes); same
+ * workspace, same sums layout, same fixed summation order. */
+int gdl_dice_loss_opt_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
+                          const gdl_dice_options* opt, float* sums, float* loss, float* workspace, int64_t workspace_bytes,
+                          gdl_stream_t stream);
+int gdl_dice_loss_opt_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
+                          const gdl_dice_options* opt, const float* sums, const float* upstream, float grad_scale,
+                          float* dlogits, int accumulate, gdl_stream_t stream);
 /* The same loss WITHOUT the full-resolution logits (round 5): the reference's training step computes
  * DiceLoss(F.interpolate(head(x), size=image_size, mode="bilinear")) (dofa.py:89-105, segmentation_dofa.py:226-229) and only needs the
  * loss and its gradient.  low = the [B, Hi, Wi, K] f32 map of gdl_head_1x1; the bilinear logit of every [Ho, Wo] pixel is
@@ -524,6 +550,14 @@ int64_t gdl_dice_loss_lowres_bwd_workspace(int B, int K, int Hi, int Wi, int Ho,
 int gdl_dice_loss_lowres_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
                              const float* sums, const float* upstream, float grad_scale, float* dlow, float* ws, int64_t ws_bytes,
                              gdl_stream_t stream);
+/* ... with gdl_dice_options: ignored full-resolution pixels are left out of the sums and of the gather / tile backward, so a
+ * training step with ignore_index still never materialises the [B, K, Ho, Wo] logits.  Workspaces as above. */
+int gdl_dice_loss_lowres_opt_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
+                                 const gdl_dice_options* opt, float* sums, float* loss, float* ws, int64_t ws_bytes,
+                                 gdl_stream_t stream);
+int gdl_dice_loss_lowres_opt_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
+                                 const gdl_dice_options* opt, const float* sums, const float* upstream, float grad_scale,
+                                 float* dlow, float* ws, int64_t ws_bytes, gdl_stream_t stream);
 
 /* smp DiceLoss(mode="binary", smooth=0, eps=1e-7) on `total` = B*H*W logits of the single class (the reference's
  * UNet++ config: configs/unetplus_config_RGB.yaml:40-47 with num_classes 1; smp 0.5.0 losses/dice.py): p =
@@ -534,6 +568,13 @@ int gdl_dice_binary_loss_fwd(const float* logits, const int64_t* target, int64_t
 int gdl_dice_binary_loss_bwd(const float* logits, const int64_t* target, int64_t total, float eps,
                              const float* sums, const float* upstream, float grad_scale, float* dlogits,
                              int accumulate, gdl_stream_t stream);
+/* ... with gdl_dice_options (K = 1: `classes` may only be empty or {0}); an ignored pixel counts in none of the three sums. */
+int gdl_dice_binary_loss_opt_fwd(const float* logits, const int64_t* target, int64_t total, float eps,
+                                 const gdl_dice_options* opt, float* sums, float* loss, float* workspace,
+                                 int64_t workspace_bytes, gdl_stream_t stream);
+int gdl_dice_binary_loss_opt_bwd(const float* logits, const int64_t* target, int64_t total, float eps,
+                                 const gdl_dice_options* opt, const float* sums, const float* upstream, float grad_scale,
+                                 float* dlogits, int accumulate, gdl_stream_t stream);
 
 /* ---- fused bilinear x4 upsample -> 3x3 conv (multilevel_neck.py:157-158, scale 4) -------------------------------
  * gdl_pad_nhwc: NHWC border padding by (pad_h, pad_w), replicate (zero_mode 0) or zeros (1): out [B,H+2ph,W+2pw,C] dense.
