@@ -274,9 +274,15 @@ __global__ __launch_bounds__(256) void head_1x1_kernel(const void* __restrict__ 
 //   * the f32 weights live in registers as bf16 hi + lo fragments (w = hi + lo to 2^-17: f32-grade logits), two MFMAs per 32 channels;
 //   * lane (pixel j, group g) ends with classes 4g .. 4g+3 of its pixel: 4-float stores.
 // Dense bf16 features with C = 32 NKS and no Dropout2d scale; everything else takes the kernel above.
-template <int NKS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void head_1x1_mfma_kernel(const uint16_t* __restrict__ feat, int64_t P, const float* __restrict__ w,
-                                                            const float* __restrict__ bias, int K, float* __restrict__ out) {
+// BN (decoder tail): feat is the PRE-BatchNorm convolution output and the head's features z = bf16(relu(bn(feat))) are formed on the
+// way from the load registers into the LDS slot -- the f32 expression and the one bf16 rounding of bn_apply_kernel (norm.hip), so the
+// fragments are bit for bit what the head reads from bn_apply's output, which is then never written.  A lane's 16-byte pieces are
+// always the same eight channels (1024 % ROW == 0): 24 per-channel constants in registers.
+template <int NKS, bool BN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BN ? 2 : 3, BN ? 2 : 3))) void head_1x1_mfma_kernel(const uint16_t* __restrict__ feat, int64_t P, const float* __restrict__ w,
+                                                            const float* __restrict__ bias, int K, float* __restrict__ out,
+                                                            const float* __restrict__ mean, const float* __restrict__ var,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int relu) {
   constexpr int C = NKS * 32, ROW = C * 2, TILE = 16 * ROW;
   extern __shared__ __attribute__((aligned(16))) unsigned char hsm[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -301,6 +307,23 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   for (int r = 0; r < 4; ++r) bv[r] = (bias && 4 * g + r < K) ? bias[4 * g + r] : 0.f;
   const int64_t ntiles = (P + 15) / 16, stride = (int64_t)gridDim.x * 4;
   uint4 rg[NKS];
+  float mu[BN ? 8 : 1], sc[BN ? 8 : 1], be[BN ? 8 : 1];
+  if constexpr (BN) {
+    const int c0 = 8 * (lane % (ROW / 16));
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { mu[e] = mean[c0 + e]; sc[e] = rsqrtf(var[c0 + e] + eps) * gamma[c0 + e]; be[e] = beta[c0 + e]; }
+  }
+  auto bn_relu = [&](const uint4& r) {
+    const uint32_t in[4] = {r.x, r.y, r.z, r.w};
+    uint32_t o[4];
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      const float a = (__uint_as_float(in[h] << 16) - mu[2 * h]) * sc[2 * h] + be[2 * h];
+      const float b = (__uint_as_float(in[h] & 0xffff0000u) - mu[2 * h + 1]) * sc[2 * h + 1] + be[2 * h + 1];
+      o[h] = pack_bf16x2(relu ? fmaxf(a, 0.f) : a, relu ? fmaxf(b, 0.f) : b);
+    }
+    return make_uint4(o[0], o[1], o[2], o[3]);
+  };
   auto gload = [&](int64_t tile) {
     const unsigned char* base = (const unsigned char*)feat + tile * TILE;
 #pragma unroll
@@ -315,7 +338,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
     for (int u = 0; u < NKS; ++u) {
       const int off = u * 1024 + lane * 16, row = off / ROW, c = (off % ROW) >> 4;
-      *(uint4*)(st + row * ROW + ((c ^ (row & 15)) << 4)) = rg[u];
+      if constexpr (BN) *(uint4*)(st + row * ROW + ((c ^ (row & 15)) << 4)) = bn_relu(rg[u]);
+      else *(uint4*)(st + row * ROW + ((c ^ (row & 15)) << 4)) = rg[u];
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (wave-private slot: the LDS queue is in order, no barrier needed)
     if (t + stride < ntiles) gload(t + stride);
@@ -1824,10 +1848,11 @@ extern "C" int gdl_head_1x1(const void* feat, int dtype, int64_t P, int C, int64
   if (g_head_mfma.load(std::memory_order_relaxed) && dtype == GDL_BF16 && !chan_scale && f_sP == C && (C == 128 || C == 256) && K >= 1 &&
       K <= 16 && P >= 1024 && (uintptr_t)feat % 16 == 0) {
     const int64_t ntiles = (P + 15) / 16;
-    const int cap = 3 * gdl_num_cus();     // all workgroups resident at once (155 registers: three waves per SIMD), each wave walks its share
+    const int cap = 3 * gdl_num_cus();     // all workgroups resident at once (156 registers: three waves per SIMD), each wave walks its share
     const unsigned blocks = (unsigned)((ntiles + 3) / 4 < cap ? (ntiles + 3) / 4 : cap);
-    if (C == 256) hipLaunchKernelGGL((head_1x1_mfma_kernel<8>), dim3(blocks), dim3(256), 4 * 16 * 512, s, (const uint16_t*)feat, P, w, bias, K, out);
-    else hipLaunchKernelGGL((head_1x1_mfma_kernel<4>), dim3(blocks), dim3(256), 4 * 16 * 256, s, (const uint16_t*)feat, P, w, bias, K, out);
+    const float* none = nullptr;
+    if (C == 256) hipLaunchKernelGGL((head_1x1_mfma_kernel<8, false>), dim3(blocks), dim3(256), 4 * 16 * 512, s, (const uint16_t*)feat, P, w, bias, K, out, none, none, none, none, 0.f, 0);
+    else hipLaunchKernelGGL((head_1x1_mfma_kernel<4, false>), dim3(blocks), dim3(256), 4 * 16 * 256, s, (const uint16_t*)feat, P, w, bias, K, out, none, none, none, none, 0.f, 0);
     GDL_CHECK_LAUNCH("gdl_head_1x1(mfma)");
     return GDL_OK;
   }
@@ -1859,6 +1884,36 @@ extern "C" int gdl_head_1x1(const void* feat, int dtype, int64_t P, int C, int64
   K_SWITCH(K, if (dtype == GDL_BF16) hipLaunchKernelGGL((head_1x1_kernel<uint16_t, KK>), dim3(grid), dim3(256), 0, s, feat, P, C, f_sP, w, bias, chan_scale, pix_per_img, out);
               else hipLaunchKernelGGL((head_1x1_kernel<float, KK>), dim3(grid), dim3(256), 0, s, feat, P, C, f_sP, w, bias, chan_scale, pix_per_img, out));
   GDL_CHECK_LAUNCH("gdl_head_1x1");
+  return GDL_OK;
+}
+
+// The 256-channel head over relu?(bn(x)) without the normalised map (decoder tail in training): x is the saved convolution output,
+// the features are formed inside head_1x1_mfma_kernel<8, true>.  Dense bf16, C == 256, K <= 8, P >= 4096 (gdl_head_1x1_bn_ok: the
+// range of the backward that goes with it, gdl_bn_head_bwd_ok); every other shape is an error -- the caller runs gdl_bn_apply +
+// gdl_head_1x1 there.  gdl_debug_set_head_mfma does not reach this form (there is no wave-per-pixel kernel with BatchNorm on load).
+extern "C" int gdl_head_1x1_bn_ok(int dtype, int64_t P, int C, int K) {
+  return dtype == GDL_BF16 && C == 256 && K >= 1 && K <= 8 && P >= 4096;
+}
+
+extern "C" int gdl_head_1x1_bn(const void* x, int dtype, int64_t P, int C, const float* mean, const float* var, const float* gamma,
+                               const float* beta, float eps, int relu, const float* w, const float* bias, float* out, int K,
+                               gdl_stream_t stream) {
+  GDL_CHECK_ARG(x && mean && var && gamma && beta && w && out, "gdl_head_1x1_bn: null pointer");
+  GDL_CHECK_ARG(gdl_head_1x1_bn_ok(dtype, P, C, K) && (uintptr_t)x % 16 == 0,
+                "gdl_head_1x1_bn: needs dense 16-byte aligned bf16 features with C == 256, K <= 8, P >= 4096");
+  const int64_t ntiles = (P + 15) / 16;
+  const int cap = 2 * gdl_num_cus();       // all workgroups resident at once (two waves per SIMD), each wave walks its share
+  const unsigned blocks = (unsigned)((ntiles + 3) / 4 < cap ? (ntiles + 3) / 4 : cap);
+  hipLaunchKernelGGL((head_1x1_mfma_kernel<8, true>), dim3(blocks), dim3(256), 4 * 16 * 512, (hipStream_t)stream, (const uint16_t*)x, P, w,
+                     bias, K, out, mean, var, gamma, beta, eps, relu);
+  GDL_CHECK_LAUNCH("gdl_head_1x1_bn");
+  return GDL_OK;
+}
+
+// final reduction of head weight-gradient partial rows ws[nsplit][K + 1][C] written by another translation unit's kernel
+// (gdl_bn_head_bwd_reduce, norm.hip): the last launch of gdl_head_1x1_bwd
+int head_bwd_w_final_launch(const float* ws, int nsplit, int C, int K, float* dw, float* db, hipStream_t s) {
+  K_SWITCH(K, hipLaunchKernelGGL((head_1x1_bwd_w_final<KK>), dim3((KK * C + KK + 7) / 8), dim3(1024), 0, s, ws, nsplit, C, dw, db));
   return GDL_OK;
 }
 

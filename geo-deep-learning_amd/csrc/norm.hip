@@ -415,6 +415,198 @@ __global__ __launch_bounds__(256) void bn_bwd_dx(const void* __restrict__ x, con
   }
 }
 
+// ---------------------------------------------------------------- BatchNorm(+ReLU) backward under a 1x1 classifier head
+// Decoder tail in training: z = relu?(bn(x)) feeds only the K <= 8 class head, logits[p][k] = sum_c W[k][c] z[p][c] + b[k].  The
+// gradient of z is five fused multiply-adds per element of a [P][K] f32 tensor 1 / 50 the size of the map, so neither z nor dz is
+// ever stored: both backward passes re-form them from the saved convolution output x and dlogits, with the expressions (and the
+// bf16 roundings) of the kernels they replace --
+//   z  = bf16((x - mean) * (rstd gamma) + beta, relu)          bn_apply_kernel
+//   dz = bf16(fma chain over k of dlogit[k] * W[k][c])          head_1x1_bwd_feat8_kernel (misc.hip)
+// C == 256: thread t owns the eight channels 8 (t % 32) of pixel row t / 32 (the mapping of bn_bwd_partial8<256> and of
+// head_1x1_bwd_w_partial8), so the K x 8 head weights and the per-channel constants live in registers.
+template <int K>
+struct HeadDz {
+  float wr[K][8];
+  __device__ __forceinline__ void load(const float* __restrict__ w, int g) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float4 a = *(const float4*)(w + k * 256 + g * 8), b = *(const float4*)(w + k * 256 + g * 8 + 4);
+      wr[k][0] = a.x; wr[k][1] = a.y; wr[k][2] = a.z; wr[k][3] = a.w; wr[k][4] = b.x; wr[k][5] = b.y; wr[k][6] = b.z; wr[k][7] = b.w;
+    }
+  }
+  __device__ __forceinline__ void dz(const float (&gk)[K], float (&d)[8]) const {
+    float o[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o[e] = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = fmaf(gk[k], wr[k][e], o[e]);
+    }
+    unpack8(make_uint4(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])), d);
+  }
+};
+
+// pass 1: the BatchNorm sums of bn_bwd_partial8<256> AND the head's weight / bias gradient partials of head_1x1_bwd_w_partial8 in
+// one read of x.  Same pixel partition (nsplit contiguous ranges), same per-thread accumulation order and same in-block
+// reduction as those two kernels: ws_bn[nsplit][2][256] -> bn_bwd_final, ws_head[nsplit][K + 1][256] -> head_1x1_bwd_w_final.
+// (K = 5 wants 276 registers unconstrained -- one wave per SIMD; held to two, the VALU work of one wave hides the loads of the other)
+template <int K>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(K <= 5 ? 2 : 1))) void bn_head_bwd_partial8(const uint16_t* __restrict__ x, const float* __restrict__ dlog, int64_t P,
+                                                            const float* __restrict__ w, const float* __restrict__ mean,
+                                                            const float* __restrict__ var, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, float eps, int relu,
+                                                            float* __restrict__ ws_bn, float* __restrict__ ws_head) {
+  constexpr int C = 256, G = 32, R = 8;
+  __shared__ float red[2][256][9];
+  const int t = threadIdx.x, g = t % G, prow = t / G;
+  const int nsplit = gridDim.x;
+  const int64_t per = (P + nsplit - 1) / nsplit;
+  const int64_t p0 = per * blockIdx.x, p1 = p0 + per < P ? p0 + per : P;
+  HeadDz<K> hd;
+  hd.load(w, g);
+  float s[8], q[8], mu[8], rs[8], ga[8], be[8], acc[K][8], accb[K];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = 8 * g + j;
+    s[j] = 0.f; q[j] = 0.f;
+    mu[j] = mean[c]; rs[j] = rsqrtf(var[c] + eps); ga[j] = gamma[c]; be[j] = beta[c];
+  }
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    accb[k] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[k][j] = 0.f;
+  }
+  auto add = [&](const uint4& xv, const float (&gk)[K]) {
+    float v[8], d[8], z[8];
+    unpack8(xv, v);
+    hd.dz(gk, d);
+    float zf[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float xh = (v[j] - mu[j]) * rs[j];
+      const float gg = (relu && !(xh * ga[j] + be[j] > 0.f)) ? 0.f : d[j];
+      s[j] += gg; q[j] += gg * xh;
+      const float o = (v[j] - mu[j]) * (rs[j] * ga[j]) + be[j];
+      zf[j] = relu ? fmaxf(o, 0.f) : o;
+    }
+    unpack8(make_uint4(pack_bf16x2(zf[0], zf[1]), pack_bf16x2(zf[2], zf[3]), pack_bf16x2(zf[4], zf[5]), pack_bf16x2(zf[6], zf[7])), z);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      accb[k] += gk[k];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[k][j] = fmaf(gk[k], z[j], acc[k][j]);
+    }
+  };
+  constexpr int U = K <= 3 ? 4 : 2;     // rows in flight (four need more than the 256 registers of two waves per SIMD from K = 4 on);
+  int64_t p = p0 + prow;                // the rows are added one after the other either way: same sums
+  for (; p + (U - 1) * R < p1; p += U * R) {
+    uint4 xv[U];
+    float gk[U][K];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      xv[u] = *(const uint4*)(x + (p + (int64_t)u * R) * C + 8 * g);
+#pragma unroll
+      for (int k = 0; k < K; ++k) gk[u][k] = dlog[(p + (int64_t)u * R) * K + k];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) add(xv[u], gk[u]);
+  }
+  for (; p < p1; p += R) {
+    float gk[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) gk[k] = dlog[p * K + k];
+    add(*(const uint4*)(x + p * C + 8 * g), gk);
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { red[0][t][j] = s[j]; red[1][t][j] = q[j]; }
+  __syncthreads();
+  {
+    const int c = t;
+    float ss = 0.f, qq = 0.f;
+    for (int r = 0; r < R; ++r) { ss += red[0][r * G + (c >> 3)][c & 7]; qq += red[1][r * G + (c >> 3)][c & 7]; }
+    ws_bn[((int64_t)blockIdx.x * 2 + 0) * C + c] = ss;
+    ws_bn[((int64_t)blockIdx.x * 2 + 1) * C + c] = qq;
+  }
+  __syncthreads();
+  float* wsb = ws_head + (int64_t)blockIdx.x * (K + 1) * C;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[0][t][j] = acc[k][j];
+    red[0][t][8] = accb[k];
+    __syncthreads();
+    {
+      const int c = t;
+      float ss = 0.f;
+      for (int r = 0; r < R; ++r) ss += red[0][r * G + (c >> 3)][c & 7];
+      wsb[(int64_t)k * C + c] = ss;
+    }
+    if (t == 0) {
+      float sb = 0.f;
+      for (int r = 0; r < R; ++r) sb += red[0][r * G][8];
+      wsb[(int64_t)K * C + k] = sb;
+    }
+    __syncthreads();
+  }
+}
+
+// pass 2: dx = gamma rstd (dz' - dbeta / P - xhat dgamma / P) with dz' = dz [bn(x) > 0] -- the per-element expression of bn_bwd_dx
+// with dz re-formed from dlogits; dx may alias x (a thread reads an element before it writes it).  Grid-stride over pixel rows, four
+// rows requested before the first is used.
+template <int K>
+__global__ __launch_bounds__(256) void bn_head_bwd_dx8(const uint16_t* x, const float* __restrict__ dlog, uint16_t* dx, int64_t P,
+                                                       int64_t P_total, const float* __restrict__ w, const float* __restrict__ mean,
+                                                       const float* __restrict__ var, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, float eps, int relu,
+                                                       const float* __restrict__ dgamma, const float* __restrict__ dbeta) {
+  constexpr int C = 256, G = 32, R = 8;
+  const float invP = 1.0f / (float)P_total;
+  const int t = threadIdx.x, g = t % G, prow = t / G;
+  HeadDz<K> hd;
+  hd.load(w, g);
+  float mu[8], rs[8], ga[8], be[8], k1[8], k2[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = 8 * g + j;
+    mu[j] = mean[c]; rs[j] = rsqrtf(var[c] + eps); ga[j] = gamma[c]; be[j] = beta[c];
+    k1[j] = dbeta[c] * invP; k2[j] = dgamma[c] * invP;
+  }
+  auto one = [&](int64_t p, const uint4& xv, const float (&gk)[K]) {
+    float v[8], d[8];
+    unpack8(xv, v);
+    hd.dz(gk, d);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float xh = (v[j] - mu[j]) * rs[j];
+      const float gg = (relu && !(xh * ga[j] + be[j] > 0.f)) ? 0.f : d[j];
+      v[j] = ga[j] * rs[j] * (gg - k1[j] - xh * k2[j]);
+    }
+    *(uint4*)(dx + p * C + 8 * g) = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7]));
+  };
+  const int64_t step = (int64_t)gridDim.x * R;
+  int64_t p = (int64_t)blockIdx.x * R + prow;
+  for (; p + 3 * step < P; p += 4 * step) {
+    uint4 xv[4];
+    float gk[4][K];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      xv[u] = *(const uint4*)(x + (p + u * step) * C + 8 * g);
+#pragma unroll
+      for (int k = 0; k < K; ++k) gk[u][k] = dlog[(p + u * step) * K + k];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) one(p + u * step, xv[u], gk[u]);
+  }
+  for (; p < P; p += step) {
+    float gk[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) gk[k] = dlog[p * K + k];
+    one(p, *(const uint4*)(x + p * C + 8 * g), gk);
+  }
+}
+
 // ---------------------------------------------------------------- BatchNorm -> GELU (erf), NHWC [P][C]
 // UperNet scale_modules fpn1.1 / fpn1.2 (models/decoders/upernet.py:40-42: BatchNorm2d -> GELU between the two transposed
 // convolutions).  Same split as the ReLU kernels above -- apply | backward reduce -> [all-reduce] -> backward dx -- and the same
@@ -1002,6 +1194,70 @@ extern "C" int gdl_bn_bwd_dx(const void* x, const void* dy, void* dx, int dtype,
   GDL_CHECK_LAUNCH("gdl_bn_bwd_dx");
   return GDL_OK;
 }
+
+// BatchNorm(+ReLU) backward under a K <= 8 class 1x1 head, straight from the head's logit gradient (bn_head_bwd_partial8 /
+// bn_head_bwd_dx8): what gdl_head_1x1_bwd + gdl_bn_bwd_reduce + gdl_bn_bwd_dx compute, without dz or the normalised map in memory.
+// Dense 16-byte aligned bf16 x with C == 256, P >= 4096 (the shapes where those three take their 16-byte kernels), f32 head
+// weights w [K][256] 16-byte aligned.  Single-process statistics.  The A/B hooks of the kernels these replace (gdl_debug_set_bn_wide,
+// gdl_debug_set_head_mfma) do not reach here: there is one form of each pass, selected by the caller (GDL_FUSE_BN_TAIL in gdlhip/nn.py).
+// K goes through a switch of its own: misc.hip's K_SWITCH instantiates up to 16 classes, these kernels hold K x 8 weights per lane.
+int head_bwd_w_final_launch(const float* ws, int nsplit, int C, int K, float* dw, float* db, hipStream_t s);   // misc.hip
+
+extern "C" int gdl_bn_head_bwd_ok(int dtype, int64_t P, int C, int K) {
+  return dtype == GDL_BF16 && C == 256 && K >= 1 && K <= 8 && P >= 4096;
+}
+
+extern "C" int64_t gdl_bn_head_bwd_workspace(int64_t P, int C, int K) {
+  return (int64_t)bn_nsplit(P, C) * (2 + K + 1) * C * sizeof(float);
+}
+
+#define BN_HEAD_K_SWITCH(K, ...)                          \
+  switch (K) {                                            \
+    case 1: { constexpr int KK = 1; __VA_ARGS__; } break; \
+    case 2: { constexpr int KK = 2; __VA_ARGS__; } break; \
+    case 3: { constexpr int KK = 3; __VA_ARGS__; } break; \
+    case 4: { constexpr int KK = 4; __VA_ARGS__; } break; \
+    case 5: { constexpr int KK = 5; __VA_ARGS__; } break; \
+    case 6: { constexpr int KK = 6; __VA_ARGS__; } break; \
+    case 7: { constexpr int KK = 7; __VA_ARGS__; } break; \
+    case 8: { constexpr int KK = 8; __VA_ARGS__; } break; \
+    default: gdl_set_error("bn_head_bwd: K=%d unsupported (1..8)", K); return GDL_ERR_UNSUPPORTED; \
+  }
+
+extern "C" int gdl_bn_head_bwd_reduce(const void* x, int dtype, const float* dlog, int64_t P, int C, int K, const float* w,
+                                      const float* mean, const float* var, const float* gamma, const float* beta, float eps,
+                                      int relu, float* dgamma, float* dbeta, float* dw, float* db, float* ws, int64_t ws_bytes,
+                                      gdl_stream_t stream) {
+  GDL_CHECK_ARG(x && dlog && w && mean && var && gamma && beta && dgamma && dbeta && dw && ws, "gdl_bn_head_bwd_reduce: null pointer");
+  GDL_CHECK_ARG(gdl_bn_head_bwd_ok(dtype, P, C, K) && (uintptr_t)x % 16 == 0 && (uintptr_t)w % 16 == 0,
+                "gdl_bn_head_bwd_reduce: needs dense 16-byte aligned bf16 x with C == 256, K <= 8, P >= 4096");
+  GDL_CHECK_ARG(ws_bytes >= gdl_bn_head_bwd_workspace(P, C, K), "gdl_bn_head_bwd_reduce: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int nsplit = bn_nsplit(P, C);
+  float* ws_head = ws + (int64_t)nsplit * 2 * C;
+  BN_HEAD_K_SWITCH(K, hipLaunchKernelGGL((bn_head_bwd_partial8<KK>), dim3(nsplit), dim3(256), 0, s, (const uint16_t*)x, dlog, P, w, mean, var,
+                                         gamma, beta, eps, relu, ws, ws_head));
+  hipLaunchKernelGGL(bn_bwd_final, dim3((C + 3) / 4), dim3(BN_FINAL_T), 0, s, ws, nsplit, C, dgamma, dbeta);
+  (void)head_bwd_w_final_launch(ws_head, nsplit, C, K, dw, db, s);      // (cannot refuse: K was checked before the first launch)
+  GDL_CHECK_LAUNCH("gdl_bn_head_bwd_reduce");
+  return GDL_OK;
+}
+
+extern "C" int gdl_bn_head_bwd_dx(const void* x, int dtype, const float* dlog, void* dx, int64_t P, int C, int K, const float* w,
+                                  const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
+                                  const float* dgamma_sum, const float* dbeta_sum, int64_t P_total, gdl_stream_t stream) {
+  GDL_CHECK_ARG(x && dlog && dx && w && mean && var && gamma && beta && dgamma_sum && dbeta_sum && P_total > 0,
+                "gdl_bn_head_bwd_dx: bad arguments");
+  GDL_CHECK_ARG(gdl_bn_head_bwd_ok(dtype, P, C, K) && (uintptr_t)x % 16 == 0 && (uintptr_t)dx % 16 == 0 && (uintptr_t)w % 16 == 0,
+                "gdl_bn_head_bwd_dx: needs dense 16-byte aligned bf16 x / dx with C == 256, K <= 8, P >= 4096");
+  const int64_t rows = (P + 7) / 8;
+  const unsigned blocks = (unsigned)(rows < 2048 ? rows : 2048);
+  BN_HEAD_K_SWITCH(K, hipLaunchKernelGGL((bn_head_bwd_dx8<KK>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint16_t*)x, dlog,
+                                         (uint16_t*)dx, P, P_total, w, mean, var, gamma, beta, eps, relu, dgamma_sum, dbeta_sum));
+  GDL_CHECK_LAUNCH("gdl_bn_head_bwd_dx");
+  return GDL_OK;
+}
+#undef BN_HEAD_K_SWITCH
 
 // gdl_bn_bwd_dx for SyncBatchNorm: dgamma_sum / dbeta_sum are the all-reduced (global) sums and the global pixel count is read
 // from device memory (total_count: one f32, the count entry of the forward's all-reduced message).

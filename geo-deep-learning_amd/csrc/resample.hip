@@ -424,10 +424,17 @@ __global__ __launch_bounds__(256) void bilinear_fwd8_rows_kernel(const void* __r
 // those four -- loads them once and writes F x F outputs (the row kernel above loads four 16-byte pieces per 16 bytes stored:
 // 2.65 TB/s on a write-bound op).  Gaps -1 and Hi - 1 (Wi - 1) are the clamped borders with F / 2 rows (columns).  Same
 // source indices, weights and expression per output as bilinear_fwd8_rows_kernel: bit-identical results.
-template <int F>
+// BN (the top-down add of a TRAINING lateral): acc_src is the lateral's PRE-BatchNorm convolution output and every vector read from
+// it becomes bf16(relu?((x - mean) * (rstd gamma) + beta)) first -- bn_apply_kernel's f32 expression and its one bf16 rounding
+// (norm.hip), so the sum is bit for bit what bn_apply followed by this kernel gives and the normalised lateral is never written.
+// A thread's channels are fixed: 24 constants in registers.
+template <int F, bool BN>
 __global__ __launch_bounds__(256) void bilinear_fwd8_gap_kernel(const void* __restrict__ in, int Hi, int Wi, int C,
                                                                 int64_t isB, int64_t isH, int64_t isW, void* out,
-                                                                int64_t osB, int64_t osH, int64_t osW, const void* acc_src) {
+                                                                int64_t osB, int64_t osH, int64_t osW, const void* acc_src,
+                                                                const float* __restrict__ mean, const float* __restrict__ var,
+                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                float eps, int relu) {
   // acc_src: nullptr, `out` itself (out += result) or another map with out's strides (out = that + result: the FPN top-down add
   // without first copying the lateral into the output)
   const int cv = C / 8;
@@ -447,6 +454,11 @@ __global__ __launch_bounds__(256) void bilinear_fwd8_gap_kernel(const void* __re
   V8::ld(in, base + y0 * isH + x1 * isW, bb);
   V8::ld(in, base + y1 * isH + x0 * isW, cc);
   V8::ld(in, base + y1 * isH + x1 * isW, d);
+  float mu[BN ? 8 : 1], sc[BN ? 8 : 1], be[BN ? 8 : 1];
+  if constexpr (BN) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { mu[e] = mean[c + e]; sc[e] = rsqrtf(var[c + e] + eps) * gamma[c + e]; be[e] = beta[c + e]; }
+  }
 #pragma unroll
   for (int jy = 0; jy < F; ++jy) {
     const int oy = F * gy - F / 2 + jy;
@@ -467,6 +479,14 @@ __global__ __launch_bounds__(256) void bilinear_fwd8_gap_kernel(const void* __re
       else {
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = 0.f;
+      }
+      if constexpr (BN) {
+#pragma unroll
+        for (int e = 0; e < 8; e += 2) {
+          const float u = (o[e] - mu[e]) * sc[e] + be[e], v = (o[e + 1] - mu[e + 1]) * sc[e + 1] + be[e + 1];
+          const uint32_t z = pack_bf16x2(relu ? fmaxf(u, 0.f) : u, relu ? fmaxf(v, 0.f) : v);
+          o[e] = __uint_as_float(z << 16); o[e + 1] = __uint_as_float(z & 0xffff0000u);
+        }
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) o[e] += hy * (hx * a[e] + lx * bb[e]) + ly * (hx * cc[e] + lx * d[e]);
@@ -2667,8 +2687,9 @@ static int bilinear_fwd_impl(const void* in, int in_dtype, int B, int Hi, int Wi
     if (gap) {
       const dim3 grid((unsigned)(((Wi + 1) * (C / 8) + 255) / 256), (unsigned)(B * (Hi + 1)));
       const void* acc_src = base ? base : (accumulate ? out : nullptr);
-      if (fac == 2) hipLaunchKernelGGL(bilinear_fwd8_gap_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, in, Hi, Wi, C, isB, isH, isW, out, osB, osH, osW, acc_src);
-      else hipLaunchKernelGGL(bilinear_fwd8_gap_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, in, Hi, Wi, C, isB, isH, isW, out, osB, osH, osW, acc_src);
+      const float* none = nullptr;
+      if (fac == 2) hipLaunchKernelGGL((bilinear_fwd8_gap_kernel<2, false>), grid, dim3(256), 0, (hipStream_t)stream, in, Hi, Wi, C, isB, isH, isW, out, osB, osH, osW, acc_src, none, none, none, none, 0.f, 0);
+      else hipLaunchKernelGGL((bilinear_fwd8_gap_kernel<4, false>), grid, dim3(256), 0, (hipStream_t)stream, in, Hi, Wi, C, isB, isH, isW, out, osB, osH, osW, acc_src, none, none, none, none, 0.f, 0);
     } else if ((int64_t)B * Ho <= 65535 && g_flat_resample != 1)
       hipLaunchKernelGGL(bilinear_fwd8_rows_kernel, dim3((unsigned)((Wo * (C / 8) + 255) / 256), (unsigned)(B * Ho)), dim3(256), 0,
                          (hipStream_t)stream, in, Hi, Wi, C, isB, isH, isW, out, Ho, Wo, osB, osH, osW, accumulate);
@@ -2704,6 +2725,30 @@ extern "C" int gdl_bilinear_fwd_add(const void* in, int in_dtype, int B, int Hi,
   const int st2 = gdl_copy_cast(base, out_dtype, B, Ho, Wo, C, osB, osH, osW, out, out_dtype, osB, osH, osW, stream);
   if (st2 != GDL_OK) return st2;
   return bilinear_fwd_impl(in, in_dtype, B, Hi, Wi, C, isB, isH, isW, out, out_dtype, Ho, Wo, osB, osH, osW, 1, nullptr, stream);
+}
+
+// gdl_bilinear_fwd_add with base = relu?(bn(x)) formed on the fly from the pre-BatchNorm map x [B, Ho, Wo, C] (dense) and the
+// per-channel statistics / affine parameters: the top-down add of a training lateral without the bn_apply pass.  Only the one-pass
+// gap kernel has this form (dense 16-byte aligned bf16, C % 8 == 0, factor 2 or 4: gdl_bilinear_fwd_add_bn_ok); there is no copy +
+// accumulate fallback -- other shapes fail and the caller runs gdl_bn_apply + gdl_bilinear_fwd_add.
+extern "C" int gdl_bilinear_fwd_add_bn_ok(int dtype, int B, int Hi, int Wi, int Ho, int Wo, int C) {
+  const int fac = (Hi > 1 && Wi > 1 && Ho % Hi == 0 && Wo % Wi == 0 && Ho / Hi == Wo / Wi) ? Ho / Hi : 0;
+  return dtype == GDL_BF16 && B > 0 && C > 0 && C % 8 == 0 && (fac == 2 || fac == 4) && (int64_t)B * (Hi + 1) <= 65535 && !g_flat_resample;
+}
+
+extern "C" int gdl_bilinear_fwd_add_bn(const void* in, int dtype, int B, int Hi, int Wi, int C, const void* x, const float* mean,
+                                       const float* var, const float* gamma, const float* beta, float eps, int relu, void* out,
+                                       int Ho, int Wo, gdl_stream_t stream) {
+  GDL_CHECK_ARG(in && x && mean && var && gamma && beta && out, "gdl_bilinear_fwd_add_bn: null pointer");
+  GDL_CHECK_ARG(gdl_bilinear_fwd_add_bn_ok(dtype, B, Hi, Wi, Ho, Wo, C) && (uintptr_t)in % 16 == 0 && (uintptr_t)x % 16 == 0 &&
+                    (uintptr_t)out % 16 == 0,
+                "gdl_bilinear_fwd_add_bn: needs dense 16-byte aligned bf16 maps, C %% 8 == 0 and a resize factor of 2 or 4");
+  const int64_t isW = C, isH = (int64_t)Wi * C, isB = (int64_t)Hi * isH, osW = C, osH = (int64_t)Wo * C, osB = (int64_t)Ho * osH;
+  const dim3 grid((unsigned)(((Wi + 1) * (C / 8) + 255) / 256), (unsigned)(B * (Hi + 1)));
+  if (Ho / Hi == 2) hipLaunchKernelGGL((bilinear_fwd8_gap_kernel<2, true>), grid, dim3(256), 0, (hipStream_t)stream, in, Hi, Wi, C, isB, isH, isW, out, osB, osH, osW, x, mean, var, gamma, beta, eps, relu);
+  else hipLaunchKernelGGL((bilinear_fwd8_gap_kernel<4, true>), grid, dim3(256), 0, (hipStream_t)stream, in, Hi, Wi, C, isB, isH, isW, out, osB, osH, osW, x, mean, var, gamma, beta, eps, relu);
+  GDL_CHECK_LAUNCH("gdl_bilinear_fwd_add_bn");
+  return GDL_OK;
 }
 
 extern "C" int gdl_copy_cast(const void* in, int in_dtype, int B, int H, int W, int C, int64_t isB, int64_t isH, int64_t isW,

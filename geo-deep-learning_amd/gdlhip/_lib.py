@@ -157,6 +157,14 @@ SIGNATURES = {
     "gdl_head_1x1_bwd_workspace": (c_l, [c_l, c_i, c_i]),
     "gdl_head_1x1_bwd": (c_i, [c_p, c_i, c_p, c_l, c_i, c_l, c_p, c_p, c_l, c_p, c_l, c_p, c_p, c_i,
                                c_p, c_l, c_p]),
+    "gdl_bilinear_fwd_add_bn_ok": (c_i, [c_i, c_i, c_i, c_i, c_i, c_i, c_i]),
+    "gdl_bilinear_fwd_add_bn": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_p, c_i, c_i, c_p]),
+    "gdl_head_1x1_bn_ok": (c_i, [c_i, c_l, c_i, c_i]),
+    "gdl_head_1x1_bn": (c_i, [c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_p, c_i, c_p]),
+    "gdl_bn_head_bwd_ok": (c_i, [c_i, c_l, c_i, c_i]),
+    "gdl_bn_head_bwd_workspace": (c_l, [c_l, c_i, c_i]),
+    "gdl_bn_head_bwd_reduce": (c_i, [c_p, c_i, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_bn_head_bwd_dx": (c_i, [c_p, c_i, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_l, c_p]),
     "gdl_upsample_logits": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p]),
     "gdl_upsample_logits_bwd_workspace": (c_l, [c_i, c_i, c_i, c_i]),
     "gdl_upsample_logits_bwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_l, c_p]),

@@ -626,6 +626,55 @@ GROUP_SYNC_BN = True   # A/B switch: False = one statistics exchange per ConvMod
 FUSE_CONCAT_BWD = True   # A/B switch: False = keep the concat buffer and run the full-resolution data / weight gradients
 
 
+def _concat_resize_conv(weight, levels):
+    """(y, chans): the 3x3 convolution of _ConcatResizeConvBNTrain over the concat of the resized levels, before BatchNorm."""
+    cd = levels[0].dtype
+    B, H, W, _ = levels[0].shape
+    chans = [lv.shape[3] for lv in levels]
+    if _tapsum_levels_ok(levels):
+        # per level (the convolution is linear over the concat): the native level runs the 3x3 kernel on its own
+        # channel slice; every upsampled level contributes its nine tap products, computed at ITS resolution, through
+        # one gather-sum pass whose result enters the native level's GEMM as the residual operand
+        offs = [sum(chans[:j]) for j in range(len(chans))]
+        zs = [ops.conv_gemm(lv, tap_weight(weight, cd, o, o + c)) for lv, o, c in zip(levels[1:], offs[1:], chans[1:])]
+        y = ops.conv_gemm(levels[0], slice_weight(weight, cd, 0, chans[0]), R=3, S=3, pad=1,
+                          resid=ops.resize_conv3x3_fwd_sum(zs, (H, W)))
+        del zs
+    else:
+        cat = torch.empty((B, H, W, sum(chans)), device=levels[0].device, dtype=cd)
+        off = 0
+        for lv, c in zip(levels, chans):
+            ops.bilinear(lv, (H, W), out=cat[..., off:off + c])
+            off += c
+        y = ops.conv_gemm(cat, gemm_weight(weight, cd), R=3, S=3, pad=1)
+        del cat
+    return y, chans
+
+
+def _concat_resize_conv_grads(weight, dy, levels, chans, want_dw, need_dxs):
+    """(dw, [d level_j]) of _concat_resize_conv from the gradient dy of its output."""
+    n, ctot = weight.shape[0], weight.shape[1]
+    H, W = dy.shape[1], dy.shape[2]
+    wd = dgrad_weight(weight, dy.dtype)                        # [sum(C_j), 9 N]: the rows of a level are contiguous
+    dw = torch.empty((n, 9, ctot), device=dy.device, dtype=torch.float32) if want_dw else None
+    dls, off = [], 0
+    for j, (lv, c) in enumerate(zip(levels, chans)):
+        need_dx = need_dxs[j]
+        if (lv.shape[1], lv.shape[2]) == (H, W):
+            dls.append(ops.conv_gemm(dy, wd[off:off + c], R=3, S=3, pad=1) if need_dx else None)
+            if want_dw:
+                dw[:, :, off:off + c] = ops.conv_wgrad(lv, dy, R=3, S=3, pad=1).view(n, 9, c)
+        else:
+            dx, dwl = ops.resize_conv3x3_bwd(lv, dy, wd[off:off + c] if need_dx else None, want_dw=want_dw)
+            dls.append(dx)
+            if want_dw:
+                dw[:, :, off:off + c] = dwl.view(n, 9, c)
+        off += c
+    if want_dw:
+        dw = dw.view(n, 3, 3, ctot).permute(0, 3, 1, 2)
+    return dw, dls
+
+
 class _ConcatResizeConvBNTrain(Function):
     """conv3x3(pad 1)(cat([l_0, bilinear(l_1 -> size), ..., bilinear(l_k -> size)])) -> BatchNorm(batch stats) -> ReLU
     (UperNet `fpn_bottleneck` over the upsampled FPN levels, upernet.py:144-152).  Forward: the levels are resized straight
@@ -636,27 +685,8 @@ class _ConcatResizeConvBNTrain(Function):
 
     @staticmethod
     def forward(ctx, weight, gamma, beta, running_mean, running_var, momentum, eps, relu, sync_group, *levels):
-        cd = levels[0].dtype
         n = weight.shape[0]
-        B, H, W, _ = levels[0].shape
-        chans = [lv.shape[3] for lv in levels]
-        if _tapsum_levels_ok(levels):
-            # per level (the convolution is linear over the concat): the native level runs the 3x3 kernel on its own
-            # channel slice; every upsampled level contributes its nine tap products, computed at ITS resolution, through
-            # one gather-sum pass whose result enters the native level's GEMM as the residual operand
-            offs = [sum(chans[:j]) for j in range(len(chans))]
-            zs = [ops.conv_gemm(lv, tap_weight(weight, cd, o, o + c)) for lv, o, c in zip(levels[1:], offs[1:], chans[1:])]
-            y = ops.conv_gemm(levels[0], slice_weight(weight, cd, 0, chans[0]), R=3, S=3, pad=1,
-                              resid=ops.resize_conv3x3_fwd_sum(zs, (H, W)))
-            del zs
-        else:
-            cat = torch.empty((B, H, W, sum(chans)), device=levels[0].device, dtype=cd)
-            off = 0
-            for lv, c in zip(levels, chans):
-                ops.bilinear(lv, (H, W), out=cat[..., off:off + c])
-                off += c
-            y = ops.conv_gemm(cat, gemm_weight(weight, cd), R=3, S=3, pad=1)
-            del cat
+        y, chans = _concat_resize_conv(weight, levels)
         mean, var, world, p_local, p_share = _bn_train_stats(y, n, running_mean, running_var, momentum, sync_group)
         out = ops.bn_apply(y, mean, var, gamma.detach(), beta.detach(), eps, relu)
         ctx.save_for_backward(weight, y, mean, var, gamma, beta, *levels)
@@ -667,30 +697,60 @@ class _ConcatResizeConvBNTrain(Function):
     def backward(ctx, gout):
         weight, y, mean, var, gamma, beta, *levels = ctx.saved_tensors
         relu, eps, sync_group, world, p_local, p_share, chans = ctx.cfg
-        n, ctot = weight.shape[0], weight.shape[1]
-        cd = y.dtype
         dy, dgamma, dbeta = _bn_train_backward(y, gout, mean, var, gamma.detach(), beta.detach(), eps, relu, sync_group,
                                                world, p_local, p_share)
-        H, W = dy.shape[1], dy.shape[2]
-        wd = dgrad_weight(weight, cd)                              # [sum(C_j), 9 N]: the rows of a level are contiguous
-        want_dw = ctx.needs_input_grad[0]
-        dw = torch.empty((n, 9, ctot), device=y.device, dtype=torch.float32) if want_dw else None
-        dls, off = [], 0
-        for j, (lv, c) in enumerate(zip(levels, chans)):
-            need_dx = ctx.needs_input_grad[9 + j]
-            if (lv.shape[1], lv.shape[2]) == (H, W):
-                dls.append(ops.conv_gemm(dy, wd[off:off + c], R=3, S=3, pad=1) if need_dx else None)
-                if want_dw:
-                    dw[:, :, off:off + c] = ops.conv_wgrad(lv, dy, R=3, S=3, pad=1).view(n, 9, c)
-            else:
-                dx, dwl = ops.resize_conv3x3_bwd(lv, dy, wd[off:off + c] if need_dx else None, want_dw=want_dw)
-                dls.append(dx)
-                if want_dw:
-                    dw[:, :, off:off + c] = dwl.view(n, 9, c)
-            off += c
-        if want_dw:
-            dw = dw.view(n, 3, 3, ctot).permute(0, 3, 1, 2)
+        dw, dls = _concat_resize_conv_grads(weight, dy, levels, chans, ctx.needs_input_grad[0], ctx.needs_input_grad[9:])
         return (dw, dgamma, dbeta, None, None, None, None, None, None, *dls)
+
+
+# A/B switch: 0 = the decoder tail runs bn_apply -> head and head backward -> BatchNorm backward as separate launches
+FUSE_BN_TAIL = os.environ.get("GDL_FUSE_BN_TAIL", "1") != "0"
+
+
+class _ConcatResizeConvBNHeadTrain(Function):
+    """_ConcatResizeConvBNTrain and the 1x1 classifier head on its output as ONE node (bf16, single-process statistics): the
+    head is the only consumer of z = ReLU(BN(y)) in a training step, its gradient dz = dlogits . W is five multiply-adds per
+    element of a tensor 1 / 50 the size of the map, and z is one f32 expression of the saved convolution output y.  So neither
+    z nor dz is ever written: the head forms z from y on load (ops.head_1x1_bn, bit-identical logits), the backward forms z
+    and dz from y and dlogits inside the BatchNorm sums pass -- which also accumulates the head's dW / db -- and inside the
+    dx pass (ops.bn_head_bwd_reduce / bn_head_bwd_dx).  Output: the head's [B, H, W, K] f32 logits."""
+
+    @staticmethod
+    def forward(ctx, weight, gamma, beta, running_mean, running_var, momentum, eps, relu, head_w, head_b, *levels):
+        n = weight.shape[0]
+        y, chans = _concat_resize_conv(weight, levels)
+        mean, var, _, p_local, _ = _bn_train_stats(y, n, running_mean, running_var, momentum, False)
+        low = ops.head_1x1_bn(y, mean, var, gamma.detach(), beta.detach(), eps, relu, head_w.detach(),
+                              None if head_b is None else head_b.detach())
+        ctx.save_for_backward(weight, y, mean, var, gamma, beta, head_w, *levels)
+        ctx.cfg = (relu, eps, p_local, chans, head_b is not None)
+        return low
+
+    @staticmethod
+    def backward(ctx, dlow):
+        weight, y, mean, var, gamma, beta, head_w, *levels = ctx.saved_tensors
+        relu, eps, p_local, chans, has_bias = ctx.cfg
+        dlow = dlow.contiguous()
+        g, b, hw = gamma.detach(), beta.detach(), head_w.detach()
+        dgamma, dbeta, dhw, dhb = ops.bn_head_bwd_reduce(y, dlow, hw, mean, var, g, b, eps, relu)
+        dy = ops.bn_head_bwd_dx(y, dlow, hw, mean, var, g, b, eps, relu, dgamma, dbeta, p_local, out=y)
+        dw, dls = _concat_resize_conv_grads(weight, dy, levels, chans, ctx.needs_input_grad[0], ctx.needs_input_grad[10:])
+        return (dw, dgamma, dbeta, None, None, None, None, None, dhw.view(head_w.shape), dhb if has_bias else None, *dls)
+
+
+def bn_tail_fusable(y_shape, dtype: torch.dtype, norm: nn.Module, head_conv: nn.Conv2d) -> bool:
+    """Shapes / modes the fused BatchNorm + head tail takes: bf16, train-mode statistics of ONE process, a dense 256-channel
+    map and a 1x1 head of at most 8 classes with f32 parameters (gdl_head_1x1_bn_ok / gdl_bn_head_bwd_ok)."""
+    if not (FUSE_BN_TAIL and norm.training and dtype == torch.bfloat16 and torch.is_grad_enabled()):
+        return False
+    if not single_process_bn_train(norm):
+        return False
+    hw = head_conv.weight
+    if head_conv.kernel_size != (1, 1) or hw.dtype != torch.float32 or not hw.is_contiguous() or hw.shape[1] != y_shape[3]:
+        return False
+    P, C, K = y_shape[0] * y_shape[1] * y_shape[2], y_shape[3], hw.shape[0]
+    lib = ops._lib.load()
+    return bool(lib.gdl_head_1x1_bn_ok(ops.BF16, P, C, K)) and bool(lib.gdl_bn_head_bwd_ok(ops.BF16, P, C, K))
 
 
 def _tapsum_levels_ok(levels) -> bool:
@@ -702,9 +762,13 @@ def _tapsum_levels_ok(levels) -> bool:
                     or ops.resize_conv3x3_any_ok((lv.shape[1], lv.shape[2]), (H, W), B) for lv in levels[1:]))
 
 
-def concat_resize_conv_bn_act(levels: list[Tensor], conv: nn.Conv2d, norm: nn.Module, *, relu: bool = True) -> Tensor:
+def concat_resize_conv_bn_act(levels: list[Tensor], conv: nn.Conv2d, norm: nn.Module, *, relu: bool = True,
+                              head_conv: nn.Conv2d | None = None) -> Tensor:
     """ConvModule(3x3, pad 1, no bias) over cat([levels[0]] + [bilinear(l -> levels[0]'s size) for l in levels[1:]]) on NHWC
-    maps.  Training: see _ConcatResizeConvBNTrain; eval (and resize factors above 8): concat_upsample + conv_bn_act."""
+    maps.  Training: see _ConcatResizeConvBNTrain; eval (and resize factors above 8): concat_upsample + conv_bn_act.
+    ``head_conv``: the caller has checked bn_tail_fusable() and wants the [B, H, W, K] f32 logits of that 1x1 head over the
+    result instead of the result (_ConcatResizeConvBNHeadTrain); when the fused training node does not apply the head runs
+    on the materialised map (_Head1x1)."""
     size = (levels[0].shape[1], levels[0].shape[2])
     def factor_ok(lv):
         fy, fx = size[0] / lv.shape[1], size[1] / lv.shape[2]
@@ -739,9 +803,15 @@ def concat_resize_conv_bn_act(levels: list[Tensor], conv: nn.Conv2d, norm: nn.Mo
         if FUSE_CONCAT_BWD and norm.training:
             warn_unfused("3x3 ConvModule over a concat of resized levels", f"levels {[tuple(lv.shape) for lv in levels]}: needs "
                          "contiguous levels, resize factors <= 10, N % 8 == 0 and batch * rows <= 65535")
-        return conv_bn_act(concat_upsample(levels, size), conv, norm, relu=relu)
+        out = conv_bn_act(concat_upsample(levels, size), conv, norm, relu=relu)
+        return out if head_conv is None else _Head1x1.apply(out, head_conv.weight, head_conv.bias, None)
     sync_group = norm.process_group if isinstance(norm, nn.SyncBatchNorm) else False
     momentum = 0.1 if norm.momentum is None else norm.momentum
+    if head_conv is not None:
+        low = _ConcatResizeConvBNHeadTrain.apply(conv.weight, norm.weight, norm.bias, norm.running_mean, norm.running_var, momentum,
+                                                 norm.eps, relu, head_conv.weight, head_conv.bias, *levels)
+        bump(norm.num_batches_tracked)
+        return low
     out = _ConcatResizeConvBNTrain.apply(conv.weight, norm.weight, norm.bias, norm.running_mean, norm.running_var, momentum,
                                          norm.eps, relu, sync_group, *levels)
     bump(norm.num_batches_tracked)
@@ -1125,6 +1195,64 @@ def upsample_add(a: Tensor, b: Tensor) -> Tensor:
     return _UpsampleAdd.apply(a, b)
 
 
+class _ConvBNActUpsampleAddTrain(Function):
+    """_ConvBNActTrain (statistics of one process) and _UpsampleAdd on its output as ONE node: ReLU(BN(conv(x))) + bilinear(b) --
+    a UperNet lateral and the top-down add that is its only consumer (upernet.py:127-135).  The add kernel reads the lateral
+    once anyway, so it forms BN + ReLU from the convolution output y on load (ops.bilinear_add_bn, bit-identical sum) and the
+    normalised lateral is never written.  Backward: the gradient of the sum IS the gradient of the lateral's BatchNorm output
+    (_UpsampleAdd passes it through), so the BatchNorm / convolution backward is _ConvBNActTrain's, plus the resize's for b."""
+
+    @staticmethod
+    def forward(ctx, x, weight, conv_bias, gamma, beta, running_mean, running_var, momentum, eps, pad, relu, b):
+        cb = None if conv_bias is None else conv_bias.detach()
+        y, stats_done = _cba_conv(x, weight, cb, pad, 0, False, running_mean, running_var, momentum)
+        mean, var = stats_done if stats_done is not None else ops.bn_stats(y, running_mean, running_var, momentum)
+        if running_mean is not None:
+            mark_updated(running_mean)
+            mark_updated(running_var)
+        out = ops.bilinear_add_bn(y, mean, var, gamma.detach(), beta.detach(), eps, relu, b)
+        ctx.save_for_backward(x, weight, y, mean, var, gamma, beta)
+        ctx.cfg = (pad, relu, eps, conv_bias is not None, y.numel() // weight.shape[0], (b.shape[1], b.shape[2]))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, y, mean, var, gamma, beta = ctx.saved_tensors
+        pad, relu, eps, has_bias, p_local, b_size = ctx.cfg
+        db = ops.bilinear_bwd(g, b_size) if ctx.needs_input_grad[11] else None
+        gout = g if g.dtype == y.dtype else to_compute(g, y.dtype)
+        gm, bt = gamma.detach(), beta.detach()
+        dgamma, dbeta = ops.bn_bwd_reduce(y, gout, mean, var, gm, bt, eps, relu)
+        dbias = torch.zeros(weight.shape[0], device=x.device, dtype=torch.float32) if has_bias and ctx.needs_input_grad[2] else None
+        dx, dw = _bn_bwd_and_grads(x, weight, y, gout, mean, var, gm, bt, eps, relu, dgamma, dbeta, p_local, pad, 0,
+                                   ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return dx, dw, dbias, dgamma, dbeta, None, None, None, None, None, None, db
+
+
+def single_process_bn_train(norm: nn.Module) -> bool:
+    """Train-mode BatchNorm whose batch statistics do not cross ranks."""
+    return norm.training and not (isinstance(norm, nn.SyncBatchNorm) and _world(norm.process_group) > 1)
+
+
+def conv_bn_act_upsample_add(x: Tensor, conv: nn.Conv2d, norm: nn.Module, b: Tensor, *, relu: bool = True) -> Tensor:
+    """upsample_add(conv_bn_act(x, conv, norm), b) for a ConvModule whose output has no other consumer.  bf16 training with the
+    statistics of one process and a resize factor of 2 or 4: one node that never writes the normalised map
+    (_ConvBNActUpsampleAddTrain, GDL_FUSE_BN_TAIL); everything else: the two separate nodes."""
+    B, H, W = x.shape[0], x.shape[1], x.shape[2]
+    n = conv.weight.shape[0]
+    fused = (FUSE_BN_TAIL and single_process_bn_train(norm) and x.dtype == torch.bfloat16 and b.dtype == x.dtype and x.dim() == 4
+             and b.dim() == 4 and b.is_contiguous() and conv.kernel_size == (1, 1) and conv.stride == (1, 1) and b.shape[3] == n
+             and not 0 < B * H * W <= ops.BN_SMALL_MAX_PIXELS      # (small maps: the one-launch BatchNorm of _ConvBNActTrain)
+             and bool(ops._lib.load().gdl_bilinear_fwd_add_bn_ok(ops.BF16, B, b.shape[1], b.shape[2], H, W, n)))
+    if not fused:
+        return upsample_add(conv_bn_act(x, conv, norm, relu=relu), b)
+    momentum = 0.1 if norm.momentum is None else norm.momentum
+    out = _ConvBNActUpsampleAddTrain.apply(x, conv.weight, conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var,
+                                           momentum, norm.eps, conv.padding[0], relu, b)
+    bump(norm.num_batches_tracked)
+    return out
+
+
 class _ConcatUpsample(Function):
     """cat([bilinear(x_i -> size) for x_i], channel dim) written straight into one NHWC buffer
     (upernet.py:103-109,144-152: no separate concat copy)."""
@@ -1245,6 +1373,13 @@ def head_logits(feat: Tensor, conv: nn.Conv2d, size, chan_scale: Tensor | None =
     if lowres:
         return LowresLogits(_Head1x1.apply(feat, conv.weight, conv.bias, chan_scale), (int(size[0]), int(size[1])))
     return _HeadLogits.apply(feat, conv.weight, conv.bias, chan_scale, (int(size[0]), int(size[1])))
+
+
+def logits_from_low(low: Tensor, size, lowres: bool = False):
+    """What head_logits returns, from logits the head has already written at the feature resolution ([B, h, w, K] f32)."""
+    if lowres:
+        return LowresLogits(low, (int(size[0]), int(size[1])))
+    return _UpsampleLogits.apply(low, (int(size[0]), int(size[1])))
 
 
 class _DiceLoss(Function):

@@ -689,6 +689,22 @@ def bilinear_add(base: Tensor, x: Tensor) -> Tensor:
     return out
 
 
+def bilinear_add_bn(x_pre: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, beta: Tensor, eps: float, relu: bool, x: Tensor) -> Tensor:
+    """bilinear_add(bn_apply(x_pre, ...), x) without the normalised map: the top-down add of a training lateral from its
+    pre-BatchNorm convolution output ``x_pre``, bit-identical to the two separate ops (gdl_bilinear_fwd_add_bn: dense bf16 maps,
+    resize factor 2 or 4; other shapes raise)."""
+    _need_cuda(x_pre, x)
+    b4, x4 = _nhwc4(x_pre, "bilinear_add_bn base"), _nhwc4(x, "bilinear_add_bn x")
+    B, Ho, Wo, Cc = b4.shape
+    if x4.shape[0] != B or x4.shape[3] != Cc or x4.dtype != b4.dtype or not b4.is_contiguous() or not x4.is_contiguous():
+        raise ValueError(f"bilinear_add_bn: dense maps of one dtype expected, {tuple(x4.shape)} {x4.dtype} onto {tuple(b4.shape)} {b4.dtype}")
+    out = torch.empty((B, Ho, Wo, Cc), device=x_pre.device, dtype=x_pre.dtype)
+    check(_lib.load().gdl_bilinear_fwd_add_bn(_p(x4), dt(x4), B, x4.shape[1], x4.shape[2], Cc, _p(b4), _p(_f32vec(mean, Cc, "mean")),
+                                              _p(_f32vec(var, Cc, "var")), _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")),
+                                              eps, int(relu), _p(out), Ho, Wo, _stream()), "gdl_bilinear_fwd_add_bn")
+    return out
+
+
 GATHER_TWO_PASS = True    # A/B switch (tools / tests): separable two-pass gather for large resize factors
 
 
@@ -1710,6 +1726,69 @@ def head_1x1_bwd(feat: Tensor, dlog: Tensor, w: Tensor, chan_scale: Tensor | Non
                                _p(dfeat), Cc, _p(dw), _p(db), K, _p(ws), nbytes, _stream()),
           "gdl_head_1x1_bwd")
     return dfeat, dw, db
+
+
+def _head_bn_args(x: Tensor, w: Tensor, who: str):
+    x4 = _nhwc4(x, who)
+    B, H, W, Cc = x4.shape
+    if x4.dtype != torch.bfloat16 or not x4.is_contiguous():
+        raise ValueError(f"{who}: dense bf16 NHWC map expected")
+    K = w.shape[0]
+    w2 = w.reshape(K, Cc)
+    if w2.dtype != torch.float32 or not w2.is_contiguous():
+        raise ValueError(f"{who}: weight must be contiguous f32 [K, C]")
+    return x4, B * H * W, Cc, K, w2
+
+
+def head_1x1_bn(x: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, beta: Tensor, eps: float, relu: bool, w: Tensor,
+                bias: Tensor | None) -> Tensor:
+    """head_1x1(bn_apply(x, ...), w, bias) without the normalised map: f32 NHWC logits [B,H,W,K] from the pre-BatchNorm bf16 map
+    ``x`` (C == 256), bit-identical to the two separate ops."""
+    _need_cuda(x, w)
+    x4, P, Cc, K, w2 = _head_bn_args(x, w, "head_1x1_bn x")
+    out = torch.empty((*x4.shape[:3], K), device=x.device, dtype=torch.float32)
+    check(_lib.load().gdl_head_1x1_bn(_p(x4), dt(x4), P, Cc, _p(_f32vec(mean, Cc, "mean")), _p(_f32vec(var, Cc, "var")),
+                                      _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")), eps, int(relu), _p(w2),
+                                      _p(bias), _p(out), K, _stream()), "gdl_head_1x1_bn")
+    return out
+
+
+def bn_head_bwd_reduce(x: Tensor, dlog: Tensor, w: Tensor, mean, var, gamma, beta, eps, relu):
+    """(dgamma, dbeta, dw [K, C], db [K]) of head_1x1(relu?(bn(x))) from the head's logit gradient ``dlog`` [B,H,W,K] f32: the sums
+    of bn_bwd_reduce and the parameter gradients of head_1x1_bwd in one read of ``x``."""
+    _need_cuda(x, dlog, w)
+    x4, P, Cc, K, w2 = _head_bn_args(x, w, "bn_head_bwd x")
+    if dlog.dtype != torch.float32 or not dlog.is_contiguous() or dlog.numel() != P * K:
+        raise ValueError("bn_head_bwd: dlog must be contiguous f32 [B, H, W, K]")
+    dgamma = torch.empty(Cc, device=x.device, dtype=torch.float32)
+    dbeta = torch.empty_like(dgamma)
+    dw = torch.empty((K, Cc), device=x.device, dtype=torch.float32)
+    db = torch.empty(K, device=x.device, dtype=torch.float32)
+    lib = _lib.load()
+    nbytes = lib.gdl_bn_head_bwd_workspace(P, Cc, K)
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
+    check(lib.gdl_bn_head_bwd_reduce(_p(x4), dt(x4), _p(dlog), P, Cc, K, _p(w2), _p(_f32vec(mean, Cc, "mean")), _p(_f32vec(var, Cc, "var")),
+                                     _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")), eps,
+                                     int(relu), _p(dgamma), _p(dbeta), _p(dw), _p(db), _p(ws), nbytes, _stream()),
+          "gdl_bn_head_bwd_reduce")
+    return dgamma, dbeta, dw, db
+
+
+def bn_head_bwd_dx(x: Tensor, dlog: Tensor, w: Tensor, mean, var, gamma, beta, eps, relu, dgamma_sum, dbeta_sum, p_total,
+                   out: Tensor | None = None) -> Tensor:
+    """bn_bwd_dx with the gradient of the normalised map re-formed from the head's logit gradient; ``out`` may be ``x``."""
+    _need_cuda(x, dlog, w)
+    x4, P, Cc, K, w2 = _head_bn_args(x, w, "bn_head_bwd x")
+    if dlog.dtype != torch.float32 or not dlog.is_contiguous() or dlog.numel() != P * K:
+        raise ValueError("bn_head_bwd: dlog must be contiguous f32 [B, H, W, K]")
+    dx = out if out is not None else torch.empty(x.shape, device=x.device, dtype=x.dtype)
+    if dx.dtype != x.dtype or dx.shape != x.shape or not dx.is_contiguous():
+        raise ValueError("bn_head_bwd_dx: out must be a dense map of x's shape and dtype")
+    check(_lib.load().gdl_bn_head_bwd_dx(_p(x4), dt(x4), _p(dlog), _p(dx), P, Cc, K, _p(w2), _p(_f32vec(mean, Cc, "mean")),
+                                         _p(_f32vec(var, Cc, "var")), _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")),
+                                         eps, int(relu), _p(_f32vec(dgamma_sum, Cc, "dgamma_sum")), _p(_f32vec(dbeta_sum, Cc, "dbeta_sum")),
+                                         p_total, _stream()), "gdl_bn_head_bwd_dx")
+    return dx
 
 
 def upsample_logits(x: Tensor, size: tuple[int, int]) -> Tensor:

@@ -58,20 +58,37 @@ class UperNetDecoder(nn.Module):
         return [gnn.conv_transpose2x2(half, self.fpn1[3]), gnn.conv_transpose2x2(inputs[1], self.fpn2[0]), inputs[2],
                 gnn.maxpool2x2(inputs[3])]
 
-    def forward_nhwc(self, inputs: list[torch.Tensor]) -> torch.Tensor:
+    def tail_fusable(self, inputs: list[torch.Tensor], head_conv: nn.Conv2d) -> bool:
+        """True when ``forward_nhwc(inputs, head_conv=head_conv)`` can hand the 1x1 head's logits back without writing the
+        normalised ``fpn_bottleneck`` output (gdlhip.nn.bn_tail_fusable: bf16 training step, statistics of one process)."""
+        if self.scale_modules:      # (the output size is that of the scaled inputs[0]; DOFA's decoder has no scale_modules: not wired)
+            return False
+        x = inputs[0]
+        return gnn.bn_tail_fusable((x.shape[0], x.shape[1], x.shape[2], self.channels), x.dtype, self.fpn_bottleneck.norm, head_conv)
+
+    def forward_nhwc(self, inputs: list[torch.Tensor], head_conv: nn.Conv2d | None = None) -> torch.Tensor:
+        """``head_conv`` (only where ``tail_fusable``): the [B, H, W, K] f32 logits of that 1x1 head over the decoder output are
+        returned instead of the output itself."""
         if self.scale_modules:
             inputs = self.scale_inputs_nhwc(inputs)
         # lateral 1x1 convolutions and the PPM branches are independent: one group (one SyncBatchNorm message per direction)
-        lat_items = [dict(x=inputs[i], conv=m.conv, norm=m.norm) for i, m in enumerate(self.lateral_convs)]
+        # a lateral's only consumer is its top-down add: with statistics of one process (no group message to share) each lateral
+        # runs inside the add's node, which applies BatchNorm + ReLU on load (gnn.conv_bn_act_upsample_add, GDL_FUSE_BN_TAIL)
+        lat_in_add = gnn.FUSE_BN_TAIL and all(gnn.single_process_bn_train(m.norm) for m in self.lateral_convs)
+        lat_items = [] if lat_in_add else [dict(x=inputs[i], conv=m.conv, norm=m.norm) for i, m in enumerate(self.lateral_convs)]
         ppm_items = self.psp_modules.items_nhwc(inputs[-1])
         res = gnn.conv_bn_act_group(lat_items + ppm_items)
-        laterals = res[:len(lat_items)]
+        laterals = res[:len(lat_items)] if not lat_in_add else [None] * len(self.lateral_convs)
         x = inputs[-1]
         cat = gnn.concat_upsample([x, *res[len(lat_items):]], (x.shape[1], x.shape[2]))      # upernet.py:103-109
         laterals.append(self.bottleneck.forward_nhwc(cat))
         n = len(laterals)
         for i in range(n - 1, 0, -1):  # top-down: lat[i-1] += up(lat[i])
-            laterals[i - 1] = gnn.upsample_add(laterals[i - 1], laterals[i])
+            if lat_in_add:
+                m = self.lateral_convs[i - 1]
+                laterals[i - 1] = gnn.conv_bn_act_upsample_add(inputs[i - 1], m.conv, m.norm, laterals[i])
+            else:
+                laterals[i - 1] = gnn.upsample_add(laterals[i - 1], laterals[i])
         fpn_outs = gnn.conv_bn_act_group([dict(x=laterals[i], conv=self.fpn_convs[i].conv, norm=self.fpn_convs[i].norm)
                                           for i in range(n - 1)])
         fpn_outs.append(laterals[-1])
@@ -79,7 +96,7 @@ class UperNetDecoder(nn.Module):
         # 3x3 bottleneck over the concat of the upsampled levels; in training the upsampled levels' gradients are computed at
         # their own resolution (gdlhip.nn.concat_resize_conv_bn_act)
         return gnn.concat_resize_conv_bn_act(fpn_outs, self.fpn_bottleneck.conv, self.fpn_bottleneck.norm,
-                                             relu=self.fpn_bottleneck.act is not None)
+                                             relu=self.fpn_bottleneck.act is not None, head_conv=head_conv)
 
     def forward(self, inputs: list[torch.Tensor]) -> torch.Tensor:
         cd = gnn.compute_dtype()

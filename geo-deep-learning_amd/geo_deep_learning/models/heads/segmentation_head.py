@@ -27,6 +27,11 @@ class SegmentationHead(nn.Module):
         """head conv + bilinear resize to ``size`` fused: NCHW f32 logits (dofa.py:89-96); ``lowres``: gdlhip.nn.LowresLogits."""
         return gnn.head_logits(x_nhwc, self.conv, size, lowres=lowres)
 
+    def logits_from_low(self, low: torch.Tensor, size, lowres: bool = False):
+        """What ``forward_logits`` returns, from this head's logits already written at the feature resolution ([B, h, w, K] f32:
+        the decoder applied ``self.conv`` inside its last node, UperNetDecoder.forward_nhwc(head_conv=...))."""
+        return gnn.logits_from_low(low, size, lowres=lowres)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         xn = gnn.to_compute(ops.as_nhwc(x), gnn.compute_dtype())
         return self.forward_logits(xn, (xn.shape[1], xn.shape[2]))

@@ -57,9 +57,15 @@ class DOFASegmentationModel(BaseSegmentationModel):
                 taps = self.encoder.forward_features_nhwc(x, wavelengths, drop_masks)
             with rng("neck"):
                 feats = self.neck.forward_nhwc(taps)
+            # training: the head is the decoder output's only consumer, so BatchNorm + ReLU of fpn_bottleneck is applied
+            # inside the head's kernels and the normalised map is never written (gdlhip.nn._ConcatResizeConvBNHeadTrain)
+            fused_tail = self.decoder.tail_fusable(feats, self.head.conv)
             with rng("decoder"):
-                dec = self.decoder.forward_nhwc(feats)
+                dec = self.decoder.forward_nhwc(feats, head_conv=self.head.conv if fused_tail else None)
             with rng("heads"):
-                out = self.head.forward_logits(dec, image_size, lowres=lowres_logits)
+                if fused_tail:
+                    out = self.head.logits_from_low(dec, image_size, lowres=lowres_logits)
+                else:
+                    out = self.head.forward_logits(dec, image_size, lowres=lowres_logits)
                 aux = self.aux_head.forward_logits(feats[-1], image_size, aux_drop_mask, lowres=lowres_logits)
         return self.output_struct(out=out, aux=aux)

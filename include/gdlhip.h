@@ -483,6 +483,33 @@ int gdl_head_1x1_bwd(const void* feat, int dtype, const float* dlog, int64_t P, 
                      const float* w, const float* chan_scale, int64_t pix_per_img, void* dfeat,
                      int64_t d_sP, float* dw, float* db, int K, float* workspace,
                      int64_t workspace_bytes, gdl_stream_t stream);
+/* Decoder tail in training (bf16, single-process statistics): the head over z = relu?(bn(x)) and the BatchNorm backward under it,
+ * from the saved convolution output x [P][256] and the head's logit gradient dlog [P][K] f32 -- neither z nor dz is stored.
+ * gdl_head_1x1_bn: logits as gdl_bn_apply + gdl_head_1x1 give them, bit for bit (the same f32 expression and one bf16 rounding per
+ * feature).  gdl_bn_head_bwd_reduce: dgamma / dbeta as gdl_bn_bwd_reduce and the head's dw [K][256] / db [K] (may be NULL) as
+ * gdl_head_1x1_bwd, one read of x; workspace gdl_bn_head_bwd_workspace() bytes.  gdl_bn_head_bwd_dx: dx as gdl_bn_bwd_dx (dx may
+ * alias x).  The *_ok predicates name the shapes each takes (dense 16-byte aligned bf16, C == 256, K <= 8, P >= 4096, the
+ * same for both); other shapes fail and the caller runs the separate kernels. */
+/* gdl_bilinear_fwd_add with base = relu?(bn(x)) formed on load from the pre-BatchNorm map x [B, Ho, Wo, C]: the top-down add
+ * of a training lateral, bit-identical to gdl_bn_apply + gdl_bilinear_fwd_add.  All maps dense bf16, C % 8 == 0, factor 2 or 4
+ * (gdl_bilinear_fwd_add_bn_ok); no copy + accumulate fallback: other shapes fail. */
+int gdl_bilinear_fwd_add_bn_ok(int dtype, int B, int Hi, int Wi, int Ho, int Wo, int C);
+int gdl_bilinear_fwd_add_bn(const void* in, int dtype, int B, int Hi, int Wi, int C, const void* x, const float* mean,
+                            const float* var, const float* gamma, const float* beta, float eps, int relu, void* out, int Ho,
+                            int Wo, gdl_stream_t stream);
+int gdl_head_1x1_bn_ok(int dtype, int64_t P, int C, int K);
+int gdl_head_1x1_bn(const void* x, int dtype, int64_t P, int C, const float* mean, const float* var, const float* gamma,
+                    const float* beta, float eps, int relu, const float* w, const float* bias, float* out, int K,
+                    gdl_stream_t stream);
+int gdl_bn_head_bwd_ok(int dtype, int64_t P, int C, int K);
+int64_t gdl_bn_head_bwd_workspace(int64_t P, int C, int K);
+int gdl_bn_head_bwd_reduce(const void* x, int dtype, const float* dlog, int64_t P, int C, int K, const float* w,
+                           const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
+                           float* dgamma, float* dbeta, float* dw, float* db, float* workspace, int64_t workspace_bytes,
+                           gdl_stream_t stream);
+int gdl_bn_head_bwd_dx(const void* x, int dtype, const float* dlog, void* dx, int64_t P, int C, int K, const float* w,
+                       const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
+                       const float* dgamma_sum, const float* dbeta_sum, int64_t P_total, gdl_stream_t stream);
 /* bilinear (align_corners=False) NHWC [B,Hi,Wi,K] -> NCHW f32 [B,K,Ho,Wo] logits (dofa.py:89-105) */
 int gdl_upsample_logits(const float* in, int B, int Hi, int Wi, int K, float* out, int Ho, int Wo,
                         gdl_stream_t stream);
