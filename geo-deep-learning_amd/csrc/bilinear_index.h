@@ -1,0 +1,48 @@
+// Index arithmetic of the bilinear (align_corners=False) logit resize, shared by the kernels that evaluate it on the fly
+// (misc.hip: gdl_upsample_logits, gdl_upsample_argmax, gdl_dice_loss_lowres_*; loss_ce.hip: gdl_soft_ce_lowres_*).  One
+// definition, so that every kernel forms the bits gdl_upsample_logits writes.
+#pragma once
+#include "gdl_common.h"
+
+namespace {
+
+__device__ __forceinline__ void src_index2(float ratio, int dst, int in_size, int& i0, int& i1, float& l1) {
+  float s = ratio * ((float)dst + 0.5f) - 0.5f;
+  s = s < 0.f ? 0.f : s;
+  i0 = (int)s;
+  if (i0 > in_size - 1) i0 = in_size - 1;
+  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
+  l1 = s - (float)i0;
+  l1 = l1 < 0.f ? 0.f : (l1 > 1.f ? 1.f : l1);
+}
+
+// output positions [lo, hi] that can interpolate from input position i (a superset; callers test the weight)
+__device__ __forceinline__ void cand_range(int i, float ratio, int out_size, int& lo, int& hi) {
+  lo = (int)floorf(((float)i - 0.5f) / ratio - 0.5f) - 1;
+  hi = (int)ceilf(((float)i + 1.5f) / ratio - 0.5f) + 1;
+  lo = lo < 0 ? 0 : lo;
+  hi = hi > out_size - 1 ? out_size - 1 : hi;
+}
+
+// low-resolution index range [lo, hi] that the full-resolution positions [p0, p1] interpolate from
+__device__ __forceinline__ void touched_range(float ratio, int p0, int p1, int in_size, int& lo, int& hi) {
+  int a0, a1, b0, b1; float l;
+  src_index2(ratio, p0, in_size, a0, a1, l);
+  src_index2(ratio, p1, in_size, b0, b1, l);
+  lo = a0; hi = b1;
+}
+
+// the K bilinear logits of one output pixel from the NHWC map [B, Hi, Wi, K]: the expression of upsample_logits_kernel
+template <int K>
+__device__ __forceinline__ void bilinear_logits(const float* __restrict__ in, int b, int Hi, int Wi, int y0, int y1, int x0, int x1,
+                                                float ly, float lx, float (&x)[K]) {
+  const float* p00 = in + (((int64_t)b * Hi + y0) * Wi + x0) * K;
+  const float* p01 = in + (((int64_t)b * Hi + y0) * Wi + x1) * K;
+  const float* p10 = in + (((int64_t)b * Hi + y1) * Wi + x0) * K;
+  const float* p11 = in + (((int64_t)b * Hi + y1) * Wi + x1) * K;
+  const float hy = 1.f - ly, hx = 1.f - lx;
+#pragma unroll
+  for (int k = 0; k < K; ++k) x[k] = hy * (hx * p00[k] + lx * p01[k]) + ly * (hx * p10[k] + lx * p11[k]);
+}
+
+}  // namespace

@@ -5,6 +5,7 @@
 #include <atomic>
 
 #include "gdl_common.h"
+#include "bilinear_index.h"
 
 namespace {
 
@@ -854,16 +855,6 @@ __global__ __launch_bounds__(1024) void head_1x1_bwd_w_final(const float* __rest
   else db[i - K * C] = (float)s;
 }
 
-__device__ __forceinline__ void src_index2(float ratio, int dst, int in_size, int& i0, int& i1, float& l1) {
-  float s = ratio * ((float)dst + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  i0 = (int)s;
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-  l1 = l1 < 0.f ? 0.f : (l1 > 1.f ? 1.f : l1);
-}
-
 // NHWC [B,Hi,Wi,K] f32 -> NCHW [B,K,Ho,Wo] f32, bilinear align_corners=False
 template <int K>
 __global__ __launch_bounds__(256) void upsample_logits_kernel(const float* __restrict__ in, int B, int Hi, int Wi,
@@ -891,13 +882,6 @@ __global__ __launch_bounds__(256) void upsample_logits_kernel(const float* __res
 // Backward of the logit upsample, separable (bilinear weights factor as wy*wx), gather form:
 //   pass 1: tmp[b,k,iy,ox] = sum_oy wy(oy->iy) * dout[b,k,oy,ox]      (coalesced along ox)
 //   pass 2: din[b,iy,ix,k] = sum_ox wx(ox->ix) * tmp[b,k,iy,ox]
-__device__ __forceinline__ void cand_range(int i, float ratio, int out_size, int& lo, int& hi) {
-  lo = (int)floorf(((float)i - 0.5f) / ratio - 0.5f) - 1;
-  hi = (int)ceilf(((float)i + 1.5f) / ratio - 0.5f) + 1;
-  lo = lo < 0 ? 0 : lo;
-  hi = hi > out_size - 1 ? out_size - 1 : hi;
-}
-
 __global__ __launch_bounds__(256) void upsample_logits_bwd_pass1(const float* __restrict__ dout, int BK, int Ho, int Wo,
                                                                  float* __restrict__ tmp, int Hi) {
   const int64_t total = (int64_t)BK * Hi * Wo;
@@ -1154,18 +1138,6 @@ __global__ __launch_bounds__(256) void dice_bwd_kernel(const float* __restrict__
 //   forward  -- the three per-class sums of dice_partial_kernel, same workgroup count and pixel order (the same partial sums);
 //   backward -- one thread per LOW-resolution logit vector gathers wy * wx * dL/dlogit over the full-resolution pixels that
 //               interpolate from it (softmax and Dice coefficients recomputed there): d(low) in one pass, f32, fixed order.
-template <int K>
-__device__ __forceinline__ void bilinear_logits(const float* __restrict__ in, int b, int Hi, int Wi, int y0, int y1, int x0, int x1,
-                                                float ly, float lx, float (&x)[K]) {
-  const float* p00 = in + (((int64_t)b * Hi + y0) * Wi + x0) * K;
-  const float* p01 = in + (((int64_t)b * Hi + y0) * Wi + x1) * K;
-  const float* p10 = in + (((int64_t)b * Hi + y1) * Wi + x0) * K;
-  const float* p11 = in + (((int64_t)b * Hi + y1) * Wi + x1) * K;
-  const float hy = 1.f - ly, hx = 1.f - lx;
-#pragma unroll
-  for (int k = 0; k < K; ++k) x[k] = hy * (hx * p00[k] + lx * p01[k]) + ly * (hx * p10[k] + lx * p11[k]);
-}
-
 // softmax(dim=1).argmax(dim=1) of the resized logits straight from the head's low-resolution map (validation / test / inference:
 // `outputs.out.softmax(dim=1).argmax(dim=1)`, segmentation_dofa.py:278-281): the bilinear logits of a pixel with the expression of
 // upsample_logits_kernel, then softmax_argmax_kernel's decision -- the same mask, bit for bit, without the [B, K, H, W] f32 tensor
@@ -1328,14 +1300,6 @@ struct DiceTile {
   int64_t ignore;
   DiceCoef o;
 };
-
-// low-resolution index range [lo, hi] that the full-resolution positions [p0, p1] interpolate from
-__device__ __forceinline__ void touched_range(float ratio, int p0, int p1, int in_size, int& lo, int& hi) {
-  int a0, a1, b0, b1; float l;
-  src_index2(ratio, p0, in_size, a0, a1, l);
-  src_index2(ratio, p1, in_size, b0, b1, l);
-  lo = a0; hi = b1;
-}
 
 template <int K, bool IGN>
 __global__ __launch_bounds__(DT_T) void dice_lowres_bwd_tile_kernel(const DiceTile a) {

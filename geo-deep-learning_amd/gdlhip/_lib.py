@@ -193,6 +193,16 @@ SIGNATURES = {
     "gdl_maxpool2x2s2_fwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_p, c_l, c_l, c_l, c_p]),
     "gdl_maxpool2x2s2_bwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_l, c_l,
                                    c_p]),
+    "gdl_soft_ce_workspace": (c_l, [c_i, c_i, c_l]),
+    "gdl_soft_ce_fwd": (c_i, [c_p, c_p, c_i, c_i, c_l, c_f, c_i, c_l, c_i, c_p, c_p, c_l, c_p]),
+    "gdl_soft_ce_bwd": (c_i, [c_p, c_p, c_i, c_i, c_l, c_f, c_i, c_l, c_i, c_p, c_f, c_p, c_i, c_p]),
+    "gdl_soft_ce_lowres_workspace": (c_l, [c_i, c_i, c_i, c_i]),
+    "gdl_soft_ce_lowres_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_l, c_i, c_p, c_p, c_l, c_p]),
+    "gdl_soft_ce_lowres_bwd_workspace": (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "gdl_soft_ce_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_l, c_i, c_p, c_f, c_p, c_p, c_l, c_p]),
+    "gdl_soft_ce_lowres_fused_state": (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "gdl_soft_ce_lowres_fused_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_l, c_i, c_p, c_p, c_l, c_p]),
+    "gdl_soft_ce_lowres_fused_bwd": (c_i, [c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_f, c_p, c_p]),
     "gdl_dice_binary_loss_fwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_l, c_p]),
     "gdl_dice_binary_loss_bwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_f, c_p, c_i, c_p]),
     "gdl_dice_binary_loss_opt_fwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),

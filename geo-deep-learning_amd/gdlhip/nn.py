@@ -1503,6 +1503,107 @@ class DiceLoss(nn.Module):
         return _DiceLoss.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
 
 
+class _SoftCE(Function):
+    """smp SoftCrossEntropyLoss on full-resolution NCHW logits; the backward recomputes the softmax from the saved logits."""
+
+    @staticmethod
+    def forward(ctx, logits, target, options):
+        loss = ops.soft_ce_fwd(logits, target, options)
+        ctx.save_for_backward(logits, target)
+        ctx.options = options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target = ctx.saved_tensors
+        return ops.soft_ce_bwd(logits, target, g.contiguous().float(), 1.0, ctx.options), None, None
+
+
+class _SoftCELowres(Function):
+    """smp SoftCrossEntropyLoss of bilinear(low -> size) from the low-resolution map.  ``fused``: the forward also leaves the
+    unscaled patches of d(low) behind and the backward only reduces them (ops.soft_ce_lowres_fwd)."""
+
+    @staticmethod
+    def forward(ctx, low, target, size, options, fused):
+        loss, state = ops.soft_ce_lowres_fwd(low, target, size, options, fused=fused and ctx.needs_input_grad[0])
+        ctx.save_for_backward(low, target, state)
+        ctx.size, ctx.options = size, options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        low, target, state = ctx.saved_tensors
+        dlow = ops.soft_ce_lowres_bwd(low, target, ctx.size, g.contiguous().float(), 1.0, ctx.options, state=state)
+        return dlow, None, None, None, None
+
+
+# The low-resolution backward form: 1 = the forward emits the patches of d(low) (one softmax evaluation per pixel and step), 0 = the
+# backward recomputes them.  The default is the faster of the two at batch 64, K = 5, both DOFA heads (DESIGN.md section 2).
+SOFT_CE_LOWRES_FUSED = os.environ.get("GDL_SOFT_CE_FUSED", "1") != "0"
+
+
+class SoftCrossEntropyLoss(nn.Module):
+    """Drop-in for ``segmentation_models_pytorch.losses.SoftCrossEntropyLoss`` (smp 0.5.0 losses/soft_ce.py and
+    ``label_smoothed_nll_loss`` in losses/_functional.py), the loss of the reference's quick-start notebook
+    (notebooks/00_quickstart.ipynb: ``SoftCrossEntropyLoss(smooth_factor=0.1)``), evaluated by the gdl_soft_ce_* HIP kernels.
+    smp is not installed where this was written, so parity with smp itself is unpinned: the formula below is restated from its
+    source and tested against ``F.cross_entropy(..., label_smoothing=e, reduction="sum") / N``, which it equals.
+
+    With ``e = smooth_factor`` (None = 0), ``K`` classes and ``N = B*H*W`` (every pixel, ignored ones included), per valid pixel
+    ``L_i = logsumexp_k x_ik - (1 - e) x_{i,y_i} - (e / K) sum_k x_ik``; ``reduction="mean"`` is ``sum_i L_i / N`` -- the divisor is
+    N, not the valid count (smp zero-fills the masked entries and calls ``.mean()``; ``torch.nn.CrossEntropyLoss`` divides by the
+    valid count) -- and ``reduction="sum"`` is ``sum_i L_i``.  A pixel whose target equals ``ignore_index`` (compared as int64;
+    ``None``: no pixel) adds nothing and gets an exactly zero gradient.  A target outside ``0..K-1`` that is not ``ignore_index``
+    would trip a device assert in smp's ``gather``; here it is treated as ignored.  ``reduction="none"`` and ``dim != 1`` raise
+    ``NotImplementedError``.  Targets are ``[B,H,W]`` or ``[B,1,H,W]``.
+
+    ``y_pred`` may be ``LowresLogits`` (a DOFA training / validation step): the loss and d(low) come straight from the head's own
+    map, the [B, K, H, W] tensor is never written (K <= 16, factor <= 64 as for DiceLoss; other shapes materialise)."""
+
+    def __init__(self, reduction: str = "mean", smooth_factor: float | None = None, ignore_index: int | None = -100,
+                 dim: int = 1) -> None:
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            if reduction == "none":
+                raise NotImplementedError("gdlhip SoftCrossEntropyLoss implements reduction='mean' and 'sum' (got 'none')")
+            raise ValueError(f"SoftCrossEntropyLoss: unknown reduction {reduction!r}")
+        if dim != 1:
+            raise NotImplementedError(f"gdlhip SoftCrossEntropyLoss takes the class dimension at dim=1 (got dim={dim})")
+        eps = 0.0 if smooth_factor is None else float(smooth_factor)
+        if not math.isfinite(eps) or not 0.0 <= eps <= 1.0:
+            raise ValueError(f"SoftCrossEntropyLoss: smooth_factor must be a finite value in [0, 1] (got {smooth_factor!r})")
+        if ignore_index is not None:
+            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
+                raise ValueError(f"SoftCrossEntropyLoss: ignore_index must be an int64 value or None (got {ignore_index!r})")
+            ignore_index = int(ignore_index)
+        self.reduction, self.smooth_factor, self.ignore_index, self.dim = reduction, smooth_factor, ignore_index, dim
+        self.options = ops.SoftCEOptions(eps, ignore_index, reduction == "mean")
+
+    def forward(self, y_pred, y_true: Tensor) -> Tensor:
+        if isinstance(y_pred, LowresLogits):
+            size = (int(y_pred.size[0]), int(y_pred.size[1]))
+            yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
+            if (FUSE_LOWRES_DICE and ops.soft_ce_lowres_ok(y_pred.low, size) and y_pred.low.dtype == torch.float32
+                    and tuple(yt.shape[1:]) == size):
+                return _SoftCELowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.options, SOFT_CE_LOWRES_FUSED)
+            y_pred = y_pred.materialise()
+        if y_pred.dim() != 4:
+            raise ValueError(f"SoftCrossEntropyLoss: [B, K, H, W] logits expected (got {tuple(y_pred.shape)})")
+        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
+            y_pred = y_pred.float().contiguous()
+        if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
+            y_true = y_true[:, 0]
+        return _SoftCE.apply(y_pred, y_true.long().contiguous(), self.options)
+
+
+def reads_lowres(loss) -> bool:
+    """True for a loss that evaluates itself (and its gradient) from ``LowresLogits``: a task may then ask the model for the heads'
+    own maps instead of the resized [B, K, H, W] logits.  gdlhip's multiclass DiceLoss and SoftCrossEntropyLoss."""
+    if isinstance(loss, DiceLoss):
+        return loss.mode == "multiclass"
+    return isinstance(loss, SoftCrossEntropyLoss)
+
+
 def predict_mask(logits) -> Tensor:
     """``softmax(dim=1).argmax(dim=1)`` (segmentation_dofa.py:281).  For not-yet-resized logits (LowresLogits) the resize is
     evaluated per pixel inside the kernel: the same mask without the [B, K, H, W] tensor."""

@@ -2007,6 +2007,104 @@ def dice_binary_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream:
     return out
 
 
+class SoftCEOptions(NamedTuple):
+    """The constructor options of smp's SoftCrossEntropyLoss as the gdl_soft_ce_* entry points take them: ``smooth_factor`` in
+    [0, 1], ``ignore_index`` (any int64, or None) and ``mean`` (reduction "mean": divide by every pixel, ignored ones included)."""
+
+    smooth_factor: float = 0.0
+    ignore_index: int | None = -100
+    mean: bool = True
+
+    def c_args(self) -> tuple:
+        """(smooth, has_ignore, ignore, mean) in the order of the C calls"""
+        return (float(self.smooth_factor), int(self.ignore_index is not None), int(self.ignore_index or 0), int(bool(self.mean)))
+
+
+def _soft_ce_check(who: str, logits: Tensor, target: Tensor, want_target: tuple, layout: str) -> None:
+    _need_cuda(logits, target)
+    if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 4:
+        raise ValueError(f"{who}: contiguous f32 {layout} logits expected")
+    if target.dtype != torch.int64 or not target.is_contiguous() or tuple(target.shape) != want_target:
+        raise ValueError(f"{who}: contiguous int64 target {list(want_target)} expected, got {tuple(target.shape)}")
+
+
+def soft_ce_fwd(logits: Tensor, target: Tensor, options: SoftCEOptions = SoftCEOptions()) -> Tensor:
+    """smp SoftCrossEntropyLoss on NCHW f32 logits [B,K,H,W] and an int64 target [B,H,W]: the loss (0-dim f32)."""
+    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
+    _soft_ce_check("soft_ce", logits, target, (B, H, W), "NCHW")
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    lib = _lib.load()
+    nbytes = lib.gdl_soft_ce_workspace(B, K, H * W)
+    ws = torch.empty(nbytes // 8, device=logits.device, dtype=torch.float64)
+    check(lib.gdl_soft_ce_fwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(loss), _p(ws), nbytes, _stream()),
+          "gdl_soft_ce_fwd")
+    return loss
+
+
+def soft_ce_bwd(logits: Tensor, target: Tensor, upstream: Tensor | None, grad_scale: float = 1.0,
+                options: SoftCEOptions = SoftCEOptions(), out: Tensor | None = None, accumulate: bool = False) -> Tensor:
+    """d loss / d logits * upstream[0] * grad_scale (softmax recomputed from ``logits``); ``out``/``accumulate`` as dice_loss_bwd."""
+    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
+    _soft_ce_check("soft_ce", logits, target, (B, H, W), "NCHW")
+    _need_cuda(upstream, out)
+    if out is None:
+        out = torch.empty_like(logits)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != logits.shape:
+        raise ValueError("soft_ce_bwd: out must be a contiguous f32 tensor of the logits' shape")
+    check(_lib.load().gdl_soft_ce_bwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(upstream), grad_scale, _p(out),
+                                      int(accumulate), _stream()), "gdl_soft_ce_bwd")
+    return out
+
+
+def soft_ce_lowres_ok(low: Tensor, size: tuple[int, int]) -> bool:
+    """Shapes gdl_soft_ce_lowres_* take: those of gdl_dice_loss_lowres_* (K <= 16, an upsample by at most 64 per direction)."""
+    return dice_lowres_ok(low, size)
+
+
+def soft_ce_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], options: SoftCEOptions = SoftCEOptions(),
+                       fused: bool = False):
+    """The loss of bilinear(low -> size) vs target [B, H, W] without the full-resolution logits: ``(loss, state)``.  ``fused``: the
+    same pass also leaves the unscaled partial patches of d(low) in ``state`` (for soft_ce_lowres_bwd); where the shape does not
+    take that form (K > 8, resize close to 1:1), and without ``fused``, ``state`` is None and the backward recomputes."""
+    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
+    _soft_ce_check("soft_ce_lowres", low, target, (B, int(size[0]), int(size[1])), "NHWC low-resolution [B, h, w, K]")
+    loss = torch.empty((), device=low.device, dtype=torch.float32)
+    lib = _lib.load()
+    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
+    nstate = lib.gdl_soft_ce_lowres_fused_state(*dims) if fused else 0
+    if nstate:
+        state = torch.empty(nstate // 8 + 1, device=low.device, dtype=torch.float64)
+        check(lib.gdl_soft_ce_lowres_fused_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(state), state.numel() * 8,
+                                               _stream()), "gdl_soft_ce_lowres_fused_fwd")
+        return loss, state
+    nbytes = lib.gdl_soft_ce_lowres_workspace(B, K, dims[4], dims[5])
+    ws = torch.empty(nbytes // 8, device=low.device, dtype=torch.float64)
+    check(lib.gdl_soft_ce_lowres_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(ws), nbytes, _stream()),
+          "gdl_soft_ce_lowres_fwd")
+    return loss, None
+
+
+def soft_ce_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], upstream: Tensor | None, grad_scale: float = 1.0,
+                       options: SoftCEOptions = SoftCEOptions(), state: Tensor | None = None) -> Tensor:
+    """d loss / d low [B, h, w, K] * upstream[0] * grad_scale: the reduce of the forward's patches (``state`` of a fused forward)
+    or the recompute form (tile kernel for K <= 8, gather kernel otherwise)."""
+    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
+    _soft_ce_check("soft_ce_lowres", low, target, (B, int(size[0]), int(size[1])), "NHWC low-resolution [B, h, w, K]")
+    _need_cuda(upstream, state)
+    dlow = torch.empty_like(low)
+    lib = _lib.load()
+    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
+    if state is not None:
+        check(lib.gdl_soft_ce_lowres_fused_bwd(_p(state), state.numel() * state.element_size(), *dims, int(bool(options.mean)),
+                                               _p(upstream), grad_scale, _p(dlow), _stream()), "gdl_soft_ce_lowres_fused_bwd")
+        return dlow
+    nbytes = lib.gdl_soft_ce_lowres_bwd_workspace(*dims)
+    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    check(lib.gdl_soft_ce_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(upstream), grad_scale, _p(dlow), _p(ws), nbytes,
+                                     _stream()), "gdl_soft_ce_lowres_bwd")
+    return dlow
+
+
 # ------------------------------------------------------------------ optimizer
 def sumsq_accum(x: Tensor, acc: Tensor) -> None:
     check(_lib.load().gdl_sumsq(_p(x), x.numel(), _p(acc), _stream()), "gdl_sumsq")

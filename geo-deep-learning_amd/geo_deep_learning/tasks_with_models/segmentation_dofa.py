@@ -97,19 +97,18 @@ class SegmentationDOFA(SegmentationTaskHooks, LightningModule):
     def training_step(self, batch: dict[str, Any], batch_idx: int) -> Tensor:  # noqa: ARG002
         """segmentation_dofa.py:213-241."""
         from gdlhip import nn as gnn
-        fused = gnn.FUSE_LOWRES_DICE and isinstance(self.loss, gnn.DiceLoss) and self.loss.mode == "multiclass"
+        fused = gnn.FUSE_LOWRES_DICE and gnn.reads_lowres(self.loss)
         _, _, loss, bs = self._loss(batch, lowres_logits=fused)
         self.train_samples_count += bs
         self._log_loss("train_loss", loss, bs)
         return loss
 
     def _lowres_eval(self) -> bool:
-        """Validation / test need the two Dice terms and the arg-max mask of ``outputs.out``, nothing else of the logits: with gdlhip's
-        multiclass DiceLoss both come straight from the heads' own maps (``gnn.DiceLoss`` / ``gnn.predict_mask`` on LowresLogits: the
+        """Validation / test need the two loss terms and the arg-max mask of ``outputs.out``, nothing else of the logits: with gdlhip's
+        multiclass DiceLoss or SoftCrossEntropyLoss (``gnn.reads_lowres``) both come straight from the heads' own maps (``gnn.DiceLoss`` / ``gnn.predict_mask`` on LowresLogits: the
         same values, bit for bit, as from the resized [B, K, H, W] tensors, which are then never written)."""
         from gdlhip import nn as gnn
-        return (gnn.FUSE_LOWRES_DICE and isinstance(self.loss, gnn.DiceLoss) and self.loss.mode == "multiclass"
-                and self.num_classes > 1)
+        return gnn.FUSE_LOWRES_DICE and gnn.reads_lowres(self.loss) and self.num_classes > 1
 
     def validation_step(self, batch: dict[str, Any], batch_idx: int) -> Tensor:  # noqa: ARG002
         """segmentation_dofa.py:251-283."""

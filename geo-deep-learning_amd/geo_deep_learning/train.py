@@ -11,7 +11,8 @@ What is read from the yaml: ``model`` (any of the three task classes), ``data`` 
 default_root_dir plus the ``ModelCheckpoint`` / ``EarlyStopping`` entries of ``callbacks`` (monitor, mode, filename,
 patience).  MLflow logger, visualisation callbacks and strategy objects are control plane outside the hot path (SURVEY.md
 section 2) and are skipped with a log line.  Third-party classes that are absent map to the build's own:
-``segmentation_models_pytorch.losses.DiceLoss`` -> ``gdlhip.nn.DiceLoss``.
+``segmentation_models_pytorch.losses.DiceLoss`` -> ``gdlhip.nn.DiceLoss``,
+``segmentation_models_pytorch.losses.SoftCrossEntropyLoss`` -> ``gdlhip.nn.SoftCrossEntropyLoss``.
 """
 
 from __future__ import annotations
@@ -32,7 +33,8 @@ from gdlhip.trainer import MiniTrainer, seed_everything
 
 logger = logging.getLogger(__name__)
 
-CLASS_ALIASES = {"segmentation_models_pytorch.losses.DiceLoss": "gdlhip.nn.DiceLoss"}
+CLASS_ALIASES = {"segmentation_models_pytorch.losses.DiceLoss": "gdlhip.nn.DiceLoss",
+                 "segmentation_models_pytorch.losses.SoftCrossEntropyLoss": "gdlhip.nn.SoftCrossEntropyLoss"}
 CALLABLE_KEYS = ("optimizer", "scheduler")       # LightningCLI OptimizerCallable / LRSchedulerCallable arguments
 TRAINER_KEYS = ("max_epochs", "precision", "gradient_clip_val", "sync_batchnorm", "accumulate_grad_batches",
                 "limit_train_batches", "limit_val_batches", "limit_test_batches", "default_root_dir", "fast_dev_run")

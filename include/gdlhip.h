@@ -603,6 +603,45 @@ int gdl_dice_binary_loss_opt_bwd(const float* logits, const int64_t* target, int
                                  const gdl_dice_options* opt, const float* sums, const float* upstream, float grad_scale,
                                  float* dlogits, int accumulate, gdl_stream_t stream);
 
+/* smp 0.5.0 SoftCrossEntropyLoss(reduction, smooth_factor, ignore_index) (losses/soft_ce.py, label_smoothed_nll_loss in
+ * losses/_functional.py; the loss of notebooks/00_quickstart.ipynb) on NCHW f32 logits [B,K,HW] and an int64 target [B,HW].
+ * With e = smooth (in [0, 1]), N = B*HW and valid_i = (target_i != ignore when has_ignore) && 0 <= target_i < K (compared as
+ * int64; an out-of-range target is treated as ignored and never used as an index):
+ *   L_i = logsumexp_k x_ik - (1-e) x_{i,y_i} - (e/K) sum_k x_ik;   loss = sum_i valid_i L_i / N (mean != 0: the divisor counts
+ *   ignored pixels, as smp's zero-fill + .mean() does) or the plain sum (mean == 0);
+ *   dlogits_ik = upstream[0] (device scalar, may be null) * grad_scale * [/ N] * valid_i (softmax_k - (1-e)[k==y_i] - e/K).
+ * fwd: f64 per-workgroup partials in `workspace` (gdl_soft_ce_workspace() bytes, 8-byte aligned) added in a fixed order: no float
+ * atomics, the same bits on every launch.  bwd recomputes the softmax from the logits.  Any K >= 1 (K <= 16 from registers). */
+int64_t gdl_soft_ce_workspace(int B, int K, int64_t HW);
+int gdl_soft_ce_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float smooth, int has_ignore,
+                    int64_t ignore, int mean, float* loss, void* workspace, int64_t workspace_bytes, gdl_stream_t stream);
+int gdl_soft_ce_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float smooth, int has_ignore,
+                    int64_t ignore, int mean, const float* upstream, float grad_scale, float* dlogits, int accumulate,
+                    gdl_stream_t stream);
+/* The same loss of F.interpolate(head(x), size=(Ho, Wo), mode="bilinear") (dofa.py:89-105) WITHOUT the full-resolution logits:
+ * low = the [B, Hi, Wi, K] f32 map of gdl_head_1x1, target [B, Ho, Wo]; every output pixel's logits are evaluated on the fly with
+ * the expression of gdl_upsample_logits.  K <= 16, upsampling factors up to 64 per direction (as gdl_dice_loss_lowres_*).
+ * Recompute form: _fwd is a partial-sum pass (ws: gdl_soft_ce_lowres_workspace() bytes); _bwd writes dlow [B, Hi, Wi, K] f32 =
+ * d loss / d low, scaled as above, tile by tile when K <= 8 and ws holds gdl_soft_ce_lowres_bwd_workspace() bytes (each
+ * full-resolution softmax once, partial patches added in a fixed order), otherwise by one gather kernel (ws may be null). */
+int64_t gdl_soft_ce_lowres_workspace(int B, int K, int Ho, int Wo);
+int gdl_soft_ce_lowres_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float smooth,
+                           int has_ignore, int64_t ignore, int mean, float* loss, void* ws, int64_t ws_bytes, gdl_stream_t stream);
+int64_t gdl_soft_ce_lowres_bwd_workspace(int B, int K, int Hi, int Wi, int Ho, int Wo);
+int gdl_soft_ce_lowres_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float smooth,
+                           int has_ignore, int64_t ignore, int mean, const float* upstream, float grad_scale, float* dlow,
+                           float* ws, int64_t ws_bytes, gdl_stream_t stream);
+/* Fused form of the same pair (cross-entropy's per-pixel gradient needs no global sums): _fused_fwd forms the loss AND leaves the
+ * unscaled partial patches of d(low) in `state` (gdl_soft_ce_lowres_fused_state() bytes, 8-byte aligned, kept until the backward;
+ * 0: the shape does not take this form -- K > 8 or a resize too close to 1:1 -- use the recompute form); _fused_bwd is the
+ * fixed-order reduce of those patches times upstream[0] * grad_scale [/ N].  The full-resolution softmax is evaluated once per step. */
+int64_t gdl_soft_ce_lowres_fused_state(int B, int K, int Hi, int Wi, int Ho, int Wo);
+int gdl_soft_ce_lowres_fused_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float smooth,
+                                 int has_ignore, int64_t ignore, int mean, float* loss, void* state, int64_t state_bytes,
+                                 gdl_stream_t stream);
+int gdl_soft_ce_lowres_fused_bwd(const void* state, int64_t state_bytes, int B, int K, int Hi, int Wi, int Ho, int Wo, int mean,
+                                 const float* upstream, float grad_scale, float* dlow, gdl_stream_t stream);
+
 /* ---- fused bilinear x4 upsample -> 3x3 conv (multilevel_neck.py:157-158, scale 4) -------------------------------
  * gdl_pad_nhwc: NHWC border padding by (pad_h, pad_w), replicate (zero_mode 0) or zeros (1): out [B,H+2ph,W+2pw,C] dense.
  * gdl_subpix4_weights: the 16 phase weight sets of the sub-pixel decomposition from the 3x3 weights w [N][9*C]
