@@ -3,6 +3,7 @@
 #include <type_traits>
 
 #include <atomic>
+#include <cmath>
 
 #include "gdl_common.h"
 #include "bilinear_index.h"
@@ -978,13 +979,37 @@ __global__ __launch_bounds__(256) void class_probs_kernel(const float* __restric
 //   smooth, log_loss, classes -- DiceCoef: they only change how the per-class sums become the loss (dice_final_kernel) and the two
 //                   per-class gradient coefficients (dice_coeffs); `plain` (smooth == 0, no log, every class) selects the original
 //                   expressions so that the defaults stay bit-identical.
+// The Jaccard and Tversky losses (gdl_overlap_*) are other functions of the same three sums: `overlap` selects
+//   score_c = (I_c + smooth) / max(I_c + alpha (S_c - I_c) + beta (N_c - I_c) + smooth, eps)      (Jaccard: alpha = beta = 1)
+// and loss = m^gamma, m = the class mean of L(score_c).  Only dice_final_kernel and dice_coeffs read these fields: every pixel
+// pass is shared with Dice.
 struct DiceCoef {
   float smooth;
   uint32_t cls;     // bit k: class k takes part in the mean
   int nsel;         // number of set bits (the mean's divisor)
   int log_loss;
   int plain;
+  int overlap;      // 0: Dice.  1: the score above (plain == 0)
+  float alpha, beta, gamma;
 };
+
+// d(m^gamma)/dm = gamma m^(gamma-1) from the sums (K <= 21 scores: cheaper than a device scalar carried from forward to backward).
+// DEFINED AS 0 for m <= 0 when gamma != 1: torch gives inf (gamma < 1) and nan further down the chain for a perfect prediction.
+template <int K>
+__device__ __forceinline__ float overlap_focal_factor(const float* __restrict__ sums, float eps, const DiceCoef o) {
+  if (o.gamma == 1.f) return 1.f;
+  float m = 0.f;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const float I = sums[k], num = I + o.smooth;
+    const float den = I + o.alpha * (sums[K + k] - I) + o.beta * (sums[2 * K + k] - I) + o.smooth;
+    const float score = num / (den > eps ? den : eps);
+    const float l = o.log_loss ? -logf(score > eps ? score : eps) : 1.f - score;
+    m += (sums[2 * K + k] > 0.f && ((o.cls >> k) & 1u)) ? l : 0.f;
+  }
+  m /= (float)o.nsel;
+  return m > 0.f ? o.gamma * powf(m, o.gamma - 1.f) : 0.f;
+}
 
 // dL/dp_c = ca[c]*[y==c] + cb[c] from sums = [I | S | N]:  loss_c = L(score_c), score_c = (2 I_c + smooth) / max(S_c + N_c + smooth, eps),
 // L(s) = 1 - s or -log(max(s, eps)); weight [N_c > 0] * [c selected] / nsel.  `up` = upstream * grad_scale.
@@ -998,6 +1023,21 @@ __device__ __forceinline__ void dice_coeffs(const float* __restrict__ sums, floa
       const bool on = sums[2 * K + k] > 0.f && card > eps;
       ca[k] = on ? -2.f / (K * card) * up : 0.f;
       cb[k] = on ? 2.f * I / (K * card * card) * up : 0.f;
+    }
+  } else if (o.overlap) {
+    // score = N / D, N = I + smooth, D = I + alpha (S - I) + beta (Y - I) + smooth:  dD/dI = 1 - alpha - beta, dD/dS = alpha, so
+    // d score / dp = [y==c] (D - N dD/dI) / D^2 - N alpha / D^2; a clamped D is a constant (cb = 0), as in the Dice branch below
+    const float w = up / (float)o.nsel * overlap_focal_factor<K>(sums, eps, o);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float I = sums[k], num = I + o.smooth;
+      const float den = I + o.alpha * (sums[K + k] - I) + o.beta * (sums[2 * K + k] - I) + o.smooth;
+      const bool clamped = !(den > eps);
+      const float denc = clamped ? eps : den, score = num / denc;
+      float f = (sums[2 * K + k] > 0.f && ((o.cls >> k) & 1u)) ? -w : 0.f;
+      if (o.log_loss) f = score > eps ? f / score : 0.f;
+      ca[k] = clamped ? f / denc : f * (denc - num * (1.f - o.alpha - o.beta)) / (denc * denc);
+      cb[k] = clamped ? 0.f : -f * num * o.alpha / (denc * denc);
     }
   } else {
     const float w = up / (float)o.nsel;
@@ -1079,6 +1119,17 @@ __global__ __launch_bounds__(256) void dice_final_kernel(const float* __restrict
       if (tot[2 * K + k] > 0) l += 1.0 - dice;
     }
     loss[0] = (float)(l / K);
+  } else if (t == 0 && o.overlap) {
+    double l = 0;
+    for (int k = 0; k < K; ++k) {
+      if (!((o.cls >> k) & 1u) || !(tot[2 * K + k] > 0)) continue;
+      const double I = tot[k], num = I + o.smooth;
+      const double den = I + (double)o.alpha * (tot[K + k] - I) + (double)o.beta * (tot[2 * K + k] - I) + o.smooth;
+      const double score = num / (den > eps ? den : eps);
+      l += o.log_loss ? -log(score > eps ? score : (double)eps) : 1.0 - score;
+    }
+    const double m = l / o.nsel;
+    loss[0] = (float)(o.gamma == 1.f ? m : (m > 0 ? pow(m, (double)o.gamma) : 0.0));      // m <= 0: overlap_focal_factor
   } else if (t == 0) {
     double l = 0;
     for (int k = 0; k < K; ++k) {
@@ -2004,55 +2055,101 @@ extern "C" int64_t gdl_dice_loss_workspace(int B, int K, int64_t HW) {
 
 // gdl_dice_options (host) -> the kernels' arguments.  Null = smp's defaults.
 struct DiceHostOpt { bool ign; int64_t ignore; DiceCoef o; };
+// `classes` -> the bit mask and the mean's divisor (none listed: all K)
+static int dice_host_classes(const int* classes, int num_classes, int K, const char* who, DiceCoef& o) {
+  o.cls = K >= 32 ? 0xffffffffu : ((1u << K) - 1u); o.nsel = K;
+  if (num_classes < 0 || (num_classes > 0 && !classes)) {
+    gdl_set_error("%s: bad class list", who);
+    return GDL_ERR_INVALID;
+  }
+  if (num_classes > 0) {
+    o.cls = 0;
+    for (int i = 0; i < num_classes; ++i) {
+      const int c = classes[i];
+      if (c < 0 || c >= K || ((o.cls >> c) & 1u)) {
+        gdl_set_error("%s: classes must be distinct indices in 0..%d (got %d)", who, K - 1, c);
+        return GDL_ERR_INVALID;
+      }
+      o.cls |= 1u << c;
+    }
+    o.nsel = num_classes;
+  }
+  return GDL_OK;
+}
 static int dice_host_opt(const gdl_dice_options* opt, int K, const char* who, DiceHostOpt& h) {
   const uint32_t all = K >= 32 ? 0xffffffffu : ((1u << K) - 1u);
   h.ign = false; h.ignore = 0;
   h.o.smooth = 0.f; h.o.cls = all; h.o.nsel = K; h.o.log_loss = 0; h.o.plain = 1;
+  h.o.overlap = 0; h.o.alpha = h.o.beta = 0.5f; h.o.gamma = 1.f;
   if (!opt) return GDL_OK;
-  if (opt->num_classes < 0 || (opt->num_classes > 0 && !opt->classes)) {
-    gdl_set_error("%s: bad class list", who);
-    return GDL_ERR_INVALID;
-  }
-  if (opt->num_classes > 0) {
-    h.o.cls = 0;
-    for (int i = 0; i < opt->num_classes; ++i) {
-      const int c = opt->classes[i];
-      if (c < 0 || c >= K || ((h.o.cls >> c) & 1u)) {
-        gdl_set_error("%s: classes must be distinct indices in 0..%d (got %d)", who, K - 1, c);
-        return GDL_ERR_INVALID;
-      }
-      h.o.cls |= 1u << c;
-    }
-    h.o.nsel = opt->num_classes;
-  }
+  { const int st = dice_host_classes(opt->classes, opt->num_classes, K, who, h.o); if (st != GDL_OK) return st; }
   h.ign = opt->has_ignore_index != 0; h.ignore = opt->ignore_index;
   h.o.smooth = opt->smooth; h.o.log_loss = opt->log_loss != 0;
   h.o.plain = h.o.smooth == 0.f && !h.o.log_loss && h.o.cls == all;
   return GDL_OK;
 }
-#define DICE_OPT(who, K)                                                      \
+// gdl_overlap_options (host) -> the same arguments with DiceCoef::overlap set.  Jaccard is the Tversky score with alpha = beta = 1
+// and no focal exponent; it takes no ignore_index (smp's JaccardLoss has none).
+static int overlap_host_opt(const gdl_overlap_options* opt, int K, const char* who, DiceHostOpt& h) {
+  if (!opt) { gdl_set_error("%s: null options", who); return GDL_ERR_INVALID; }
+  { const int st = dice_host_classes(opt->classes, opt->nclasses, K, who, h.o); if (st != GDL_OK) return st; }
+  h.o.plain = 0; h.o.overlap = 1;
+  h.o.smooth = opt->smooth; h.o.log_loss = opt->log_loss != 0;
+  if (!std::isfinite(h.o.smooth)) { gdl_set_error("%s: smooth must be finite", who); return GDL_ERR_INVALID; }
+  if (opt->kind == GDL_OVERLAP_JACCARD) {
+    if (opt->has_ignore) { gdl_set_error("%s: the Jaccard loss takes no ignore_index", who); return GDL_ERR_INVALID; }
+    h.ign = false; h.ignore = 0;
+    h.o.alpha = h.o.beta = 1.f; h.o.gamma = 1.f;
+  } else if (opt->kind == GDL_OVERLAP_TVERSKY) {
+    if (!(opt->alpha >= 0.f && opt->beta >= 0.f && opt->gamma > 0.f) || !std::isfinite(opt->alpha) || !std::isfinite(opt->beta) ||
+        !std::isfinite(opt->gamma)) {
+      gdl_set_error("%s: finite alpha, beta >= 0 and gamma > 0 expected (got %g, %g, %g)", who, opt->alpha, opt->beta, opt->gamma);
+      return GDL_ERR_INVALID;
+    }
+    h.ign = opt->has_ignore != 0; h.ignore = opt->ignore_index;
+    h.o.alpha = opt->alpha; h.o.beta = opt->beta; h.o.gamma = opt->gamma;
+  } else {
+    gdl_set_error("%s: unknown kind %d (GDL_OVERLAP_JACCARD or GDL_OVERLAP_TVERSKY)", who, opt->kind);
+    return GDL_ERR_INVALID;
+  }
+  return GDL_OK;
+}
+// The *_run helpers serve both families: `oopt` (gdl_overlap_options) when the caller is a gdl_overlap_* entry point (`overlap`),
+// else `opt` (gdl_dice_options, may be null).  Converted after the pointer / size checks, as the Dice entry points always did.
+#define FAMILY_OPT(who, K)                                                    \
   DiceHostOpt h;                                                              \
-  { const int st_ = dice_host_opt(opt, K, who, h); if (st_ != GDL_OK) return st_; }
+  { const int st_ = overlap ? overlap_host_opt(oopt, K, who, h) : dice_host_opt(opt, K, who, h); if (st_ != GDL_OK) return st_; }
 // launch `kernel<..., IGN>` with IGN = h.ign (two instantiations; IGN = false is the code without the test)
 #define IGN_SWITCH(...)                                                       \
   if (h.ign) { constexpr bool IG = true; __VA_ARGS__; } else { constexpr bool IG = false; __VA_ARGS__; }
 
-extern "C" int gdl_dice_loss_opt_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
-                                     const gdl_dice_options* opt, float* sums, float* loss, float* ws, int64_t ws_bytes,
-                                     gdl_stream_t stream) {
-  GDL_CHECK_ARG(logits && target && sums && loss && ws, "gdl_dice_loss_fwd: null pointer");
-  GDL_CHECK_ARG(ws_bytes >= gdl_dice_loss_workspace(B, K, HW), "gdl_dice_loss_fwd: workspace too small");
-  DICE_OPT("gdl_dice_loss_fwd", K);
+// The launches behind the gdl_dice_*_opt_* and gdl_overlap_* entry points; `who` names the caller in error messages.
+static int dice_fwd_run(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps, const gdl_dice_options* opt,
+                        const gdl_overlap_options* oopt, bool overlap, const char* who, float* sums, float* loss, float* ws,
+                        int64_t ws_bytes, gdl_stream_t stream) {
+  GDL_CHECK_ARG(logits && target && sums && loss && ws, "%s: null pointer", who);
+  GDL_CHECK_ARG(ws_bytes >= gdl_dice_loss_workspace(B, K, HW), "%s: workspace too small", who);
+  FAMILY_OPT(who, K);
   const int nblk = dice_blocks((int64_t)B * HW);
   hipStream_t s = (hipStream_t)stream;
   K_SWITCH(K, IGN_SWITCH(hipLaunchKernelGGL((dice_partial_kernel<KK, IG>), dim3(nblk), dim3(256), 0, s, logits, target, B, HW, ws, h.ignore));
               hipLaunchKernelGGL((dice_final_kernel<KK>), dim3(1), dim3(256), 0, s, ws, nblk, eps, sums, loss, h.o));
-  GDL_CHECK_LAUNCH("gdl_dice_loss_fwd");
+  GDL_CHECK_LAUNCH(who);
   return GDL_OK;
+}
+extern "C" int gdl_dice_loss_opt_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
+                                     const gdl_dice_options* opt, float* sums, float* loss, float* ws, int64_t ws_bytes,
+                                     gdl_stream_t stream) {
+  return dice_fwd_run(logits, target, B, K, HW, eps, opt, nullptr, false, "gdl_dice_loss_fwd", sums, loss, ws, ws_bytes, stream);
 }
 extern "C" int gdl_dice_loss_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
                                  float* sums, float* loss, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
   return gdl_dice_loss_opt_fwd(logits, target, B, K, HW, eps, nullptr, sums, loss, ws, ws_bytes, stream);
+}
+extern "C" int gdl_overlap_loss_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
+                                    const gdl_overlap_options* opt, float* sums, float* loss, float* ws, int64_t ws_bytes,
+                                    gdl_stream_t stream) {
+  return dice_fwd_run(logits, target, B, K, HW, eps, nullptr, opt, true, "gdl_overlap_loss_fwd", sums, loss, ws, ws_bytes, stream);
 }
 
 // (four times the workgroups of dice_partial_kernel: the scattered 4-byte loads of the on-the-fly bilinear logit are a chain of L2
@@ -2068,25 +2165,36 @@ extern "C" int64_t gdl_dice_loss_lowres_workspace(int B, int K, int Ho, int Wo) 
 // Dice loss (multiclass) of bilinear(low -> [Ho, Wo]) against target [B, Ho, Wo] WITHOUT the full-resolution logits: low = the
 // [B, Hi, Wi, K] f32 map gdl_head_1x1 writes.  sums / loss as gdl_dice_loss_fwd; workspace of gdl_dice_loss_lowres_workspace(B, K, Ho,
 // Wo) bytes.  Upsampling factors up to 64 per direction.
-extern "C" int gdl_dice_loss_lowres_opt_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo,
-                                            float eps, const gdl_dice_options* opt, float* sums, float* loss, float* ws,
-                                            int64_t ws_bytes, gdl_stream_t stream) {
-  GDL_CHECK_ARG(low && target && sums && loss && ws, "gdl_dice_loss_lowres_fwd: null pointer");
-  GDL_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi, "gdl_dice_loss_lowres_fwd: bad sizes (an upsample is expected)");
+static int dice_lowres_fwd_run(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
+                               const gdl_dice_options* opt, const gdl_overlap_options* oopt, bool overlap,
+                               const char* who, float* sums, float* loss, float* ws, int64_t ws_bytes,
+                               gdl_stream_t stream) {
+  GDL_CHECK_ARG(low && target && sums && loss && ws, "%s: null pointer", who);
+  GDL_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi, "%s: bad sizes (an upsample is expected)", who);
   GDL_CHECK_ARG((Ho + Hi - 1) / Hi <= DICE_LOWRES_MAX_FACTOR && (Wo + Wi - 1) / Wi <= DICE_LOWRES_MAX_FACTOR,
-                "gdl_dice_loss_lowres_fwd: upsampling factors above 64 are not supported");
-  GDL_CHECK_ARG(ws_bytes >= gdl_dice_loss_lowres_workspace(B, K, Ho, Wo), "gdl_dice_loss_lowres_fwd: workspace too small");
-  DICE_OPT("gdl_dice_loss_lowres_fwd", K);
+                "%s: upsampling factors above 64 are not supported", who);
+  GDL_CHECK_ARG(ws_bytes >= gdl_dice_loss_lowres_workspace(B, K, Ho, Wo), "%s: workspace too small", who);
+  FAMILY_OPT(who, K);
   const int nblk = dice_lowres_blocks((int64_t)B * Ho * Wo);
   hipStream_t s = (hipStream_t)stream;
   K_SWITCH(K, IGN_SWITCH(hipLaunchKernelGGL((dice_lowres_partial_kernel<KK, IG>), dim3(nblk), dim3(256), 0, s, low, target, B, Hi, Wi, Ho, Wo, ws, h.ignore));
               hipLaunchKernelGGL((dice_final_kernel<KK>), dim3(1), dim3(256), 0, s, ws, nblk, eps, sums, loss, h.o));
-  GDL_CHECK_LAUNCH("gdl_dice_loss_lowres_fwd");
+  GDL_CHECK_LAUNCH(who);
   return GDL_OK;
+}
+extern "C" int gdl_dice_loss_lowres_opt_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo,
+                                            float eps, const gdl_dice_options* opt, float* sums, float* loss, float* ws,
+                                            int64_t ws_bytes, gdl_stream_t stream) {
+  return dice_lowres_fwd_run(low, target, B, K, Hi, Wi, Ho, Wo, eps, opt, nullptr, false, "gdl_dice_loss_lowres_fwd", sums, loss, ws, ws_bytes, stream);
 }
 extern "C" int gdl_dice_loss_lowres_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
                                         float* sums, float* loss, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
   return gdl_dice_loss_lowres_opt_fwd(low, target, B, K, Hi, Wi, Ho, Wo, eps, nullptr, sums, loss, ws, ws_bytes, stream);
+}
+extern "C" int gdl_overlap_loss_lowres_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo,
+                                           float eps, const gdl_overlap_options* opt, float* sums, float* loss, float* ws,
+                                           int64_t ws_bytes, gdl_stream_t stream) {
+  return dice_lowres_fwd_run(low, target, B, K, Hi, Wi, Ho, Wo, eps, nullptr, opt, true, "gdl_overlap_loss_lowres_fwd", sums, loss, ws, ws_bytes, stream);
 }
 
 static std::atomic<int> g_dice_tiled{1};
@@ -2109,14 +2217,15 @@ extern "C" int64_t gdl_dice_loss_lowres_bwd_workspace(int B, int K, int Hi, int 
 
 // d loss / d low [B, Hi, Wi, K] (f32, overwritten) from the sums of the forward; upstream (device scalar, may be null) * grad_scale
 // multiplies the gradient.  ws: gdl_dice_loss_lowres_bwd_workspace() bytes (may be null when that is 0).
-extern "C" int gdl_dice_loss_lowres_opt_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo,
-                                            float eps, const gdl_dice_options* opt, const float* sums, const float* upstream,
-                                            float grad_scale, float* dlow, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
-  GDL_CHECK_ARG(low && target && sums && dlow, "gdl_dice_loss_lowres_bwd: null pointer");
-  GDL_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi, "gdl_dice_loss_lowres_bwd: bad sizes");
+static int dice_lowres_bwd_run(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
+                               const gdl_dice_options* opt, const gdl_overlap_options* oopt, bool overlap,
+                               const char* who, const float* sums, const float* upstream, float grad_scale,
+                               float* dlow, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
+  GDL_CHECK_ARG(low && target && sums && dlow, "%s: null pointer", who);
+  GDL_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi, "%s: bad sizes", who);
   GDL_CHECK_ARG((Ho + Hi - 1) / Hi <= DICE_LOWRES_MAX_FACTOR && (Wo + Wi - 1) / Wi <= DICE_LOWRES_MAX_FACTOR,
-                "gdl_dice_loss_lowres_bwd: upsampling factors above 64 are not supported");
-  DICE_OPT("gdl_dice_loss_lowres_bwd", K);
+                "%s: upsampling factors above 64 are not supported", who);
+  FAMILY_OPT(who, K);
   {
     int ny, nx;
     const int64_t need = gdl_dice_loss_lowres_bwd_workspace(B, K, Hi, Wi, Ho, Wo);
@@ -2135,15 +2244,21 @@ extern "C" int gdl_dice_loss_lowres_opt_bwd(const float* low, const int64_t* tar
                                hipLaunchKernelGGL((dice_lowres_bwd_tile_kernel<(KK <= 8 ? KK : 8), IG>), dim3(tiles), dim3(DT_T), lds, st, a));
                     hipLaunchKernelGGL((dice_lowres_bwd_reduce_kernel<(KK <= 8 ? KK : 8)>), dim3(grid_for(total)), dim3(256), 0, st, a);
                   });
-      GDL_CHECK_LAUNCH("gdl_dice_loss_lowres_bwd");
+      GDL_CHECK_LAUNCH(who);
       return GDL_OK;
     }
   }
   const int64_t total = (int64_t)B * Hi * Wi;
   K_SWITCH(K, IGN_SWITCH(hipLaunchKernelGGL((dice_lowres_bwd_kernel<KK, IG>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, low,
                                             target, B, Hi, Wi, Ho, Wo, sums, eps, upstream, grad_scale, dlow, h.ignore, h.o)));
-  GDL_CHECK_LAUNCH("gdl_dice_loss_lowres_bwd");
+  GDL_CHECK_LAUNCH(who);
   return GDL_OK;
+}
+extern "C" int gdl_dice_loss_lowres_opt_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo,
+                                            float eps, const gdl_dice_options* opt, const float* sums, const float* upstream,
+                                            float grad_scale, float* dlow, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
+  return dice_lowres_bwd_run(low, target, B, K, Hi, Wi, Ho, Wo, eps, opt, nullptr, false, "gdl_dice_loss_lowres_bwd", sums, upstream, grad_scale, dlow,
+                             ws, ws_bytes, stream);
 }
 extern "C" int gdl_dice_loss_lowres_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
                                         const float* sums, const float* upstream, float grad_scale, float* dlow, float* ws,
@@ -2151,55 +2266,92 @@ extern "C" int gdl_dice_loss_lowres_bwd(const float* low, const int64_t* target,
   return gdl_dice_loss_lowres_opt_bwd(low, target, B, K, Hi, Wi, Ho, Wo, eps, nullptr, sums, upstream, grad_scale, dlow, ws, ws_bytes,
                                       stream);
 }
+extern "C" int gdl_overlap_loss_lowres_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo,
+                                           float eps, const gdl_overlap_options* opt, const float* sums, const float* upstream,
+                                           float grad_scale, float* dlow, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
+  return dice_lowres_bwd_run(low, target, B, K, Hi, Wi, Ho, Wo, eps, nullptr, opt, true, "gdl_overlap_loss_lowres_bwd", sums, upstream, grad_scale,
+                             dlow, ws, ws_bytes, stream);
+}
 
+static int dice_bwd_run(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps, const gdl_dice_options* opt,
+                        const gdl_overlap_options* oopt, bool overlap, const char* who, const float* sums, const float* upstream, float grad_scale, float* dlogits,
+                        int accumulate, gdl_stream_t stream) {
+  GDL_CHECK_ARG(logits && target && sums && dlogits, "%s: null pointer", who);
+  FAMILY_OPT(who, K);
+  const int64_t total = (int64_t)B * HW;
+  K_SWITCH(K, IGN_SWITCH(hipLaunchKernelGGL((dice_bwd_kernel<KK, IG>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, logits, target, B, HW, sums, eps, upstream, grad_scale, dlogits, accumulate, h.ignore, h.o)));
+  GDL_CHECK_LAUNCH(who);
+  return GDL_OK;
+}
 extern "C" int gdl_dice_loss_opt_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
                                      const gdl_dice_options* opt, const float* sums, const float* upstream, float grad_scale,
                                      float* dlogits, int accumulate, gdl_stream_t stream) {
-  GDL_CHECK_ARG(logits && target && sums && dlogits, "gdl_dice_loss_bwd: null pointer");
-  DICE_OPT("gdl_dice_loss_bwd", K);
-  const int64_t total = (int64_t)B * HW;
-  K_SWITCH(K, IGN_SWITCH(hipLaunchKernelGGL((dice_bwd_kernel<KK, IG>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, logits, target, B, HW, sums, eps, upstream, grad_scale, dlogits, accumulate, h.ignore, h.o)));
-  GDL_CHECK_LAUNCH("gdl_dice_loss_bwd");
-  return GDL_OK;
+  return dice_bwd_run(logits, target, B, K, HW, eps, opt, nullptr, false, "gdl_dice_loss_bwd", sums, upstream, grad_scale, dlogits, accumulate, stream);
 }
 extern "C" int gdl_dice_loss_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
                                  const float* sums, const float* upstream, float grad_scale, float* dlogits,
                                  int accumulate, gdl_stream_t stream) {
   return gdl_dice_loss_opt_bwd(logits, target, B, K, HW, eps, nullptr, sums, upstream, grad_scale, dlogits, accumulate, stream);
 }
+extern "C" int gdl_overlap_loss_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
+                                    const gdl_overlap_options* opt, const float* sums, const float* upstream, float grad_scale,
+                                    float* dlogits, int accumulate, gdl_stream_t stream) {
+  return dice_bwd_run(logits, target, B, K, HW, eps, nullptr, opt, true, "gdl_overlap_loss_bwd", sums, upstream, grad_scale, dlogits, accumulate, stream);
+}
 
-extern "C" int gdl_dice_binary_loss_opt_fwd(const float* logits, const int64_t* target, int64_t total, float eps,
-                                            const gdl_dice_options* opt, float* sums, float* loss, float* ws, int64_t ws_bytes,
-                                            gdl_stream_t stream) {
-  GDL_CHECK_ARG(logits && target && sums && loss && ws, "gdl_dice_binary_loss_fwd: null pointer");
+static int dice_binary_fwd_run(const float* logits, const int64_t* target, int64_t total, float eps, const gdl_dice_options* opt,
+                               const gdl_overlap_options* oopt, bool overlap, const char* who, float* sums, float* loss, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
+  GDL_CHECK_ARG(logits && target && sums && loss && ws, "%s: null pointer", who);
   const int nblk = dice_blocks(total);
-  GDL_CHECK_ARG(ws_bytes >= (int64_t)nblk * 3 * (int64_t)sizeof(float), "gdl_dice_binary_loss_fwd: workspace too small");
-  DICE_OPT("gdl_dice_binary_loss_fwd", 1);
+  GDL_CHECK_ARG(ws_bytes >= (int64_t)nblk * 3 * (int64_t)sizeof(float), "%s: workspace too small", who);
+  FAMILY_OPT(who, 1);
   hipStream_t s = (hipStream_t)stream;
   IGN_SWITCH(hipLaunchKernelGGL((dice_binary_partial_kernel<IG>), dim3(nblk), dim3(256), 0, s, logits, target, total, ws, h.ignore));
   hipLaunchKernelGGL((dice_final_kernel<1>), dim3(1), dim3(256), 0, s, ws, nblk, eps, sums, loss, h.o);
-  GDL_CHECK_LAUNCH("gdl_dice_binary_loss_fwd");
+  GDL_CHECK_LAUNCH(who);
   return GDL_OK;
+}
+extern "C" int gdl_dice_binary_loss_opt_fwd(const float* logits, const int64_t* target, int64_t total, float eps,
+                                            const gdl_dice_options* opt, float* sums, float* loss, float* ws, int64_t ws_bytes,
+                                            gdl_stream_t stream) {
+  return dice_binary_fwd_run(logits, target, total, eps, opt, nullptr, false, "gdl_dice_binary_loss_fwd", sums, loss, ws, ws_bytes, stream);
 }
 extern "C" int gdl_dice_binary_loss_fwd(const float* logits, const int64_t* target, int64_t total, float eps,
                                         float* sums, float* loss, float* ws, int64_t ws_bytes, gdl_stream_t stream) {
   return gdl_dice_binary_loss_opt_fwd(logits, target, total, eps, nullptr, sums, loss, ws, ws_bytes, stream);
 }
+extern "C" int gdl_overlap_binary_loss_fwd(const float* logits, const int64_t* target, int64_t total, float eps,
+                                           const gdl_overlap_options* opt, float* sums, float* loss, float* ws, int64_t ws_bytes,
+                                           gdl_stream_t stream) {
+  return dice_binary_fwd_run(logits, target, total, eps, nullptr, opt, true, "gdl_overlap_binary_loss_fwd", sums, loss, ws, ws_bytes, stream);
+}
 
+static int dice_binary_bwd_run(const float* logits, const int64_t* target, int64_t total, float eps, const gdl_dice_options* opt,
+                               const gdl_overlap_options* oopt, bool overlap, const char* who, const float* sums, const float* upstream, float grad_scale, float* dlogits,
+                               int accumulate, gdl_stream_t stream) {
+  GDL_CHECK_ARG(logits && target && sums && dlogits, "%s: null pointer", who);
+  FAMILY_OPT(who, 1);
+  IGN_SWITCH(hipLaunchKernelGGL((dice_binary_bwd_kernel<IG>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, logits, target,
+                                total, sums, eps, upstream, grad_scale, dlogits, accumulate, h.ignore, h.o));
+  GDL_CHECK_LAUNCH(who);
+  return GDL_OK;
+}
 extern "C" int gdl_dice_binary_loss_opt_bwd(const float* logits, const int64_t* target, int64_t total, float eps,
                                             const gdl_dice_options* opt, const float* sums, const float* upstream,
                                             float grad_scale, float* dlogits, int accumulate, gdl_stream_t stream) {
-  GDL_CHECK_ARG(logits && target && sums && dlogits, "gdl_dice_binary_loss_bwd: null pointer");
-  DICE_OPT("gdl_dice_binary_loss_bwd", 1);
-  IGN_SWITCH(hipLaunchKernelGGL((dice_binary_bwd_kernel<IG>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, logits, target,
-                                total, sums, eps, upstream, grad_scale, dlogits, accumulate, h.ignore, h.o));
-  GDL_CHECK_LAUNCH("gdl_dice_binary_loss_bwd");
-  return GDL_OK;
+  return dice_binary_bwd_run(logits, target, total, eps, opt, nullptr, false, "gdl_dice_binary_loss_bwd", sums, upstream, grad_scale, dlogits,
+                             accumulate, stream);
 }
 extern "C" int gdl_dice_binary_loss_bwd(const float* logits, const int64_t* target, int64_t total, float eps,
                                         const float* sums, const float* upstream, float grad_scale, float* dlogits,
                                         int accumulate, gdl_stream_t stream) {
   return gdl_dice_binary_loss_opt_bwd(logits, target, total, eps, nullptr, sums, upstream, grad_scale, dlogits, accumulate, stream);
+}
+extern "C" int gdl_overlap_binary_loss_bwd(const float* logits, const int64_t* target, int64_t total, float eps,
+                                           const gdl_overlap_options* opt, const float* sums, const float* upstream,
+                                           float grad_scale, float* dlogits, int accumulate, gdl_stream_t stream) {
+  return dice_binary_bwd_run(logits, target, total, eps, nullptr, opt, true, "gdl_overlap_binary_loss_bwd", sums, upstream, grad_scale, dlogits,
+                             accumulate, stream);
 }
 
 extern "C" int gdl_sumsq(const float* x, int64_t n, float* out_accum, gdl_stream_t stream) {

@@ -63,6 +63,18 @@ class DiceOptions(C.Structure):
     ]
 
 
+OVERLAP_JACCARD, OVERLAP_TVERSKY = 1, 2
+
+
+class OverlapOptions(C.Structure):
+    """Mirror of gdl_overlap_options (include/gdlhip.h)."""
+
+    _fields_ = [
+        ("kind", c_i), ("has_ignore", c_i), ("ignore_index", c_l), ("smooth", c_f), ("log_loss", c_i),
+        ("alpha", c_f), ("beta", c_f), ("gamma", c_f), ("classes", C.POINTER(c_i)), ("nclasses", c_i),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/gdlhip.h
 SIGNATURES = {
     "gdl_version": (c_i, []),
@@ -207,6 +219,12 @@ SIGNATURES = {
     "gdl_dice_binary_loss_bwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_f, c_p, c_i, c_p]),
     "gdl_dice_binary_loss_opt_fwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),
     "gdl_dice_binary_loss_opt_bwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_f, c_p, c_i, c_p]),
+    "gdl_overlap_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_l, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_overlap_loss_bwd": (c_i, [c_p, c_p, c_i, c_i, c_l, c_f, c_p, c_p, c_p, c_f, c_p, c_i, c_p]),
+    "gdl_overlap_loss_lowres_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_overlap_loss_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_f, c_p, c_p, c_l, c_p]),
+    "gdl_overlap_binary_loss_fwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_overlap_binary_loss_bwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_f, c_p, c_i, c_p]),
     "gdl_sumsq": (c_i, [c_p, c_l, c_p, c_p]),
     "gdl_clip_coef": (c_i, [c_p, c_f, c_p, c_p]),
     "gdl_multi_sumsq": (c_i, [c_p, c_i, c_p, c_p]),

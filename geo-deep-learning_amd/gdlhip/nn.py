@@ -1432,7 +1432,114 @@ class _DiceBinaryLoss(Function):
                 None, None, None)
 
 
-class DiceLoss(nn.Module):
+class _OverlapLoss(Function):
+    """Jaccard / Tversky (mode='multiclass') on full-resolution NCHW logits; ``options``: ops.OverlapOptions."""
+
+    @staticmethod
+    def forward(ctx, logits, target, eps, options):
+        loss, sums = ops.overlap_loss_fwd(logits, target, options, eps)
+        ctx.save_for_backward(logits, target, sums)
+        ctx.eps, ctx.options = eps, options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, sums = ctx.saved_tensors
+        return ops.overlap_loss_bwd(logits, target, sums, g.contiguous().float(), ctx.options, 1.0, ctx.eps), None, None, None
+
+
+class _OverlapLowres(Function):
+    """Jaccard / Tversky (mode='multiclass') of bilinear(low -> size), forward and backward from the low-resolution map."""
+
+    @staticmethod
+    def forward(ctx, low, target, size, eps, options):
+        loss, sums = ops.overlap_loss_lowres_fwd(low, target, size, options, eps)
+        ctx.save_for_backward(low, target, sums)
+        ctx.size, ctx.eps, ctx.options = size, eps, options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        low, target, sums = ctx.saved_tensors
+        dlow = ops.overlap_loss_lowres_bwd(low, target, ctx.size, sums, g.contiguous().float(), ctx.options, 1.0, ctx.eps)
+        return dlow, None, None, None, None
+
+
+class _OverlapBinaryLoss(Function):
+    """Jaccard / Tversky (mode='binary')."""
+
+    @staticmethod
+    def forward(ctx, logits, target, eps, options):
+        loss, sums = ops.overlap_binary_loss_fwd(logits, target, options, eps)
+        ctx.save_for_backward(logits, target, sums)
+        ctx.eps, ctx.options = eps, options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, sums = ctx.saved_tensors
+        return (ops.overlap_binary_loss_bwd(logits, target, sums, g.contiguous().float(), ctx.options, 1.0, ctx.eps),
+                None, None, None)
+
+
+class _DiceFamily(nn.Module):
+    """What DiceLoss, JaccardLoss and TverskyLoss share: the checks of smp's common constructor arguments and the forward that
+    picks the full-resolution, low-resolution (LowresLogits) or binary kernels.  A subclass names its three Functions and sets
+    ``mode``, ``eps``, ``classes`` and ``options``."""
+
+    _full = _lowres = _binary = None
+
+    def _check_common(self, mode, classes, from_logits, ignore_index, **floats):
+        """The validated (classes, ignore_index); ``floats``: named values that must be finite."""
+        name = type(self).__name__
+        if mode not in ("multiclass", "binary"):
+            msg = f"gdlhip {name} implements mode='multiclass' and mode='binary' (got {mode!r})"
+            raise NotImplementedError(msg)
+        if not from_logits:
+            raise NotImplementedError(f"gdlhip {name} takes logits (from_logits=True); from_logits=False is not implemented")
+        if classes is not None:
+            classes = tuple(int(c) for c in classes)
+            if len(classes) == 0 or len(set(classes)) != len(classes) or min(classes) < 0:
+                raise ValueError(f"{name}: classes must be a non-empty list of distinct class indices >= 0 (got {classes})")
+            if mode == "binary" and classes != (0,):
+                raise ValueError(f"{name}(binary) has the single class 0: classes must be None or [0] (got {list(classes)})")
+        if ignore_index is not None:
+            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
+                raise ValueError(f"{name}: ignore_index must be an int64 value or None (got {ignore_index!r})")
+            ignore_index = int(ignore_index)
+        for key, v in floats.items():
+            if not math.isfinite(v):
+                raise ValueError(f"{name}: {key} must be finite (got {v})")
+        return classes, ignore_index
+
+    def _check_classes(self, K: int) -> None:
+        if self.classes is not None and max(self.classes) >= K:
+            raise ValueError(f"{type(self).__name__}: classes {list(self.classes)} out of range for {K} classes")
+
+    def forward(self, y_pred, y_true: Tensor) -> Tensor:
+        if isinstance(y_pred, LowresLogits):
+            # a training step's not-yet-resized logits: the loss (and its gradient) straight from the low-resolution map
+            size = (int(y_pred.size[0]), int(y_pred.size[1]))
+            yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
+            if (self.mode == "multiclass" and FUSE_LOWRES_DICE and ops.dice_lowres_ok(y_pred.low, size)
+                    and y_pred.low.dtype == torch.float32 and tuple(yt.shape[1:]) == size):
+                self._check_classes(y_pred.low.shape[3])
+                return self._lowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.eps, self.options)
+            y_pred = y_pred.materialise()
+        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
+            y_pred = y_pred.float().contiguous()
+        if self.mode == "binary":
+            if y_pred.shape[0] != y_true.shape[0] or y_pred.numel() != y_true.numel():
+                msg = f"{type(self).__name__}(binary): y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} do not match"
+                raise ValueError(msg)
+            return self._binary.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
+        if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
+            y_true = y_true[:, 0]          # smp views the target as [B, -1]: an un-squeezed [B,1,H,W] mask is the same
+        self._check_classes(y_pred.shape[1])
+        return self._full.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
+
+
+class DiceLoss(_DiceFamily):
     """Drop-in for ``segmentation_models_pytorch.losses.DiceLoss`` (smp 0.5.0 losses/dice.py) in the two modes the reference's
     configs use: ``mode="multiclass"`` (configs/dofa_config_RGB.yaml:58-61, segformer) and ``mode="binary"``
     (configs/unetplus_config_RGB.yaml, ``num_classes: 1``), with smp's constructor options evaluated inside the HIP kernels:
@@ -1448,27 +1555,13 @@ class DiceLoss(nn.Module):
     option at its default the plain kernels run and the results are bit-identical to earlier builds.  ``from_logits=False`` is
     not implemented and raises."""
 
+    _full, _lowres, _binary = _DiceLoss, _DiceLowres, _DiceBinaryLoss
+
     def __init__(self, mode: str = "multiclass", classes=None, log_loss: bool = False, from_logits: bool = True,
                  smooth: float = 0.0, ignore_index=None, eps: float = 1e-7) -> None:
         super().__init__()
-        if mode not in ("multiclass", "binary"):
-            msg = f"gdlhip DiceLoss implements mode='multiclass' and mode='binary' (got {mode!r})"
-            raise NotImplementedError(msg)
-        if not from_logits:
-            raise NotImplementedError("gdlhip DiceLoss takes logits (from_logits=True); from_logits=False is not implemented")
-        if classes is not None:
-            classes = tuple(int(c) for c in classes)
-            if len(classes) == 0 or len(set(classes)) != len(classes) or min(classes) < 0:
-                raise ValueError(f"DiceLoss: classes must be a non-empty list of distinct class indices >= 0 (got {classes})")
-            if mode == "binary" and classes != (0,):
-                raise ValueError(f"DiceLoss(binary) has the single class 0: classes must be None or [0] (got {list(classes)})")
-        if ignore_index is not None:
-            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
-                raise ValueError(f"DiceLoss: ignore_index must be an int64 value or None (got {ignore_index!r})")
-            ignore_index = int(ignore_index)
         smooth = float(smooth)
-        if not math.isfinite(smooth):
-            raise ValueError(f"DiceLoss: smooth must be finite (got {smooth})")
+        classes, ignore_index = self._check_common(mode, classes, from_logits, ignore_index, smooth=smooth)
         self.mode, self.eps = mode, eps
         self.classes, self.log_loss, self.smooth, self.ignore_index = classes, bool(log_loss), smooth, ignore_index
         # None = smp's defaults: the plain entry points
@@ -1476,31 +1569,63 @@ class DiceLoss(nn.Module):
         if classes is not None or self.log_loss or smooth != 0.0 or ignore_index is not None:
             self.options = ops.DiceOptions(ignore_index, smooth, self.log_loss, classes)
 
-    def _check_classes(self, K: int) -> None:
-        if self.classes is not None and max(self.classes) >= K:
-            raise ValueError(f"DiceLoss: classes {list(self.classes)} out of range for {K} classes")
 
-    def forward(self, y_pred, y_true: Tensor) -> Tensor:
-        if isinstance(y_pred, LowresLogits):
-            # a training step's not-yet-resized logits: the loss (and its gradient) straight from the low-resolution map
-            size = (int(y_pred.size[0]), int(y_pred.size[1]))
-            yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
-            if (self.mode == "multiclass" and FUSE_LOWRES_DICE and ops.dice_lowres_ok(y_pred.low, size)
-                    and y_pred.low.dtype == torch.float32 and tuple(yt.shape[1:]) == size):
-                self._check_classes(y_pred.low.shape[3])
-                return _DiceLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.eps, self.options)
-            y_pred = y_pred.materialise()
-        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
-            y_pred = y_pred.float().contiguous()
-        if self.mode == "binary":
-            if y_pred.shape[0] != y_true.shape[0] or y_pred.numel() != y_true.numel():
-                msg = f"DiceLoss(binary): y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} do not match"
-                raise ValueError(msg)
-            return _DiceBinaryLoss.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
-        if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
-            y_true = y_true[:, 0]          # smp views the target as [B, -1]: an un-squeezed [B,1,H,W] mask is the same
-        self._check_classes(y_pred.shape[1])
-        return _DiceLoss.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
+class JaccardLoss(_DiceFamily):
+    """Stand-in for ``segmentation_models_pytorch.losses.JaccardLoss`` (smp 0.5.0 constructor signature and defaults) in modes
+    ``"multiclass"`` and ``"binary"``, evaluated by the gdl_overlap_* HIP entry points on the per-class sums the Dice kernels
+    reduce.  smp is not installed where this was written, so parity with smp itself is unpinned; the formula is:
+
+    with ``p`` = softmax (binary: sigmoid) of the logits, ``I_k = sum p_k [y=k]``, ``P_k = sum p_k``, ``Y_k = count(y=k)`` over
+    batch and pixels, ``score_k = (I_k + smooth) / max(P_k + Y_k - I_k + smooth, eps)``; the per-class loss is ``1 - score_k``, or
+    ``-log(max(score_k, eps))`` with ``log_loss``; a class with ``Y_k = 0`` contributes 0; the result is the mean over ``classes``
+    (all K when None; absent classes still count in the divisor).  There is no ``ignore_index``, as in smp.
+
+    Targets are ``[B,H,W]`` or ``[B,1,H,W]``.  ``y_pred`` may be ``LowresLogits``: in multiclass mode the loss and d(low) come
+    from the head's own map under DiceLoss's conditions (f32, K <= 16, factor <= 64); other cases materialise the logits.
+    ``mode="multilabel"`` and ``from_logits=False`` raise ``NotImplementedError``."""
+
+    _full, _lowres, _binary = _OverlapLoss, _OverlapLowres, _OverlapBinaryLoss
+
+    def __init__(self, mode: str = "multiclass", classes=None, log_loss: bool = False, from_logits: bool = True,
+                 smooth: float = 0.0, eps: float = 1e-7) -> None:
+        super().__init__()
+        smooth = float(smooth)
+        classes, _ = self._check_common(mode, classes, from_logits, None, smooth=smooth)
+        self.mode, self.eps = mode, eps
+        self.classes, self.log_loss, self.smooth = classes, bool(log_loss), smooth
+        self.options = ops.OverlapOptions("jaccard", None, smooth, self.log_loss, classes)
+
+
+class TverskyLoss(_DiceFamily):
+    """Stand-in for ``segmentation_models_pytorch.losses.TverskyLoss`` (smp 0.5.0 constructor signature and defaults), focal form
+    included, in modes ``"multiclass"`` and ``"binary"``, evaluated by the gdl_overlap_* HIP entry points.  smp is not installed
+    where this was written, so parity with smp itself is unpinned; the formula is:
+
+    with ``I_k``, ``P_k``, ``Y_k`` as in JaccardLoss, taken over the pixels whose target is not ``ignore_index``,
+    ``score_k = (I_k + smooth) / max(I_k + alpha (P_k - I_k) + beta (Y_k - I_k) + smooth, eps)`` (``alpha`` weighs false
+    positives, ``beta`` false negatives; ``alpha = beta = 0.5`` is Dice, ``alpha = beta = 1`` Jaccard); per-class loss, ``Y_k = 0``
+    rule and the mean ``m`` over ``classes`` as in JaccardLoss; the result is ``m ** gamma``.  Its gradient carries the factor
+    ``gamma * m ** (gamma - 1)``, which is DEFINED AS 0 WHEN ``m <= 0`` and ``gamma != 1`` (torch would give inf or nan there for
+    ``gamma < 1``: a perfect prediction gets a zero gradient, not a non-finite one), and the result itself is 0 there.
+    An ignored pixel gets an exactly zero gradient in every class.  ``alpha, beta >= 0`` and ``gamma > 0`` are required.
+
+    Targets, ``LowresLogits`` and the unimplemented arguments: as JaccardLoss."""
+
+    _full, _lowres, _binary = _OverlapLoss, _OverlapLowres, _OverlapBinaryLoss
+
+    def __init__(self, mode: str = "multiclass", classes=None, log_loss: bool = False, from_logits: bool = True,
+                 smooth: float = 0.0, ignore_index=None, eps: float = 1e-7, alpha: float = 0.5, beta: float = 0.5,
+                 gamma: float = 1.0) -> None:
+        super().__init__()
+        smooth, alpha, beta, gamma = float(smooth), float(alpha), float(beta), float(gamma)
+        classes, ignore_index = self._check_common(mode, classes, from_logits, ignore_index, smooth=smooth, alpha=alpha,
+                                                   beta=beta, gamma=gamma)
+        if alpha < 0.0 or beta < 0.0 or gamma <= 0.0:
+            raise ValueError(f"TverskyLoss: alpha, beta >= 0 and gamma > 0 are required (got {alpha}, {beta}, {gamma})")
+        self.mode, self.eps = mode, eps
+        self.classes, self.log_loss, self.smooth, self.ignore_index = classes, bool(log_loss), smooth, ignore_index
+        self.alpha, self.beta, self.gamma = alpha, beta, gamma
+        self.options = ops.OverlapOptions("tversky", ignore_index, smooth, self.log_loss, classes, alpha, beta, gamma)
 
 
 class _SoftCE(Function):
@@ -1598,8 +1723,9 @@ class SoftCrossEntropyLoss(nn.Module):
 
 def reads_lowres(loss) -> bool:
     """True for a loss that evaluates itself (and its gradient) from ``LowresLogits``: a task may then ask the model for the heads'
-    own maps instead of the resized [B, K, H, W] logits.  gdlhip's multiclass DiceLoss and SoftCrossEntropyLoss."""
-    if isinstance(loss, DiceLoss):
+    own maps instead of the resized [B, K, H, W] logits.  gdlhip's multiclass DiceLoss, JaccardLoss and TverskyLoss, and
+    SoftCrossEntropyLoss."""
+    if isinstance(loss, _DiceFamily):
         return loss.mode == "multiclass"
     return isinstance(loss, SoftCrossEntropyLoss)
 

@@ -2007,6 +2007,121 @@ def dice_binary_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream:
     return out
 
 
+class OverlapOptions(NamedTuple):
+    """What the gdl_overlap_* entry points take (gdl_overlap_options in include/gdlhip.h): ``kind`` "jaccard" or "tversky", then
+    ``ignore_index`` (any int64, or None; Tversky only), ``smooth``, ``log_loss``, ``classes`` as in DiceOptions, and Tversky's
+    ``alpha``, ``beta``, ``gamma`` (not read for Jaccard)."""
+
+    kind: str
+    ignore_index: int | None = None
+    smooth: float = 0.0
+    log_loss: bool = False
+    classes: tuple | None = None
+    alpha: float = 0.5
+    beta: float = 0.5
+    gamma: float = 1.0
+
+    def c_arg(self):
+        """(pointer for the C call, objects that must stay alive during it)"""
+        kind = {"jaccard": _lib.OVERLAP_JACCARD, "tversky": _lib.OVERLAP_TVERSKY}[self.kind]
+        arr = (C.c_int * len(self.classes))(*self.classes) if self.classes else None
+        o = _lib.OverlapOptions(kind, int(self.ignore_index is not None), int(self.ignore_index or 0), float(self.smooth),
+                                int(bool(self.log_loss)), float(self.alpha), float(self.beta), float(self.gamma),
+                                C.cast(arr, C.POINTER(C.c_int)) if arr is not None else None,
+                                len(self.classes) if self.classes else 0)
+        return C.addressof(o), (o, arr)
+
+
+def overlap_loss_fwd(logits: Tensor, target: Tensor, options: OverlapOptions, eps: float = 1e-7):
+    """(loss, sums) of the Jaccard / Tversky loss (mode "multiclass") on NCHW f32 logits; sums as dice_loss_fwd."""
+    _need_cuda(logits, target)
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("overlap_loss: contiguous f32 NCHW logits expected")
+    if target.dtype != torch.int64 or not target.is_contiguous():
+        raise ValueError("overlap_loss: contiguous int64 target expected")
+    B, K, H, W = logits.shape
+    sums = torch.empty(3 * K, device=logits.device, dtype=torch.float32)
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    lib = _lib.load()
+    nbytes = lib.gdl_dice_loss_workspace(B, K, H * W)
+    ws = torch.empty(nbytes // 4, device=logits.device, dtype=torch.float32)
+    opt, keep = options.c_arg()
+    check(lib.gdl_overlap_loss_fwd(_p(logits), _p(target), B, K, H * W, eps, opt, _p(sums), _p(loss), _p(ws), nbytes, _stream()),
+          "gdl_overlap_loss_fwd")
+    return loss, sums
+
+
+def overlap_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream: Tensor | None, options: OverlapOptions,
+                     grad_scale: float = 1.0, eps: float = 1e-7, out: Tensor | None = None, accumulate: bool = False) -> Tensor:
+    B, K, H, W = logits.shape
+    if out is None:
+        out = torch.empty_like(logits)
+    opt, keep = options.c_arg()
+    check(_lib.load().gdl_overlap_loss_bwd(_p(logits), _p(target), B, K, H * W, eps, opt, _p(sums), _p(upstream), grad_scale,
+                                           _p(out), int(accumulate), _stream()), "gdl_overlap_loss_bwd")
+    return out
+
+
+def overlap_loss_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], options: OverlapOptions, eps: float = 1e-7):
+    """The same loss of bilinear(low -> size) vs target [B, H, W] without the full-resolution logits (shapes: dice_lowres_ok)."""
+    _need_cuda(low, target)
+    if low.dtype != torch.float32 or not low.is_contiguous() or low.dim() != 4:
+        raise ValueError("overlap_loss_lowres: contiguous f32 NHWC low-resolution logits [B, h, w, K] expected")
+    B, Hi, Wi, K = low.shape
+    if target.dtype != torch.int64 or not target.is_contiguous() or tuple(target.shape) != (B, size[0], size[1]):
+        raise ValueError(f"overlap_loss_lowres: contiguous int64 target [B, {size[0]}, {size[1]}] expected, got {tuple(target.shape)}")
+    sums = torch.empty(3 * K, device=low.device, dtype=torch.float32)
+    loss = torch.empty((), device=low.device, dtype=torch.float32)
+    lib = _lib.load()
+    nbytes = lib.gdl_dice_loss_lowres_workspace(B, K, size[0], size[1])
+    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32)
+    opt, keep = options.c_arg()
+    check(lib.gdl_overlap_loss_lowres_fwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, opt, _p(sums), _p(loss), _p(ws),
+                                          nbytes, _stream()), "gdl_overlap_loss_lowres_fwd")
+    return loss, sums
+
+
+def overlap_loss_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], sums: Tensor, upstream: Tensor | None,
+                            options: OverlapOptions, grad_scale: float = 1.0, eps: float = 1e-7) -> Tensor:
+    B, Hi, Wi, K = low.shape
+    dlow = torch.empty_like(low)
+    lib = _lib.load()
+    nbytes = lib.gdl_dice_loss_lowres_bwd_workspace(B, K, Hi, Wi, size[0], size[1])
+    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    opt, keep = options.c_arg()
+    check(lib.gdl_overlap_loss_lowres_bwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, opt, _p(sums), _p(upstream),
+                                          grad_scale, _p(dlow), _p(ws), nbytes, _stream()), "gdl_overlap_loss_lowres_bwd")
+    return dlow
+
+
+def overlap_binary_loss_fwd(logits: Tensor, target: Tensor, options: OverlapOptions, eps: float = 1e-7):
+    """Mode "binary": logits [B,1,H,W] (or any shape) f32, target of the same numel, int64 0/1."""
+    _need_cuda(logits, target)
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("overlap_binary_loss: contiguous f32 logits expected")
+    if target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != logits.numel():
+        raise ValueError("overlap_binary_loss: contiguous int64 target with one entry per logit expected")
+    total = logits.numel()
+    sums = torch.empty(3, device=logits.device, dtype=torch.float32)
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    lib = _lib.load()
+    nbytes = lib.gdl_dice_loss_workspace(1, 1, total)
+    ws = torch.empty(nbytes // 4, device=logits.device, dtype=torch.float32)
+    opt, keep = options.c_arg()
+    check(lib.gdl_overlap_binary_loss_fwd(_p(logits), _p(target), total, eps, opt, _p(sums), _p(loss), _p(ws), nbytes, _stream()),
+          "gdl_overlap_binary_loss_fwd")
+    return loss, sums
+
+
+def overlap_binary_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream: Tensor | None, options: OverlapOptions,
+                            grad_scale: float = 1.0, eps: float = 1e-7) -> Tensor:
+    out = torch.empty_like(logits)
+    opt, keep = options.c_arg()
+    check(_lib.load().gdl_overlap_binary_loss_bwd(_p(logits), _p(target), logits.numel(), eps, opt, _p(sums), _p(upstream),
+                                                  grad_scale, _p(out), 0, _stream()), "gdl_overlap_binary_loss_bwd")
+    return out
+
+
 class SoftCEOptions(NamedTuple):
     """The constructor options of smp's SoftCrossEntropyLoss as the gdl_soft_ce_* entry points take them: ``smooth_factor`` in
     [0, 1], ``ignore_index`` (any int64, or None) and ``mean`` (reduction "mean": divide by every pixel, ignored ones included)."""

@@ -12,7 +12,9 @@ default_root_dir plus the ``ModelCheckpoint`` / ``EarlyStopping`` entries of ``c
 patience).  MLflow logger, visualisation callbacks and strategy objects are control plane outside the hot path (SURVEY.md
 section 2) and are skipped with a log line.  Third-party classes that are absent map to the build's own:
 ``segmentation_models_pytorch.losses.DiceLoss`` -> ``gdlhip.nn.DiceLoss``,
-``segmentation_models_pytorch.losses.SoftCrossEntropyLoss`` -> ``gdlhip.nn.SoftCrossEntropyLoss``.
+``segmentation_models_pytorch.losses.SoftCrossEntropyLoss`` -> ``gdlhip.nn.SoftCrossEntropyLoss``,
+``segmentation_models_pytorch.losses.JaccardLoss`` -> ``gdlhip.nn.JaccardLoss``,
+``segmentation_models_pytorch.losses.TverskyLoss`` -> ``gdlhip.nn.TverskyLoss``.
 """
 
 from __future__ import annotations
@@ -34,7 +36,9 @@ from gdlhip.trainer import MiniTrainer, seed_everything
 logger = logging.getLogger(__name__)
 
 CLASS_ALIASES = {"segmentation_models_pytorch.losses.DiceLoss": "gdlhip.nn.DiceLoss",
-                 "segmentation_models_pytorch.losses.SoftCrossEntropyLoss": "gdlhip.nn.SoftCrossEntropyLoss"}
+                 "segmentation_models_pytorch.losses.SoftCrossEntropyLoss": "gdlhip.nn.SoftCrossEntropyLoss",
+                 "segmentation_models_pytorch.losses.JaccardLoss": "gdlhip.nn.JaccardLoss",
+                 "segmentation_models_pytorch.losses.TverskyLoss": "gdlhip.nn.TverskyLoss"}
 CALLABLE_KEYS = ("optimizer", "scheduler")       # LightningCLI OptimizerCallable / LRSchedulerCallable arguments
 TRAINER_KEYS = ("max_epochs", "precision", "gradient_clip_val", "sync_batchnorm", "accumulate_grad_batches",
                 "limit_train_batches", "limit_val_batches", "limit_test_batches", "default_root_dir", "fast_dev_run")

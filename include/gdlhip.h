@@ -603,6 +603,58 @@ int gdl_dice_binary_loss_opt_bwd(const float* logits, const int64_t* target, int
                                  const gdl_dice_options* opt, const float* sums, const float* upstream, float grad_scale,
                                  float* dlogits, int accumulate, gdl_stream_t stream);
 
+/* The Jaccard and Tversky losses: the other members of the Dice family, functions of the same masked sums (I, P, Y) the
+ * gdl_dice_* kernels reduce (gdl_dice_options above defines them), run through the same pixel kernels.  `opt` must not be null;
+ * it is read on the host when the call is made.  With N_k = I_k + smooth:
+ *   kind GDL_OVERLAP_JACCARD: D_k = P_k + Y_k - I_k + smooth.  has_ignore must be 0 (smp's JaccardLoss has no ignore_index);
+ *                             alpha, beta, gamma are not read.
+ *   kind GDL_OVERLAP_TVERSKY: D_k = I_k + alpha (P_k - I_k) + beta (Y_k - I_k) + smooth;  finite alpha, beta >= 0, gamma > 0.
+ *   score_k = N_k / max(D_k, eps);  loss_k = 1 - score_k, or -log(max(score_k, eps)) with log_loss;  loss_k *= [Y_k > 0];
+ *   m = mean of loss_k over `classes` (nclasses distinct indices in 0..K-1; nclasses == 0: all K);  loss = m (Jaccard), m^gamma (Tversky).
+ * The gradient carries gamma m^(gamma-1), DEFINED AS 0 when m <= 0 and gamma != 1 (the loss is 0 there too): a perfect prediction
+ * gets a zero gradient where torch's pow would give inf / nan for gamma < 1.  m is recomputed from `sums` in the backward.  A
+ * denominator clamped to eps is a constant in the gradient, as for gdl_dice_options.  An ignored pixel's gradient is exactly 0. */
+#define GDL_OVERLAP_JACCARD 1
+#define GDL_OVERLAP_TVERSKY 2
+typedef struct {
+  int kind;
+  int has_ignore;
+  int64_t ignore_index;
+  float smooth;
+  int log_loss;
+  float alpha;
+  float beta;
+  float gamma;
+  const int* classes; /* host pointer; may be null when nclasses == 0 */
+  int nclasses;
+} gdl_overlap_options;
+
+/* smp 0.5.0 JaccardLoss / TverskyLoss(mode="multiclass") (losses/jaccard.py, losses/tversky.py) forward + backward on NCHW f32
+ * logits: arguments, sums [3*K], workspace (gdl_dice_loss_workspace) and summation order of gdl_dice_loss_opt_fwd / _bwd. */
+int gdl_overlap_loss_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
+                         const gdl_overlap_options* opt, float* sums, float* loss, float* workspace, int64_t workspace_bytes,
+                         gdl_stream_t stream);
+int gdl_overlap_loss_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float eps,
+                         const gdl_overlap_options* opt, const float* sums, const float* upstream, float grad_scale,
+                         float* dlogits, int accumulate, gdl_stream_t stream);
+/* The same losses of F.interpolate(head(x), size=(Ho, Wo), mode="bilinear") WITHOUT the full-resolution logits, as
+ * gdl_dice_loss_lowres_opt_fwd / _bwd: workspaces of gdl_dice_loss_lowres_workspace() / gdl_dice_loss_lowres_bwd_workspace() bytes,
+ * tiled backward for K <= 8, gather kernel otherwise, fixed order, no atomics. */
+int gdl_overlap_loss_lowres_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
+                                const gdl_overlap_options* opt, float* sums, float* loss, float* ws, int64_t ws_bytes,
+                                gdl_stream_t stream);
+int gdl_overlap_loss_lowres_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float eps,
+                                const gdl_overlap_options* opt, const float* sums, const float* upstream, float grad_scale,
+                                float* dlow, float* ws, int64_t ws_bytes, gdl_stream_t stream);
+/* smp JaccardLoss / TverskyLoss(mode="binary") on `total` logits of the single class, as gdl_dice_binary_loss_opt_fwd / _bwd
+ * (p = exp(logsigmoid(x)), [y==k] is y itself, workspace gdl_dice_loss_workspace(B, 1, HW); `classes` may only be empty or {0}). */
+int gdl_overlap_binary_loss_fwd(const float* logits, const int64_t* target, int64_t total, float eps,
+                                const gdl_overlap_options* opt, float* sums, float* loss, float* workspace,
+                                int64_t workspace_bytes, gdl_stream_t stream);
+int gdl_overlap_binary_loss_bwd(const float* logits, const int64_t* target, int64_t total, float eps,
+                                const gdl_overlap_options* opt, const float* sums, const float* upstream, float grad_scale,
+                                float* dlogits, int accumulate, gdl_stream_t stream);
+
 /* smp 0.5.0 SoftCrossEntropyLoss(reduction, smooth_factor, ignore_index) (losses/soft_ce.py, label_smoothed_nll_loss in
  * losses/_functional.py; the loss of notebooks/00_quickstart.ipynb) on NCHW f32 logits [B,K,HW] and an int64 target [B,HW].
  * With e = smooth (in [0, 1]), N = B*HW and valid_i = (target_i != ignore when has_ignore) && 0 <= target_i < K (compared as
