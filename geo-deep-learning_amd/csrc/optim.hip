@@ -1,5 +1,5 @@
 // Multi-tensor optimizer kernels: ONE launch covers every parameter tensor of the step.
-// The host passes a device table of chunks; row = {param, grad, exp_avg, exp_avg_sq, count, shadow} with the
+// The host passes a device table of chunks; row = {param, grad, buf0, buf1, count, shadow} (Adam / AdamW: exp_avg, exp_avg_sq; SGD: momentum buffer, 0) with the
 // pointers already offset to the chunk (<= 65536 elements each), all f32, dense.  shadow (0 = none) = a bf16 copy of the
 // parameter in the same element order (the GEMM operand the next forward reads): the update writes it too, so the step has
 // no per-parameter cast launches (28 per DOFA + UperNet step).
@@ -27,10 +27,13 @@ __global__ __launch_bounds__(256) void multi_sumsq_kernel(const int64_t* __restr
   if (threadIdx.x == 0) atomicAdd(acc, (red[0] + red[1]) + (red[2] + red[3]));
 }
 
-__global__ __launch_bounds__(256) void multi_adam_kernel(const int64_t* __restrict__ table, float lr, float b1, float b2,
-                                                         float eps, float wd, float bc1, float bc2,
-                                                         const float* __restrict__ clip_coef) {
-  const int64_t* row = table + (int64_t)blockIdx.x * ROW;
+// One chunk of the Adam / AdamW update, shared by the host- and device-hyper-parameter kernels.
+// DECOUPLED = false: torch.optim.Adam (weight decay added to the gradient).
+// DECOUPLED = true:  torch.optim.AdamW (the parameter is scaled by 1 - lr * wd first; the moments see the plain gradient).  With
+// wd == 0 the factor is exactly 1 and the results are the bits of the Adam instantiation.
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_chunk(const int64_t* __restrict__ row, float lr, float b1, float b2, float eps, float wd,
+                                           float bc1, float bc2, const float* __restrict__ clip_coef) {
   float* p = (float*)row[0];
   const float* g = (const float*)row[1];
   float* m = (float*)row[2];
@@ -39,17 +42,30 @@ __global__ __launch_bounds__(256) void multi_adam_kernel(const int64_t* __restri
   uint16_t* sh = (uint16_t*)row[5];
   const float cc = clip_coef ? clip_coef[0] : 1.f;
   const float step = lr / bc1, rs = 1.f / sqrtf(bc2);
+  // (in double, like the host's `1 - lr * weight_decay`: an f32 product would be off by an ulp of 1 for common lr * wd)
+  const float keep = DECOUPLED ? (float)(1.0 - (double)lr * (double)wd) : 1.f;
   for (int i = threadIdx.x; i < n; i += 256) {
     float gi = g[i] * cc;
     const float pi = p[i];
-    if (wd != 0.f) gi += wd * pi;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    // The fused multiply-adds are written out, in the form the compiler chose for the Adam kernel before it became a template:
+    // left to contraction, the two instantiations fused different products of the moment updates and differed in the last bit.
+    if (!DECOUPLED && wd != 0.f) gi = fmaf(wd, pi, gi);
+    const float mi = fmaf(b1, m[i], (1.f - b1) * gi);
+    const float vi = fmaf(b2, v[i], (1.f - b2) * gi * gi);
     m[i] = mi; v[i] = vi;
-    const float pn = pi - step * mi / (sqrtf(vi) * rs + eps);
+    const float q = step * mi / fmaf(sqrtf(vi), rs, eps);
+    // (decoupled: decay and update rounded once; with keep == 1 exactly the Adam difference)
+    const float pn = DECOUPLED ? fmaf(pi, keep, -q) : pi - q;
     p[i] = pn;
     if (sh) sh[i] = f32_to_bf16(pn);
   }
+}
+
+template <bool DECOUPLED>
+__global__ __launch_bounds__(256) void multi_adam_kernel(const int64_t* __restrict__ table, float lr, float b1, float b2,
+                                                         float eps, float wd, float bc1, float bc2,
+                                                         const float* __restrict__ clip_coef) {
+  adam_chunk<DECOUPLED>(table + (int64_t)blockIdx.x * ROW, lr, b1, b2, eps, wd, bc1, bc2, clip_coef);
 }
 
 // hipGraph-capturable form: the step count and the hyper-parameters live in DEVICE memory, so that a captured optimizer step
@@ -67,29 +83,60 @@ __global__ void adam_tick_kernel(float* __restrict__ st, double b1, double b2) {
   }
 }
 
+template <bool DECOUPLED>
 __global__ __launch_bounds__(256) void multi_adam_dev_kernel(const int64_t* __restrict__ table, const float* __restrict__ st,
                                                              const float* __restrict__ clip_coef) {
-  const int64_t* row = table + (int64_t)blockIdx.x * ROW;
+  adam_chunk<DECOUPLED>(table + (int64_t)blockIdx.x * ROW, st[1], st[2], st[3], st[4], st[5], st[6], st[7], clip_coef);
+}
+
+// torch.optim.SGD over the same chunk table: row = {param, grad, momentum_buffer (0 when momentum == 0), 0, count, shadow}.
+// `first` = this is the first step of the chunk's parameter: torch clones the gradient into the momentum buffer then, WITHOUT
+// the (1 - dampening) factor -- which a zero-initialised buffer would apply.
+__device__ __forceinline__ void sgd_chunk(const int64_t* __restrict__ row, float lr, float mu, float damp, bool nesterov, float wd,
+                                          bool first, const float* __restrict__ clip_coef) {
   float* p = (float*)row[0];
   const float* g = (const float*)row[1];
-  float* m = (float*)row[2];
-  float* v = (float*)row[3];
+  float* buf = (float*)row[2];
   const int n = (int)row[4];
   uint16_t* sh = (uint16_t*)row[5];
-  const float lr = st[1], b1 = st[2], b2 = st[3], eps = st[4], wd = st[5], bc1 = st[6], bc2 = st[7];
   const float cc = clip_coef ? clip_coef[0] : 1.f;
-  const float step = lr / bc1, rs = 1.f / sqrtf(bc2);
+  const float keep = 1.f - damp;
+  const bool momentum = mu != 0.f && buf != nullptr;
   for (int i = threadIdx.x; i < n; i += 256) {
     float gi = g[i] * cc;
     const float pi = p[i];
-    if (wd != 0.f) gi += wd * pi;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float pn = pi - step * mi / (sqrtf(vi) * rs + eps);
+    // (fused multiply-adds written out: the host- and the device-state kernel must round alike, whatever the compiler contracts)
+    if (wd != 0.f) gi = fmaf(wd, pi, gi);
+    if (momentum) {
+      const float bi = first ? gi : fmaf(mu, buf[i], keep * gi);
+      buf[i] = bi;
+      gi = nesterov ? fmaf(mu, bi, gi) : bi;
+    }
+    const float pn = fmaf(-lr, gi, pi);
     p[i] = pn;
     if (sh) sh[i] = f32_to_bf16(pn);
   }
+}
+
+__global__ __launch_bounds__(256) void multi_sgd_kernel(const int64_t* __restrict__ table, float lr, float mu, float damp,
+                                                        int nesterov, float wd, int first, const float* __restrict__ clip_coef) {
+  sgd_chunk(table + (int64_t)blockIdx.x * ROW, lr, mu, damp, nesterov != 0, wd, first != 0, clip_coef);
+}
+
+// capturable form: state = {step, lr, momentum, dampening, nesterov, weight_decay, first, 0} (f32) -- step and lr where the Adam
+// state keeps them; gdl_sgd_tick advances the step and derives `first` from it.
+__global__ void sgd_tick_kernel(float* __restrict__ st) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const float step = st[0] + 1.f;
+    st[0] = step;
+    st[6] = step == 1.f ? 1.f : 0.f;
+    st[7] = 0.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void multi_sgd_dev_kernel(const int64_t* __restrict__ table, const float* __restrict__ st,
+                                                            const float* __restrict__ clip_coef) {
+  sgd_chunk(table + (int64_t)blockIdx.x * ROW, st[1], st[2], st[3], st[4] != 0.f, st[5], st[6] != 0.f, clip_coef);
 }
 
 // Derived GEMM operands of the conv parameters, rebuilt from the freshly updated f32 parameters in ONE launch (the fused optimizer
@@ -159,7 +206,7 @@ extern "C" int gdl_adam_tick(float* state, double beta1, double beta2, gdl_strea
 extern "C" int gdl_multi_adam_dev(const int64_t* table, int nchunks, const float* state, const float* clip_coef, gdl_stream_t stream) {
   GDL_CHECK_ARG(table && state && nchunks >= 0, "gdl_multi_adam_dev: bad args");
   if (nchunks == 0) return GDL_OK;
-  hipLaunchKernelGGL(multi_adam_dev_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table, state, clip_coef);
+  hipLaunchKernelGGL(multi_adam_dev_kernel<false>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table, state, clip_coef);
   GDL_CHECK_LAUNCH("gdl_multi_adam_dev");
   return GDL_OK;
 }
@@ -176,8 +223,51 @@ extern "C" int gdl_multi_adam(const int64_t* table, int nchunks, float lr, float
                               float weight_decay, float bc1, float bc2, const float* clip_coef, gdl_stream_t stream) {
   GDL_CHECK_ARG(table && nchunks >= 0, "gdl_multi_adam: bad args");
   if (nchunks == 0) return GDL_OK;
-  hipLaunchKernelGGL(multi_adam_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table, lr, beta1, beta2, eps,
+  hipLaunchKernelGGL(multi_adam_kernel<false>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table, lr, beta1, beta2, eps,
                      weight_decay, bc1, bc2, clip_coef);
   GDL_CHECK_LAUNCH("gdl_multi_adam");
+  return GDL_OK;
+}
+
+extern "C" int gdl_multi_adamw(const int64_t* table, int nchunks, float lr, float beta1, float beta2, float eps,
+                               float weight_decay, float bc1, float bc2, const float* clip_coef, gdl_stream_t stream) {
+  GDL_CHECK_ARG(table && nchunks >= 0, "gdl_multi_adamw: bad args");
+  if (nchunks == 0) return GDL_OK;
+  hipLaunchKernelGGL(multi_adam_kernel<true>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table, lr, beta1, beta2, eps,
+                     weight_decay, bc1, bc2, clip_coef);
+  GDL_CHECK_LAUNCH("gdl_multi_adamw");
+  return GDL_OK;
+}
+
+extern "C" int gdl_multi_adamw_dev(const int64_t* table, int nchunks, const float* state, const float* clip_coef, gdl_stream_t stream) {
+  GDL_CHECK_ARG(table && state && nchunks >= 0, "gdl_multi_adamw_dev: bad args");
+  if (nchunks == 0) return GDL_OK;
+  hipLaunchKernelGGL(multi_adam_dev_kernel<true>, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table, state, clip_coef);
+  GDL_CHECK_LAUNCH("gdl_multi_adamw_dev");
+  return GDL_OK;
+}
+
+extern "C" int gdl_multi_sgd(const int64_t* table, int nchunks, float lr, float momentum, float dampening, int nesterov,
+                             float weight_decay, int first_step, const float* clip_coef, gdl_stream_t stream) {
+  GDL_CHECK_ARG(table && nchunks >= 0, "gdl_multi_sgd: bad args");
+  if (nchunks == 0) return GDL_OK;
+  hipLaunchKernelGGL(multi_sgd_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table, lr, momentum, dampening, nesterov,
+                     weight_decay, first_step, clip_coef);
+  GDL_CHECK_LAUNCH("gdl_multi_sgd");
+  return GDL_OK;
+}
+
+extern "C" int gdl_sgd_tick(float* state, gdl_stream_t stream) {
+  GDL_CHECK_ARG(state, "gdl_sgd_tick: null state");
+  hipLaunchKernelGGL(sgd_tick_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state);
+  GDL_CHECK_LAUNCH("gdl_sgd_tick");
+  return GDL_OK;
+}
+
+extern "C" int gdl_multi_sgd_dev(const int64_t* table, int nchunks, const float* state, const float* clip_coef, gdl_stream_t stream) {
+  GDL_CHECK_ARG(table && state && nchunks >= 0, "gdl_multi_sgd_dev: bad args");
+  if (nchunks == 0) return GDL_OK;
+  hipLaunchKernelGGL(multi_sgd_dev_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table, state, clip_coef);
+  GDL_CHECK_LAUNCH("gdl_multi_sgd_dev");
   return GDL_OK;
 }

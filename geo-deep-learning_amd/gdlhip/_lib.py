@@ -231,6 +231,11 @@ SIGNATURES = {
     "gdl_multi_adam": (c_i, [c_p, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p]),
     "gdl_adam_tick": (c_i, [c_p, C.c_double, C.c_double, c_p]),
     "gdl_multi_adam_dev": (c_i, [c_p, c_i, c_p, c_p, c_p]),
+    "gdl_multi_adamw": (c_i, [c_p, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p]),
+    "gdl_multi_adamw_dev": (c_i, [c_p, c_i, c_p, c_p, c_p]),
+    "gdl_multi_sgd": (c_i, [c_p, c_i, c_f, c_f, c_f, c_i, c_f, c_i, c_p, c_p]),
+    "gdl_sgd_tick": (c_i, [c_p, c_p]),
+    "gdl_multi_sgd_dev": (c_i, [c_p, c_i, c_p, c_p, c_p]),
     "gdl_multi_repack": (c_i, [c_p, c_i, c_l, c_p]),
     "gdl_adam_step": (c_i, [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p]),
 }

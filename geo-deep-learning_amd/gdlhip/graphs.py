@@ -5,8 +5,8 @@ At the reference's own per-GPU batch of 4 (configs/dofa_config_RGB.yaml:85) a DO
 launches of 5-20 us each: the GPU finishes them faster than the host can issue them (batch 2 and batch 4 took the same
 9.7 ms).  A captured step has no host work per kernel.  Everything the step does runs on torch's current stream through
 the C-ABI, allocates through torch's caching allocator (graph-private pool under capture) and keeps per-step scalars on
-the device (``FusedAdam(capturable=True)``: step count, bias corrections, learning rate), so ``torch.cuda.graph`` can
-record forward + loss + backward + clipping + Adam as they are.
+the device (``FusedAdam`` / ``FusedAdamW`` / ``FusedSGD`` with ``capturable=True``: step count, bias corrections, learning rate), so
+``torch.cuda.graph`` can record forward + loss + backward + clipping + the optimizer's update as they are.
 
 Rules (torch.cuda.graphs): static input buffers (new batches are COPIED into them), no host read-backs inside the step, a
 few eager warm-up steps on a side stream first (lazy initialisations, cached weight casts, kernel attributes).  DropPath /
@@ -126,8 +126,8 @@ def _copy_into(static: dict[str, Any], batch: dict[str, Any]) -> None:
 class GraphedTrainStep:
     """``loss = step(batch)`` == zero_grad -> autocast(training_step) -> backward -> optimizer.step(), replayed from a hipGraph.
 
-    ``task``: a LightningModule-shaped task (``training_step(batch, idx) -> loss``); ``optimizer``: ``FusedAdam`` created with
-    ``capturable=True``.  The returned loss is a static device tensor (read it after the next synchronisation point)."""
+    ``task``: a LightningModule-shaped task (``training_step(batch, idx) -> loss``); ``optimizer``: a gdlhip fused optimizer
+    (``FusedAdam``, ``FusedAdamW``, ``FusedSGD``) created with ``capturable=True``.  The returned loss is a static device tensor (read it after the next synchronisation point)."""
 
     def __init__(self, task, optimizer, example_batch: dict[str, Any], *, autocast_dtype: torch.dtype | None = torch.bfloat16,
                  warmup: int = 3, restore_state: bool = False) -> None:
@@ -137,7 +137,8 @@ class GraphedTrainStep:
         GEMM operands the optimizer kernel keeps in step with the parameters, and the CUDA RNG state are put back IN PLACE after
         the capture (the graph holds their addresses), so the first replay is the first training step."""
         if not getattr(optimizer, "capturable", False):
-            msg = "GraphedTrainStep needs FusedAdam(capturable=True): step count and learning rate must live on the device"
+            msg = ("GraphedTrainStep needs a fused optimizer created with capturable=True (FusedAdam, FusedAdamW, FusedSGD): step count "
+                   "and learning rate must live on the device")
             raise ValueError(msg)
         self.ddp = find_ddp(task)
         self.capture_stream = None

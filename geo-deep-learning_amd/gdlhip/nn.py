@@ -1742,18 +1742,21 @@ def predict_mask(logits) -> Tensor:
 
 
 # ------------------------------------------------------------------ optimizer
-class FusedAdam(torch.optim.Optimizer):
-    """torch.optim.Adam semantics with the update (and optional global-norm clipping, Lightning's
-    ``gradient_clip_val``) done by HIP kernels.  Reference: configs/dofa_config_RGB.yaml:11,62-65."""
+class _FusedOptimizer(torch.optim.Optimizer):
+    """What the fused optimizers share: one chunk table per param group (rows {param, grad, buf0, buf1, count, shadow}, cached on
+    the addresses), the fused global-norm clip (Lightning's ``gradient_clip_val``), the bf16 GEMM operands rewritten by the
+    update kernel, the one-launch rebuild of the derived operands, and the device-side state of the capturable form.  A subclass
+    supplies the per-parameter state, the two buffer columns of a row, slots 2..5 of the device state and the two launches."""
 
-    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0, max_grad_norm: float | None = None, capturable: bool = False) -> None:
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    CHUNK = 65536
+
+    def __init__(self, params, defaults: dict, max_grad_norm: float | None, capturable: bool) -> None:
+        super().__init__(params, defaults)
         self.max_grad_norm = max_grad_norm
         # capturable (torch.optim.Adam(capturable=True)): step count, bias corrections and hyper-parameters live in device
         # memory, so that a hipGraph-captured step (gdlhip.graphs) replays correctly; chunk tables come from pinned memory
         self.capturable = capturable
-        self._dev_state: dict = {}    # param group index -> f32[8] {step, lr, b1, b2, eps, wd, bc1, bc2}
+        self._dev_state: dict = {}    # param group index -> f32[8] {step, lr, <four hyper-parameters>, <two slots the tick kernel derives>}
         self._dev_lr: dict = {}       # param group index -> the learning rate last written to the device state
         self._table_bufs: dict = {}   # param group index -> (pinned, device) chunk-table buffers, allocated once
         self._acc = None
@@ -1765,6 +1768,34 @@ class FusedAdam(torch.optim.Optimizer):
         self._repack = None          # (signature, device table, tiles) of the derived-operand rebuild (refresh_derived)
         self._derived_last: list = []   # (cache key, operand, parameter) of the last refresh_derived
         self._repack_scan = None     # ((operand builds so far, registered parameters, updated parameters), entries) of the last scan
+
+    # ---- what a subclass supplies
+    def _init_state(self, group: dict, p: Tensor, st: dict) -> None:
+        """Create what is missing in the state of ``p`` (torch's key names; ``step`` is a host integer)."""
+        raise NotImplementedError
+
+    def _buffers(self, group: dict, st: dict) -> tuple:
+        """Addresses for columns 2 and 3 of the parameter's chunk rows (0 = none)."""
+        raise NotImplementedError
+
+    def _dev_hyper(self, group: dict) -> list:
+        """Slots 2..5 of the device state (slot 0 = step, 1 = lr; 6..7 are written by the tick kernel)."""
+        raise NotImplementedError
+
+    def _update(self, group: dict, table: Tensor, step: int, clip) -> None:
+        """The update of one chunk table with host hyper-parameters."""
+        raise NotImplementedError
+
+    def _update_dev(self, group: dict, table: Tensor, state: Tensor, clip) -> None:
+        """Tick + update of one chunk table with the hyper-parameters of the device state."""
+        raise NotImplementedError
+
+    def load_state_dict(self, state_dict) -> None:
+        """torch's own optimizers keep ``step`` as a tensor: here it is a host integer (it keys the chunk tables)."""
+        super().load_state_dict(state_dict)
+        for st in self.state.values():
+            if isinstance(st.get("step"), Tensor):
+                st["step"] = int(st["step"].item())
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -1780,10 +1811,7 @@ class FusedAdam(torch.optim.Optimizer):
         shadowed: list = []
         for gi, group, p in todo:
             st = self.state[p]
-            if not st:
-                st["step"] = 0
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            self._init_state(group, p, st)
             st["step"] += 1
             if p.grad.stride() != p.stride():
                 p.grad = _restride(p.grad, p)
@@ -1792,7 +1820,7 @@ class FusedAdam(torch.optim.Optimizer):
             sh = gemm_weight_shadow(p) if self.shadows else None
             if sh is not None:
                 shadowed.append((sh[0], sh[1], p))     # the tensor is held: the table's address stays valid
-            sig.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(),
+            sig.append((p.data_ptr(), p.grad.data_ptr(), *self._buffers(group, st), p.numel(),
                         0 if sh is None else sh[1].data_ptr()))
             mark_updated(p)
         tables = {}
@@ -1800,7 +1828,8 @@ class FusedAdam(torch.optim.Optimizer):
             sig = tuple(sig)
             hit = self._tables.get(key[0])
             if hit is None or hit[0] != sig:
-                rows = [(pp + 4 * off, gp + 4 * off, mp + 4 * off, vp + 4 * off, min(self.CHUNK, n - off), sp + 2 * off if sp else 0)
+                rows = [(pp + 4 * off, gp + 4 * off, mp + 4 * off if mp else 0, vp + 4 * off if vp else 0, min(self.CHUNK, n - off),
+                         sp + 2 * off if sp else 0)
                         for pp, gp, mp, vp, n, sp in sig for off in range(0, n, self.CHUNK)]
                 host = torch.tensor(rows, dtype=torch.int64)
                 hit = (sig, self._upload(key[0], host, dev))
@@ -1822,10 +1851,9 @@ class FusedAdam(torch.optim.Optimizer):
         for (gi, step), t in tables.items():
             group = self.param_groups[gi]
             if self.capturable:
-                ops.adam_tick(self.device_state(gi, dev), *group["betas"])
-                ops.multi_adam_dev(t, self._dev_state[gi], clip)
+                self._update_dev(group, t, self.device_state(gi, dev), clip)
             else:
-                ops.multi_adam(t, group["lr"], *group["betas"], group["eps"], group["weight_decay"], step, clip)
+                self._update(group, t, step, clip)
         self._shadowed = shadowed
         for key, val, p in shadowed:      # the kernels above rewrote the bf16 GEMM operands too
             refresh_shadow(key, val, p)
@@ -1896,7 +1924,7 @@ class FusedAdam(torch.optim.Optimizer):
                 n, c, t = p.shape[0], p.shape[1], p.shape[2] * p.shape[3]
                 cs = c1 - c0
                 if val.numel() != n * t * cs:
-                    msg = f"gdlhip FusedAdam: derived operand {tuple(val.shape)} does not match parameter {tuple(p.shape)}[{c0}:{c1}]"
+                    msg = f"gdlhip {type(self).__name__}: derived operand {tuple(val.shape)} does not match parameter {tuple(p.shape)}[{c0}:{c1}]"
                     raise ValueError(msg)
                 tiles_c = (cs + 31) // 32
                 rows.append((p.data_ptr(), val.data_ptr(), n, t, c, c0, cs, mode, tile0, tiles_c))
@@ -1909,14 +1937,15 @@ class FusedAdam(torch.optim.Optimizer):
         return len(ents)
 
     def device_state(self, gi: int, dev=None) -> Tensor:
-        """The device-side {step, lr, b1, b2, eps, wd, bc1, bc2} of param group gi (capturable mode), created from the group's
-        current hyper-parameters on first use.  A scheduler's new learning rate reaches a captured step through sync_lr()."""
+        """The device-side f32[8] state of param group gi (capturable mode; Adam / AdamW: {step, lr, b1, b2, eps, wd, bc1, bc2}),
+        created from the group's current hyper-parameters on first use.  A scheduler's new learning rate reaches a captured step
+        through sync_lr()."""
         st = self._dev_state.get(gi)
         if st is None:
             g = self.param_groups[gi]
             steps = {self.state[p]["step"] - 1 for p in g["params"] if p in self.state and self.state[p]}
             step0 = float(steps.pop()) if len(steps) == 1 else 0.0
-            st = torch.tensor([step0, g["lr"], *g["betas"], g["eps"], g["weight_decay"], 0.0, 0.0], dtype=torch.float32).to(dev)
+            st = torch.tensor([step0, g["lr"], *self._dev_hyper(g), 0.0, 0.0], dtype=torch.float32).to(dev)
             self._dev_state[gi] = st
             self._dev_lr[gi] = float(g["lr"])
         return st
@@ -1939,7 +1968,98 @@ class FusedAdam(torch.optim.Optimizer):
                 if st:
                     st["step"] += 1
 
-    CHUNK = 65536
+
+class _FusedAdamBase(_FusedOptimizer):
+    """Adam and AdamW: the same state, rows and device state; they differ in the kernel instantiation only."""
+
+    def __init__(self, params, lr, betas, eps, weight_decay, max_grad_norm, capturable) -> None:
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), max_grad_norm, capturable)
+
+    def _init_state(self, group, p, st) -> None:
+        if not st:
+            st["step"] = 0
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+
+    def _buffers(self, group, st) -> tuple:
+        return st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+
+    def _dev_hyper(self, group) -> list:
+        return [*group["betas"], group["eps"], group["weight_decay"]]
+
+
+class FusedAdam(_FusedAdamBase):
+    """torch.optim.Adam semantics with the update (and optional global-norm clipping, Lightning's
+    ``gradient_clip_val``) done by HIP kernels.  Reference: configs/dofa_config_RGB.yaml:11,62-65."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 0.0, max_grad_norm: float | None = None, capturable: bool = False) -> None:
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, capturable)
+
+    def _update(self, group, table, step, clip) -> None:
+        ops.multi_adam(table, group["lr"], *group["betas"], group["eps"], group["weight_decay"], step, clip)
+
+    def _update_dev(self, group, table, state, clip) -> None:
+        ops.adam_tick(state, *group["betas"])
+        ops.multi_adam_dev(table, state, clip)
+
+
+class FusedAdamW(_FusedAdamBase):
+    """torch.optim.AdamW semantics (decoupled weight decay: the parameter is scaled by ``1 - lr * weight_decay``, the moments
+    see the gradient alone) on the FusedAdam machinery: one launch per param group, fused clip, bf16 operands rewritten by the
+    update, capturable.  With ``weight_decay=0`` the results are FusedAdam's bits."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
+                 weight_decay: float = 1e-2, max_grad_norm: float | None = None, capturable: bool = False) -> None:
+        super().__init__(params, lr, betas, eps, weight_decay, max_grad_norm, capturable)
+
+    def _update(self, group, table, step, clip) -> None:
+        ops.multi_adamw(table, group["lr"], *group["betas"], group["eps"], group["weight_decay"], step, clip)
+
+    def _update_dev(self, group, table, state, clip) -> None:
+        ops.adam_tick(state, *group["betas"])
+        ops.multi_adamw_dev(table, state, clip)
+
+
+class FusedSGD(_FusedOptimizer):
+    """torch.optim.SGD semantics (momentum, dampening, nesterov, weight decay) on the FusedAdam machinery.  State keys are
+    torch's: ``momentum_buffer`` (absent when the group's momentum is 0) plus an integer ``step``.  The momentum buffer of a
+    parameter's first step is the gradient itself, dampening not applied; the kernel takes that from the step count (capturable:
+    from the group's device-side count, as the Adam bias corrections do), never from a zero-filled buffer."""
+
+    def __init__(self, params, lr: float, momentum: float = 0, dampening: float = 0, weight_decay: float = 0,
+                 nesterov: bool = False, max_grad_norm: float | None = None, capturable: bool = False) -> None:
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov),
+                         max_grad_norm, capturable)
+
+    def _init_state(self, group, p, st) -> None:
+        if group["momentum"] != 0 and st.get("momentum_buffer") is None:
+            st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["step"] = 0
+        # (a state written by torch.optim.SGD has a buffer and no count: whatever its count, the first step is behind it)
+        st.setdefault("step", 1 if "momentum_buffer" in st else 0)
+
+    def _buffers(self, group, st) -> tuple:
+        buf = st.get("momentum_buffer") if group["momentum"] != 0 else None
+        return (0 if buf is None else buf.data_ptr()), 0
+
+    def _dev_hyper(self, group) -> list:
+        return [group["momentum"], group["dampening"], float(bool(group["nesterov"])), group["weight_decay"]]
+
+    def _update(self, group, table, step, clip) -> None:
+        ops.multi_sgd(table, group["lr"], group["momentum"], group["dampening"], group["nesterov"], group["weight_decay"], step, clip)
+
+    def _update_dev(self, group, table, state, clip) -> None:
+        ops.sgd_tick(state)
+        ops.multi_sgd_dev(table, state, clip)
 
 
 def _flat(t: Tensor) -> Tensor:
@@ -1948,7 +2068,7 @@ def _flat(t: Tensor) -> Tensor:
         return t.view(-1)
     if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last):
         return t.permute(0, 2, 3, 1).reshape(-1)
-    msg = f"gdlhip FusedAdam: parameter layout {t.stride()} is not dense"
+    msg = f"gdlhip fused optimizer: parameter layout {t.stride()} is not dense"
     raise ValueError(msg)
 
 

@@ -2250,6 +2250,35 @@ def multi_adam_dev(table: Tensor, state: Tensor, clip: Tensor | None) -> None:
     check(_lib.load().gdl_multi_adam_dev(_p(table), table.shape[0], _p(state), _p(clip), _stream()), "gdl_multi_adam_dev")
 
 
+def multi_adamw(table: Tensor, lr: float, b1: float, b2: float, eps: float, wd: float, step: int,
+                clip: Tensor | None) -> None:
+    """torch.optim.AdamW (decoupled weight decay) over the chunk table, see gdl_multi_adamw."""
+    bc1, bc2 = 1.0 - b1**step, 1.0 - b2**step
+    check(_lib.load().gdl_multi_adamw(_p(table), table.shape[0], lr, b1, b2, eps, wd, bc1, bc2, _p(clip),
+                                      _stream()), "gdl_multi_adamw")
+
+
+def multi_adamw_dev(table: Tensor, state: Tensor, clip: Tensor | None) -> None:
+    check(_lib.load().gdl_multi_adamw_dev(_p(table), table.shape[0], _p(state), _p(clip), _stream()), "gdl_multi_adamw_dev")
+
+
+def multi_sgd(table: Tensor, lr: float, momentum: float, dampening: float, nesterov: bool, wd: float, step: int,
+              clip: Tensor | None) -> None:
+    """torch.optim.SGD over the chunk table, see gdl_multi_sgd; ``step`` = the step count of the table's parameters (the
+    momentum buffer is the gradient itself at step 1)."""
+    check(_lib.load().gdl_multi_sgd(_p(table), table.shape[0], lr, momentum, dampening, int(bool(nesterov)), wd, int(step == 1),
+                                    _p(clip), _stream()), "gdl_multi_sgd")
+
+
+def sgd_tick(state: Tensor) -> None:
+    """state[0] += 1 and the first-step flag refreshed, on the device (capturable SGD, see gdl_sgd_tick)."""
+    check(_lib.load().gdl_sgd_tick(_p(state), _stream()), "gdl_sgd_tick")
+
+
+def multi_sgd_dev(table: Tensor, state: Tensor, clip: Tensor | None) -> None:
+    check(_lib.load().gdl_multi_sgd_dev(_p(table), table.shape[0], _p(state), _p(clip), _stream()), "gdl_multi_sgd_dev")
+
+
 def multi_repack(table: Tensor, total_tiles: int) -> None:
     """Rebuild the bf16 operands derived from 3x3 conv parameters (channel-slice, tap-major, data-gradient layouts) listed in
     ``table`` (device int64 [rows, 10], see gdl_multi_repack) in one launch."""

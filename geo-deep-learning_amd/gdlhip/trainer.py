@@ -9,8 +9,10 @@ not installed.  It drives the task classes through exactly the 
 
 One process per GPU: under ``torchrun`` the inner ``model.model`` is wrapped in ``DistributedDataParallel`` (RCCL =
 backend "nccl"; "gloo" for the CPU tests), ``sync_batchnorm`` converts the BatchNorm containers, metrics are averaged
-over ranks.  ``torch.optim.Adam`` from ``configure_optimizers`` is executed by the fused multi-tensor Adam + clip kernels
-(``gdlhip.nn.FusedAdam``) on the SAME param groups, so schedulers keep working; any other optimizer runs as is.
+over ranks.  ``torch.optim.Adam``, ``AdamW`` or ``SGD`` from ``configure_optimizers`` is executed by the fused multi-tensor update
++ clip kernels (``gdlhip.nn.FusedAdam`` / ``FusedAdamW`` / ``FusedSGD``) on the SAME param groups, so schedulers keep working and the
+step can be captured into a hipGraph; any other optimizer, and one with ``amsgrad`` / ``maximize`` / ``capturable`` /
+``differentiable`` set, runs as is.
 Host logic only -- no tensor arithmetic of the hot path lives here.
 """
 
@@ -329,15 +331,25 @@ class MiniTrainer:
             dist.barrier()
 
     def _maybe_fuse(self, opt: torch.optim.Optimizer, device: torch.device, capturable: bool = False):
-        """torch.optim.Adam -> the fused multi-tensor Adam + clip kernels on the same param groups."""
-        if not (self.use_fused_adam and device.type == "cuda" and type(opt) is torch.optim.Adam):
+        """torch.optim.Adam / AdamW / SGD (exact types) -> the fused multi-tensor update + clip kernels on the same param groups
+        (SURVEY 8(f) rank 3).  Anything else, and any group with an option the kernels do not implement, runs as torch's own."""
+        if not (self.use_fused_adam and device.type == "cuda"):
             return opt
-        g0 = opt.param_groups[0]
-        if any(g.get("amsgrad") or g.get("maximize") or g.get("capturable") for g in opt.param_groups):
+        if any(g.get(k) for g in opt.param_groups for k in ("amsgrad", "maximize", "capturable", "differentiable")):
             return opt
-        from gdlhip.nn import FusedAdam
-        fused = FusedAdam(opt.param_groups, lr=g0["lr"], betas=g0["betas"], eps=g0["eps"],
-                          weight_decay=g0["weight_decay"], max_grad_norm=self.gradient_clip_val, capturable=capturable)
+        g0, clip = opt.param_groups[0], self.gradient_clip_val
+        from gdlhip import nn as gnn
+        if type(opt) is torch.optim.Adam:
+            fused = gnn.FusedAdam(opt.param_groups, lr=g0["lr"], betas=g0["betas"], eps=g0["eps"],
+                                  weight_decay=g0["weight_decay"], max_grad_norm=clip, capturable=capturable)
+        elif type(opt) is torch.optim.AdamW:
+            fused = gnn.FusedAdamW(opt.param_groups, lr=g0["lr"], betas=g0["betas"], eps=g0["eps"],
+                                   weight_decay=g0["weight_decay"], max_grad_norm=clip, capturable=capturable)
+        elif type(opt) is torch.optim.SGD:
+            fused = gnn.FusedSGD(opt.param_groups, lr=g0["lr"], momentum=g0["momentum"], dampening=g0["dampening"],
+                                 weight_decay=g0["weight_decay"], nesterov=g0["nesterov"], max_grad_norm=clip, capturable=capturable)
+        else:
+            return opt
         fused.param_groups = opt.param_groups            # the scheduler keeps writing `lr` into these dicts
         return fused
 

@@ -733,6 +733,24 @@ int gdl_multi_adam(const int64_t* table, int nchunks, float lr, float beta1, flo
  * advances the step and refreshes the two bias corrections, gdl_multi_adam_dev reads everything from `state` */
 int gdl_adam_tick(float* state, double beta1, double beta2, gdl_stream_t stream);   /* betas in double: bc = 1 - beta^step as the host computes it */
 int gdl_multi_adam_dev(const int64_t* table, int nchunks, const float* state, const float* clip_coef, gdl_stream_t stream);
+/* torch.optim.AdamW (decoupled weight decay) over the same chunk table: p *= 1 - lr * weight_decay first, the moments see the
+ * clipped gradient alone, then the Adam update.  Same kernel body as gdl_multi_adam; with weight_decay == 0 the same bits.
+ * gdl_multi_adamw_dev = torch.optim.AdamW(capturable=True): the Adam device state, advanced by gdl_adam_tick. */
+int gdl_multi_adamw(const int64_t* table, int nchunks, float lr, float beta1, float beta2, float eps,
+                    float weight_decay, float bc1, float bc2, const float* clip_coef,
+                    gdl_stream_t stream);
+int gdl_multi_adamw_dev(const int64_t* table, int nchunks, const float* state, const float* clip_coef, gdl_stream_t stream);
+/* torch.optim.SGD (momentum, dampening, nesterov, weight_decay) over the chunk table, rows {param*, grad*, momentum_buffer*
+ * (0 when momentum == 0), 0, count, shadow*}: g = grad * clip (+ weight_decay * p); with momentum buf = g on the first step of
+ * the parameter (first_step != 0: torch clones the gradient, dampening not applied), afterwards buf = momentum * buf +
+ * (1 - dampening) * g; g = g + momentum * buf (nesterov) or buf; p -= lr * g.  The bf16 shadow is rewritten like Adam's. */
+int gdl_multi_sgd(const int64_t* table, int nchunks, float lr, float momentum, float dampening, int nesterov,
+                  float weight_decay, int first_step, const float* clip_coef, gdl_stream_t stream);
+/* capturable form of torch.optim.SGD for a hipGraph replay: state = {step, lr, momentum, dampening, nesterov, weight_decay,
+ * first, 0} f32 in DEVICE memory (step and lr in the Adam state's slots); gdl_sgd_tick advances the step and sets
+ * first = (step == 1), gdl_multi_sgd_dev reads everything from `state` */
+int gdl_sgd_tick(float* state, gdl_stream_t stream);
+int gdl_multi_sgd_dev(const int64_t* table, int nchunks, const float* state, const float* clip_coef, gdl_stream_t stream);
 /* The bf16 GEMM operands DERIVED from 3x3 conv parameters, rebuilt in one launch behind the update (the reference has no
  * counterpart: cuDNN re-reads the f32 parameter; here they are the operands of models/decoders/upernet.py:144-152 and
  * models/necks/multilevel_neck.py:157-158 in their low-resolution forms and of every data gradient).  `table`: DEVICE array of
