@@ -172,3 +172,30 @@ __device__ __forceinline__ ACC ordered_sum8(int begin, int end, int step, F f) {
   for (; i < end; i += step) s += f(i);
   return s;
 }
+
+// ---- host launch helpers shared by the small-kernel files
+inline unsigned grid_for(int64_t total, int per_block = 256) {
+  int64_t g = (total + per_block - 1) / per_block;
+  return (unsigned)(g < 1 ? 1 : (g > 32768 ? 32768 : g));
+}
+// `__VA_ARGS__` with KK = the class count as a compile-time constant
+#define K_SWITCH(K, ...)                                                     \
+  switch (K) {                                                               \
+    case 1: { constexpr int KK = 1; __VA_ARGS__; } break;                    \
+    case 2: { constexpr int KK = 2; __VA_ARGS__; } break;                    \
+    case 3: { constexpr int KK = 3; __VA_ARGS__; } break;                    \
+    case 4: { constexpr int KK = 4; __VA_ARGS__; } break;                    \
+    case 5: { constexpr int KK = 5; __VA_ARGS__; } break;                    \
+    case 6: { constexpr int KK = 6; __VA_ARGS__; } break;                    \
+    case 7: { constexpr int KK = 7; __VA_ARGS__; } break;                    \
+    case 8: { constexpr int KK = 8; __VA_ARGS__; } break;                    \
+    case 9: { constexpr int KK = 9; __VA_ARGS__; } break;                    \
+    case 10: { constexpr int KK = 10; __VA_ARGS__; } break;                  \
+    case 11: { constexpr int KK = 11; __VA_ARGS__; } break;                  \
+    case 12: { constexpr int KK = 12; __VA_ARGS__; } break;                  \
+    case 13: { constexpr int KK = 13; __VA_ARGS__; } break;                  \
+    case 14: { constexpr int KK = 14; __VA_ARGS__; } break;                  \
+    case 15: { constexpr int KK = 15; __VA_ARGS__; } break;                  \
+    case 16: { constexpr int KK = 16; __VA_ARGS__; } break;                  \
+    default: gdl_set_error("num classes K=%d unsupported (1..16)", K); return GDL_ERR_UNSUPPORTED; \
+  }

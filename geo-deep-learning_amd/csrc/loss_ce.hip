@@ -28,11 +28,6 @@
 
 namespace {
 
-inline unsigned grid_for(int64_t total, int per_block = 256) {
-  int64_t g = (total + per_block - 1) / per_block;
-  return (unsigned)(g < 1 ? 1 : (g > 32768 ? 32768 : g));
-}
-
 struct CeOpt {
   float keep;       // 1 - smooth_factor
   float uni;        // smooth_factor / K
@@ -434,27 +429,6 @@ __global__ __launch_bounds__(256) void ce_lowres_reduce_kernel(const CeTile a) {
 }  // namespace
 
 // ============================================================================ C ABI
-#define CE_K_SWITCH(K, ...)                                                  \
-  switch (K) {                                                               \
-    case 1: { constexpr int KK = 1; __VA_ARGS__; } break;                    \
-    case 2: { constexpr int KK = 2; __VA_ARGS__; } break;                    \
-    case 3: { constexpr int KK = 3; __VA_ARGS__; } break;                    \
-    case 4: { constexpr int KK = 4; __VA_ARGS__; } break;                    \
-    case 5: { constexpr int KK = 5; __VA_ARGS__; } break;                    \
-    case 6: { constexpr int KK = 6; __VA_ARGS__; } break;                    \
-    case 7: { constexpr int KK = 7; __VA_ARGS__; } break;                    \
-    case 8: { constexpr int KK = 8; __VA_ARGS__; } break;                    \
-    case 9: { constexpr int KK = 9; __VA_ARGS__; } break;                    \
-    case 10: { constexpr int KK = 10; __VA_ARGS__; } break;                  \
-    case 11: { constexpr int KK = 11; __VA_ARGS__; } break;                  \
-    case 12: { constexpr int KK = 12; __VA_ARGS__; } break;                  \
-    case 13: { constexpr int KK = 13; __VA_ARGS__; } break;                  \
-    case 14: { constexpr int KK = 14; __VA_ARGS__; } break;                  \
-    case 15: { constexpr int KK = 15; __VA_ARGS__; } break;                  \
-    case 16: { constexpr int KK = 16; __VA_ARGS__; } break;                  \
-    default: gdl_set_error("num classes K=%d unsupported (1..16)", K); return GDL_ERR_UNSUPPORTED; \
-  }
-
 static int ce_host_opt(const char* who, int K, float smooth, int has_ignore, int64_t ignore, CeOpt& o) {
   GDL_CHECK_ARG(K >= 1, "%s: K=%d classes", who, K);
   GDL_CHECK_ARG(smooth >= 0.f && smooth <= 1.f, "%s: smooth_factor %g outside [0, 1]", who, (double)smooth);
@@ -492,7 +466,7 @@ extern "C" int gdl_soft_ce_fwd(const float* logits, const int64_t* target, int B
   if (K > 16) {
     hipLaunchKernelGGL(ce_partial_any_kernel, dim3(nblk), dim3(256), 0, s, logits, target, B, K, HW, part, o);
   } else {
-    CE_K_SWITCH(K, hipLaunchKernelGGL((ce_partial_kernel<KK>), dim3(nblk), dim3(256), 0, s, logits, target, B, HW, part, o));
+    K_SWITCH(K, hipLaunchKernelGGL((ce_partial_kernel<KK>), dim3(nblk), dim3(256), 0, s, logits, target, B, HW, part, o));
   }
   hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, mean ? 1.0 / (double)total : 1.0, loss);
   GDL_CHECK_LAUNCH("gdl_soft_ce_fwd");
@@ -511,7 +485,7 @@ extern "C" int gdl_soft_ce_bwd(const float* logits, const int64_t* target, int B
   if (K > 16) {
     hipLaunchKernelGGL(ce_bwd_any_kernel, dim3(grid_for(total)), dim3(256), 0, s, logits, target, B, K, HW, upstream, scale, dlogits, accumulate, o);
   } else {
-    CE_K_SWITCH(K, hipLaunchKernelGGL((ce_bwd_kernel<KK>), dim3(grid_for(total)), dim3(256), 0, s, logits, target, B, HW, upstream, scale, dlogits, accumulate, o));
+    K_SWITCH(K, hipLaunchKernelGGL((ce_bwd_kernel<KK>), dim3(grid_for(total)), dim3(256), 0, s, logits, target, B, HW, upstream, scale, dlogits, accumulate, o));
   }
   GDL_CHECK_LAUNCH("gdl_soft_ce_bwd");
   return GDL_OK;
@@ -547,7 +521,7 @@ extern "C" int gdl_soft_ce_lowres_fwd(const float* low, const int64_t* target, i
   const int nblk = ce_lowres_blocks(total);
   hipStream_t s = (hipStream_t)stream;
   double* part = (double*)ws;
-  CE_K_SWITCH(K, hipLaunchKernelGGL((ce_lowres_partial_kernel<KK>), dim3(nblk), dim3(256), 0, s, low, target, B, Hi, Wi, Ho, Wo, part, o));
+  K_SWITCH(K, hipLaunchKernelGGL((ce_lowres_partial_kernel<KK>), dim3(nblk), dim3(256), 0, s, low, target, B, Hi, Wi, Ho, Wo, part, o));
   hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, mean ? 1.0 / (double)total : 1.0, loss);
   GDL_CHECK_LAUNCH("gdl_soft_ce_lowres_fwd");
   return GDL_OK;
@@ -568,7 +542,7 @@ static int64_t ce_tiles(int B, int Ho, int Wo) { return (int64_t)B * ((Ho + CT_H
 template <bool LOSS>
 static int ce_launch_tiles(CeTile& a, int K, int ny, int nx, hipStream_t st) {
   const unsigned tiles = (unsigned)ce_tiles(a.B, a.Ho, a.Wo);
-  CE_K_SWITCH(K, if (KK <= 8) {
+  K_SWITCH(K, if (KK <= 8) {
                    constexpr int K8 = KK <= 8 ? KK : 8;
                    const size_t lds = ((size_t)K8 * CT_H * CT_W + (size_t)K8 * ny * (CT_W + 1) + (size_t)ny * CT_H + (size_t)nx * CT_W) * sizeof(float);
                    GDL_SET_MAX_LDS_ONCE((ce_lowres_tile_kernel<K8, LOSS>), 159 * 1024);
@@ -578,7 +552,7 @@ static int ce_launch_tiles(CeTile& a, int K, int ny, int nx, hipStream_t st) {
 }
 static int ce_launch_reduce(const CeTile& a, int K, hipStream_t st) {
   const int64_t total = (int64_t)a.B * a.Hi * a.Wi;
-  CE_K_SWITCH(K, if (KK <= 8) hipLaunchKernelGGL((ce_lowres_reduce_kernel<(KK <= 8 ? KK : 8)>), dim3(grid_for(total)), dim3(256), 0, st, a));
+  K_SWITCH(K, if (KK <= 8) hipLaunchKernelGGL((ce_lowres_reduce_kernel<(KK <= 8 ? KK : 8)>), dim3(grid_for(total)), dim3(256), 0, st, a));
   return GDL_OK;
 }
 
@@ -614,7 +588,7 @@ extern "C" int gdl_soft_ce_lowres_bwd(const float* low, const int64_t* target, i
     return GDL_OK;
   }
   const int64_t total = (int64_t)B * Hi * Wi;
-  CE_K_SWITCH(K, hipLaunchKernelGGL((ce_lowres_bwd_gather_kernel<KK>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, low, target, B, Hi,
+  K_SWITCH(K, hipLaunchKernelGGL((ce_lowres_bwd_gather_kernel<KK>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, low, target, B, Hi,
                                     Wi, Ho, Wo, upstream, scale, dlow, o));
   GDL_CHECK_LAUNCH("gdl_soft_ce_lowres_bwd");
   return GDL_OK;

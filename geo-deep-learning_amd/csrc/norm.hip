@@ -1200,7 +1200,7 @@ extern "C" int gdl_bn_bwd_dx(const void* x, const void* dy, void* dx, int dtype,
 // Dense 16-byte aligned bf16 x with C == 256, P >= 4096 (the shapes where those three take their 16-byte kernels), f32 head
 // weights w [K][256] 16-byte aligned.  Single-process statistics.  The A/B hooks of the kernels these replace (gdl_debug_set_bn_wide,
 // gdl_debug_set_head_mfma) do not reach here: there is one form of each pass, selected by the caller (GDL_FUSE_BN_TAIL in gdlhip/nn.py).
-// K goes through a switch of its own: misc.hip's K_SWITCH instantiates up to 16 classes, these kernels hold K x 8 weights per lane.
+// K goes through a switch of its own: gdl_common.h's K_SWITCH instantiates up to 16 classes, these kernels hold K x 8 weights per lane.
 int head_bwd_w_final_launch(const float* ws, int nsplit, int C, int K, float* dw, float* db, hipStream_t s);   // misc.hip
 
 extern "C" int gdl_bn_head_bwd_ok(int dtype, int64_t P, int C, int K) {

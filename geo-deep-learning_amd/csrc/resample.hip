@@ -2308,7 +2308,7 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const void* __restrict
   }
 }
 
-inline unsigned grid_for(int64_t total) {
+inline unsigned resample_grid_for(int64_t total) {
   int64_t g = (total + 255) / 256;
   return (unsigned)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
 }
@@ -2694,14 +2694,14 @@ static int bilinear_fwd_impl(const void* in, int in_dtype, int B, int Hi, int Wi
       hipLaunchKernelGGL(bilinear_fwd8_rows_kernel, dim3((unsigned)((Wo * (C / 8) + 255) / 256), (unsigned)(B * Ho)), dim3(256), 0,
                          (hipStream_t)stream, in, Hi, Wi, C, isB, isH, isW, out, Ho, Wo, osB, osH, osW, accumulate);
     else
-    hipLaunchKernelGGL(bilinear_fwd8_kernel, dim3(grid_for(total8)), dim3(256), 0, (hipStream_t)stream, in, B, Hi, Wi, C,
+    hipLaunchKernelGGL(bilinear_fwd8_kernel, dim3(resample_grid_for(total8)), dim3(256), 0, (hipStream_t)stream, in, B, Hi, Wi, C,
                        isB, isH, isW, out, Ho, Wo, osB, osH, osW, accumulate);
     GDL_CHECK_LAUNCH("gdl_bilinear_fwd");
     return GDL_OK;
   }
   if (base) return GDL_ERR_UNSUPPORTED;
   const int64_t total = (int64_t)B * Ho * Wo * (C / 4);
-  DISPATCH2(bilinear_fwd_kernel, in_dtype, out_dtype, dim3(grid_for(total)), dim3(256), 0,
+  DISPATCH2(bilinear_fwd_kernel, in_dtype, out_dtype, dim3(resample_grid_for(total)), dim3(256), 0,
             (hipStream_t)stream, in, B, Hi, Wi, C, isB, isH, isW, out, Ho, Wo, osB, osH, osW, accumulate);
   GDL_CHECK_LAUNCH("gdl_bilinear_fwd");
   return GDL_OK;
@@ -2820,13 +2820,13 @@ extern "C" int gdl_bilinear_bwd(const void* dout, int dout_dtype, int B, int Ho,
                          (hipStream_t)stream, dout, Ho, Wo, C, osB, osH, osW, din, Hi, Wi, isB, isH, isW, accumulate);
     } else
 #undef BWD_ROWS
-    hipLaunchKernelGGL(bilinear_bwd8_kernel, dim3(grid_for(total8)), dim3(256), 0, (hipStream_t)stream, dout, B, Ho, Wo,
+    hipLaunchKernelGGL(bilinear_bwd8_kernel, dim3(resample_grid_for(total8)), dim3(256), 0, (hipStream_t)stream, dout, B, Ho, Wo,
                        C, osB, osH, osW, din, Hi, Wi, isB, isH, isW, accumulate);
     GDL_CHECK_LAUNCH("gdl_bilinear_bwd");
     return GDL_OK;
   }
   const int64_t total = (int64_t)B * Hi * Wi * (C / 4);
-  DISPATCH2(bilinear_bwd_kernel, dout_dtype, din_dtype, dim3(grid_for(total)), dim3(256), 0,
+  DISPATCH2(bilinear_bwd_kernel, dout_dtype, din_dtype, dim3(resample_grid_for(total)), dim3(256), 0,
             (hipStream_t)stream, dout, B, Ho, Wo, C, osB, osH, osW, din, Hi, Wi, isB, isH, isW, accumulate);
   GDL_CHECK_LAUNCH("gdl_bilinear_bwd");
   return GDL_OK;
@@ -2913,7 +2913,7 @@ extern "C" int gdl_adaptive_avgpool_fwd(const void* in, int dtype, int B, int Hi
     GDL_CHECK_LAUNCH("gdl_adaptive_avgpool_fwd");
     return GDL_OK;
   }
-  DISPATCH2(avgpool_fwd_kernel, dtype, out_dtype, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in,
+  DISPATCH2(avgpool_fwd_kernel, dtype, out_dtype, dim3(resample_grid_for(total)), dim3(256), 0, (hipStream_t)stream, in,
             B, Hi, Wi, C, isB, isH, isW, out, So);
   GDL_CHECK_LAUNCH("gdl_adaptive_avgpool_fwd");
   return GDL_OK;
@@ -2925,7 +2925,7 @@ extern "C" int gdl_adaptive_avgpool_bwd(const void* dout, int dtype, int B, int 
   GDL_CHECK_ARG(dout && din && So > 0, "gdl_adaptive_avgpool_bwd: bad args");
   GDL_CHECK_ARG(C % 4 == 0 && isB % 4 == 0 && isH % 4 == 0 && isW % 4 == 0, "gdl_adaptive_avgpool_bwd: C/strides % 4");
   const int64_t total = (int64_t)B * Hi * Wi * (C / 4);
-  DISPATCH2(avgpool_bwd_kernel, dtype, din_dtype, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream,
+  DISPATCH2(avgpool_bwd_kernel, dtype, din_dtype, dim3(resample_grid_for(total)), dim3(256), 0, (hipStream_t)stream,
             dout, B, So, C, din, Hi, Wi, isB, isH, isW, accumulate);
   GDL_CHECK_LAUNCH("gdl_adaptive_avgpool_bwd");
   return GDL_OK;

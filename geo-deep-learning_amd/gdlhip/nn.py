@@ -1383,7 +1383,8 @@ def logits_from_low(low: Tensor, size, lowres: bool = False):
 
 
 class _DiceLoss(Function):
-    """smp DiceLoss(mode='multiclass') (configs/dofa_config_RGB.yaml:58-61); ``options``: ops.DiceOptions or None (defaults)."""
+    """smp DiceLoss(mode='multiclass') (configs/dofa_config_RGB.yaml:58-61), and Jaccard / Tversky on the same kernels;
+    ``options``: None (Dice defaults), ops.DiceOptions or ops.OverlapOptions."""
 
     @staticmethod
     def forward(ctx, logits, target, eps, options=None):
@@ -1399,7 +1400,7 @@ class _DiceLoss(Function):
 
 
 class _DiceLowres(Function):
-    """smp DiceLoss(mode='multiclass') of bilinear(low -> size), forward and backward from the low-resolution map."""
+    """The same losses of bilinear(low -> size), forward and backward from the low-resolution map."""
 
     @staticmethod
     def forward(ctx, low, target, size, eps, options=None):
@@ -1416,7 +1417,7 @@ class _DiceLowres(Function):
 
 
 class _DiceBinaryLoss(Function):
-    """smp DiceLoss(mode='binary') (configs/unetplus_config_RGB.yaml:40-47, num_classes 1)."""
+    """smp DiceLoss(mode='binary') (configs/unetplus_config_RGB.yaml:40-47, num_classes 1), and Jaccard / Tversky (binary)."""
 
     @staticmethod
     def forward(ctx, logits, target, eps, options=None):
@@ -1432,62 +1433,10 @@ class _DiceBinaryLoss(Function):
                 None, None, None)
 
 
-class _OverlapLoss(Function):
-    """Jaccard / Tversky (mode='multiclass') on full-resolution NCHW logits; ``options``: ops.OverlapOptions."""
-
-    @staticmethod
-    def forward(ctx, logits, target, eps, options):
-        loss, sums = ops.overlap_loss_fwd(logits, target, options, eps)
-        ctx.save_for_backward(logits, target, sums)
-        ctx.eps, ctx.options = eps, options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, target, sums = ctx.saved_tensors
-        return ops.overlap_loss_bwd(logits, target, sums, g.contiguous().float(), ctx.options, 1.0, ctx.eps), None, None, None
-
-
-class _OverlapLowres(Function):
-    """Jaccard / Tversky (mode='multiclass') of bilinear(low -> size), forward and backward from the low-resolution map."""
-
-    @staticmethod
-    def forward(ctx, low, target, size, eps, options):
-        loss, sums = ops.overlap_loss_lowres_fwd(low, target, size, options, eps)
-        ctx.save_for_backward(low, target, sums)
-        ctx.size, ctx.eps, ctx.options = size, eps, options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        low, target, sums = ctx.saved_tensors
-        dlow = ops.overlap_loss_lowres_bwd(low, target, ctx.size, sums, g.contiguous().float(), ctx.options, 1.0, ctx.eps)
-        return dlow, None, None, None, None
-
-
-class _OverlapBinaryLoss(Function):
-    """Jaccard / Tversky (mode='binary')."""
-
-    @staticmethod
-    def forward(ctx, logits, target, eps, options):
-        loss, sums = ops.overlap_binary_loss_fwd(logits, target, options, eps)
-        ctx.save_for_backward(logits, target, sums)
-        ctx.eps, ctx.options = eps, options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, target, sums = ctx.saved_tensors
-        return (ops.overlap_binary_loss_bwd(logits, target, sums, g.contiguous().float(), ctx.options, 1.0, ctx.eps),
-                None, None, None)
-
-
 class _DiceFamily(nn.Module):
     """What DiceLoss, JaccardLoss and TverskyLoss share: the checks of smp's common constructor arguments and the forward that
-    picks the full-resolution, low-resolution (LowresLogits) or binary kernels.  A subclass names its three Functions and sets
-    ``mode``, ``eps``, ``classes`` and ``options``."""
-
-    _full = _lowres = _binary = None
+    picks the full-resolution, low-resolution (LowresLogits) or binary kernels.  A subclass sets ``mode``, ``eps``, ``classes``
+    and ``options`` (which selects the loss)."""
 
     def _check_common(self, mode, classes, from_logits, ignore_index, **floats):
         """The validated (classes, ignore_index); ``floats``: named values that must be finite."""
@@ -1524,7 +1473,7 @@ class _DiceFamily(nn.Module):
             if (self.mode == "multiclass" and FUSE_LOWRES_DICE and ops.dice_lowres_ok(y_pred.low, size)
                     and y_pred.low.dtype == torch.float32 and tuple(yt.shape[1:]) == size):
                 self._check_classes(y_pred.low.shape[3])
-                return self._lowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.eps, self.options)
+                return _DiceLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.eps, self.options)
             y_pred = y_pred.materialise()
         if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
             y_pred = y_pred.float().contiguous()
@@ -1532,11 +1481,11 @@ class _DiceFamily(nn.Module):
             if y_pred.shape[0] != y_true.shape[0] or y_pred.numel() != y_true.numel():
                 msg = f"{type(self).__name__}(binary): y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} do not match"
                 raise ValueError(msg)
-            return self._binary.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
+            return _DiceBinaryLoss.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
         if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
             y_true = y_true[:, 0]          # smp views the target as [B, -1]: an un-squeezed [B,1,H,W] mask is the same
         self._check_classes(y_pred.shape[1])
-        return self._full.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
+        return _DiceLoss.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
 
 
 class DiceLoss(_DiceFamily):
@@ -1554,8 +1503,6 @@ class DiceLoss(_DiceFamily):
     ``ignore_index`` matches no class while its probabilities still count in the denominators (unchanged behaviour).  With every
     option at its default the plain kernels run and the results are bit-identical to earlier builds.  ``from_logits=False`` is
     not implemented and raises."""
-
-    _full, _lowres, _binary = _DiceLoss, _DiceLowres, _DiceBinaryLoss
 
     def __init__(self, mode: str = "multiclass", classes=None, log_loss: bool = False, from_logits: bool = True,
                  smooth: float = 0.0, ignore_index=None, eps: float = 1e-7) -> None:
@@ -1584,8 +1531,6 @@ class JaccardLoss(_DiceFamily):
     from the head's own map under DiceLoss's conditions (f32, K <= 16, factor <= 64); other cases materialise the logits.
     ``mode="multilabel"`` and ``from_logits=False`` raise ``NotImplementedError``."""
 
-    _full, _lowres, _binary = _OverlapLoss, _OverlapLowres, _OverlapBinaryLoss
-
     def __init__(self, mode: str = "multiclass", classes=None, log_loss: bool = False, from_logits: bool = True,
                  smooth: float = 0.0, eps: float = 1e-7) -> None:
         super().__init__()
@@ -1610,8 +1555,6 @@ class TverskyLoss(_DiceFamily):
     An ignored pixel gets an exactly zero gradient in every class.  ``alpha, beta >= 0`` and ``gamma > 0`` are required.
 
     Targets, ``LowresLogits`` and the unimplemented arguments: as JaccardLoss."""
-
-    _full, _lowres, _binary = _OverlapLoss, _OverlapLowres, _OverlapBinaryLoss
 
     def __init__(self, mode: str = "multiclass", classes=None, log_loss: bool = False, from_logits: bool = True,
                  smooth: float = 0.0, ignore_index=None, eps: float = 1e-7, alpha: float = 0.5, beta: float = 0.5,

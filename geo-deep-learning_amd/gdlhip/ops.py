@@ -1880,133 +1880,6 @@ class DiceOptions(NamedTuple):
         return C.addressof(o), (o, arr)
 
 
-def dice_loss_fwd(logits: Tensor, target: Tensor, eps: float = 1e-7, options: DiceOptions | None = None):
-    """(loss, sums) of smp DiceLoss(mode="multiclass"); ``options`` None = smp's defaults through the plain entry point."""
-    _need_cuda(logits, target)
-    if logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise ValueError("dice_loss: contiguous f32 NCHW logits expected")
-    if target.dtype != torch.int64 or not target.is_contiguous():
-        raise ValueError("dice_loss: contiguous int64 target expected")
-    B, K, H, W = logits.shape
-    sums = torch.empty(3 * K, device=logits.device, dtype=torch.float32)
-    loss = torch.empty((), device=logits.device, dtype=torch.float32)
-    lib = _lib.load()
-    nbytes = lib.gdl_dice_loss_workspace(B, K, H * W)
-    ws = torch.empty(nbytes // 4, device=logits.device, dtype=torch.float32)
-    if options is None:
-        check(lib.gdl_dice_loss_fwd(_p(logits), _p(target), B, K, H * W, eps, _p(sums), _p(loss), _p(ws),
-                                    nbytes, _stream()), "gdl_dice_loss_fwd")
-    else:
-        opt, keep = options.c_arg()
-        check(lib.gdl_dice_loss_opt_fwd(_p(logits), _p(target), B, K, H * W, eps, opt, _p(sums), _p(loss), _p(ws),
-                                        nbytes, _stream()), "gdl_dice_loss_opt_fwd")
-    return loss, sums
-
-
-def dice_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream: Tensor | None,
-                  grad_scale: float = 1.0, eps: float = 1e-7, out: Tensor | None = None,
-                  accumulate: bool = False, options: DiceOptions | None = None) -> Tensor:
-    B, K, H, W = logits.shape
-    if out is None:
-        out = torch.empty_like(logits)
-    if options is None:
-        check(_lib.load().gdl_dice_loss_bwd(_p(logits), _p(target), B, K, H * W, eps, _p(sums),
-                                            _p(upstream), grad_scale, _p(out), int(accumulate),
-                                            _stream()), "gdl_dice_loss_bwd")
-    else:
-        opt, keep = options.c_arg()
-        check(_lib.load().gdl_dice_loss_opt_bwd(_p(logits), _p(target), B, K, H * W, eps, opt, _p(sums),
-                                                _p(upstream), grad_scale, _p(out), int(accumulate),
-                                                _stream()), "gdl_dice_loss_opt_bwd")
-    return out
-
-
-def dice_lowres_ok(low: Tensor, size: tuple[int, int]) -> bool:
-    """Shapes gdl_dice_loss_lowres_* take: an upsample by at most 64 per direction (DOFA's auxiliary head: 16 x 16 -> 512 x 512), at
-    most 16 classes."""
-    if low.dim() != 4 or low.shape[3] > 16:
-        return False
-    hi, wi = low.shape[1], low.shape[2]
-    return size[0] >= hi and size[1] >= wi and -(-size[0] // hi) <= 64 and -(-size[1] // wi) <= 64
-
-
-def dice_loss_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], eps: float = 1e-7,
-                         options: DiceOptions | None = None):
-    """Dice(multiclass) of bilinear(low -> size) vs target [B, H, W] without the full-resolution logits: (loss, sums)."""
-    _need_cuda(low, target)
-    if low.dtype != torch.float32 or not low.is_contiguous() or low.dim() != 4:
-        raise ValueError("dice_loss_lowres: contiguous f32 NHWC low-resolution logits [B, h, w, K] expected")
-    B, Hi, Wi, K = low.shape
-    if target.dtype != torch.int64 or not target.is_contiguous() or tuple(target.shape) != (B, size[0], size[1]):
-        raise ValueError(f"dice_loss_lowres: contiguous int64 target [B, {size[0]}, {size[1]}] expected, got {tuple(target.shape)}")
-    sums = torch.empty(3 * K, device=low.device, dtype=torch.float32)
-    loss = torch.empty((), device=low.device, dtype=torch.float32)
-    lib = _lib.load()
-    nbytes = lib.gdl_dice_loss_lowres_workspace(B, K, size[0], size[1])
-    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32)
-    if options is None:
-        check(lib.gdl_dice_loss_lowres_fwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, _p(sums), _p(loss), _p(ws), nbytes,
-                                           _stream()), "gdl_dice_loss_lowres_fwd")
-    else:
-        opt, keep = options.c_arg()
-        check(lib.gdl_dice_loss_lowres_opt_fwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, opt, _p(sums), _p(loss),
-                                               _p(ws), nbytes, _stream()), "gdl_dice_loss_lowres_opt_fwd")
-    return loss, sums
-
-
-def dice_loss_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], sums: Tensor, upstream: Tensor | None,
-                         grad_scale: float = 1.0, eps: float = 1e-7, options: DiceOptions | None = None) -> Tensor:
-    B, Hi, Wi, K = low.shape
-    dlow = torch.empty_like(low)
-    lib = _lib.load()
-    nbytes = lib.gdl_dice_loss_lowres_bwd_workspace(B, K, Hi, Wi, size[0], size[1])
-    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
-    if options is None:
-        check(lib.gdl_dice_loss_lowres_bwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, _p(sums), _p(upstream),
-                                           grad_scale, _p(dlow), _p(ws), nbytes, _stream()), "gdl_dice_loss_lowres_bwd")
-    else:
-        opt, keep = options.c_arg()
-        check(lib.gdl_dice_loss_lowres_opt_bwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, opt, _p(sums), _p(upstream),
-                                               grad_scale, _p(dlow), _p(ws), nbytes, _stream()), "gdl_dice_loss_lowres_opt_bwd")
-    return dlow
-
-
-def dice_binary_loss_fwd(logits: Tensor, target: Tensor, eps: float = 1e-7, options: DiceOptions | None = None):
-    """smp DiceLoss(mode="binary"): logits [B,1,H,W] (or any shape) f32, target of the same numel, int64 0/1."""
-    _need_cuda(logits, target)
-    if logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise ValueError("dice_binary_loss: contiguous f32 logits expected")
-    if target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != logits.numel():
-        raise ValueError("dice_binary_loss: contiguous int64 target with one entry per logit expected")
-    total = logits.numel()
-    sums = torch.empty(3, device=logits.device, dtype=torch.float32)
-    loss = torch.empty((), device=logits.device, dtype=torch.float32)
-    lib = _lib.load()
-    nbytes = lib.gdl_dice_loss_workspace(1, 1, total)
-    ws = torch.empty(nbytes // 4, device=logits.device, dtype=torch.float32)
-    if options is None:
-        check(lib.gdl_dice_binary_loss_fwd(_p(logits), _p(target), total, eps, _p(sums), _p(loss), _p(ws), nbytes,
-                                           _stream()), "gdl_dice_binary_loss_fwd")
-    else:
-        opt, keep = options.c_arg()
-        check(lib.gdl_dice_binary_loss_opt_fwd(_p(logits), _p(target), total, eps, opt, _p(sums), _p(loss), _p(ws), nbytes,
-                                               _stream()), "gdl_dice_binary_loss_opt_fwd")
-    return loss, sums
-
-
-def dice_binary_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream: Tensor | None,
-                         grad_scale: float = 1.0, eps: float = 1e-7, options: DiceOptions | None = None) -> Tensor:
-    out = torch.empty_like(logits)
-    if options is None:
-        check(_lib.load().gdl_dice_binary_loss_bwd(_p(logits), _p(target), logits.numel(), eps, _p(sums), _p(upstream),
-                                                   grad_scale, _p(out), 0, _stream()), "gdl_dice_binary_loss_bwd")
-    else:
-        opt, keep = options.c_arg()
-        check(_lib.load().gdl_dice_binary_loss_opt_bwd(_p(logits), _p(target), logits.numel(), eps, opt, _p(sums), _p(upstream),
-                                                       grad_scale, _p(out), 0, _stream()), "gdl_dice_binary_loss_opt_bwd")
-    return out
-
-
 class OverlapOptions(NamedTuple):
     """What the gdl_overlap_* entry points take (gdl_overlap_options in include/gdlhip.h): ``kind`` "jaccard" or "tversky", then
     ``ignore_index`` (any int64, or None; Tversky only), ``smooth``, ``log_loss``, ``classes`` as in DiceOptions, and Tversky's
@@ -2032,93 +1905,115 @@ class OverlapOptions(NamedTuple):
         return C.addressof(o), (o, arr)
 
 
-def overlap_loss_fwd(logits: Tensor, target: Tensor, options: OverlapOptions, eps: float = 1e-7):
-    """(loss, sums) of the Jaccard / Tversky loss (mode "multiclass") on NCHW f32 logits; sums as dice_loss_fwd."""
+def _dice_entry(stem: str, way: str, options):
+    """The C entry point of the Dice / Jaccard / Tversky family for ``options``: (symbol, function, the option arguments that
+    follow ``eps`` in its signature, objects to keep alive during the call).  None: the plain ``gdl_dice_<stem>_<way>`` (no option
+    argument); DiceOptions: ``gdl_dice_<stem>_opt_<way>``; OverlapOptions: ``gdl_overlap_<stem>_<way>``."""
+    if options is None:
+        name, opt, keep = f"gdl_dice_{stem}_{way}", (), None
+    else:
+        name = f"gdl_overlap_{stem}_{way}" if isinstance(options, OverlapOptions) else f"gdl_dice_{stem}_opt_{way}"
+        addr, keep = options.c_arg()
+        opt = (addr,)
+    return name, getattr(_lib.load(), name), opt, keep
+
+
+def _dice_buffers(like: Tensor, K: int, nbytes: int):
+    """(sums [3K], loss [], workspace of ``nbytes``) for a forward of the family, on ``like``'s device."""
+    sums = torch.empty(3 * K, device=like.device, dtype=torch.float32)
+    loss = torch.empty((), device=like.device, dtype=torch.float32)
+    return sums, loss, torch.empty(nbytes // 4, device=like.device, dtype=torch.float32)
+
+
+def dice_loss_fwd(logits: Tensor, target: Tensor, eps: float = 1e-7, options: DiceOptions | OverlapOptions | None = None):
+    """(loss, sums) of smp DiceLoss(mode="multiclass"); ``options`` None = smp's defaults through the plain entry point.  This and
+    the five functions below serve the whole family: an OverlapOptions selects the Jaccard / Tversky loss on the same sums."""
     _need_cuda(logits, target)
     if logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise ValueError("overlap_loss: contiguous f32 NCHW logits expected")
+        raise ValueError("dice_loss: contiguous f32 NCHW logits expected")
     if target.dtype != torch.int64 or not target.is_contiguous():
-        raise ValueError("overlap_loss: contiguous int64 target expected")
+        raise ValueError("dice_loss: contiguous int64 target expected")
     B, K, H, W = logits.shape
-    sums = torch.empty(3 * K, device=logits.device, dtype=torch.float32)
-    loss = torch.empty((), device=logits.device, dtype=torch.float32)
-    lib = _lib.load()
-    nbytes = lib.gdl_dice_loss_workspace(B, K, H * W)
-    ws = torch.empty(nbytes // 4, device=logits.device, dtype=torch.float32)
-    opt, keep = options.c_arg()
-    check(lib.gdl_overlap_loss_fwd(_p(logits), _p(target), B, K, H * W, eps, opt, _p(sums), _p(loss), _p(ws), nbytes, _stream()),
-          "gdl_overlap_loss_fwd")
+    nbytes = _lib.load().gdl_dice_loss_workspace(B, K, H * W)
+    sums, loss, ws = _dice_buffers(logits, K, nbytes)
+    name, fn, opt, keep = _dice_entry("loss", "fwd", options)
+    check(fn(_p(logits), _p(target), B, K, H * W, eps, *opt, _p(sums), _p(loss), _p(ws), nbytes, _stream()), name)
     return loss, sums
 
 
-def overlap_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream: Tensor | None, options: OverlapOptions,
-                     grad_scale: float = 1.0, eps: float = 1e-7, out: Tensor | None = None, accumulate: bool = False) -> Tensor:
+def dice_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream: Tensor | None,
+                  grad_scale: float = 1.0, eps: float = 1e-7, out: Tensor | None = None,
+                  accumulate: bool = False, options: DiceOptions | OverlapOptions | None = None) -> Tensor:
     B, K, H, W = logits.shape
     if out is None:
         out = torch.empty_like(logits)
-    opt, keep = options.c_arg()
-    check(_lib.load().gdl_overlap_loss_bwd(_p(logits), _p(target), B, K, H * W, eps, opt, _p(sums), _p(upstream), grad_scale,
-                                           _p(out), int(accumulate), _stream()), "gdl_overlap_loss_bwd")
+    name, fn, opt, keep = _dice_entry("loss", "bwd", options)
+    check(fn(_p(logits), _p(target), B, K, H * W, eps, *opt, _p(sums), _p(upstream), grad_scale, _p(out), int(accumulate),
+             _stream()), name)
     return out
 
 
-def overlap_loss_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], options: OverlapOptions, eps: float = 1e-7):
-    """The same loss of bilinear(low -> size) vs target [B, H, W] without the full-resolution logits (shapes: dice_lowres_ok)."""
+def dice_lowres_ok(low: Tensor, size: tuple[int, int]) -> bool:
+    """Shapes gdl_dice_loss_lowres_* take: an upsample by at most 64 per direction (DOFA's auxiliary head: 16 x 16 -> 512 x 512), at
+    most 16 classes."""
+    if low.dim() != 4 or low.shape[3] > 16:
+        return False
+    hi, wi = low.shape[1], low.shape[2]
+    return size[0] >= hi and size[1] >= wi and -(-size[0] // hi) <= 64 and -(-size[1] // wi) <= 64
+
+
+def dice_loss_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], eps: float = 1e-7,
+                         options: DiceOptions | OverlapOptions | None = None):
+    """Dice(multiclass) -- or the family member ``options`` selects -- of bilinear(low -> size) vs target [B, H, W] without the
+    full-resolution logits: (loss, sums)."""
     _need_cuda(low, target)
     if low.dtype != torch.float32 or not low.is_contiguous() or low.dim() != 4:
-        raise ValueError("overlap_loss_lowres: contiguous f32 NHWC low-resolution logits [B, h, w, K] expected")
+        raise ValueError("dice_loss_lowres: contiguous f32 NHWC low-resolution logits [B, h, w, K] expected")
     B, Hi, Wi, K = low.shape
     if target.dtype != torch.int64 or not target.is_contiguous() or tuple(target.shape) != (B, size[0], size[1]):
-        raise ValueError(f"overlap_loss_lowres: contiguous int64 target [B, {size[0]}, {size[1]}] expected, got {tuple(target.shape)}")
-    sums = torch.empty(3 * K, device=low.device, dtype=torch.float32)
-    loss = torch.empty((), device=low.device, dtype=torch.float32)
-    lib = _lib.load()
-    nbytes = lib.gdl_dice_loss_lowres_workspace(B, K, size[0], size[1])
-    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32)
-    opt, keep = options.c_arg()
-    check(lib.gdl_overlap_loss_lowres_fwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, opt, _p(sums), _p(loss), _p(ws),
-                                          nbytes, _stream()), "gdl_overlap_loss_lowres_fwd")
+        raise ValueError(f"dice_loss_lowres: contiguous int64 target [B, {size[0]}, {size[1]}] expected, got {tuple(target.shape)}")
+    nbytes = _lib.load().gdl_dice_loss_lowres_workspace(B, K, size[0], size[1])
+    sums, loss, ws = _dice_buffers(low, K, nbytes)
+    name, fn, opt, keep = _dice_entry("loss_lowres", "fwd", options)
+    check(fn(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, *opt, _p(sums), _p(loss), _p(ws), nbytes, _stream()), name)
     return loss, sums
 
 
-def overlap_loss_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], sums: Tensor, upstream: Tensor | None,
-                            options: OverlapOptions, grad_scale: float = 1.0, eps: float = 1e-7) -> Tensor:
+def dice_loss_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], sums: Tensor, upstream: Tensor | None,
+                         grad_scale: float = 1.0, eps: float = 1e-7,
+                         options: DiceOptions | OverlapOptions | None = None) -> Tensor:
     B, Hi, Wi, K = low.shape
     dlow = torch.empty_like(low)
-    lib = _lib.load()
-    nbytes = lib.gdl_dice_loss_lowres_bwd_workspace(B, K, Hi, Wi, size[0], size[1])
+    nbytes = _lib.load().gdl_dice_loss_lowres_bwd_workspace(B, K, Hi, Wi, size[0], size[1])
     ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
-    opt, keep = options.c_arg()
-    check(lib.gdl_overlap_loss_lowres_bwd(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, opt, _p(sums), _p(upstream),
-                                          grad_scale, _p(dlow), _p(ws), nbytes, _stream()), "gdl_overlap_loss_lowres_bwd")
+    name, fn, opt, keep = _dice_entry("loss_lowres", "bwd", options)
+    check(fn(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, *opt, _p(sums), _p(upstream), grad_scale, _p(dlow), _p(ws),
+             nbytes, _stream()), name)
     return dlow
 
 
-def overlap_binary_loss_fwd(logits: Tensor, target: Tensor, options: OverlapOptions, eps: float = 1e-7):
-    """Mode "binary": logits [B,1,H,W] (or any shape) f32, target of the same numel, int64 0/1."""
+def dice_binary_loss_fwd(logits: Tensor, target: Tensor, eps: float = 1e-7, options: DiceOptions | OverlapOptions | None = None):
+    """smp DiceLoss(mode="binary") -- or the family member ``options`` selects: logits [B,1,H,W] (or any shape) f32, target of
+    the same numel, int64 0/1."""
     _need_cuda(logits, target)
     if logits.dtype != torch.float32 or not logits.is_contiguous():
-        raise ValueError("overlap_binary_loss: contiguous f32 logits expected")
+        raise ValueError("dice_binary_loss: contiguous f32 logits expected")
     if target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != logits.numel():
-        raise ValueError("overlap_binary_loss: contiguous int64 target with one entry per logit expected")
+        raise ValueError("dice_binary_loss: contiguous int64 target with one entry per logit expected")
     total = logits.numel()
-    sums = torch.empty(3, device=logits.device, dtype=torch.float32)
-    loss = torch.empty((), device=logits.device, dtype=torch.float32)
-    lib = _lib.load()
-    nbytes = lib.gdl_dice_loss_workspace(1, 1, total)
-    ws = torch.empty(nbytes // 4, device=logits.device, dtype=torch.float32)
-    opt, keep = options.c_arg()
-    check(lib.gdl_overlap_binary_loss_fwd(_p(logits), _p(target), total, eps, opt, _p(sums), _p(loss), _p(ws), nbytes, _stream()),
-          "gdl_overlap_binary_loss_fwd")
+    nbytes = _lib.load().gdl_dice_loss_workspace(1, 1, total)
+    sums, loss, ws = _dice_buffers(logits, 1, nbytes)
+    name, fn, opt, keep = _dice_entry("binary_loss", "fwd", options)
+    check(fn(_p(logits), _p(target), total, eps, *opt, _p(sums), _p(loss), _p(ws), nbytes, _stream()), name)
     return loss, sums
 
 
-def overlap_binary_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream: Tensor | None, options: OverlapOptions,
-                            grad_scale: float = 1.0, eps: float = 1e-7) -> Tensor:
+def dice_binary_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream: Tensor | None,
+                         grad_scale: float = 1.0, eps: float = 1e-7,
+                         options: DiceOptions | OverlapOptions | None = None) -> Tensor:
     out = torch.empty_like(logits)
-    opt, keep = options.c_arg()
-    check(_lib.load().gdl_overlap_binary_loss_bwd(_p(logits), _p(target), logits.numel(), eps, opt, _p(sums), _p(upstream),
-                                                  grad_scale, _p(out), 0, _stream()), "gdl_overlap_binary_loss_bwd")
+    name, fn, opt, keep = _dice_entry("binary_loss", "bwd", options)
+    check(fn(_p(logits), _p(target), logits.numel(), eps, *opt, _p(sums), _p(upstream), grad_scale, _p(out), 0, _stream()), name)
     return out
 
 

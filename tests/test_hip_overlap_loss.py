@@ -30,7 +30,7 @@ TVERSKY = [dict(alpha=0.3, beta=0.7), dict(alpha=0.7, beta=0.3, gamma=0.75), dic
 GRID = [("jaccard", kw) for kw in JACCARD] + [("tversky", kw) for kw in TVERSKY]
 GRID_IDS = ["jaccard-default", "jaccard-smooth", "jaccard-log", "jaccard-classes", "tversky-a3b7", "tversky-a7b3-g075",
             "tversky-g2-smooth", "tversky-ignore", "tversky-log-classes"]
-# low [B, h, w, K] -> (H, W).  K <= 8 takes the tiled backward, K > 8 the gather kernel (dice_tile_dims in csrc/misc.hip: the
+# low [B, h, w, K] -> (H, W).  K <= 8 takes the tiled backward, K > 8 the gather kernel (dice_tile_dims in csrc/loss_dice.hip: the
 # two tile-extent conditions always hold for an upsample, so the class count alone decides): K = 8 and K = 9 are the smallest
 # change of shape across that condition.
 LOWRES = [(2, 4, 4, 5, 32, 32), (2, 2, 2, 5, 64, 64), (2, 3, 5, 3, 24, 40), (2, 3, 4, 8, 9, 10), (2, 3, 4, 9, 9, 10)]
@@ -210,8 +210,8 @@ def test_low_resolution_is_deterministic(shape):
     for opt in (ops.OverlapOptions("tversky", 255, 1.0, False, None, 0.3, 0.7, 0.75), ops.OverlapOptions("jaccard")):
         runs = []
         for _ in range(2):
-            loss, sums = ops.overlap_loss_lowres_fwd(low, y, (ho, wo), opt)
-            runs.append((loss, sums, ops.overlap_loss_lowres_bwd(low, y, (ho, wo), sums, up, opt)))
+            loss, sums = ops.dice_loss_lowres_fwd(low, y, (ho, wo), options=opt)
+            runs.append((loss, sums, ops.dice_loss_lowres_bwd(low, y, (ho, wo), sums, up, options=opt)))
         assert all(torch.equal(a, b) for a, b in zip(*runs))
 
 

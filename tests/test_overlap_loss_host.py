@@ -126,14 +126,65 @@ def test_ops_refuse_cpu_tensors():
     x, y = torch.zeros(1, 3, 4, 4), torch.zeros(1, 4, 4, dtype=torch.int64)
     opt = ops.OverlapOptions("tversky")
     with pytest.raises(ValueError):
-        ops.overlap_loss_fwd(x, y, opt)
+        ops.dice_loss_fwd(x, y, options=opt)
     with pytest.raises(ValueError):
-        ops.overlap_loss_lowres_fwd(torch.zeros(1, 2, 2, 3), y, (4, 4), opt)
+        ops.dice_loss_lowres_fwd(torch.zeros(1, 2, 2, 3), y, (4, 4), options=opt)
     with pytest.raises(ValueError):
-        ops.overlap_binary_loss_fwd(torch.zeros(1, 1, 4, 4), y, opt)
+        ops.dice_binary_loss_fwd(torch.zeros(1, 1, 4, 4), y, options=opt)
     for crit in (gnn.JaccardLoss(), gnn.TverskyLoss(), gnn.JaccardLoss(mode="binary")):
         with pytest.raises(ValueError):
             crit(x[:, :1] if crit.mode == "binary" else x, y)
+
+
+# ------------------------------------------------------------------------------------------------ routing
+ROUTES = [(None, "gdl_dice_{}_{}"), (ops.DiceOptions(255), "gdl_dice_{}_opt_{}"), (ops.OverlapOptions("tversky", 255), "gdl_overlap_{}_{}")]
+
+
+@pytest.mark.parametrize("options,pattern", ROUTES, ids=["plain", "dice-options", "overlap-options"])
+def test_ops_route_options_to_the_entry_point_and_argument_positions(monkeypatch, options, pattern):
+    """The one decision gdlhip.ops makes for this family: ``options`` picks the C symbol, the option pointer follows ``eps``
+    (absent for None), and ``eps`` / ``grad_scale`` land on the float positions of _lib.SIGNATURES.  No library is loaded."""
+    import ctypes as C
+
+    from gdlhip import _lib
+    calls, checked = [], []
+
+    class Recorder:
+        def __getattr__(self, name):
+            if name.endswith("_workspace"):
+                return lambda *a: 48
+            return lambda *a: calls.append((name, a)) or 0
+
+    monkeypatch.setattr(_lib, "load", lambda: Recorder())
+    monkeypatch.setattr(ops, "_need_cuda", lambda *ts: None)
+    monkeypatch.setattr(ops, "_stream", lambda: 7)
+    monkeypatch.setattr(ops, "check", lambda status, what: checked.append((status, what)))
+    EPS, GS = 3e-5, 0.25
+    x, y, low, xb = torch.zeros(1, 3, 4, 4), torch.zeros(1, 4, 4, dtype=torch.int64), torch.zeros(1, 2, 2, 3), torch.zeros(1, 1, 4, 4)
+    sums, up = torch.zeros(9), torch.ones(())
+    runs = [("loss", "fwd", lambda: ops.dice_loss_fwd(x, y, EPS, options=options)),
+            ("loss", "bwd", lambda: ops.dice_loss_bwd(x, y, sums, up, GS, EPS, options=options)),
+            ("loss_lowres", "fwd", lambda: ops.dice_loss_lowres_fwd(low, y, (4, 4), EPS, options=options)),
+            ("loss_lowres", "bwd", lambda: ops.dice_loss_lowres_bwd(low, y, (4, 4), sums, up, GS, EPS, options=options)),
+            ("binary_loss", "fwd", lambda: ops.dice_binary_loss_fwd(xb, y, EPS, options=options)),
+            ("binary_loss", "bwd", lambda: ops.dice_binary_loss_bwd(xb, y, sums[:3], up, GS, EPS, options=options))]
+    for stem, way, run in runs:
+        calls.clear(), checked.clear()
+        run()
+        want = pattern.format(stem, way)
+        assert [c[0] for c in calls] == [want] and checked == [(0, want)]
+        args, types = calls[0][1], _lib.SIGNATURES[want][1]
+        assert len(args) == len(types) and args[-1] == 7
+        floats = [i for i, t in enumerate(types) if t is C.c_float]
+        assert len(floats) == (1 if way == "fwd" else 2)
+        assert args[floats[0]] == EPS and (way == "fwd" or args[floats[1]] == GS)
+        # the option pointer is the argument after eps: one more argument than the plain symbol, a non-zero address
+        plain = _lib.SIGNATURES[f"gdl_dice_{stem}_{way}"][1]
+        if options is None:
+            assert types is plain and isinstance(args[floats[0] + 1], C.c_void_p)      # (sums: a tensor pointer)
+        else:
+            assert len(types) == len(plain) + 1
+            assert isinstance(args[floats[0] + 1], int) and args[floats[0] + 1] != 0
 
 
 # ------------------------------------------------------------------------------------------------ wiring
