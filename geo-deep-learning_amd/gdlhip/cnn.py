@@ -16,8 +16,8 @@ from torch.autograd import Function
 
 from . import nn as gnn
 from . import ops
-from .nn import (_world, cached, mark_updated, conv_weight_matrix, sync_batch_stats, sync_sum_pair, to_compute,
-                 update_running_stats)
+from .nn import (_EVAL_BN_GRAD_MSG, _bn_sync_momentum, _bn_train_backward, _bn_train_stats, cached, conv_weight_matrix,
+                 to_compute)
 from .ops import ACT_NONE, ACT_RELU, ACT_RESID_RELU
 from .tnn import _dense
 
@@ -330,18 +330,7 @@ class _ConvBNTrain(Function):
         else:
             wq, _ = padded_operands(weight, cd, cpad, npad)
             y = ops.conv_gemm(x, wq, R=r, S=s, stride=stride, pad=pad)
-        world = _world(sync_group) if sync_group is not False else 1
-        p_local, p_share, total = y.numel() // npad, None, y.numel() // npad
-        in_kernel = world == 1 and running_mean is not None and npad == n   # the statistics kernel updates the buffers itself
-        mean, var = ops.bn_stats(y, running_mean, running_var, momentum) if in_kernel else ops.bn_stats(y)
-        if world > 1:
-            mean, var, total = sync_batch_stats(mean, var, sync_group or None, count=p_local)
-            p_share = p_local / total
-        if in_kernel:     # written through raw pointers: invalidate the eval-mode fold cache
-            mark_updated(running_mean)
-            mark_updated(running_var)
-        elif running_mean is not None:
-            update_running_stats(running_mean, running_var, mean[:n], var[:n], momentum, total)
+        mean, var, world, p_local, p_share, _ = _bn_train_stats(y, n, running_mean, running_var, momentum, sync_group)
         g, b = _padvec(gamma, npad), _padvec(beta, npad)
         out = ops.bn_apply(y, mean, var, g, b, eps, relu)
         ctx.save_for_backward(x, weight, y, mean, var, g, b)
@@ -354,12 +343,7 @@ class _ConvBNTrain(Function):
         stride, pad, relu, eps, sync_group, world, cpad, npad, p_local, p_share = ctx.cfg
         n, c, r, s = _wshape(weight)
         gout = _dense(gout if gout.dtype == y.dtype else to_compute(gout, y.dtype))
-        dgamma, dbeta = ops.bn_bwd_reduce(y, gout, mean, var, g, b, eps, relu)
-        sg, sb = dgamma, dbeta
-        if world > 1:
-            sg, sb = sync_sum_pair(dgamma, dbeta, sync_group or None)
-            sg, sb = sg * p_share, sb * p_share      # see gdlhip.nn._ConvBNActTrain.backward
-        dy = ops.bn_bwd_dx(y, gout, mean, var, g, b, eps, relu, sg, sb, p_local, out=y)
+        dy, dgamma, dbeta = _bn_train_backward(y, gout, mean, var, g, b, eps, relu, sync_group, world, p_local, p_share)
         dw = None
         stem = hasattr(weight, "_gdl_stem")
         sg = supergroups(weight, cpad, npad, x.dtype)
@@ -387,8 +371,7 @@ def conv_bn(x: Tensor, weight: Tensor, norm: nn.Module, *, stride: int = 1, pad:
     cd = x.dtype
     n, c, r, s = _wshape(weight)
     if norm.training:
-        sync_group = norm.process_group if isinstance(norm, nn.SyncBatchNorm) else False
-        momentum = 0.1 if norm.momentum is None else norm.momentum
+        sync_group, momentum = _bn_sync_momentum(norm)
         y = _ConvBNTrain.apply(x, weight, norm.weight, norm.bias, norm.running_mean, norm.running_var, momentum,
                                norm.eps, stride, pad, relu and resid is None, sync_group)
         gnn.bump(norm.num_batches_tracked)
@@ -396,9 +379,7 @@ def conv_bn(x: Tensor, weight: Tensor, norm: nn.Module, *, stride: int = 1, pad:
             y = add_relu(y, resid) if relu else y + resid
         return y
     if torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad):
-        msg = ("gdlhip: autograd through eval-mode BatchNorm is not implemented; call under torch.no_grad() for "
-               "inference or model.train() for training")
-        raise NotImplementedError(msg)
+        raise NotImplementedError(_EVAL_BN_GRAD_MSG)
     cpad, npad = x.shape[-1], pad_to(n, grain(cd))
 
     def fold():

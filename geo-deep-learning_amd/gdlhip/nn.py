@@ -128,6 +128,13 @@ def mark_updated(p: Tensor) -> None:
     _RAW_WRITES[id(p)] = _RAW_WRITES.get(id(p), 0) + 1
 
 
+def _mark_running(running_mean: Tensor | None, running_var: Tensor | None) -> None:
+    """The running estimates were written through raw pointers: invalidate the eval-mode fold cache."""
+    if running_mean is not None:
+        mark_updated(running_mean)
+        mark_updated(running_var)
+
+
 def cached(params: tuple, kind: str, builder):
     """Memoise ``builder()`` on the identity + version of ``params`` (tensors).  Frozen
     parameters never change version, so e.g. the DOFA dynamic patch-embed kernel of a frozen
@@ -275,6 +282,20 @@ def _world(group=None) -> int:
     return dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
 
 
+def _sync_world(sync_group) -> int:
+    """Ranks a train-mode BatchNorm merges its statistics over; ``sync_group``: False = none (nn.BatchNorm2d), None = default group."""
+    return _world(sync_group) if sync_group is not False else 1
+
+
+def _bn_sync_momentum(norm: nn.Module) -> tuple:
+    """(sync_group, momentum) of a BatchNorm module, as the training nodes take them."""
+    return (norm.process_group if isinstance(norm, nn.SyncBatchNorm) else False), (0.1 if norm.momentum is None else norm.momentum)
+
+
+_EVAL_BN_GRAD_MSG = ("gdlhip: autograd through eval-mode BatchNorm is not implemented; call under "
+                     "torch.no_grad() for inference or model.train() for training")
+
+
 # ------------------------------------------------------------------ SyncBatchNorm exchange
 FUSE_SYNC_MESSAGE = os.environ.get("GDL_SYNC_MESSAGE_KERNELS", "1") != "0"   # A/B switch: 0 = the message is built by torch expressions
 
@@ -319,6 +340,54 @@ def sync_sum_pair(a: Tensor, b: Tensor, group=None) -> tuple[Tensor, Tensor]:
     dist.all_reduce(packed, group=group)
     SYNC_MESSAGES[1] += 1
     return packed[0].contiguous(), packed[1].contiguous()
+
+
+# ------------------------------------------------------------------ train-mode BatchNorm protocol of the conv + BN nodes
+# forward:  local statistics -> count-weighted cross-rank merge -> running-estimate update -> invalidate the eval-mode fold cache
+# backward: sums pass -> ONE all-reduce of the pair -> rescale to the global count -> dx pass
+def _bn_local_stats(y, stats_done, running_mean=None, running_var=None, momentum: float = 0.1):
+    """This rank's (mean, biased var): ``stats_done`` when they came with y (_cba_conv), else one pass that also updates the
+    running buffers it is given."""
+    return stats_done if stats_done is not None else ops.bn_stats(y, running_mean, running_var, momentum)
+
+
+def _bn_train_stats(y, n, running_mean, running_var, momentum, sync_group, stats_done=None):
+    """Forward half for the conv output y (n real channels of y.shape[-1]: gdlhip.cnn pads) -> (mean, var, world, p_local,
+    p_share, total); p_share = p_local / total and total (global pixel count, 0-dim DEVICE tensor) are None in one process.
+    A kernel writes the running buffers only for one process and unpadded channels -- the pass here or the producer of
+    ``stats_done`` (_cba_conv gave it the buffers on the same condition); else update_running_stats on the real channels."""
+    world = _sync_world(sync_group)
+    p_local, p_share, total = y.numel() // y.shape[-1], None, None
+    in_kernel = world == 1 and y.shape[-1] == n
+    mean, var = _bn_local_stats(y, stats_done, *((running_mean, running_var) if in_kernel else (None, None)), momentum)
+    if world > 1:
+        mean, var, total = sync_batch_stats(mean, var, sync_group or None, count=p_local)
+    if in_kernel:
+        _mark_running(running_mean, running_var)
+    elif running_mean is not None:
+        update_running_stats(running_mean, running_var, mean[:n], var[:n], momentum, p_local if total is None else total)
+    if world > 1:
+        p_share = p_local / total          # this rank's share of the global pixel count (device scalar)
+    return mean, var, world, p_local, p_share, total
+
+
+def _bn_sync_sums(dgamma, dbeta, sync_group, world, p_share=None):
+    """The two backward sums as a dx kernel takes them: all-reduced in one message and, given ``p_share``, scaled by p_local /
+    P_global so that the kernel's division by the LOCAL count gives the global mean (a kernel that reads the global count passes none)."""
+    if world == 1:
+        return dgamma, dbeta
+    sg, sb = sync_sum_pair(dgamma, dbeta, sync_group or None)
+    return (sg, sb) if p_share is None else (sg * p_share, sb * p_share)
+
+
+def _bn_train_backward(y, gout, mean, var, g, b, eps, relu, sync_group, world, p_local, p_share):
+    """(dy written over y, dgamma, dbeta) of BatchNorm(batch stats) (+ ReLU): sums pass, exchange, dx pass."""
+    if gout.dtype != y.dtype:
+        gout = to_compute(gout, y.dtype)
+    dgamma, dbeta = ops.bn_bwd_reduce(y, gout, mean, var, g, b, eps, relu)
+    sg, sb = _bn_sync_sums(dgamma, dbeta, sync_group, world, p_share)
+    dy = ops.bn_bwd_dx(y, gout, mean, var, g, b, eps, relu, sg, sb, p_local, out=y)
+    return dy, dgamma, dbeta
 
 
 FUSE_UP4 = True   # A/B switch: False = materialise the x4 upsample and run the ordinary 3x3 kernel
@@ -366,7 +435,7 @@ def _cba_conv(x, weight, cb, pad, up4, sync_group, running_mean, running_var, mo
         z, size = ops.conv_gemm(x, tap_weight(weight, cd)), (up4 * x.shape[1], up4 * x.shape[2])
         if FUSE_TAPSUM_STATS and ops.resize_conv3x3_fwd_bn_ok(cd, n, cb):
             # ... and the batch statistics of the output come out of the same pass (per-block partial sums)
-            own = (_world(sync_group) if sync_group is not False else 1) == 1
+            own = _sync_world(sync_group) == 1
             y, mean, var = ops.resize_conv3x3_fwd_sum_bn([z], size, addvec=cb, running_mean=running_mean if own else None,
                                                          running_var=running_var if own else None, momentum=momentum)
             return y, (mean, var)
@@ -376,7 +445,7 @@ def _cba_conv(x, weight, cb, pad, up4, sync_group, running_mean, running_var, mo
     if up4:        # other resize factors: the upsampled map is a temporary of the forward only (backward works on x)
         return ops.conv_gemm(ops.bilinear(x, (up4 * x.shape[1], up4 * x.shape[2])), gemm_weight(weight, cd), R=r, S=s, pad=pad,
                              bias=cb), None
-    small = (sync_group is False or _world(sync_group) == 1) and x.dim() == 4 and ops.BN_SMALL_MAX_PIXELS > 0 and \
+    small = _sync_world(sync_group) == 1 and x.dim() == 4 and ops.BN_SMALL_MAX_PIXELS > 0 and \
         x.shape[0] * ((x.shape[1] + 2 * pad - r) + 1) * ((x.shape[2] + 2 * pad - s) + 1) <= ops.BN_SMALL_MAX_PIXELS
     if FUSE_CONV_STATS and cd == torch.bfloat16 and not small:     # (small maps: the whole BatchNorm is ONE launch, ops.bn_small_fwd)
         # the batch statistics as a side output of the convolution's epilogue (per-wave partial sums of the bf16 outputs)
@@ -384,7 +453,7 @@ def _cba_conv(x, weight, cb, pad, up4, sync_group, running_mean, running_var, mo
         y, partials, rows = ops.conv_gemm(x, gemm_weight(weight, cd), R=r, S=s, pad=pad, bias=cb, want_stats=True)
         if not rows:
             return y, None
-        own = (_world(sync_group) if sync_group is not False else 1) == 1
+        own = _sync_world(sync_group) == 1
         return y, ops.bn_stats_finalize(partials, rows, n, y.numel() // n, running_mean if own else None,
                                         running_var if own else None, momentum)
     return ops.conv_gemm(x, gemm_weight(weight, cd), R=r, S=s, pad=pad, bias=cb), None
@@ -445,30 +514,16 @@ class _ConvBNActTrain(Function):
         n = weight.shape[0]
         cb = None if conv_bias is None else conv_bias.detach()
         y, stats_done = _cba_conv(x, weight, cb, pad, up4, sync_group, running_mean, running_var, momentum)
-        world = _world(sync_group) if sync_group is not False else 1
-        p_local, p_share = y.numel() // n, None
-        if world > 1:
-            mean, var = stats_done if stats_done is not None else ops.bn_stats(y)
-            mean, var, total = sync_batch_stats(mean, var, sync_group or None, count=p_local)
-            if running_mean is not None:
-                update_running_stats(running_mean, running_var, mean, var, momentum, total)
-            p_share = p_local / total          # this rank's share of the global pixel count (device scalar)
+        g, b = gamma.detach(), beta.detach()
+        if _sync_world(sync_group) == 1 and stats_done is None and ops.bn_small_ok(y):
+            # a small map (the reference's own per-GPU batch of 4 makes most decoder layers small): statistics, running
+            # estimates and the normalised output in ONE launch
+            out, mean, var = ops.bn_small_fwd(y, g, b, eps, relu, running_mean, running_var, momentum)
+            _mark_running(running_mean, running_var)
+            world, p_local, p_share = 1, y.numel() // n, None
         else:
-            out = None
-            if stats_done is None and ops.bn_small_ok(y):
-                # a small map (the reference's own per-GPU batch of 4 makes most decoder layers small): statistics, running
-                # estimates and the normalised output in ONE launch
-                out, mean, var = ops.bn_small_fwd(y, gamma.detach(), beta.detach(), eps, relu, running_mean, running_var, momentum)
-            else:
-                mean, var = stats_done if stats_done is not None else ops.bn_stats(y, running_mean, running_var, momentum)
-            if running_mean is not None:     # written through raw pointers: invalidate the eval-mode fold cache
-                mark_updated(running_mean)
-                mark_updated(running_var)
-            if out is not None:
-                ctx.save_for_backward(x, weight, y, mean, var, gamma, beta)
-                ctx.cfg = (pad, relu, eps, conv_bias is not None, sync_group, world, p_local, p_share, up4)
-                return out
-        out = ops.bn_apply(y, mean, var, gamma.detach(), beta.detach(), eps, relu)
+            mean, var, world, p_local, p_share, _ = _bn_train_stats(y, n, running_mean, running_var, momentum, sync_group, stats_done)
+            out = ops.bn_apply(y, mean, var, g, b, eps, relu)
         ctx.save_for_backward(x, weight, y, mean, var, gamma, beta)
         ctx.cfg = (pad, relu, eps, conv_bias is not None, sync_group, world, p_local, p_share, up4)
         return out
@@ -488,11 +543,7 @@ class _ConvBNActTrain(Function):
             dx, dw = _cba_grads(x, weight, dy, pad, up4, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
             return dx, dw, dbias, dgamma, dbeta, None, None, None, None, None, None, None, None
         dgamma, dbeta = ops.bn_bwd_reduce(y, gout, mean, var, g, b, eps, relu)
-        sg, sb = dgamma, dbeta
-        if world > 1:
-            # the kernel divides the two sums by p_local: scaling them by p_local / P_global makes that the global mean
-            sg, sb = sync_sum_pair(dgamma, dbeta, sync_group or None)
-            sg, sb = sg * p_share, sb * p_share
+        sg, sb = _bn_sync_sums(dgamma, dbeta, sync_group, world, p_share)
         dbias = None
         if has_bias and ctx.needs_input_grad[2]:
             # a bias feeding train-mode BN has an analytically zero gradient
@@ -520,7 +571,7 @@ class _ConvBNActGroupTrain(Function):
             cb = None if conv_bias is None else conv_bias.detach()
             y, stats_done = _cba_conv(x, weight, cb, pad, up4, sync_group, rm, rv, momentum)
             ys.append(y)
-            locals_.append(stats_done if stats_done is not None else ops.bn_stats(y))
+            locals_.append(_bn_local_stats(y, stats_done))
             counts.append(y.numel() // weight.shape[0])
         # one message: per member [n * mean, n * E[x^2], n]  (count-weighted merge, see sync_batch_stats)
         fused = FUSE_SYNC_MESSAGE and ys[0].is_cuda
@@ -541,9 +592,7 @@ class _ConvBNActGroupTrain(Function):
             total = packed[off + 2 * c]
             if fused:  # global statistics + the running-estimate update in one kernel
                 gmean, gvar = ops.syncbn_unpack(packed[off:off + 2 * c + 1], c, rm, rv, momentum)
-                if rm is not None:
-                    mark_updated(rm)
-                    mark_updated(rv)
+                _mark_running(rm, rv)
             else:
                 gmean = (packed[off:off + c] / total).contiguous()
                 gvar = (packed[off + c:off + 2 * c] / total - gmean * gmean).clamp_min_(0).contiguous()
@@ -611,8 +660,7 @@ def conv_bn_act_group(items: list[dict]) -> list[Tensor]:
     metas, flat = [], []
     for it in items:
         conv, norm = it["conv"], it["norm"]
-        momentum = 0.1 if norm.momentum is None else norm.momentum
-        metas.append((momentum, norm.eps, conv.padding[0], it.get("relu", True), int(it.get("up", 1)) if it.get("up", 1) > 1 else 0))
+        metas.append((_bn_sync_momentum(norm)[1], norm.eps, conv.padding[0], it.get("relu", True), int(it.get("up", 1)) if it.get("up", 1) > 1 else 0))
         flat += [it["x"], conv.weight, conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var]
     outs = _ConvBNActGroupTrain.apply(tuple(metas), norms[0].process_group, *flat)
     for norm in norms:
@@ -687,7 +735,7 @@ class _ConcatResizeConvBNTrain(Function):
     def forward(ctx, weight, gamma, beta, running_mean, running_var, momentum, eps, relu, sync_group, *levels):
         n = weight.shape[0]
         y, chans = _concat_resize_conv(weight, levels)
-        mean, var, world, p_local, p_share = _bn_train_stats(y, n, running_mean, running_var, momentum, sync_group)
+        mean, var, world, p_local, p_share, _ = _bn_train_stats(y, n, running_mean, running_var, momentum, sync_group)
         out = ops.bn_apply(y, mean, var, gamma.detach(), beta.detach(), eps, relu)
         ctx.save_for_backward(weight, y, mean, var, gamma, beta, *levels)
         ctx.cfg = (relu, eps, sync_group, world, p_local, p_share, chans)
@@ -719,7 +767,7 @@ class _ConcatResizeConvBNHeadTrain(Function):
     def forward(ctx, weight, gamma, beta, running_mean, running_var, momentum, eps, relu, head_w, head_b, *levels):
         n = weight.shape[0]
         y, chans = _concat_resize_conv(weight, levels)
-        mean, var, _, p_local, _ = _bn_train_stats(y, n, running_mean, running_var, momentum, False)
+        mean, var, _, p_local, _, _ = _bn_train_stats(y, n, running_mean, running_var, momentum, False)
         low = ops.head_1x1_bn(y, mean, var, gamma.detach(), beta.detach(), eps, relu, head_w.detach(),
                               None if head_b is None else head_b.detach())
         ctx.save_for_backward(weight, y, mean, var, gamma, beta, head_w, *levels)
@@ -805,8 +853,7 @@ def concat_resize_conv_bn_act(levels: list[Tensor], conv: nn.Conv2d, norm: nn.Mo
                          "contiguous levels, resize factors <= 10, N % 8 == 0 and batch * rows <= 65535")
         out = conv_bn_act(concat_upsample(levels, size), conv, norm, relu=relu)
         return out if head_conv is None else _Head1x1.apply(out, head_conv.weight, head_conv.bias, None)
-    sync_group = norm.process_group if isinstance(norm, nn.SyncBatchNorm) else False
-    momentum = 0.1 if norm.momentum is None else norm.momentum
+    sync_group, momentum = _bn_sync_momentum(norm)
     if head_conv is not None:
         low = _ConcatResizeConvBNHeadTrain.apply(conv.weight, norm.weight, norm.bias, norm.running_mean, norm.running_var, momentum,
                                                  norm.eps, relu, head_conv.weight, head_conv.bias, *levels)
@@ -819,37 +866,6 @@ def concat_resize_conv_bn_act(levels: list[Tensor], conv: nn.Conv2d, norm: nn.Mo
 
 
 FUSE_PYRAMID = True   # A/B switch: False = upsample every level into a concat buffer and run one wide 1x1 convolution
-
-
-def _bn_train_stats(y, n, running_mean, running_var, momentum, sync_group):
-    """Batch statistics of a conv output (+ cross-rank merge and the running-stat update): (mean, var, world, p_local, p_share)."""
-    world = _world(sync_group) if sync_group is not False else 1
-    p_local, p_share = y.numel() // n, None
-    if world > 1:
-        mean, var = ops.bn_stats(y)
-        mean, var, total = sync_batch_stats(mean, var, sync_group or None, count=p_local)
-        if running_mean is not None:
-            update_running_stats(running_mean, running_var, mean, var, momentum, total)
-        p_share = p_local / total
-    else:
-        mean, var = ops.bn_stats(y, running_mean, running_var, momentum)
-        if running_mean is not None:
-            mark_updated(running_mean)
-            mark_updated(running_var)
-    return mean, var, world, p_local, p_share
-
-
-def _bn_train_backward(y, gout, mean, var, g, b, eps, relu, sync_group, world, p_local, p_share):
-    """(dy written over y, dgamma, dbeta) of BatchNorm(batch stats) (+ ReLU)."""
-    if gout.dtype != y.dtype:
-        gout = to_compute(gout, y.dtype)
-    dgamma, dbeta = ops.bn_bwd_reduce(y, gout, mean, var, g, b, eps, relu)
-    sg, sb = dgamma, dbeta
-    if world > 1:
-        sg, sb = sync_sum_pair(dgamma, dbeta, sync_group or None)
-        sg, sb = sg * p_share, sb * p_share
-    dy = ops.bn_bwd_dx(y, gout, mean, var, g, b, eps, relu, sg, sb, p_local, out=y)
-    return dy, dgamma, dbeta
 
 
 class _PyramidFuseBNTrain(Function):
@@ -873,7 +889,7 @@ class _PyramidFuseBNTrain(Function):
             off += lv.shape[3]
         zs = [ops.conv_gemm(lv, wq[:, o:o + lv.shape[3]]) for lv, o in zip(levels[:-1], offs[:-1])]
         y = ops.conv_gemm(levels[-1], wq[:, offs[-1]:], resid=ops.bilinear_sum(zs, size))
-        mean, var, world, p_local, p_share = _bn_train_stats(y, n, running_mean, running_var, momentum, sync_group)
+        mean, var, world, p_local, p_share, _ = _bn_train_stats(y, n, running_mean, running_var, momentum, sync_group)
         out = ops.bn_apply(y, mean, var, gamma.detach(), beta.detach(), eps, relu)
         ctx.save_for_backward(weight, y, mean, var, gamma, beta, *levels)
         ctx.cfg = (relu, eps, sync_group, world, p_local, p_share, offs)
@@ -914,16 +930,13 @@ def pyramid_fuse_bn_act(levels: list[Tensor], conv: nn.Conv2d, norm: nn.Module, 
                          "contiguous levels, no bias and batch * rows <= 65535")
         return conv_bn_act(concat_upsample(levels, size), conv, norm, relu=relu)
     if norm.training:
-        sync_group = norm.process_group if isinstance(norm, nn.SyncBatchNorm) else False
-        momentum = 0.1 if norm.momentum is None else norm.momentum
+        sync_group, momentum = _bn_sync_momentum(norm)
         out = _PyramidFuseBNTrain.apply(conv.weight, norm.weight, norm.bias, norm.running_mean, norm.running_var,
                                         momentum, norm.eps, relu, sync_group, *levels)
         bump(norm.num_batches_tracked)
         return out
     if torch.is_grad_enabled() and (conv.weight.requires_grad or any(lv.requires_grad for lv in levels)):
-        msg = ("gdlhip: autograd through eval-mode BatchNorm is not implemented; call under "
-               "torch.no_grad() for inference or model.train() for training")
-        raise NotImplementedError(msg)
+        raise NotImplementedError(_EVAL_BN_GRAD_MSG)
     cd = levels[0].dtype
 
     def fold():
@@ -963,22 +976,15 @@ def conv_bn_act(x: Tensor, conv: nn.Conv2d, norm: nn.Module, *, relu: bool = Tru
             warn_unfused(f"ConvModule on a x{up4} resized input", f"input {tuple(x.shape)}, {conv.weight.shape[0]} output channels: "
                          "needs a 3x3 / pad 1 filter, N % 8 == 0 and batch * rows <= 65535")
         x, up4 = bilinear(x, (up4 * x.shape[1], up4 * x.shape[2])), 0
-    training = norm.training
-    if training:
-        if isinstance(norm, nn.SyncBatchNorm):
-            sync_group = norm.process_group  # None -> default group
-        else:
-            sync_group = False
-        momentum = 0.1 if norm.momentum is None else norm.momentum
+    if norm.training:
+        sync_group, momentum = _bn_sync_momentum(norm)
         out = _ConvBNActTrain.apply(x, conv.weight, conv.bias, norm.weight, norm.bias,
                                     norm.running_mean, norm.running_var, momentum, norm.eps, pad,
                                     relu, sync_group, up4)
         bump(norm.num_batches_tracked)
         return out
     if torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad):
-        msg = ("gdlhip: autograd through eval-mode BatchNorm is not implemented; call under "
-               "torch.no_grad() for inference or model.train() for training")
-        raise NotImplementedError(msg)
+        raise NotImplementedError(_EVAL_BN_GRAD_MSG)
     cd = x.dtype
     scale, shift = cached((norm.weight, norm.bias, norm.running_mean, norm.running_var), "bnfold",
                           lambda: ops.bn_fold(norm.weight.detach(), norm.bias.detach(),
@@ -1006,8 +1012,6 @@ def conv_bn_act(x: Tensor, conv: nn.Conv2d, norm: nn.Module, *, relu: bool = Tru
 
 
 # ------------------------------------------------------------------ UperNet scale_modules (upernet.py:37-54,113-119)
-_EVAL_BN_GRAD_MSG = ("gdlhip: autograd through eval-mode BatchNorm is not implemented; call under "
-                     "torch.no_grad() for inference or model.train() for training")
 
 
 def _nhwc_grad(g: Tensor, dtype: torch.dtype) -> Tensor:
@@ -1080,18 +1084,8 @@ class _ConvT2x2BNGeluTrain(Function):
     def forward(ctx, x, weight, bias, gamma, beta, running_mean, running_var, momentum, eps, sync_group, w_fwd, w_dgrad):
         n = w_fwd.shape[1]
         y = ops.convt2x2(x, w_fwd, None if bias is None else bias.detach())
-        world = _world(sync_group) if sync_group is not False else 1
-        p_local, total = y.numel() // n, None
-        if world > 1:
-            mean, var = ops.bn_stats(y)
-            mean, var, total = sync_batch_stats(mean, var, sync_group or None, count=p_local)
-            if running_mean is not None:
-                update_running_stats(running_mean, running_var, mean, var, momentum, total)
-        else:
-            mean, var = ops.bn_stats(y, running_mean, running_var, momentum)
-            if running_mean is not None:     # written through raw pointers
-                mark_updated(running_mean)
-                mark_updated(running_var)
+        # (the dx kernel reads the global count `total` itself: no p_share)
+        mean, var, world, p_local, _, total = _bn_train_stats(y, n, running_mean, running_var, momentum, sync_group)
         out = ops.bn_gelu_apply(y, mean, var, gamma.detach(), beta.detach(), eps)
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         ctx.save_for_backward(x if need_dw else None, w_dgrad if need_dx else None, y, mean, var, gamma, beta, total)
@@ -1106,9 +1100,7 @@ class _ConvT2x2BNGeluTrain(Function):
         gout = _nhwc_grad(gout, y.dtype)
         g, b = gamma.detach(), beta.detach()
         dgamma, dbeta = ops.bn_gelu_bwd_reduce(y, gout, mean, var, g, b, eps)
-        sg, sb = dgamma, dbeta
-        if world > 1:
-            sg, sb = sync_sum_pair(dgamma, dbeta, sync_group or None)
+        sg, sb = _bn_sync_sums(dgamma, dbeta, sync_group, world)
         dx = dw = None
         if need_dx or need_dw:
             dy = ops.bn_gelu_bwd_dx(y, gout, mean, var, g, b, eps, sg, sb, p_local, total_count=total, out=y)
@@ -1124,8 +1116,7 @@ def conv_transpose2x2_bn_gelu(x: Tensor, convt: nn.ConvTranspose2d, norm: nn.Mod
     _check_convt2x2(convt)
     w_fwd, w_dgrad = convt2x2_operands(convt, x.dtype)
     if norm.training:
-        sync_group = norm.process_group if isinstance(norm, nn.SyncBatchNorm) else False
-        momentum = 0.1 if norm.momentum is None else norm.momentum
+        sync_group, momentum = _bn_sync_momentum(norm)
         out = _ConvT2x2BNGeluTrain.apply(x, convt.weight, convt.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var,
                                          momentum, norm.eps, sync_group, w_fwd, w_dgrad)
         bump(norm.num_batches_tracked)
@@ -1206,13 +1197,10 @@ class _ConvBNActUpsampleAddTrain(Function):
     def forward(ctx, x, weight, conv_bias, gamma, beta, running_mean, running_var, momentum, eps, pad, relu, b):
         cb = None if conv_bias is None else conv_bias.detach()
         y, stats_done = _cba_conv(x, weight, cb, pad, 0, False, running_mean, running_var, momentum)
-        mean, var = stats_done if stats_done is not None else ops.bn_stats(y, running_mean, running_var, momentum)
-        if running_mean is not None:
-            mark_updated(running_mean)
-            mark_updated(running_var)
+        mean, var, _, p_local, _, _ = _bn_train_stats(y, weight.shape[0], running_mean, running_var, momentum, False, stats_done)
         out = ops.bilinear_add_bn(y, mean, var, gamma.detach(), beta.detach(), eps, relu, b)
         ctx.save_for_backward(x, weight, y, mean, var, gamma, beta)
-        ctx.cfg = (pad, relu, eps, conv_bias is not None, y.numel() // weight.shape[0], (b.shape[1], b.shape[2]))
+        ctx.cfg = (pad, relu, eps, conv_bias is not None, p_local, (b.shape[1], b.shape[2]))
         return out
 
     @staticmethod
@@ -1231,7 +1219,7 @@ class _ConvBNActUpsampleAddTrain(Function):
 
 def single_process_bn_train(norm: nn.Module) -> bool:
     """Train-mode BatchNorm whose batch statistics do not cross ranks."""
-    return norm.training and not (isinstance(norm, nn.SyncBatchNorm) and _world(norm.process_group) > 1)
+    return norm.training and _sync_world(_bn_sync_momentum(norm)[0]) == 1
 
 
 def conv_bn_act_upsample_add(x: Tensor, conv: nn.Conv2d, norm: nn.Module, b: Tensor, *, relu: bool = True) -> Tensor:
@@ -1246,9 +1234,8 @@ def conv_bn_act_upsample_add(x: Tensor, conv: nn.Conv2d, norm: nn.Module, b: Ten
              and bool(ops._lib.load().gdl_bilinear_fwd_add_bn_ok(ops.BF16, B, b.shape[1], b.shape[2], H, W, n)))
     if not fused:
         return upsample_add(conv_bn_act(x, conv, norm, relu=relu), b)
-    momentum = 0.1 if norm.momentum is None else norm.momentum
     out = _ConvBNActUpsampleAddTrain.apply(x, conv.weight, conv.bias, norm.weight, norm.bias, norm.running_mean, norm.running_var,
-                                           momentum, norm.eps, conv.padding[0], relu, b)
+                                           _bn_sync_momentum(norm)[1], norm.eps, conv.padding[0], relu, b)
     bump(norm.num_batches_tracked)
     return out
 
