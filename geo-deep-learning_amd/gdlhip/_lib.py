@@ -75,6 +75,11 @@ class OverlapOptions(C.Structure):
     ]
 
 
+# the `form` argument of gdl_focal_lowres_bwd (GDL_FOCAL_* in include/gdlhip.h)
+FOCAL_AUTO, FOCAL_GATHER, FOCAL_TILE = 0, 1, 2
+# gamma, has_alpha, alpha, has_threshold, threshold, has_ignore, ignore, mean: the option arguments of every gdl_focal_* call
+_FOCAL_OPT = (c_f, c_i, c_f, c_i, c_f, c_i, c_l, c_i)
+
 # name -> (restype, argtypes); every symbol declared in include/gdlhip.h
 SIGNATURES = {
     "gdl_version": (c_i, []),
@@ -215,6 +220,15 @@ SIGNATURES = {
     "gdl_soft_ce_lowres_fused_state": (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),
     "gdl_soft_ce_lowres_fused_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_l, c_i, c_p, c_p, c_l, c_p]),
     "gdl_soft_ce_lowres_fused_bwd": (c_i, [c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_f, c_p, c_p]),
+    "gdl_focal_workspace": (c_l, [c_i, c_i, c_l]),
+    "gdl_focal_fwd": (c_i, [c_p, c_p, c_i, c_i, c_l, *_FOCAL_OPT, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_focal_bwd": (c_i, [c_p, c_p, c_i, c_i, c_l, *_FOCAL_OPT, c_p, c_p, c_f, c_p, c_i, c_p]),
+    "gdl_focal_binary_fwd": (c_i, [c_p, c_p, c_l, *_FOCAL_OPT, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_focal_binary_bwd": (c_i, [c_p, c_p, c_l, *_FOCAL_OPT, c_p, c_p, c_f, c_p, c_i, c_p]),
+    "gdl_focal_lowres_workspace": (c_l, [c_i, c_i, c_i, c_i]),
+    "gdl_focal_lowres_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, *_FOCAL_OPT, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_focal_lowres_bwd_workspace": (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "gdl_focal_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, *_FOCAL_OPT, c_p, c_p, c_f, c_p, c_p, c_l, c_i, c_p]),
     "gdl_dice_binary_loss_fwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_l, c_p]),
     "gdl_dice_binary_loss_bwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_f, c_p, c_i, c_p]),
     "gdl_dice_binary_loss_opt_fwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),

@@ -1651,11 +1651,138 @@ class SoftCrossEntropyLoss(nn.Module):
         return _SoftCE.apply(y_pred, y_true.long().contiguous(), self.options)
 
 
+class _Focal(Function):
+    """smp FocalLoss(multiclass) on full-resolution NCHW logits; the backward recomputes from the saved logits and reads the
+    divisor the forward left on the device."""
+
+    @staticmethod
+    def forward(ctx, logits, target, options):
+        loss, norm = ops.focal_fwd(logits, target, options)
+        ctx.save_for_backward(logits, target, norm)
+        ctx.options = options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, norm = ctx.saved_tensors
+        return ops.focal_bwd(logits, target, norm, g.contiguous().float(), 1.0, ctx.options), None, None
+
+
+class _FocalBinary(Function):
+    """smp FocalLoss(binary): one logit per target entry, positive where the target is 1."""
+
+    @staticmethod
+    def forward(ctx, logits, target, options):
+        loss, norm = ops.focal_binary_fwd(logits, target, options)
+        ctx.save_for_backward(logits, target, norm)
+        ctx.options = options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, norm = ctx.saved_tensors
+        return ops.focal_binary_bwd(logits, target, norm, g.contiguous().float(), 1.0, ctx.options), None, None
+
+
+class _FocalLowres(Function):
+    """smp FocalLoss(multiclass) of bilinear(low -> size), forward and backward from the low-resolution map."""
+
+    @staticmethod
+    def forward(ctx, low, target, size, options):
+        loss, norm = ops.focal_lowres_fwd(low, target, size, options)
+        ctx.save_for_backward(low, target, norm)
+        ctx.size, ctx.options = size, options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        low, target, norm = ctx.saved_tensors
+        return ops.focal_lowres_bwd(low, target, ctx.size, norm, g.contiguous().float(), 1.0, ctx.options), None, None, None
+
+
+class FocalLoss(nn.Module):
+    """Stand-in for ``segmentation_models_pytorch.losses.FocalLoss`` (smp 0.5.0 constructor signature and defaults; losses/focal.py
+    and ``focal_loss_with_logits`` in losses/_functional.py) in modes ``"multiclass"`` and ``"binary"``, evaluated by the
+    gdl_focal_* HIP kernels.  smp is not installed where this was written, so parity with smp itself is unpinned; the formula is:
+
+    per element, for logit ``x`` and ``z`` in {0, 1}: ``s = (2z - 1) x``, ``L = softplus(-s)`` (BCE with logits, ``-log pt``),
+    ``q = sigmoid(-s) = 1 - pt``, ``f = q ** gamma`` -- with ``reduced_threshold = th``: ``f = (q / th) ** gamma``, and ``f = 1``
+    where ``pt < th`` --, ``a = alpha z + (1 - alpha)(1 - z)`` (1 when ``alpha`` is None); the element's loss is ``a f L``.
+    Multiclass (logits ``[B,K,H,W]``, target ``[B,H,W]`` or ``[B,1,H,W]``): ``z = [y == k]`` for every class k.  Binary (logits
+    and target of equal numel and batch size): ``z = [y == 1]``; ANY OTHER target value that is not ``ignore_index`` counts as 0.
+    A pixel is valid unless ``y == ignore_index`` (compared as int64).  The loss is the sum over classes and valid pixels, divided
+    by the number of valid pixels for ``reduction="mean"`` (smp: the mean per class over the not-ignored pixels, classes added)
+    and as it is for ``"sum"``.
+
+    - The gradient is DEFINED by the closed form ``-(2z - 1) a f (gamma pt L + q)`` (``-(2z - 1) a q`` on the ``f = 1`` branch):
+      finite for every ``gamma >= 0``, where torch's autograd of ``q ** gamma`` gives NaN at ``q = 0`` for ``0 < gamma < 1``.
+    - Without a valid pixel the loss is 0 and the gradient exactly 0 (smp's mean of an empty tensor is NaN).
+    - An ignored pixel gets an exactly zero gradient in every class.
+    - A multiclass target outside ``0..K-1`` that is not ``ignore_index`` matches no class and stays a valid all-negative pixel,
+      as in smp; the target is never used as an index.
+
+    ``y_pred`` may be ``LowresLogits``: in multiclass mode the loss and d(low) come from the head's own map under DiceLoss's
+    conditions (f32, K <= 16, factor <= 64); other cases materialise the logits.  ``normalized=True``, ``reduction="none"`` /
+    ``"batchwise_mean"`` and ``mode="multilabel"`` raise ``NotImplementedError``."""
+
+    def __init__(self, mode: str, alpha: float | None = None, gamma: float | None = 2.0, ignore_index: int | None = None,
+                 reduction: str | None = "mean", normalized: bool = False, reduced_threshold: float | None = None) -> None:
+        super().__init__()
+        if mode not in ("multiclass", "binary"):
+            if mode == "multilabel":
+                raise NotImplementedError("gdlhip FocalLoss implements mode='multiclass' and mode='binary' (got 'multilabel')")
+            raise ValueError(f"FocalLoss: unknown mode {mode!r}")
+        if normalized:
+            raise NotImplementedError("gdlhip FocalLoss implements normalized=False only")
+        if reduction not in ("mean", "sum"):
+            if reduction in ("none", "batchwise_mean"):
+                raise NotImplementedError(f"gdlhip FocalLoss implements reduction='mean' and 'sum' (got {reduction!r})")
+            raise ValueError(f"FocalLoss: unknown reduction {reduction!r}")
+        gamma = float(gamma)
+        if not math.isfinite(gamma) or gamma < 0.0:
+            raise ValueError(f"FocalLoss: gamma must be finite and >= 0 (got {gamma})")
+        if alpha is not None:
+            alpha = float(alpha)
+            if not 0.0 <= alpha <= 1.0:
+                raise ValueError(f"FocalLoss: alpha must be None or in [0, 1] (got {alpha})")
+        if reduced_threshold is not None:
+            reduced_threshold = float(reduced_threshold)
+            if not 0.0 < reduced_threshold <= 1.0:
+                raise ValueError(f"FocalLoss: reduced_threshold must be None or in (0, 1] (got {reduced_threshold})")
+        if ignore_index is not None:
+            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
+                raise ValueError(f"FocalLoss: ignore_index must be an int64 value or None (got {ignore_index!r})")
+            ignore_index = int(ignore_index)
+        self.mode, self.alpha, self.gamma, self.ignore_index = mode, alpha, gamma, ignore_index
+        self.reduction, self.normalized, self.reduced_threshold = reduction, False, reduced_threshold
+        self.options = ops.FocalOptions(gamma, alpha, ignore_index, reduction == "mean", reduced_threshold)
+
+    def forward(self, y_pred, y_true: Tensor) -> Tensor:
+        if isinstance(y_pred, LowresLogits):
+            size = (int(y_pred.size[0]), int(y_pred.size[1]))
+            yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
+            if (self.mode == "multiclass" and FUSE_LOWRES_DICE and ops.focal_lowres_ok(y_pred.low, size)
+                    and y_pred.low.dtype == torch.float32 and tuple(yt.shape[1:]) == size):
+                return _FocalLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.options)
+            y_pred = y_pred.materialise()
+        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
+            y_pred = y_pred.float().contiguous()
+        if self.mode == "binary":
+            if y_pred.shape[0] != y_true.shape[0] or y_pred.numel() != y_true.numel():
+                raise ValueError(f"FocalLoss(binary): y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} do not match")
+            return _FocalBinary.apply(y_pred, y_true.long().contiguous(), self.options)
+        if y_pred.dim() != 4:
+            raise ValueError(f"FocalLoss(multiclass): [B, K, H, W] logits expected (got {tuple(y_pred.shape)})")
+        if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
+            y_true = y_true[:, 0]
+        return _Focal.apply(y_pred, y_true.long().contiguous(), self.options)
+
+
 def reads_lowres(loss) -> bool:
     """True for a loss that evaluates itself (and its gradient) from ``LowresLogits``: a task may then ask the model for the heads'
-    own maps instead of the resized [B, K, H, W] logits.  gdlhip's multiclass DiceLoss, JaccardLoss and TverskyLoss, and
-    SoftCrossEntropyLoss."""
-    if isinstance(loss, _DiceFamily):
+    own maps instead of the resized [B, K, H, W] logits.  gdlhip's multiclass DiceLoss, JaccardLoss, TverskyLoss and FocalLoss,
+    and SoftCrossEntropyLoss."""
+    if isinstance(loss, (_DiceFamily, FocalLoss)):
         return loss.mode == "multiclass"
     return isinstance(loss, SoftCrossEntropyLoss)
 

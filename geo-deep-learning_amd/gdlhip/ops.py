@@ -2115,6 +2115,133 @@ def soft_ce_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], upstr
     return dlow
 
 
+class FocalOptions(NamedTuple):
+    """The constructor options of smp's FocalLoss as the gdl_focal_* entry points take them: ``gamma`` >= 0, ``alpha`` in [0, 1]
+    or None, ``ignore_index`` (any int64, or None), ``mean`` (reduction "mean": divide by the number of valid pixels) and
+    ``reduced_threshold`` in (0, 1] or None."""
+
+    gamma: float = 2.0
+    alpha: float | None = None
+    ignore_index: int | None = None
+    mean: bool = True
+    reduced_threshold: float | None = None
+
+    def c_args(self) -> tuple:
+        """(gamma, has_alpha, alpha, has_threshold, threshold, has_ignore, ignore, mean) in the order of the C calls"""
+        return (float(self.gamma), int(self.alpha is not None), float(self.alpha or 0.0), int(self.reduced_threshold is not None),
+                float(self.reduced_threshold or 0.0), int(self.ignore_index is not None), int(self.ignore_index or 0),
+                int(bool(self.mean)))
+
+
+FOCAL_FORMS = {"auto": _lib.FOCAL_AUTO, "gather": _lib.FOCAL_GATHER, "tile": _lib.FOCAL_TILE}
+
+
+def _focal_out(like: Tensor, nbytes: int):
+    """(loss [], norm [1], workspace of ``nbytes``) for a focal forward, on ``like``'s device."""
+    return (torch.empty((), device=like.device, dtype=torch.float32), torch.empty(1, device=like.device, dtype=torch.float32),
+            torch.empty(nbytes // 8, device=like.device, dtype=torch.float64))
+
+
+def _focal_grad_out(who: str, logits: Tensor, out: Tensor | None) -> Tensor:
+    if out is None:
+        return torch.empty_like(logits)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.shape != logits.shape:
+        raise ValueError(f"{who}: out must be a contiguous f32 tensor of the logits' shape")
+    return out
+
+
+def focal_fwd(logits: Tensor, target: Tensor, options: FocalOptions = FocalOptions()):
+    """smp FocalLoss(mode="multiclass") on NCHW f32 logits [B,K,H,W] and an int64 target [B,H,W]: ``(loss, norm)``, the 0-dim f32
+    loss and the divisor the kernels formed on the device (1 / valid pixels, or 1 for "sum"), which focal_bwd reads."""
+    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
+    _soft_ce_check("focal", logits, target, (B, H, W), "NCHW")
+    lib = _lib.load()
+    nbytes = lib.gdl_focal_workspace(B, K, H * W)
+    loss, norm, ws = _focal_out(logits, nbytes)
+    check(lib.gdl_focal_fwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes, _stream()),
+          "gdl_focal_fwd")
+    return loss, norm
+
+
+def focal_bwd(logits: Tensor, target: Tensor, norm: Tensor, upstream: Tensor | None, grad_scale: float = 1.0,
+              options: FocalOptions = FocalOptions(), out: Tensor | None = None, accumulate: bool = False) -> Tensor:
+    """d loss / d logits * upstream[0] * grad_scale (recomputed from ``logits``; ``norm`` from focal_fwd); ``out``/``accumulate``
+    as soft_ce_bwd."""
+    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
+    _soft_ce_check("focal", logits, target, (B, H, W), "NCHW")
+    _need_cuda(norm, upstream, out)
+    out = _focal_grad_out("focal_bwd", logits, out)
+    check(_lib.load().gdl_focal_bwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(norm), _p(upstream), grad_scale,
+                                    _p(out), int(accumulate), _stream()), "gdl_focal_bwd")
+    return out
+
+
+def _focal_binary_check(logits: Tensor, target: Tensor) -> None:
+    _need_cuda(logits, target)
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("focal_binary: contiguous f32 logits expected")
+    if target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != logits.numel() or logits.numel() == 0:
+        raise ValueError("focal_binary: contiguous int64 target with one entry per logit expected")
+
+
+def focal_binary_fwd(logits: Tensor, target: Tensor, options: FocalOptions = FocalOptions()):
+    """smp FocalLoss(mode="binary"): f32 logits of any shape, int64 target of the same numel (1 = positive; any other value that
+    is not ``ignore_index`` = negative): ``(loss, norm)`` as focal_fwd."""
+    _focal_binary_check(logits, target)
+    lib = _lib.load()
+    nbytes = lib.gdl_focal_workspace(1, 1, logits.numel())
+    loss, norm, ws = _focal_out(logits, nbytes)
+    check(lib.gdl_focal_binary_fwd(_p(logits), _p(target), logits.numel(), *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
+                                   _stream()), "gdl_focal_binary_fwd")
+    return loss, norm
+
+
+def focal_binary_bwd(logits: Tensor, target: Tensor, norm: Tensor, upstream: Tensor | None, grad_scale: float = 1.0,
+                     options: FocalOptions = FocalOptions(), out: Tensor | None = None, accumulate: bool = False) -> Tensor:
+    _focal_binary_check(logits, target)
+    _need_cuda(norm, upstream, out)
+    out = _focal_grad_out("focal_binary_bwd", logits, out)
+    check(_lib.load().gdl_focal_binary_bwd(_p(logits), _p(target), logits.numel(), *options.c_args(), _p(norm), _p(upstream),
+                                           grad_scale, _p(out), int(accumulate), _stream()), "gdl_focal_binary_bwd")
+    return out
+
+
+def focal_lowres_ok(low: Tensor, size: tuple[int, int]) -> bool:
+    """Shapes gdl_focal_lowres_* take: those of gdl_dice_loss_lowres_* (K <= 16, an upsample by at most 64 per direction)."""
+    return dice_lowres_ok(low, size)
+
+
+def focal_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], options: FocalOptions = FocalOptions()):
+    """The multiclass focal loss of bilinear(low -> size) vs target [B, H, W] without the full-resolution logits:
+    ``(loss, norm)`` as focal_fwd."""
+    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
+    _soft_ce_check("focal_lowres", low, target, (B, int(size[0]), int(size[1])), "NHWC low-resolution [B, h, w, K]")
+    lib = _lib.load()
+    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
+    nbytes = lib.gdl_focal_lowres_workspace(B, K, dims[4], dims[5])
+    loss, norm, ws = _focal_out(low, nbytes)
+    check(lib.gdl_focal_lowres_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes, _stream()),
+          "gdl_focal_lowres_fwd")
+    return loss, norm
+
+
+def focal_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], norm: Tensor, upstream: Tensor | None,
+                     grad_scale: float = 1.0, options: FocalOptions = FocalOptions(), form: str = "auto") -> Tensor:
+    """d loss / d low [B, h, w, K] * upstream[0] * grad_scale.  ``form``: "tile" (K <= 8: every full-resolution element once),
+    "gather" (every K <= 16) or "auto" (the tile kernel where the shape takes it, the default -- DESIGN.md section 2)."""
+    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
+    _soft_ce_check("focal_lowres", low, target, (B, int(size[0]), int(size[1])), "NHWC low-resolution [B, h, w, K]")
+    _need_cuda(norm, upstream)
+    dlow = torch.empty_like(low)
+    lib = _lib.load()
+    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
+    nbytes = lib.gdl_focal_lowres_bwd_workspace(*dims) if form != "gather" else 0
+    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    check(lib.gdl_focal_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(norm), _p(upstream), grad_scale, _p(dlow), _p(ws),
+                                   nbytes, FOCAL_FORMS[form], _stream()), "gdl_focal_lowres_bwd")
+    return dlow
+
+
 # ------------------------------------------------------------------ optimizer
 def sumsq_accum(x: Tensor, acc: Tensor) -> None:
     check(_lib.load().gdl_sumsq(_p(x), x.numel(), _p(acc), _stream()), "gdl_sumsq")

@@ -694,6 +694,57 @@ int gdl_soft_ce_lowres_fused_fwd(const float* low, const int64_t* target, int B,
 int gdl_soft_ce_lowres_fused_bwd(const void* state, int64_t state_bytes, int B, int K, int Hi, int Wi, int Ho, int Wo, int mean,
                                  const float* upstream, float grad_scale, float* dlow, gdl_stream_t stream);
 
+/* smp 0.5.0 FocalLoss(mode, alpha, gamma, ignore_index, reduction, reduced_threshold) (losses/focal.py; per-element arithmetic:
+ * focal_loss_with_logits in losses/_functional.py), mode "multiclass": NCHW f32 logits [B,K,HW], int64 target [B,HW], any K >= 1.
+ * For every class k, with z = [target_i == k] and s = (2z - 1) x_ik:
+ *   L = softplus(-s), pt = sigmoid(s), q = sigmoid(-s);  f = q^gamma, or with has_threshold (th in (0, 1]) f = (q / th)^gamma
+ *   and f = 1 where pt < th;  a = alpha z + (1 - alpha)(1 - z) (has_alpha; alpha in [0, 1]) or 1;  l = a f L;
+ *   dl/dx = -(2z - 1) a f (gamma pt L + q), on the f = 1 branch -(2z - 1) a q: finite for every finite gamma >= 0.
+ * A pixel is valid unless has_ignore and target_i == ignore (int64 compare).  A target outside 0..K-1 that is not `ignore` matches
+ * no class and stays a valid all-negative pixel; the target is never used as an index.
+ *   loss = sum_k sum_valid l * d,  d = 1 / (number of valid pixels) (mean != 0; d = 0 without a valid pixel: loss 0, gradient 0 --
+ *   smp's mean of an empty tensor is NaN) or 1 (mean == 0).  d is formed ON THE DEVICE and written to norm[0] (f32), which _bwd
+ *   reads: nothing synchronises with the host.
+ *   dlogits_ik = upstream[0] (device scalar, may be null) * grad_scale * norm[0] * valid_i * dl/dx   (= or += with accumulate).
+ * fwd: f64 per-workgroup partials of the loss and of the valid count in `workspace` (gdl_focal_workspace() bytes, 8-byte aligned),
+ * added in a fixed order: no float atomics, the same bits on every launch. */
+int64_t gdl_focal_workspace(int B, int K, int64_t HW);
+int gdl_focal_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float gamma, int has_alpha, float alpha,
+                  int has_threshold, float threshold, int has_ignore, int64_t ignore, int mean, float* loss, float* norm,
+                  void* workspace, int64_t workspace_bytes, gdl_stream_t stream);
+int gdl_focal_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, float gamma, int has_alpha, float alpha,
+                  int has_threshold, float threshold, int has_ignore, int64_t ignore, int mean, const float* norm,
+                  const float* upstream, float grad_scale, float* dlogits, int accumulate, gdl_stream_t stream);
+/* smp FocalLoss(mode="binary") (the same two smp functions): `total` logits and as many int64 targets, z = [target_i == 1]; any
+ * other value that is not `ignore` counts as 0.  Reduction, norm and determinism as above; workspace: gdl_focal_workspace(1, 1, total). */
+int gdl_focal_binary_fwd(const float* logits, const int64_t* target, int64_t total, float gamma, int has_alpha, float alpha,
+                         int has_threshold, float threshold, int has_ignore, int64_t ignore, int mean, float* loss, float* norm,
+                         void* workspace, int64_t workspace_bytes, gdl_stream_t stream);
+int gdl_focal_binary_bwd(const float* logits, const int64_t* target, int64_t total, float gamma, int has_alpha, float alpha,
+                         int has_threshold, float threshold, int has_ignore, int64_t ignore, int mean, const float* norm,
+                         const float* upstream, float grad_scale, float* dlogits, int accumulate, gdl_stream_t stream);
+/* smp FocalLoss(mode="multiclass") of F.interpolate(head(x), size=(Ho, Wo), mode="bilinear") WITHOUT the full-resolution logits:
+ * low = the [B, Hi, Wi, K] f32 map of gdl_head_1x1, target [B, Ho, Wo]; every output pixel's logits are evaluated on the fly with
+ * the expression of gdl_upsample_logits.  K <= 16, upsampling factors up to 64 per direction (as gdl_dice_loss_lowres_*).
+ * _fwd is a partial-sum pass (ws: gdl_focal_lowres_workspace() bytes, 8-byte aligned) that also leaves norm[0]; _bwd writes
+ * dlow [B, Hi, Wi, K] = d loss / d low, scaled as above, in the form `form` selects:
+ *   GDL_FOCAL_TILE    tile by tile (K <= 8; ws holds gdl_focal_lowres_bwd_workspace() > 0 bytes): every full-resolution element
+ *                     evaluated once, partial patches added in a fixed order; an error where the shape does not take it;
+ *   GDL_FOCAL_GATHER  one gather kernel per low-resolution logit vector (every K <= 16; ws may be null);
+ *   GDL_FOCAL_AUTO    the tile form where the shape takes it and ws is given, otherwise the gather kernel. */
+#define GDL_FOCAL_AUTO 0
+#define GDL_FOCAL_GATHER 1
+#define GDL_FOCAL_TILE 2
+int64_t gdl_focal_lowres_workspace(int B, int K, int Ho, int Wo);
+int gdl_focal_lowres_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float gamma,
+                         int has_alpha, float alpha, int has_threshold, float threshold, int has_ignore, int64_t ignore, int mean,
+                         float* loss, float* norm, void* ws, int64_t ws_bytes, gdl_stream_t stream);
+int64_t gdl_focal_lowres_bwd_workspace(int B, int K, int Hi, int Wi, int Ho, int Wo);
+int gdl_focal_lowres_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float gamma,
+                         int has_alpha, float alpha, int has_threshold, float threshold, int has_ignore, int64_t ignore, int mean,
+                         const float* norm, const float* upstream, float grad_scale, float* dlow, float* ws, int64_t ws_bytes,
+                         int form, gdl_stream_t stream);
+
 /* ---- fused bilinear x4 upsample -> 3x3 conv (multilevel_neck.py:157-158, scale 4) -------------------------------
  * gdl_pad_nhwc: NHWC border padding by (pad_h, pad_w), replicate (zero_mode 0) or zeros (1): out [B,H+2ph,W+2pw,C] dense.
  * gdl_subpix4_weights: the 16 phase weight sets of the sub-pixel decomposition from the 3x3 weights w [N][9*C]
