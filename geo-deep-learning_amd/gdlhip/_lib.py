@@ -79,6 +79,8 @@ class OverlapOptions(C.Structure):
 FOCAL_AUTO, FOCAL_GATHER, FOCAL_TILE = 0, 1, 2
 # gamma, has_alpha, alpha, has_threshold, threshold, has_ignore, ignore, mean: the option arguments of every gdl_focal_* call
 _FOCAL_OPT = (c_f, c_i, c_f, c_i, c_f, c_i, c_l, c_i)
+# per_image, has_ignore, ignore: the option arguments of every gdl_lovasz_* call
+_LOVASZ_OPT = (c_i, c_i, c_l)
 
 # name -> (restype, argtypes); every symbol declared in include/gdlhip.h
 SIGNATURES = {
@@ -229,6 +231,13 @@ SIGNATURES = {
     "gdl_focal_lowres_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, *_FOCAL_OPT, c_p, c_p, c_p, c_l, c_p]),
     "gdl_focal_lowres_bwd_workspace": (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),
     "gdl_focal_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, *_FOCAL_OPT, c_p, c_p, c_f, c_p, c_p, c_l, c_i, c_p]),
+    "gdl_sort_desc_workspace": (c_l, [c_i, c_l]),
+    "gdl_sort_desc_f32": (c_i, [c_p, c_i, c_l, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_lovasz_workspace": (c_l, [c_i, c_l, c_i]),
+    "gdl_lovasz_fwd": (c_i, [c_p, c_p, c_i, c_i, c_l, *_LOVASZ_OPT, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_lovasz_bwd": (c_i, [c_p, c_p, c_i, c_i, c_l, *_LOVASZ_OPT, c_p, c_p, c_p, c_f, c_p, c_i, c_p]),
+    "gdl_lovasz_binary_fwd": (c_i, [c_p, c_p, c_i, c_l, *_LOVASZ_OPT, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_lovasz_binary_bwd": (c_i, [c_p, c_p, c_i, c_l, *_LOVASZ_OPT, c_p, c_p, c_p, c_f, c_p, c_i, c_p]),
     "gdl_dice_binary_loss_fwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_l, c_p]),
     "gdl_dice_binary_loss_bwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_f, c_p, c_i, c_p]),
     "gdl_dice_binary_loss_opt_fwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),

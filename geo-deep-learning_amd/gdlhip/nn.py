@@ -1778,6 +1778,100 @@ class FocalLoss(nn.Module):
         return _Focal.apply(y_pred, y_true.long().contiguous(), self.options)
 
 
+class _Lovasz(Function):
+    """smp LovaszLoss(multiclass) on full-resolution NCHW logits; the forward leaves the Jaccard coefficients in pixel order and the
+    segments' weights on the device, the backward recomputes the softmax from the saved logits."""
+
+    @staticmethod
+    def forward(ctx, logits, target, options):
+        loss, coef, norm = ops.lovasz_fwd(logits, target, options)
+        ctx.save_for_backward(logits, target, coef, norm)
+        ctx.options = options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, coef, norm = ctx.saved_tensors
+        return ops.lovasz_bwd(logits, target, coef, norm, g.contiguous().float(), 1.0, ctx.options), None, None
+
+
+class _LovaszBinary(Function):
+    """smp LovaszLoss(binary): one logit per target entry, positive where the target is 1."""
+
+    @staticmethod
+    def forward(ctx, logits, target, options):
+        loss, coef, norm = ops.lovasz_binary_fwd(logits, target, options)
+        ctx.save_for_backward(logits, target, coef, norm)
+        ctx.options = options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, coef, norm = ctx.saved_tensors
+        return ops.lovasz_binary_bwd(logits, target, coef, norm, g.contiguous().float(), 1.0, ctx.options), None, None
+
+
+class LovaszLoss(nn.Module):
+    """Stand-in for ``segmentation_models_pytorch.losses.LovaszLoss`` (smp 0.5.0 constructor signature and defaults; losses/lovasz.py)
+    in modes ``"multiclass"`` and ``"binary"``, evaluated by the gdl_lovasz_* HIP kernels on the library's own segmented radix sort.
+    smp is not installed where this was written, so parity with smp itself is unpinned; the definition is:
+
+    **Jaccard coefficients.**  A segment of n errors is sorted descending, ties by ascending flat index
+    (``torch.sort(descending=True, stable=True)``).  At rank r (0-based), with the label bit ``z_r``, ``G = sum z``,
+    ``P_r = sum_{j<=r} z_j``, ``N_r = (r + 1) - P_r``, ``I_r = G - P_r``, ``U_r = G + N_r`` (exact integer counts):
+    ``g_r = J_r - J_{r-1}`` with ``J_r = 1 - I_r / U_r``, evaluated without the cancellation as ``1 / U_r`` where ``z_r = 1`` and
+    ``I_r / ((U_r - 1) U_r)`` where ``z_r = 0``; with ``G = 0``: ``g_0 = 1`` and every other ``g_r = 0``.
+
+    **Multiclass** (logits ``[B,K,H,W]``, target ``[B,H,W]`` or ``[B,1,H,W]``): ``p = softmax(x, dim=1)``; for class c and pixel i,
+    ``z = [y_i == c]`` and ``e = |z - p_ic|``; ``L_c = sum_r e_(r) g_r``; the loss is the mean of ``L_c`` over the classes present
+    among the valid pixels (``G_c > 0``), 0 if none is.  Gradient: ``dL_c/de_i = g_rank(i)`` (the coefficients are constants),
+    ``de/dp = -1`` where z = 1 and ``+1`` where z = 0, exactly 0 where ``e == 0``, then back through the softmax.
+
+    **Binary** (logits and target of equal numel and batch size, ``z = [y == 1]``, any other value that is not ``ignore_index``
+    counts as 0): ``e = max(0, 1 - x (2z - 1))``, ``L = sum_r e_(r) g_r`` (also with ``G = 0``);
+    ``dL/dx_i = -(2z - 1) g_rank(i)`` where ``e_i > 0`` and exactly 0 elsewhere.
+
+    - A pixel with ``y == ignore_index`` (compared as int64) gets key 0 and label bit 0: it sorts behind every positive error, adds
+      nothing to the loss and has an exactly zero gradient in every class -- the result of smp's compaction, without the pass.
+    - A multiclass target outside ``0..K-1`` that is not ignored matches no class; the target is never used as an index.
+    - ``per_image=False``: one segment of ``B H W`` per class.  ``per_image=True``: one segment of ``H W`` per image and class; the
+      result is the mean over images of each image's mean over its present classes (binary: the mean over images).
+    - NaN logits are unspecified.
+
+    ``LowresLogits`` input is materialised (``reads_lowres`` is False for this loss); bf16 or non-contiguous logits are converted.
+    ``mode="multilabel"`` and ``from_logits=False`` raise ``NotImplementedError``."""
+
+    def __init__(self, mode: str, per_image: bool = False, ignore_index: int | None = None, from_logits: bool = True) -> None:
+        super().__init__()
+        if mode not in ("multiclass", "binary"):
+            if mode == "multilabel":
+                raise NotImplementedError("gdlhip LovaszLoss implements mode='multiclass' and mode='binary' (got 'multilabel')")
+            raise ValueError(f"LovaszLoss: unknown mode {mode!r}")
+        if not from_logits:
+            raise NotImplementedError("gdlhip LovaszLoss implements from_logits=True only")
+        if ignore_index is not None:
+            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
+                raise ValueError(f"LovaszLoss: ignore_index must be an int64 value or None (got {ignore_index!r})")
+            ignore_index = int(ignore_index)
+        self.mode, self.per_image, self.ignore_index, self.from_logits = mode, bool(per_image), ignore_index, True
+        self.options = ops.LovaszOptions(self.per_image, ignore_index)
+
+    def forward(self, y_pred, y_true: Tensor) -> Tensor:
+        if isinstance(y_pred, LowresLogits):
+            y_pred = y_pred.materialise()
+        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
+            y_pred = y_pred.float().contiguous()
+        if self.mode == "binary":
+            if y_pred.dim() < 1 or y_pred.shape[0] != y_true.shape[0] or y_pred.numel() != y_true.numel():
+                raise ValueError(f"LovaszLoss(binary): y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} do not match")
+            return _LovaszBinary.apply(y_pred, y_true.long().contiguous(), self.options)
+        if y_pred.dim() != 4:
+            raise ValueError(f"LovaszLoss(multiclass): [B, K, H, W] logits expected (got {tuple(y_pred.shape)})")
+        if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
+            y_true = y_true[:, 0]
+        return _Lovasz.apply(y_pred, y_true.long().contiguous(), self.options)
+
+
 def reads_lowres(loss) -> bool:
     """True for a loss that evaluates itself (and its gradient) from ``LowresLogits``: a task may then ask the model for the heads'
     own maps instead of the resized [B, K, H, W] logits.  gdlhip's multiclass DiceLoss, JaccardLoss, TverskyLoss and FocalLoss,

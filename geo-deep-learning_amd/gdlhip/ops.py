@@ -2242,6 +2242,103 @@ def focal_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], norm: T
     return dlow
 
 
+class LovaszOptions(NamedTuple):
+    """The constructor options of smp's LovaszLoss as the gdl_lovasz_* entry points take them: ``per_image`` (one sort per image
+    and class, the loss averaged over images) and ``ignore_index`` (any int64, or None)."""
+
+    per_image: bool = False
+    ignore_index: int | None = None
+
+    def c_args(self) -> tuple:
+        """(per_image, has_ignore, ignore) in the order of the C calls"""
+        return (int(bool(self.per_image)), int(self.ignore_index is not None), int(self.ignore_index or 0))
+
+
+def sort_desc_f32(keys: Tensor):
+    """Stable descending sort of non-negative f32 keys [S, n] along dim 1 by the library's segmented radix sort: ``(sorted, perm)``
+    with ``perm`` int32, bit for bit ``torch.sort(keys, dim=1, descending=True, stable=True)`` (NaN and negative keys unspecified)."""
+    _need_cuda(keys)
+    if keys.dtype != torch.float32 or not keys.is_contiguous() or keys.dim() != 2:
+        raise ValueError("sort_desc_f32: contiguous f32 keys [S, n] expected")
+    S, n = keys.shape
+    out, perm = torch.empty_like(keys), torch.empty(S, n, device=keys.device, dtype=torch.int32)
+    lib = _lib.load()
+    nbytes = lib.gdl_sort_desc_workspace(S, n)
+    ws = torch.empty(nbytes // 8, device=keys.device, dtype=torch.float64)
+    check(lib.gdl_sort_desc_f32(_p(keys), S, n, _p(out), _p(perm), _p(ws), nbytes, _stream()), "gdl_sort_desc_f32")
+    return out, perm
+
+
+def _lovasz_out(like: Tensor, lib, segs: int, n: int, K: int):
+    """(loss [], coef like the logits, norm [segs], workspace, its bytes) for a Lovasz forward, on ``like``'s device."""
+    nbytes = lib.gdl_lovasz_workspace(segs, n, K)
+    return (torch.empty((), device=like.device, dtype=torch.float32), torch.empty(like.numel(), device=like.device, dtype=torch.float32),
+            torch.empty(max(segs, 1), device=like.device, dtype=torch.float32),
+            torch.empty(nbytes // 8, device=like.device, dtype=torch.float64), nbytes)
+
+
+def lovasz_fwd(logits: Tensor, target: Tensor, options: LovaszOptions = LovaszOptions()):
+    """smp LovaszLoss(mode="multiclass") on NCHW f32 logits [B,K,H,W] and an int64 target [B,H,W]: ``(loss, coef, norm)``, the 0-dim
+    f32 loss, the Jaccard coefficient of every (class, pixel) in pixel order and the weight of every segment in the loss (formed on
+    the device), both of which lovasz_bwd reads."""
+    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
+    _soft_ce_check("lovasz", logits, target, (B, H, W), "NCHW")
+    lib = _lib.load()
+    segs, n = (B * K, H * W) if options.per_image else (K, B * H * W)
+    loss, coef, norm, ws, nbytes = _lovasz_out(logits, lib, segs, n, K)
+    check(lib.gdl_lovasz_fwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(loss), _p(coef), _p(norm), _p(ws), nbytes,
+                             _stream()), "gdl_lovasz_fwd")
+    return loss, coef, norm
+
+
+def lovasz_bwd(logits: Tensor, target: Tensor, coef: Tensor, norm: Tensor, upstream: Tensor | None, grad_scale: float = 1.0,
+               options: LovaszOptions = LovaszOptions(), out: Tensor | None = None, accumulate: bool = False) -> Tensor:
+    """d loss / d logits * upstream[0] * grad_scale (softmax recomputed from ``logits``; ``coef``, ``norm`` from lovasz_fwd with the
+    same options); ``out``/``accumulate`` as focal_bwd."""
+    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
+    _soft_ce_check("lovasz", logits, target, (B, H, W), "NCHW")
+    _need_cuda(coef, norm, upstream, out)
+    _f32vec(coef, logits.numel(), "lovasz_bwd: coef")
+    _f32vec(norm, B * K if options.per_image else K, "lovasz_bwd: norm")
+    out = _focal_grad_out("lovasz_bwd", logits, out)
+    check(_lib.load().gdl_lovasz_bwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(coef), _p(norm), _p(upstream), grad_scale,
+                                     _p(out), int(accumulate), _stream()), "gdl_lovasz_bwd")
+    return out
+
+
+def _lovasz_binary_check(logits: Tensor, target: Tensor) -> tuple[int, int]:
+    _need_cuda(logits, target)
+    if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() < 1:
+        raise ValueError("lovasz_binary: contiguous f32 logits [B, ...] expected")
+    if target.dtype != torch.int64 or not target.is_contiguous() or target.numel() != logits.numel() or logits.numel() == 0:
+        raise ValueError("lovasz_binary: contiguous int64 target with one entry per logit expected")
+    return logits.shape[0], logits.numel() // logits.shape[0]
+
+
+def lovasz_binary_fwd(logits: Tensor, target: Tensor, options: LovaszOptions = LovaszOptions()):
+    """smp LovaszLoss(mode="binary"): f32 logits [B, ...], int64 target of the same numel (1 = positive; any other value that is not
+    ``ignore_index`` = negative): ``(loss, coef, norm)`` as lovasz_fwd."""
+    B, per = _lovasz_binary_check(logits, target)
+    lib = _lib.load()
+    segs, n = (B, per) if options.per_image else (1, B * per)
+    loss, coef, norm, ws, nbytes = _lovasz_out(logits, lib, segs, n, 1)
+    check(lib.gdl_lovasz_binary_fwd(_p(logits), _p(target), B, per, *options.c_args(), _p(loss), _p(coef), _p(norm), _p(ws), nbytes,
+                                    _stream()), "gdl_lovasz_binary_fwd")
+    return loss, coef, norm
+
+
+def lovasz_binary_bwd(logits: Tensor, target: Tensor, coef: Tensor, norm: Tensor, upstream: Tensor | None, grad_scale: float = 1.0,
+                      options: LovaszOptions = LovaszOptions(), out: Tensor | None = None, accumulate: bool = False) -> Tensor:
+    B, per = _lovasz_binary_check(logits, target)
+    _need_cuda(coef, norm, upstream, out)
+    _f32vec(coef, logits.numel(), "lovasz_binary_bwd: coef")
+    _f32vec(norm, B if options.per_image else 1, "lovasz_binary_bwd: norm")
+    out = _focal_grad_out("lovasz_binary_bwd", logits, out)
+    check(_lib.load().gdl_lovasz_binary_bwd(_p(logits), _p(target), B, per, *options.c_args(), _p(coef), _p(norm), _p(upstream),
+                                            grad_scale, _p(out), int(accumulate), _stream()), "gdl_lovasz_binary_bwd")
+    return out
+
+
 # ------------------------------------------------------------------ optimizer
 def sumsq_accum(x: Tensor, acc: Tensor) -> None:
     check(_lib.load().gdl_sumsq(_p(x), x.numel(), _p(acc), _stream()), "gdl_sumsq")

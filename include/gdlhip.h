@@ -745,6 +745,45 @@ int gdl_focal_lowres_bwd(const float* low, const int64_t* target, int B, int K, 
                          const float* norm, const float* upstream, float grad_scale, float* dlow, float* ws, int64_t ws_bytes,
                          int form, gdl_stream_t stream);
 
+/* Segmented stable sort, descending, of NON-NEGATIVE f32 keys (+0 only; NaN unspecified): keys [S][n] -> sorted [S][n] and perm
+ * [S][n] (int32: the position inside the segment each sorted key came from), equal keys in ascending position order -- what
+ * torch.sort(keys, dim=1, descending=True, stable=True) returns, bit for bit (smp 0.5.0 losses/lovasz.py sorts its errors with
+ * torch.sort).  LSD radix sort on the raw bit pattern, 8-bit digits, 4 passes; per pass a per-workgroup digit histogram, an
+ * exclusive scan of the (digit, workgroup) table and a stable scatter, every dependency between workgroups a kernel boundary.
+ * 1 <= S <= 65535, 1 <= n < 2^31; ws: gdl_sort_desc_workspace() bytes, 8-byte aligned.  keys may not alias sorted. */
+int64_t gdl_sort_desc_workspace(int S, int64_t n);
+int gdl_sort_desc_f32(const float* keys, int S, int64_t n, float* sorted, int32_t* perm, void* ws, int64_t ws_bytes,
+                      gdl_stream_t stream);
+/* smp 0.5.0 LovaszLoss(mode, per_image, ignore_index) (losses/lovasz.py: _lovasz_softmax / _lovasz_softmax_flat, _lovasz_grad),
+ * mode "multiclass": NCHW f32 logits [B,K,HW], int64 target [B,HW], any K >= 1.  p = softmax(x); for class c: z = [target_i == c],
+ * e = |z - p_ic|; the n errors of a segment (per_image == 0: one segment of n = B * HW per class; else one of n = HW per image
+ * and class) sorted descending, ties by ascending index; at rank r with G = sum z, P_r = sum_{j<=r} z_j, N_r = r + 1 - P_r,
+ * I_r = G - P_r, U_r = G + N_r (exact u32 counts):  g_r = 1 / U_r (z_r = 1), I_r / ((U_r - 1) U_r) (z_r = 0); G = 0: g_0 = 1, else 0;
+ * L = sum_r e_(r) g_r.  loss = the mean of L_c over the classes with G_c > 0 (0 without one); per_image: the mean over images of
+ * that.  A pixel with has_ignore and target_i == ignore (int64 compare) gets key 0, label bit 0 and an exactly zero gradient; a
+ * target outside 0..K-1 that is not `ignore` matches no class; the target is never used as an index.
+ * _fwd leaves coef [B,K,HW] (per_image) / [K,B,HW] (otherwise) = g_rank(i) in pixel order and norm [S] = each segment's weight in
+ * the loss (0 for an absent class), formed ON THE DEVICE; _bwd recomputes the softmax from `logits`:
+ *   dlogits_ik = upstream[0] (device scalar, may be null) * grad_scale * sum_c w_ic p_ic (delta_ck - p_ik),  w_ic = -+ g_ic norm_c
+ *   (- where z = 1), exactly 0 where e_ic == 0 or the pixel is ignored   (= or += with accumulate).
+ * ws: gdl_lovasz_workspace(S, n, K) bytes (S = K or B * K segments of n), 8-byte aligned.  B * K <= 65535, B * HW < 2^31.
+ * No float atomics, no host read-back, a fixed launch sequence per shape: the same bits on every launch, capturable. */
+int64_t gdl_lovasz_workspace(int S, int64_t n, int K);
+int gdl_lovasz_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, int per_image, int has_ignore, int64_t ignore,
+                   float* loss, float* coef, float* norm, void* ws, int64_t ws_bytes, gdl_stream_t stream);
+int gdl_lovasz_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, int per_image, int has_ignore, int64_t ignore,
+                   const float* coef, const float* norm, const float* upstream, float grad_scale, float* dlogits, int accumulate,
+                   gdl_stream_t stream);
+/* smp LovaszLoss(mode="binary") (losses/lovasz.py: _lovasz_hinge / _lovasz_hinge_flat): B images of `per` logits and as many int64
+ * targets, z = [target_i == 1], e = max(0, 1 - x (2z - 1)); one segment of B * per (per_image == 0; loss = L, also with G = 0) or one
+ * of `per` per image (loss = the mean over images); dlogits_i = -(2z - 1) g_rank(i) norm where e_i > 0, exactly 0 elsewhere.
+ * coef [B * per], norm [S]; ws: gdl_lovasz_workspace(S, n, 1) bytes. */
+int gdl_lovasz_binary_fwd(const float* logits, const int64_t* target, int B, int64_t per, int per_image, int has_ignore, int64_t ignore,
+                          float* loss, float* coef, float* norm, void* ws, int64_t ws_bytes, gdl_stream_t stream);
+int gdl_lovasz_binary_bwd(const float* logits, const int64_t* target, int B, int64_t per, int per_image, int has_ignore, int64_t ignore,
+                          const float* coef, const float* norm, const float* upstream, float grad_scale, float* dlogits,
+                          int accumulate, gdl_stream_t stream);
+
 /* ---- fused bilinear x4 upsample -> 3x3 conv (multilevel_neck.py:157-158, scale 4) -------------------------------
  * gdl_pad_nhwc: NHWC border padding by (pad_h, pad_w), replicate (zero_mode 0) or zeros (1): out [B,H+2ph,W+2pw,C] dense.
  * gdl_subpix4_weights: the 16 phase weight sets of the sub-pixel decomposition from the 3x3 weights w [N][9*C]
