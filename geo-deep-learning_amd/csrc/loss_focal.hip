@@ -127,7 +127,9 @@ __global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------ low resolution
-template <int K>
+// BIN (K = 1 only): the binary loss on the one-class head's map [B, Hi, Wi, 1] -- the class test is y == cls0 (= 1), as the
+// full-resolution kernels take it from FocalOpt; without BIN the test is y == k and the multiclass code is what it was.
+template <int K, bool BIN = false>
 __global__ __launch_bounds__(256) void focal_lowres_partial_kernel(const float* __restrict__ low, const int64_t* __restrict__ target,
                                                                    int B, int Hi, int Wi, int Ho, int Wo, double* __restrict__ ws,
                                                                    const FocalOpt o) {
@@ -146,7 +148,7 @@ __global__ __launch_bounds__(256) void focal_lowres_partial_kernel(const float* 
     float x[K], l = 0.f;
     bilinear_logits<K>(low, b, Hi, Wi, y0, y1, x0, x1, ly, lx, x);
 #pragma unroll
-    for (int k = 0; k < K; ++k) l += focal_elem<true>(x[k], t == (int64_t)k, o);
+    for (int k = 0; k < K; ++k) l += focal_elem<true>(x[k], BIN ? t == o.cls0 : t == (int64_t)k, o);
     acc += (double)l;
     cnt += 1.0;
   }
@@ -158,7 +160,7 @@ __global__ __launch_bounds__(256) void focal_lowres_partial_kernel(const float* 
 // gather form: one thread per LOW-resolution logit vector sums wy * wx * dl/dlogit over the full-resolution pixels that interpolate
 // from it, rows then columns in ascending order.  Every class count up to 16; each full-resolution element is evaluated once per
 // low-resolution neighbour (up to four times).
-template <int K>
+template <int K, bool BIN = false>
 __global__ __launch_bounds__(256) void focal_lowres_bwd_gather_kernel(const float* __restrict__ low, const int64_t* __restrict__ target,
                                                                       int B, int Hi, int Wi, int Ho, int Wo,
                                                                       const float* __restrict__ norm, const float* __restrict__ upstream,
@@ -193,7 +195,7 @@ __global__ __launch_bounds__(256) void focal_lowres_bwd_gather_kernel(const floa
         float x[K];
         bilinear_logits<K>(low, b, Hi, Wi, y0, y1, x0, x1, ly, lx, x);
 #pragma unroll
-        for (int k = 0; k < K; ++k) acc[k] += w * focal_elem<false>(x[k], t == (int64_t)k, o);
+        for (int k = 0; k < K; ++k) acc[k] += w * focal_elem<false>(x[k], BIN ? t == o.cls0 : t == (int64_t)k, o);
       }
     }
 #pragma unroll
@@ -207,7 +209,7 @@ struct FocalTile : LowresTile {
   FocalOpt o;
 };
 
-template <int K>
+template <int K, bool BIN = false>
 __global__ __launch_bounds__(CT_T) void focal_lowres_tile_kernel(const FocalTile a) {
   extern __shared__ __attribute__((aligned(16))) float csm[];
   float* dl = csm;                                   // [K][CT_H][CT_W]
@@ -227,7 +229,7 @@ __global__ __launch_bounds__(CT_T) void focal_lowres_tile_kernel(const FocalTile
         float x[K];
         bilinear_logits<K>(a.low, at.b, a.Hi, a.Wi, y0, y1, x0, x1, ly, lx, x);
 #pragma unroll
-        for (int k = 0; k < K; ++k) v[k] = focal_elem<false>(x[k], t == (int64_t)k, a.o);
+        for (int k = 0; k < K; ++k) v[k] = focal_elem<false>(x[k], BIN ? t == a.o.cls0 : t == (int64_t)k, a.o);
       }
     }
 #pragma unroll
@@ -388,5 +390,54 @@ extern "C" int gdl_focal_lowres_bwd(const float* low, const int64_t* target, int
   K_SWITCH(K, hipLaunchKernelGGL((focal_lowres_bwd_gather_kernel<KK>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, low, target, B,
                                     Hi, Wi, Ho, Wo, norm, upstream, grad_scale, dlow, o));
   GDL_CHECK_LAUNCH("gdl_focal_lowres_bwd");
+  return GDL_OK;
+}
+
+// ---- binary, from the low-resolution map: low [B, Hi, Wi, 1], target [B, Ho, Wo], z = [y == 1]; the kernels above at K = 1 with
+// the class test of FocalOpt::cls0.  Workspaces: gdl_focal_lowres_workspace(B, 1, Ho, Wo), gdl_binary_lowres_bwd_workspace().
+extern "C" int gdl_focal_binary_lowres_fwd(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo,
+                                           FOCAL_OPT_PARAMS, float* loss, float* norm, void* ws, int64_t ws_bytes, gdl_stream_t stream) {
+  const int K = 1;
+  GDL_CHECK_ARG(low && target && loss && norm && ws, "gdl_focal_binary_lowres_fwd: null pointer");
+  FOCAL_LOWRES_SHAPE("gdl_focal_binary_lowres_fwd");
+  GDL_CHECK_ARG(ws_bytes >= gdl_focal_lowres_workspace(B, K, Ho, Wo) && (uintptr_t)ws % 8 == 0,
+                "gdl_focal_binary_lowres_fwd: workspace too small or misaligned");
+  FOCAL_OPT("gdl_focal_binary_lowres_fwd", K, 1);
+  const int nblk = focal_blocks((int64_t)B * Ho * Wo, 1024);
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL((focal_lowres_partial_kernel<1, true>), dim3(nblk), dim3(256), 0, s, low, target, B, Hi, Wi, Ho, Wo, (double*)ws, o);
+  hipLaunchKernelGGL(focal_final_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, nblk, mean, loss, norm);
+  GDL_CHECK_LAUNCH("gdl_focal_binary_lowres_fwd");
+  return GDL_OK;
+}
+
+extern "C" int gdl_focal_binary_lowres_bwd(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo,
+                                           FOCAL_OPT_PARAMS, const float* norm, const float* upstream, float grad_scale, float* dlow,
+                                           float* ws, int64_t ws_bytes, int form, gdl_stream_t stream) {
+  const int K = 1;
+  GDL_CHECK_ARG(low && target && norm && dlow, "gdl_focal_binary_lowres_bwd: null pointer");
+  FOCAL_LOWRES_SHAPE("gdl_focal_binary_lowres_bwd");
+  GDL_CHECK_ARG(form == GDL_FOCAL_AUTO || form == GDL_FOCAL_GATHER || form == GDL_FOCAL_TILE, "gdl_focal_binary_lowres_bwd: unknown form %d", form);
+  FOCAL_OPT("gdl_focal_binary_lowres_bwd", K, 1);
+  hipStream_t st = (hipStream_t)stream;
+  int ny, nx;
+  const int64_t need = gdl_binary_lowres_bwd_workspace(B, Hi, Wi, Ho, Wo);
+  const bool can_tile = need > 0 && ws && ws_bytes >= need && binary_tile_dims(Hi, Wi, Ho, Wo, ny, nx);
+  GDL_CHECK_ARG(form != GDL_FOCAL_TILE || can_tile, "gdl_focal_binary_lowres_bwd: this shape or workspace does not take the tile form");
+  if (can_tile && form != GDL_FOCAL_GATHER) {
+    FocalTile a{};
+    a.low = low; a.target = target; a.upstream = upstream; a.patches = ws; a.dlow = dlow; a.norm = norm;
+    lowres_tile_shape(a, B, Hi, Wi, Ho, Wo, ny, nx);
+    a.scale = grad_scale; a.o = o;
+    hipLaunchKernelGGL((focal_lowres_tile_kernel<1, true>), dim3((unsigned)lowres_tiles(B, Ho, Wo)), dim3(CT_T), lowres_tile_lds(1, ny, nx), st, a);
+    const int rc = lowres_launch_reduce(a, K, st);
+    if (rc != GDL_OK) return rc;
+    GDL_CHECK_LAUNCH("gdl_focal_binary_lowres_bwd");
+    return GDL_OK;
+  }
+  const int64_t total = (int64_t)B * Hi * Wi;
+  hipLaunchKernelGGL((focal_lowres_bwd_gather_kernel<1, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, low, target, B, Hi, Wi,
+                     Ho, Wo, norm, upstream, grad_scale, dlow, o);
+  GDL_CHECK_LAUNCH("gdl_focal_binary_lowres_bwd");
   return GDL_OK;
 }

@@ -45,6 +45,11 @@ inline bool lowres_tile_dims(int K, int Hi, int Wi, int Ho, int Wo, int& ny_max,
   nx_max = (int)((int64_t)CT_W * Wi / Wo) + 3;
   return K <= 8 && ny_max <= CT_MAXN && nx_max <= CT_MAXN + CT_MAXN;
 }
+// one class (the binary losses): a 1:1 "resize" shares no pixel between low-resolution logits -- the gather kernel evaluates every
+// pixel exactly once there, so it is the only form
+inline bool binary_tile_dims(int Hi, int Wi, int Ho, int Wo, int& ny_max, int& nx_max) {
+  return lowres_tile_dims(1, Hi, Wi, Ho, Wo, ny_max, nx_max) && !(Ho == Hi && Wo == Wi);
+}
 inline int64_t lowres_tiles(int B, int Ho, int Wo) { return (int64_t)B * ((Ho + CT_H - 1) / CT_H) * ((Wo + CT_W - 1) / CT_W); }
 inline size_t lowres_tile_lds(int K, int ny, int nx) {
   return ((size_t)K * CT_H * CT_W + (size_t)K * ny * (CT_W + 1) + (size_t)ny * CT_H + (size_t)nx * CT_W) * sizeof(float);

@@ -998,6 +998,35 @@ __global__ __launch_bounds__(256) void upsample_argmax_kernel(const float* __res
   }
 }
 
+// One-class prediction, `(out.sigmoid().squeeze(1) > threshold).long()` (segmentation_dofa.py:279), as one pass: the sigmoid as
+// class_probs_kernel<1> writes it, 1 / (1 + exp(-x)) in f32, compared with the threshold in probability space (sigmoid(x) > 0.5 and
+// x > 0 differ for 0 < x < ~1e-7, where the f32 sigmoid rounds to 0.5).
+__device__ __forceinline__ int64_t sigmoid_over(float x, float th) { return 1.0f / (1.0f + expf(-x)) > th ? 1 : 0; }
+
+__global__ __launch_bounds__(256) void sigmoid_threshold_kernel(const float* __restrict__ logits, int64_t total, float th,
+                                                                int64_t* __restrict__ mask) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) mask[i] = sigmoid_over(logits[i], th);
+}
+
+// ... and straight from the one-class head's low-resolution map [B, Hi, Wi, 1]: the bilinear logit of upsample_logits_kernel per
+// pixel, then the same decision -- the mask of gdl_upsample_logits + gdl_sigmoid_threshold without the [B, 1, H, W] f32 tensor.
+__global__ __launch_bounds__(256) void upsample_threshold_kernel(const float* __restrict__ low, int B, int Hi, int Wi, int Ho, int Wo,
+                                                                 float th, int64_t* __restrict__ mask) {
+  const int64_t total = (int64_t)B * Ho * Wo;
+  const float ry = (float)Hi / (float)Ho, rx = (float)Wi / (float)Wo;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int ox = (int)(i % Wo);
+    const int64_t t = i / Wo;
+    const int oy = (int)(t % Ho), b = (int)(t / Ho);
+    int y0, y1, x0, x1; float ly, lx;
+    src_index2(ry, oy, Hi, y0, y1, ly);
+    src_index2(rx, ox, Wi, x0, x1, lx);
+    float x[1];
+    bilinear_logits<1>(low, b, Hi, Wi, y0, y1, x0, x1, ly, lx, x);
+    mask[i] = sigmoid_over(x[0], th);
+  }
+}
+
 // ------------------------------------------------------------------ optimizer
 __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ out) {
   __shared__ float red[4];
@@ -1445,6 +1474,24 @@ extern "C" int gdl_upsample_argmax(const float* low, int B, int Hi, int Wi, int 
   const int64_t total = (int64_t)B * Ho * Wo;
   K_SWITCH(K, hipLaunchKernelGGL((upsample_argmax_kernel<KK>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, low, B, Hi, Wi, Ho, Wo, mask));
   GDL_CHECK_LAUNCH("gdl_upsample_argmax");
+  return GDL_OK;
+}
+
+extern "C" int gdl_sigmoid_threshold(const float* logits, int64_t total, float threshold, int64_t* mask, gdl_stream_t stream) {
+  GDL_CHECK_ARG(logits && mask && total > 0, "gdl_sigmoid_threshold: bad args");
+  hipLaunchKernelGGL(sigmoid_threshold_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, logits, total, threshold, mask);
+  GDL_CHECK_LAUNCH("gdl_sigmoid_threshold");
+  return GDL_OK;
+}
+
+extern "C" int gdl_upsample_threshold(const float* low, int B, int Hi, int Wi, int64_t* mask, int Ho, int Wo, float threshold,
+                                      gdl_stream_t stream) {
+  GDL_CHECK_ARG(low && mask, "gdl_upsample_threshold: null pointer");
+  GDL_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi, "gdl_upsample_threshold: bad sizes (an upsample is expected)");
+  GDL_CHECK_ARG((Ho + Hi - 1) / Hi <= 64 && (Wo + Wi - 1) / Wi <= 64, "gdl_upsample_threshold: upsampling factors above 64 are not supported");
+  const int64_t total = (int64_t)B * Ho * Wo;
+  hipLaunchKernelGGL(upsample_threshold_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, low, B, Hi, Wi, Ho, Wo, threshold, mask);
+  GDL_CHECK_LAUNCH("gdl_upsample_threshold");
   return GDL_OK;
 }
 

@@ -189,6 +189,8 @@ SIGNATURES = {
     "gdl_upsample_logits_bwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_l, c_p]),
     "gdl_softmax_argmax": (c_i, [c_p, c_i, c_i, c_l, c_p, c_p]),
     "gdl_upsample_argmax": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p]),
+    "gdl_sigmoid_threshold": (c_i, [c_p, c_l, c_f, c_p, c_p]),
+    "gdl_upsample_threshold": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_f, c_p]),
     "gdl_class_probs": (c_i, [c_p, c_i, c_i, c_l, c_p, c_p]),
     "gdl_iou_counts": (c_i, [c_p, c_p, c_i, c_l, c_i, c_p, c_p]),
     "gdl_dice_loss_workspace": (c_l, [c_i, c_i, c_l]),
@@ -248,6 +250,15 @@ SIGNATURES = {
     "gdl_overlap_loss_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_f, c_p, c_p, c_l, c_p]),
     "gdl_overlap_binary_loss_fwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),
     "gdl_overlap_binary_loss_bwd": (c_i, [c_p, c_p, c_l, c_f, c_p, c_p, c_p, c_f, c_p, c_i, c_p]),
+    "gdl_binary_lowres_bwd_workspace": (c_l, [c_i, c_i, c_i, c_i, c_i]),
+    "gdl_dice_binary_loss_lowres_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_dice_binary_loss_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_f, c_p, c_p, c_l, c_i, c_p]),
+    "gdl_dice_binary_loss_lowres_opt_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_dice_binary_loss_lowres_opt_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_f, c_p, c_p, c_l, c_i, c_p]),
+    "gdl_overlap_binary_loss_lowres_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_overlap_binary_loss_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_f, c_p, c_p, c_l, c_i, c_p]),
+    "gdl_focal_binary_lowres_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, *_FOCAL_OPT, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_focal_binary_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, *_FOCAL_OPT, c_p, c_p, c_f, c_p, c_p, c_l, c_i, c_p]),
     "gdl_sumsq": (c_i, [c_p, c_l, c_p, c_p]),
     "gdl_clip_coef": (c_i, [c_p, c_f, c_p, c_p]),
     "gdl_multi_sumsq": (c_i, [c_p, c_i, c_p, c_p]),

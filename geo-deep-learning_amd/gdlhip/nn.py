@@ -1420,6 +1420,30 @@ class _DiceBinaryLoss(Function):
                 None, None, None)
 
 
+class _DiceBinaryLowres(Function):
+    """The binary losses of bilinear(low -> size) for a one-class head's map [B, h, w, 1], forward and backward from that map."""
+
+    @staticmethod
+    def forward(ctx, low, target, size, eps, options=None):
+        loss, sums = ops.dice_binary_lowres_fwd(low, target, size, eps, options=options)
+        ctx.save_for_backward(low, target, sums)
+        ctx.size, ctx.eps, ctx.options = size, eps, options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        low, target, sums = ctx.saved_tensors
+        dlow = ops.dice_binary_lowres_bwd(low, target, ctx.size, sums, g.contiguous().float(), 1.0, ctx.eps, options=ctx.options)
+        return dlow, None, None, None, None
+
+
+def _binary_lowres_ok(low: Tensor, size, yt: Tensor) -> bool:
+    """A one-class head's map that the binary low-resolution kernels take in place of the resized logits -- where that is the
+    faster route (ops.binary_lowres_pays: the measured factors; a larger one materialises, as every other excluded case)."""
+    return (FUSE_LOWRES_DICE and low.dim() == 4 and low.shape[3] == 1 and low.dtype == torch.float32 and ops.binary_lowres_pays(low, size)
+            and yt.dim() == 3 and tuple(yt.shape[1:]) == size)
+
+
 class _DiceFamily(nn.Module):
     """What DiceLoss, JaccardLoss and TverskyLoss share: the checks of smp's common constructor arguments and the forward that
     picks the full-resolution, low-resolution (LowresLogits) or binary kernels.  A subclass sets ``mode``, ``eps``, ``classes``
@@ -1461,6 +1485,8 @@ class _DiceFamily(nn.Module):
                     and y_pred.low.dtype == torch.float32 and tuple(yt.shape[1:]) == size):
                 self._check_classes(y_pred.low.shape[3])
                 return _DiceLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.eps, self.options)
+            if self.mode == "binary" and _binary_lowres_ok(y_pred.low, size, yt) and y_pred.low.shape[0] == yt.shape[0]:
+                return _DiceBinaryLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.eps, self.options)
             y_pred = y_pred.materialise()
         if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
             y_pred = y_pred.float().contiguous()
@@ -1489,7 +1515,13 @@ class DiceLoss(_DiceFamily):
     A class without a valid (not ignored) pixel in the batch contributes 0.  A target value outside ``0..K-1`` that is not
     ``ignore_index`` matches no class while its probabilities still count in the denominators (unchanged behaviour).  With every
     option at its default the plain kernels run and the results are bit-identical to earlier builds.  ``from_logits=False`` is
-    not implemented and raises."""
+    not implemented and raises.
+
+    ``y_pred`` may be ``LowresLogits`` (f32, ``GDL_LOWRES_DICE`` on): multiclass with K <= 16 and an upsample by at most 64 per
+    direction, or binary with the one-class head's ``[B, h, w, 1]`` map and an upsample by at most
+    ``ops.BINARY_LOWRES_MAX_FACTOR`` = 8 per direction (the kernels take factors up to 64, but beyond 8 materialising was measured
+    to be faster: ``ops.binary_lowres_pays``); the loss and d(low) then come from that map and the resized logits are never
+    written.  Other cases materialise them."""
 
     def __init__(self, mode: str = "multiclass", classes=None, log_loss: bool = False, from_logits: bool = True,
                  smooth: float = 0.0, ignore_index=None, eps: float = 1e-7) -> None:
@@ -1514,9 +1546,9 @@ class JaccardLoss(_DiceFamily):
     ``-log(max(score_k, eps))`` with ``log_loss``; a class with ``Y_k = 0`` contributes 0; the result is the mean over ``classes``
     (all K when None; absent classes still count in the divisor).  There is no ``ignore_index``, as in smp.
 
-    Targets are ``[B,H,W]`` or ``[B,1,H,W]``.  ``y_pred`` may be ``LowresLogits``: in multiclass mode the loss and d(low) come
-    from the head's own map under DiceLoss's conditions (f32, K <= 16, factor <= 64); other cases materialise the logits.
-    ``mode="multilabel"`` and ``from_logits=False`` raise ``NotImplementedError``."""
+    Targets are ``[B,H,W]`` or ``[B,1,H,W]``.  ``y_pred`` may be ``LowresLogits``: the loss and d(low) come from the head's own
+    map under DiceLoss's conditions (f32; multiclass: K <= 16 and factor <= 64, binary: K = 1 and factor <= 8); other cases
+    materialise the logits.  ``mode="multilabel"`` and ``from_logits=False`` raise ``NotImplementedError``."""
 
     def __init__(self, mode: str = "multiclass", classes=None, log_loss: bool = False, from_logits: bool = True,
                  smooth: float = 0.0, eps: float = 1e-7) -> None:
@@ -1700,6 +1732,22 @@ class _FocalLowres(Function):
         return ops.focal_lowres_bwd(low, target, ctx.size, norm, g.contiguous().float(), 1.0, ctx.options), None, None, None
 
 
+class _FocalBinaryLowres(Function):
+    """smp FocalLoss(binary) of bilinear(low -> size) for a one-class head's map [B, h, w, 1], forward and backward from that map."""
+
+    @staticmethod
+    def forward(ctx, low, target, size, options):
+        loss, norm = ops.focal_binary_lowres_fwd(low, target, size, options)
+        ctx.save_for_backward(low, target, norm)
+        ctx.size, ctx.options = size, options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        low, target, norm = ctx.saved_tensors
+        return ops.focal_binary_lowres_bwd(low, target, ctx.size, norm, g.contiguous().float(), 1.0, ctx.options), None, None, None
+
+
 class FocalLoss(nn.Module):
     """Stand-in for ``segmentation_models_pytorch.losses.FocalLoss`` (smp 0.5.0 constructor signature and defaults; losses/focal.py
     and ``focal_loss_with_logits`` in losses/_functional.py) in modes ``"multiclass"`` and ``"binary"``, evaluated by the
@@ -1721,8 +1769,9 @@ class FocalLoss(nn.Module):
     - A multiclass target outside ``0..K-1`` that is not ``ignore_index`` matches no class and stays a valid all-negative pixel,
       as in smp; the target is never used as an index.
 
-    ``y_pred`` may be ``LowresLogits``: in multiclass mode the loss and d(low) come from the head's own map under DiceLoss's
-    conditions (f32, K <= 16, factor <= 64); other cases materialise the logits.  ``normalized=True``, ``reduction="none"`` /
+    ``y_pred`` may be ``LowresLogits``: the loss and d(low) come from the head's own map under DiceLoss's conditions (f32;
+    multiclass: K <= 16 and factor <= 64, binary: K = 1 and factor <= ``ops.BINARY_LOWRES_MAX_FACTOR`` = 8, beyond which
+    materialising was measured to be faster); other cases materialise the logits.  ``normalized=True``, ``reduction="none"`` /
     ``"batchwise_mean"`` and ``mode="multilabel"`` raise ``NotImplementedError``."""
 
     def __init__(self, mode: str, alpha: float | None = None, gamma: float | None = 2.0, ignore_index: int | None = None,
@@ -1764,6 +1813,8 @@ class FocalLoss(nn.Module):
             if (self.mode == "multiclass" and FUSE_LOWRES_DICE and ops.focal_lowres_ok(y_pred.low, size)
                     and y_pred.low.dtype == torch.float32 and tuple(yt.shape[1:]) == size):
                 return _FocalLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.options)
+            if self.mode == "binary" and _binary_lowres_ok(y_pred.low, size, yt) and y_pred.low.shape[0] == yt.shape[0]:
+                return _FocalBinaryLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.options)
             y_pred = y_pred.materialise()
         if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
             y_pred = y_pred.float().contiguous()
@@ -1872,12 +1923,13 @@ class LovaszLoss(nn.Module):
         return _Lovasz.apply(y_pred, y_true.long().contiguous(), self.options)
 
 
-def reads_lowres(loss) -> bool:
+def reads_lowres(loss, num_classes: int | None = None) -> bool:
     """True for a loss that evaluates itself (and its gradient) from ``LowresLogits``: a task may then ask the model for the heads'
     own maps instead of the resized [B, K, H, W] logits.  gdlhip's multiclass DiceLoss, JaccardLoss, TverskyLoss and FocalLoss,
-    and SoftCrossEntropyLoss."""
+    and SoftCrossEntropyLoss; for a one-class model (``num_classes == 1``) also their binary modes, which read the head's
+    [B, h, w, 1] map."""
     if isinstance(loss, (_DiceFamily, FocalLoss)):
-        return loss.mode == "multiclass"
+        return loss.mode == "multiclass" or (loss.mode == "binary" and num_classes == 1)
     return isinstance(loss, SoftCrossEntropyLoss)
 
 
@@ -1890,6 +1942,26 @@ def predict_mask(logits) -> Tensor:
             return ops.upsample_argmax(low.contiguous(), logits.size)
         logits = logits.materialise()
     return ops.softmax_argmax(logits.float().contiguous())
+
+
+def predict_binary_mask(logits, threshold: float = 0.5) -> Tensor:
+    """``(out.sigmoid().squeeze(1) > threshold).long()`` (segmentation_dofa.py:279) for a one-class model: int64 [B, H, W].  For
+    not-yet-resized logits (LowresLogits) the resize is evaluated per pixel inside the kernel; resized logits take one pass.
+    A LowresLogits that is not f32, or whose shape ``ops.dice_lowres_ok`` rejects (a downsample, a factor above 64), is resized
+    first (``materialise()``) and thresholded by ``sigmoid_threshold`` -- still HIP kernels, the same mask, as ``predict_mask``
+    does for its shapes; it is the C entry point ``gdl_upsample_threshold`` and ``ops.upsample_threshold`` that refuse such a
+    shape with an error.  More than one class is an error here too."""
+    if isinstance(logits, LowresLogits):
+        low = logits.low
+        if low.dim() != 4 or low.shape[3] != 1:
+            raise ValueError(f"predict_binary_mask: one-class logits [B, h, w, 1] expected, got {tuple(low.shape)}")
+        size = (int(logits.size[0]), int(logits.size[1]))
+        if low.dtype == torch.float32 and ops.dice_lowres_ok(low, size):
+            return ops.upsample_threshold(low.contiguous(), size, threshold)
+        logits = logits.materialise()
+    if logits.dim() != 4 or logits.shape[1] != 1:
+        raise ValueError(f"predict_binary_mask: one-class logits [B, 1, H, W] expected, got {tuple(logits.shape)}")
+    return ops.sigmoid_threshold(logits.float().contiguous(), threshold)
 
 
 # ------------------------------------------------------------------ optimizer

@@ -1837,6 +1837,61 @@ def upsample_argmax(low: Tensor, size: tuple[int, int]) -> Tensor:
     return mask
 
 
+def sigmoid_threshold(logits: Tensor, threshold: float = 0.5) -> Tensor:
+    """``(logits.sigmoid() > threshold).long()`` (segmentation_dofa.py:279) in one pass: f32 logits [B, 1, H, W] -> int64 [B, H, W];
+    any other shape keeps its shape.  The comparison is made on the f32 sigmoid, as the reference makes it."""
+    _need_cuda(logits)
+    if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.numel() == 0:
+        raise ValueError("sigmoid_threshold: contiguous f32 logits expected")
+    shape = (logits.shape[0], *logits.shape[2:]) if logits.dim() == 4 and logits.shape[1] == 1 else tuple(logits.shape)
+    mask = torch.empty(shape, device=logits.device, dtype=torch.int64)
+    check(_lib.load().gdl_sigmoid_threshold(_p(logits), logits.numel(), float(threshold), _p(mask), _stream()), "gdl_sigmoid_threshold")
+    return mask
+
+
+def _binary_lowres_check(who: str, low: Tensor, size: tuple[int, int], target: Tensor | None = None) -> tuple:
+    """The shapes the one-class low-resolution entry points take, checked before anything touches the device: (B, Hi, Wi, Ho, Wo)."""
+    if low.dim() != 4 or low.shape[3] != 1:
+        raise ValueError(f"{who}: one-class NHWC low-resolution logits [B, h, w, 1] expected, got {tuple(low.shape)}")
+    B, Hi, Wi, _ = low.shape
+    Ho, Wo = int(size[0]), int(size[1])
+    if B < 1 or Hi < 1 or Wi < 1 or Ho < Hi or Wo < Wi:
+        raise ValueError(f"{who}: an upsample is expected, got {Hi} x {Wi} -> {Ho} x {Wo}")
+    if -(-Ho // Hi) > 64 or -(-Wo // Wi) > 64:
+        raise ValueError(f"{who}: upsampling factors above 64 are not supported, got {Hi} x {Wi} -> {Ho} x {Wo}")
+    _need_cuda(low, target)
+    if low.dtype != torch.float32 or not low.is_contiguous():
+        raise ValueError(f"{who}: contiguous f32 low-resolution logits expected")
+    if target is not None and (target.dtype != torch.int64 or not target.is_contiguous() or tuple(target.shape) != (B, Ho, Wo)):
+        raise ValueError(f"{who}: contiguous int64 target {[B, Ho, Wo]} expected, got {tuple(target.shape)}")
+    return B, Hi, Wi, Ho, Wo
+
+
+# Largest upsampling factor (per direction) at which the one-class low-resolution loss kernels were measured faster than materialising
+# the [B, 1, H, W] logits (tools/bench_binary_lowres.py -> profiles/bench_binary_lowres.txt: 0.90 x at factor 4, 0.95 x at 8, 1.06-1.10 x at 16, 1.10-1.17 x at 32;
+# one shape only, batch 64 to 512^2, applied to every batch and output size): with
+# one class the resized tensor is small, and at large factors a tile's transposed resize has few low-resolution logits to spread
+# over its threads.
+BINARY_LOWRES_MAX_FACTOR = 8
+
+
+def binary_lowres_pays(low: Tensor, size: tuple[int, int]) -> bool:
+    """Shapes for which a binary loss reads the one-class head's map [B, h, w, 1] instead of the resized logits: those the
+    kernels take (dice_lowres_ok) with factors up to BINARY_LOWRES_MAX_FACTOR; beyond it the materialised path is the faster one."""
+    if low.dim() != 4 or low.shape[3] != 1 or not dice_lowres_ok(low, size):
+        return False
+    return -(-size[0] // low.shape[1]) <= BINARY_LOWRES_MAX_FACTOR and -(-size[1] // low.shape[2]) <= BINARY_LOWRES_MAX_FACTOR
+
+
+def upsample_threshold(low: Tensor, size: tuple[int, int], threshold: float = 0.5) -> Tensor:
+    """``(bilinear(low -> size).sigmoid() > threshold).long()`` for the one-class head's NHWC f32 map [B, h, w, 1] -> int64
+    [B, H, W], without the resized logits (gdl_upsample_threshold; the same mask as upsample_logits + sigmoid_threshold)."""
+    B, Hi, Wi, Ho, Wo = _binary_lowres_check("upsample_threshold", low, size)
+    mask = torch.empty((B, Ho, Wo), device=low.device, dtype=torch.int64)
+    check(_lib.load().gdl_upsample_threshold(_p(low), B, Hi, Wi, _p(mask), Ho, Wo, float(threshold), _stream()), "gdl_upsample_threshold")
+    return mask
+
+
 def class_probs(logits: Tensor) -> Tensor:
     """NCHW f32 logits -> softmax(dim=1) (or sigmoid for one class) probabilities."""
     _need_cuda(logits)
@@ -1903,6 +1958,10 @@ class OverlapOptions(NamedTuple):
                                 C.cast(arr, C.POINTER(C.c_int)) if arr is not None else None,
                                 len(self.classes) if self.classes else 0)
         return C.addressof(o), (o, arr)
+
+
+# the `form` argument of the low-resolution backwards that have two
+FOCAL_FORMS = {"auto": _lib.FOCAL_AUTO, "gather": _lib.FOCAL_GATHER, "tile": _lib.FOCAL_TILE}
 
 
 def _dice_entry(stem: str, way: str, options):
@@ -2015,6 +2074,35 @@ def dice_binary_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream:
     name, fn, opt, keep = _dice_entry("binary_loss", "bwd", options)
     check(fn(_p(logits), _p(target), logits.numel(), eps, *opt, _p(sums), _p(upstream), grad_scale, _p(out), 0, _stream()), name)
     return out
+
+
+def dice_binary_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], eps: float = 1e-7,
+                           options: DiceOptions | OverlapOptions | None = None):
+    """Dice(binary) -- or the family member ``options`` selects -- of bilinear(low -> size) vs target [B, H, W] for the one-class
+    head's map [B, h, w, 1], without the full-resolution logits: (loss, sums)."""
+    B, Hi, Wi, Ho, Wo = _binary_lowres_check("dice_binary_lowres", low, size, target)
+    nbytes = _lib.load().gdl_dice_loss_lowres_workspace(B, 1, Ho, Wo)
+    sums, loss, ws = _dice_buffers(low, 1, nbytes)
+    name, fn, opt, keep = _dice_entry("binary_loss_lowres", "fwd", options)
+    check(fn(_p(low), _p(target), B, Hi, Wi, Ho, Wo, eps, *opt, _p(sums), _p(loss), _p(ws), nbytes, _stream()), name)
+    return loss, sums
+
+
+def dice_binary_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], sums: Tensor, upstream: Tensor | None,
+                           grad_scale: float = 1.0, eps: float = 1e-7, options: DiceOptions | OverlapOptions | None = None,
+                           form: str = "auto") -> Tensor:
+    """d loss / d low [B, h, w, 1] * upstream[0] * grad_scale from the forward's ``sums``.  ``form``: "tile" (every full-resolution
+    pixel once), "gather" (every shape) or "auto" (the tile kernels where the shape takes them)."""
+    B, Hi, Wi, Ho, Wo = _binary_lowres_check("dice_binary_lowres", low, size, target)
+    _need_cuda(sums, upstream)
+    dlow = torch.empty_like(low)
+    lib = _lib.load()
+    nbytes = lib.gdl_binary_lowres_bwd_workspace(B, Hi, Wi, Ho, Wo) if form != "gather" else 0
+    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    name, fn, opt, keep = _dice_entry("binary_loss_lowres", "bwd", options)
+    check(fn(_p(low), _p(target), B, Hi, Wi, Ho, Wo, eps, *opt, _p(sums), _p(upstream), grad_scale, _p(dlow), _p(ws), nbytes,
+             FOCAL_FORMS[form], _stream()), name)
+    return dlow
 
 
 class SoftCEOptions(NamedTuple):
@@ -2133,9 +2221,6 @@ class FocalOptions(NamedTuple):
                 int(bool(self.mean)))
 
 
-FOCAL_FORMS = {"auto": _lib.FOCAL_AUTO, "gather": _lib.FOCAL_GATHER, "tile": _lib.FOCAL_TILE}
-
-
 def _focal_out(like: Tensor, nbytes: int):
     """(loss [], norm [1], workspace of ``nbytes``) for a focal forward, on ``like``'s device."""
     return (torch.empty((), device=like.device, dtype=torch.float32), torch.empty(1, device=like.device, dtype=torch.float32),
@@ -2239,6 +2324,32 @@ def focal_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], norm: T
     ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
     check(lib.gdl_focal_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(norm), _p(upstream), grad_scale, _p(dlow), _p(ws),
                                    nbytes, FOCAL_FORMS[form], _stream()), "gdl_focal_lowres_bwd")
+    return dlow
+
+
+def focal_binary_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], options: FocalOptions = FocalOptions()):
+    """The binary focal loss (z = [y == 1]) of bilinear(low -> size) vs target [B, H, W] for the one-class head's map [B, h, w, 1],
+    without the full-resolution logits: ``(loss, norm)`` as focal_fwd."""
+    B, Hi, Wi, Ho, Wo = _binary_lowres_check("focal_binary_lowres", low, size, target)
+    lib = _lib.load()
+    nbytes = lib.gdl_focal_lowres_workspace(B, 1, Ho, Wo)
+    loss, norm, ws = _focal_out(low, nbytes)
+    check(lib.gdl_focal_binary_lowres_fwd(_p(low), _p(target), B, Hi, Wi, Ho, Wo, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
+                                          _stream()), "gdl_focal_binary_lowres_fwd")
+    return loss, norm
+
+
+def focal_binary_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], norm: Tensor, upstream: Tensor | None,
+                            grad_scale: float = 1.0, options: FocalOptions = FocalOptions(), form: str = "auto") -> Tensor:
+    """d loss / d low [B, h, w, 1] * upstream[0] * grad_scale; ``form`` as dice_binary_lowres_bwd."""
+    B, Hi, Wi, Ho, Wo = _binary_lowres_check("focal_binary_lowres", low, size, target)
+    _need_cuda(norm, upstream)
+    dlow = torch.empty_like(low)
+    lib = _lib.load()
+    nbytes = lib.gdl_binary_lowres_bwd_workspace(B, Hi, Wi, Ho, Wo) if form != "gather" else 0
+    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    check(lib.gdl_focal_binary_lowres_bwd(_p(low), _p(target), B, Hi, Wi, Ho, Wo, *options.c_args(), _p(norm), _p(upstream), grad_scale,
+                                          _p(dlow), _p(ws), nbytes, FOCAL_FORMS[form], _stream()), "gdl_focal_binary_lowres_bwd")
     return dlow
 
 

@@ -87,6 +87,8 @@ class SegmentationTaskHooks:
     def _predict(self, logits: Tensor) -> Tensor:
         """segmentation_dofa.py:278-281."""
         if self.num_classes == 1:
+            if isinstance(logits, gnn.LowresLogits) or logits.is_cuda:
+                return gnn.predict_binary_mask(logits, self.threshold)      # the same expression, one kernel
             return (logits.sigmoid().squeeze(1) > self.threshold).long()
         return gnn.predict_mask(logits)  # softmax(dim=1).argmax(dim=1), one kernel
 

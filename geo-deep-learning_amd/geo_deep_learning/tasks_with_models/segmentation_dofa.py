@@ -97,7 +97,7 @@ class SegmentationDOFA(SegmentationTaskHooks, LightningModule):
     def training_step(self, batch: dict[str, Any], batch_idx: int) -> Tensor:  # noqa: ARG002
         """segmentation_dofa.py:213-241."""
         from gdlhip import nn as gnn
-        fused = gnn.FUSE_LOWRES_DICE and gnn.reads_lowres(self.loss)
+        fused = gnn.FUSE_LOWRES_DICE and gnn.reads_lowres(self.loss, self.num_classes)
         _, _, loss, bs = self._loss(batch, lowres_logits=fused)
         self.train_samples_count += bs
         self._log_loss("train_loss", loss, bs)
@@ -106,9 +106,10 @@ class SegmentationDOFA(SegmentationTaskHooks, LightningModule):
     def _lowres_eval(self) -> bool:
         """Validation / test need the two loss terms and the arg-max mask of ``outputs.out``, nothing else of the logits: with gdlhip's
         multiclass DiceLoss or SoftCrossEntropyLoss (``gnn.reads_lowres``) both come straight from the heads' own maps (``gnn.DiceLoss`` / ``gnn.predict_mask`` on LowresLogits: the
-        same values, bit for bit, as from the resized [B, K, H, W] tensors, which are then never written)."""
+        same values, bit for bit, as from the resized [B, K, H, W] tensors, which are then never written).  A one-class model takes the
+        same route with a binary loss and the thresholded mask (``gnn.predict_binary_mask``)."""
         from gdlhip import nn as gnn
-        return gnn.FUSE_LOWRES_DICE and gnn.reads_lowres(self.loss) and self.num_classes > 1
+        return gnn.FUSE_LOWRES_DICE and gnn.reads_lowres(self.loss, self.num_classes)
 
     def validation_step(self, batch: dict[str, Any], batch_idx: int) -> Tensor:  # noqa: ARG002
         """segmentation_dofa.py:251-283."""

@@ -524,6 +524,15 @@ int gdl_softmax_argmax(const float* logits, int B, int K, int64_t HW, int64_t* m
  * gdl_softmax_argmax.  K >= 2 classes. */
 int gdl_upsample_argmax(const float* low, int B, int Hi, int Wi, int K, int64_t* mask, int Ho, int Wo,
                         gdl_stream_t stream);
+/* One-class prediction, (out.sigmoid().squeeze(1) > threshold).long() (segmentation_dofa.py:279), in one pass over `total` f32
+ * logits ([B,1,H,W] or flat) -> int64 0/1.  The decision is 1 / (1 + exp(-x)) > threshold in f32, in probability space as the
+ * reference takes it (not x > logit(threshold): sigmoid(0) > 0.5 is false, and so is sigmoid(x) for 0 < x < ~1e-7). */
+int gdl_sigmoid_threshold(const float* logits, int64_t total, float threshold, int64_t* mask, gdl_stream_t stream);
+/* the same mask [B,Ho,Wo] from the one-class head's own NHWC f32 map [B,Hi,Wi,1]: the threshold of F.interpolate(logits, (Ho, Wo))
+ * (dofa.py:89-95 + segmentation_dofa.py:279) without the resized tensor; equals gdl_upsample_logits + gdl_sigmoid_threshold in
+ * every pixel.  An upsample by at most 64 per direction. */
+int gdl_upsample_threshold(const float* low, int B, int Hi, int Wi, int64_t* mask, int Ho, int Wo, float threshold,
+                           gdl_stream_t stream);
 /* f.softmax(output, dim=1) (K > 1) / f.sigmoid (K == 1) of the exported inference model (tools/script_model.py:55-59) */
 int gdl_class_probs(const float* logits, int B, int K, int64_t HW, float* probs, gdl_stream_t stream);
 /* The constructor options of smp 0.5.0 DiceLoss (losses/dice.py) for the gdl_dice_*_opt_* entry points below; a null pointer
@@ -655,6 +664,34 @@ int gdl_overlap_binary_loss_bwd(const float* logits, const int64_t* target, int6
                                 const gdl_overlap_options* opt, const float* sums, const float* upstream, float grad_scale,
                                 float* dlogits, int accumulate, gdl_stream_t stream);
 
+/* smp DiceLoss / JaccardLoss / TverskyLoss(mode="binary") of F.interpolate(head(x), size=(Ho, Wo), mode="bilinear") WITHOUT the
+ * full-resolution logits (dofa.py:89-105 + the binary losses above, for a one-class model): low = the [B, Hi, Wi, 1] f32 map of
+ * gdl_head_1x1, target [B, Ho, Wo] used as a 0/1 weight; every pixel's logit is evaluated on the fly with the expression of
+ * gdl_upsample_logits and p = exp(logsigmoid(x)).  sums [3], loss and the options as gdl_dice_binary_loss_fwd / _opt_fwd /
+ * gdl_overlap_binary_loss_fwd; forward workspace: gdl_dice_loss_lowres_workspace(B, 1, Ho, Wo) bytes.  An upsample by at most 64
+ * per direction; anything else is GDL_ERR_INVALID.  _bwd writes dlow [B, Hi, Wi, 1] = d loss / d low * upstream[0] * grad_scale in
+ * the form `form` selects (GDL_FOCAL_AUTO / _GATHER / _TILE as gdl_focal_lowres_bwd; the tile form needs
+ * gdl_binary_lowres_bwd_workspace() > 0 bytes in ws, which is 0 for a 1:1 map and for shapes the tiles do not take).  No float
+ * atomics: the same input gives the same bits on every launch. */
+int64_t gdl_binary_lowres_bwd_workspace(int B, int Hi, int Wi, int Ho, int Wo);
+int gdl_dice_binary_loss_lowres_fwd(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo, float eps,
+                                    float* sums, float* loss, float* ws, int64_t ws_bytes, gdl_stream_t stream);
+int gdl_dice_binary_loss_lowres_bwd(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo, float eps,
+                                    const float* sums, const float* upstream, float grad_scale, float* dlow, float* ws,
+                                    int64_t ws_bytes, int form, gdl_stream_t stream);
+int gdl_dice_binary_loss_lowres_opt_fwd(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo, float eps,
+                                        const gdl_dice_options* opt, float* sums, float* loss, float* ws, int64_t ws_bytes,
+                                        gdl_stream_t stream);
+int gdl_dice_binary_loss_lowres_opt_bwd(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo, float eps,
+                                        const gdl_dice_options* opt, const float* sums, const float* upstream, float grad_scale,
+                                        float* dlow, float* ws, int64_t ws_bytes, int form, gdl_stream_t stream);
+int gdl_overlap_binary_loss_lowres_fwd(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo, float eps,
+                                       const gdl_overlap_options* opt, float* sums, float* loss, float* ws, int64_t ws_bytes,
+                                       gdl_stream_t stream);
+int gdl_overlap_binary_loss_lowres_bwd(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo, float eps,
+                                       const gdl_overlap_options* opt, const float* sums, const float* upstream, float grad_scale,
+                                       float* dlow, float* ws, int64_t ws_bytes, int form, gdl_stream_t stream);
+
 /* smp 0.5.0 SoftCrossEntropyLoss(reduction, smooth_factor, ignore_index) (losses/soft_ce.py, label_smoothed_nll_loss in
  * losses/_functional.py; the loss of notebooks/00_quickstart.ipynb) on NCHW f32 logits [B,K,HW] and an int64 target [B,HW].
  * With e = smooth (in [0, 1]), N = B*HW and valid_i = (target_i != ignore when has_ignore) && 0 <= target_i < K (compared as
@@ -744,6 +781,16 @@ int gdl_focal_lowres_bwd(const float* low, const int64_t* target, int B, int K, 
                          int has_alpha, float alpha, int has_threshold, float threshold, int has_ignore, int64_t ignore, int mean,
                          const float* norm, const float* upstream, float grad_scale, float* dlow, float* ws, int64_t ws_bytes,
                          int form, gdl_stream_t stream);
+/* smp FocalLoss(mode="binary") of the same resize, for a one-class model: low [B, Hi, Wi, 1], target [B, Ho, Wo], z = [y == 1] as
+ * gdl_focal_binary_fwd (dofa.py:89-105 + losses/focal.py); the kernels of gdl_focal_lowres_* at K = 1 with that class test.
+ * Workspaces: gdl_focal_lowres_workspace(B, 1, Ho, Wo) and, for the tile form, gdl_binary_lowres_bwd_workspace(). */
+int gdl_focal_binary_lowres_fwd(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo, float gamma,
+                                int has_alpha, float alpha, int has_threshold, float threshold, int has_ignore, int64_t ignore,
+                                int mean, float* loss, float* norm, void* ws, int64_t ws_bytes, gdl_stream_t stream);
+int gdl_focal_binary_lowres_bwd(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo, float gamma,
+                                int has_alpha, float alpha, int has_threshold, float threshold, int has_ignore, int64_t ignore,
+                                int mean, const float* norm, const float* upstream, float grad_scale, float* dlow, float* ws,
+                                int64_t ws_bytes, int form, gdl_stream_t stream);
 
 /* Segmented stable sort, descending, of NON-NEGATIVE f32 keys (+0 only; NaN unspecified): keys [S][n] -> sorted [S][n] and perm
  * [S][n] (int32: the position inside the segment each sorted key came from), equal keys in ascending position order -- what
