@@ -1,4 +1,4 @@
-// What the per-pixel losses share (loss_ce.hip: soft cross-entropy; loss_focal.hip: focal): the f64 partial-sum helpers, and the
+// What the per-pixel losses share (loss_ce.hip: soft cross-entropy; loss_focal.hip: focal; loss_bce.hip: soft BCE): the f64 partial-sum helpers, and the
 // tile form of the low-resolution backward.  A per-pixel loss's gradient needs no global sum, so a workgroup that owns a
 // CT_H x CT_W tile of full-resolution pixels can
 //   1. write dL/dlogit of its pixels (unscaled) to LDS            -- the loss's own kernel, the only part that differs;

@@ -79,6 +79,11 @@ class OverlapOptions(C.Structure):
 FOCAL_AUTO, FOCAL_GATHER, FOCAL_TILE = 0, 1, 2
 # gamma, has_alpha, alpha, has_threshold, threshold, has_ignore, ignore, mean: the option arguments of every gdl_focal_* call
 _FOCAL_OPT = (c_f, c_i, c_f, c_i, c_f, c_i, c_l, c_i)
+# has_smooth, smooth, has_ignore, ignore, ignore_f, weight, weight_numel, pos_weight, pos_weight_numel, scale: the option arguments
+# of every gdl_soft_bce_* call
+_BCE_OPT = (c_i, c_f, c_i, c_l, c_f, c_p, c_i, c_p, c_i, c_f)
+# the `target_type` argument of gdl_soft_bce_* (GDL_BCE_TARGET_* in include/gdlhip.h)
+BCE_TARGET_I64, BCE_TARGET_F32 = 0, 1
 # per_image, has_ignore, ignore: the option arguments of every gdl_lovasz_* call
 _LOVASZ_OPT = (c_i, c_i, c_l)
 
@@ -259,6 +264,12 @@ SIGNATURES = {
     "gdl_overlap_binary_loss_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_f, c_p, c_p, c_l, c_i, c_p]),
     "gdl_focal_binary_lowres_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, *_FOCAL_OPT, c_p, c_p, c_p, c_l, c_p]),
     "gdl_focal_binary_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, *_FOCAL_OPT, c_p, c_p, c_f, c_p, c_p, c_l, c_i, c_p]),
+    "gdl_soft_bce_workspace": (c_l, [c_i, c_i, c_l]),
+    "gdl_soft_bce_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_l, *_BCE_OPT, c_p, c_p, c_l, c_p]),
+    "gdl_soft_bce_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_l, *_BCE_OPT, c_p, c_f, c_p, c_i, c_p]),
+    "gdl_soft_bce_lowres_workspace": (c_l, [c_i, c_i, c_i]),
+    "gdl_soft_bce_lowres_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, *_BCE_OPT, c_p, c_p, c_l, c_p]),
+    "gdl_soft_bce_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, *_BCE_OPT, c_p, c_f, c_p, c_p, c_l, c_i, c_p]),
     "gdl_sumsq": (c_i, [c_p, c_l, c_p, c_p]),
     "gdl_clip_coef": (c_i, [c_p, c_f, c_p, c_p]),
     "gdl_multi_sumsq": (c_i, [c_p, c_i, c_p, c_p]),

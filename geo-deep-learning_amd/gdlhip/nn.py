@@ -1829,6 +1829,126 @@ class FocalLoss(nn.Module):
         return _Focal.apply(y_pred, y_true.long().contiguous(), self.options)
 
 
+class _SoftBCE(Function):
+    """smp SoftBCEWithLogitsLoss on full-resolution NCHW logits and an int64 or f32 target of the same numel; the backward
+    recomputes from the saved logits and target."""
+
+    @staticmethod
+    def forward(ctx, logits, target, options):
+        loss = ops.soft_bce_fwd(logits, target, options)
+        ctx.save_for_backward(logits, target)
+        ctx.options = options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target = ctx.saved_tensors
+        return ops.soft_bce_bwd(logits, target, g.contiguous().float(), 1.0, ctx.options), None, None
+
+
+class _SoftBCELowres(Function):
+    """smp SoftBCEWithLogitsLoss of bilinear(low -> size) for a one-class head's map [B, h, w, 1], forward and backward from that
+    map."""
+
+    @staticmethod
+    def forward(ctx, low, target, size, options):
+        loss = ops.soft_bce_lowres_fwd(low, target, size, options)
+        ctx.save_for_backward(low, target)
+        ctx.size, ctx.options = size, options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        low, target = ctx.saved_tensors
+        return ops.soft_bce_lowres_bwd(low, target, ctx.size, g.contiguous().float(), 1.0, ctx.options), None, None, None
+
+
+class SoftBCEWithLogitsLoss(nn.Module):
+    """Stand-in for ``segmentation_models_pytorch.losses.SoftBCEWithLogitsLoss`` (smp 0.5.0 constructor signature and defaults;
+    losses/soft_bce.py), evaluated by the gdl_soft_bce_* HIP kernels.  smp is not installed where this was written, so parity with
+    smp unpinned; the formula is:
+
+    per element, for logit ``x``, raw target value ``y``, ``w`` / ``p`` the ``weight`` / ``pos_weight`` of the element's channel
+    (1 when absent): ``t = (1 - y) smooth_factor + y (1 - smooth_factor)`` (``y`` when ``smooth_factor`` is None),
+    ``l = w ((1 - t) x + (1 + (p - 1) t) softplus(-x))`` -- ``F.binary_cross_entropy_with_logits(x, t, w, pos_weight=p)`` -- and
+    ``dl/dx = w ((1 - t) - (1 + (p - 1) t) sigmoid(-x))``.  The loss is the sum of ``l`` over the elements with
+    ``y != ignore_index``, for ``reduction="mean"`` divided by the number of ALL elements, ignored ones included (smp's
+    ``loss.mean()``; FocalLoss divides by the valid count instead), and as it is for ``"sum"``.
+
+    - The ignore test is on the raw target, before smoothing: an integer target compares as int64, a floating one as floating
+      point (torch's ``y_true != ignore_index``).
+    - Targets are values, not labels: any fractional ``y_true`` is legal.  int64 and f32 targets go to the kernels as they are;
+      other integer dtypes are converted to int64, other floating dtypes to f32.
+    - An ignored element contributes exactly 0 and gets an exactly zero gradient: a select, not a multiplication, so a non-finite
+      logit under an ignored pixel does not poison the sum.
+    - ``y_true`` may have any shape with ``y_pred``'s batch size and numel (``[B,H,W]`` against ``[B,1,H,W]`` logits, as
+      ``FocalLoss(mode="binary")`` accepts; torch itself would raise).
+    - ``weight`` and ``pos_weight`` are buffers under smp's names (the same state-dict keys): None, a tensor of numel 1, or a tensor
+      that varies only over the channel dimension of ``[B,C,H,W]`` logits, shape ``[C,1,1]`` or ``[1,C,1,1]``; any other shape raises
+      ``NotImplementedError``.  The kernels read them through device pointers at call time; nothing is copied to the host.
+    - ``reduction="none"`` raises ``NotImplementedError``.
+
+    ``y_pred`` may be ``LowresLogits``: for a one-class head's f32 map with a factor <= ``ops.BINARY_LOWRES_MAX_FACTOR`` = 8 the
+    loss and d(low) come from the map itself (the routing of ``FocalLoss(mode="binary")``); other cases materialise the logits."""
+
+    def __init__(self, weight: Tensor | None = None, ignore_index: int | None = -100, reduction: str = "mean",
+                 smooth_factor: float | None = None, pos_weight: Tensor | None = None) -> None:
+        super().__init__()
+        if reduction not in ("mean", "sum"):
+            if reduction == "none":
+                raise NotImplementedError("gdlhip SoftBCEWithLogitsLoss implements reduction='mean' and 'sum' (got 'none')")
+            raise ValueError(f"SoftBCEWithLogitsLoss: unknown reduction {reduction!r}")
+        if smooth_factor is not None:
+            smooth_factor = float(smooth_factor)
+            if not 0.0 <= smooth_factor <= 1.0:      # (NaN and the infinities fail the comparison)
+                raise ValueError(f"SoftBCEWithLogitsLoss: smooth_factor must be None or in [0, 1] (got {smooth_factor})")
+        if ignore_index is not None:
+            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
+                raise ValueError(f"SoftBCEWithLogitsLoss: ignore_index must be an int64 value or None (got {ignore_index!r})")
+            ignore_index = int(ignore_index)
+        for name, t in (("weight", weight), ("pos_weight", pos_weight)):
+            if t is None:
+                continue
+            if not isinstance(t, Tensor):
+                raise TypeError(f"SoftBCEWithLogitsLoss: {name} must be a Tensor or None (got {type(t).__name__})")
+            shape = tuple(t.shape)
+            per_channel = (len(shape) == 3 and shape[1:] == (1, 1)) or (len(shape) == 4 and shape[0] == 1 and shape[2:] == (1, 1))
+            if t.numel() != 1 and not per_channel:
+                raise NotImplementedError(f"gdlhip SoftBCEWithLogitsLoss implements a {name} of one value or one per channel, "
+                                          f"shape [C,1,1] or [1,C,1,1] (got {shape})")
+        self.ignore_index, self.reduction, self.smooth_factor = ignore_index, reduction, smooth_factor
+        self.register_buffer("weight", weight)
+        self.register_buffer("pos_weight", pos_weight)
+
+    def _options(self) -> ops.SoftBCEOptions:
+        """The options with the buffers as they are now (a ``.to(device)`` moves them): f32 and contiguous, which they already are
+        unless they were registered otherwise."""
+        w, p = (None if t is None else t.detach().float().contiguous() for t in (self.weight, self.pos_weight))
+        return ops.SoftBCEOptions(self.smooth_factor, self.ignore_index, self.reduction == "mean", w, p)
+
+    @staticmethod
+    def _target(y_true: Tensor) -> Tensor:
+        if y_true.dtype not in (torch.int64, torch.float32):
+            y_true = y_true.float() if y_true.is_floating_point() else y_true.long()
+        return y_true.contiguous()
+
+    def forward(self, y_pred, y_true: Tensor) -> Tensor:
+        options = self._options()
+        if isinstance(y_pred, LowresLogits):
+            size = (int(y_pred.size[0]), int(y_pred.size[1]))
+            yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
+            if _binary_lowres_ok(y_pred.low, size, yt) and y_pred.low.shape[0] == yt.shape[0]:
+                return _SoftBCELowres.apply(y_pred.low.contiguous(), self._target(yt), size, options)
+            y_pred = y_pred.materialise()
+        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
+            y_pred = y_pred.float().contiguous()
+        if y_pred.dim() < 1 or y_pred.shape[0] != y_true.shape[0] or y_pred.numel() != y_true.numel():
+            raise ValueError(f"SoftBCEWithLogitsLoss: y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} do not match")
+        if y_pred.dim() != 4:      # no channel dimension to speak of: one "channel" of everything behind the batch
+            y_pred = y_pred.reshape(y_pred.shape[0], 1, 1, -1)
+        return _SoftBCE.apply(y_pred, self._target(y_true), options)
+
+
 class _Lovasz(Function):
     """smp LovaszLoss(multiclass) on full-resolution NCHW logits; the forward leaves the Jaccard coefficients in pixel order and the
     segments' weights on the device, the backward recomputes the softmax from the saved logits."""
@@ -1927,9 +2047,11 @@ def reads_lowres(loss, num_classes: int | None = None) -> bool:
     """True for a loss that evaluates itself (and its gradient) from ``LowresLogits``: a task may then ask the model for the heads'
     own maps instead of the resized [B, K, H, W] logits.  gdlhip's multiclass DiceLoss, JaccardLoss, TverskyLoss and FocalLoss,
     and SoftCrossEntropyLoss; for a one-class model (``num_classes == 1``) also their binary modes, which read the head's
-    [B, h, w, 1] map."""
+    [B, h, w, 1] map, and SoftBCEWithLogitsLoss (which has no mode: its low-resolution kernels are the one-class ones)."""
     if isinstance(loss, (_DiceFamily, FocalLoss)):
         return loss.mode == "multiclass" or (loss.mode == "binary" and num_classes == 1)
+    if isinstance(loss, SoftBCEWithLogitsLoss):
+        return num_classes == 1
     return isinstance(loss, SoftCrossEntropyLoss)
 
 

@@ -2353,6 +2353,114 @@ def focal_binary_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], 
     return dlow
 
 
+class SoftBCEOptions(NamedTuple):
+    """The constructor options of smp's SoftBCEWithLogitsLoss as the gdl_soft_bce_* entry points take them: ``smooth_factor`` in
+    [0, 1] or None, ``ignore_index`` (any int64, or None), ``mean`` (reduction "mean": divide by EVERY element, ignored ones
+    included) and the device tensors ``weight`` / ``pos_weight`` (f32, one value or one per channel, or None), which the kernels read
+    through their pointers at call time."""
+
+    smooth_factor: float | None = None
+    ignore_index: int | None = -100
+    mean: bool = True
+    weight: Tensor | None = None
+    pos_weight: Tensor | None = None
+
+    def c_args(self, numel: int) -> tuple:
+        """(has_smooth, smooth, has_ignore, ignore, ignore_f, weight, weight_numel, pos_weight, pos_weight_numel, scale) in the
+        order of the C calls; ``numel``: the number of logits (the divisor of "mean")"""
+        ign = int(self.ignore_index or 0)
+        return (int(self.smooth_factor is not None), float(self.smooth_factor or 0.0), int(self.ignore_index is not None), ign,
+                float(ign), _p(self.weight), 0 if self.weight is None else self.weight.numel(), _p(self.pos_weight),
+                0 if self.pos_weight is None else self.pos_weight.numel(), 1.0 / numel if self.mean else 1.0)
+
+
+# dtype -> the `target_type` tag of gdl_soft_bce_*
+BCE_TARGET_TYPES = {torch.int64: _lib.BCE_TARGET_I64, torch.float32: _lib.BCE_TARGET_F32}
+
+
+def _soft_bce_options_check(who: str, options: SoftBCEOptions, C_: int) -> None:
+    for name, t in (("weight", options.weight), ("pos_weight", options.pos_weight)):
+        if t is None:
+            continue
+        _need_cuda(t)
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() not in (1, C_):
+            raise ValueError(f"{who}: {name} must be a contiguous f32 tensor of 1 or {C_} (channels) values, got {tuple(t.shape)} {t.dtype}")
+
+
+def _soft_bce_check(who: str, logits: Tensor, target: Tensor, options: SoftBCEOptions) -> tuple:
+    """(B, C, HW) of NCHW logits [B, C, H, W]; the target holds one value per logit, int64 or f32."""
+    _need_cuda(logits, target)
+    if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 4 or logits.numel() == 0:
+        raise ValueError(f"{who}: contiguous f32 NCHW logits [B, C, H, W] expected, got {tuple(logits.shape)} {logits.dtype}")
+    if target.dtype not in BCE_TARGET_TYPES or not target.is_contiguous() or target.numel() != logits.numel():
+        raise ValueError(f"{who}: contiguous int64 or f32 target with one value per logit expected, got {tuple(target.shape)} {target.dtype}")
+    B, C_, H, W = logits.shape
+    _soft_bce_options_check(who, options, C_)
+    return B, C_, H * W
+
+
+def soft_bce_fwd(logits: Tensor, target: Tensor, options: SoftBCEOptions = SoftBCEOptions()) -> Tensor:
+    """smp SoftBCEWithLogitsLoss on NCHW f32 logits [B,C,H,W] and an int64 or f32 target of the same numel: the loss (0-dim f32)."""
+    B, C_, HW = _soft_bce_check("soft_bce", logits, target, options)
+    lib = _lib.load()
+    nbytes = lib.gdl_soft_bce_workspace(B, C_, HW)
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    ws = torch.empty(nbytes // 8, device=logits.device, dtype=torch.float64)
+    check(lib.gdl_soft_bce_fwd(_p(logits), _p(target), BCE_TARGET_TYPES[target.dtype], B, C_, HW, *options.c_args(logits.numel()),
+                               _p(loss), _p(ws), nbytes, _stream()), "gdl_soft_bce_fwd")
+    return loss
+
+
+def soft_bce_bwd(logits: Tensor, target: Tensor, upstream: Tensor | None, grad_scale: float = 1.0,
+                 options: SoftBCEOptions = SoftBCEOptions(), out: Tensor | None = None, accumulate: bool = False) -> Tensor:
+    """d loss / d logits * upstream[0] * grad_scale (recomputed from ``logits``); ``out``/``accumulate`` as soft_ce_bwd."""
+    B, C_, HW = _soft_bce_check("soft_bce", logits, target, options)
+    _need_cuda(upstream, out)
+    out = _focal_grad_out("soft_bce_bwd", logits, out)
+    check(_lib.load().gdl_soft_bce_bwd(_p(logits), _p(target), BCE_TARGET_TYPES[target.dtype], B, C_, HW,
+                                       *options.c_args(logits.numel()), _p(upstream), grad_scale, _p(out), int(accumulate), _stream()),
+          "gdl_soft_bce_bwd")
+    return out
+
+
+def _soft_bce_lowres_check(low: Tensor, target: Tensor, size: tuple[int, int], options: SoftBCEOptions) -> tuple:
+    """(B, Hi, Wi, Ho, Wo) of the one-class map [B, h, w, 1] and a target [B, H, W], int64 or f32."""
+    B, Hi, Wi, Ho, Wo = _binary_lowres_check("soft_bce_lowres", low, size)
+    _need_cuda(target)
+    if target.dtype not in BCE_TARGET_TYPES or not target.is_contiguous() or tuple(target.shape) != (B, Ho, Wo):
+        raise ValueError(f"soft_bce_lowres: contiguous int64 or f32 target {[B, Ho, Wo]} expected, got {tuple(target.shape)} {target.dtype}")
+    _soft_bce_options_check("soft_bce_lowres", options, 1)
+    return B, Hi, Wi, Ho, Wo
+
+
+def soft_bce_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], options: SoftBCEOptions = SoftBCEOptions()) -> Tensor:
+    """The loss of bilinear(low -> size) vs target [B, H, W] for the one-class head's map [B, h, w, 1], without the full-resolution
+    logits: the loss (0-dim f32)."""
+    B, Hi, Wi, Ho, Wo = _soft_bce_lowres_check(low, target, size, options)
+    lib = _lib.load()
+    nbytes = lib.gdl_soft_bce_lowres_workspace(B, Ho, Wo)
+    loss = torch.empty((), device=low.device, dtype=torch.float32)
+    ws = torch.empty(nbytes // 8, device=low.device, dtype=torch.float64)
+    check(lib.gdl_soft_bce_lowres_fwd(_p(low), _p(target), BCE_TARGET_TYPES[target.dtype], B, Hi, Wi, Ho, Wo,
+                                      *options.c_args(target.numel()), _p(loss), _p(ws), nbytes, _stream()), "gdl_soft_bce_lowres_fwd")
+    return loss
+
+
+def soft_bce_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], upstream: Tensor | None, grad_scale: float = 1.0,
+                        options: SoftBCEOptions = SoftBCEOptions(), form: str = "auto") -> Tensor:
+    """d loss / d low [B, h, w, 1] * upstream[0] * grad_scale; ``form`` as dice_binary_lowres_bwd."""
+    B, Hi, Wi, Ho, Wo = _soft_bce_lowres_check(low, target, size, options)
+    _need_cuda(upstream)
+    dlow = torch.empty_like(low)
+    lib = _lib.load()
+    nbytes = lib.gdl_binary_lowres_bwd_workspace(B, Hi, Wi, Ho, Wo) if form != "gather" else 0
+    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    check(lib.gdl_soft_bce_lowres_bwd(_p(low), _p(target), BCE_TARGET_TYPES[target.dtype], B, Hi, Wi, Ho, Wo,
+                                      *options.c_args(target.numel()), _p(upstream), grad_scale, _p(dlow), _p(ws), nbytes,
+                                      FOCAL_FORMS[form], _stream()), "gdl_soft_bce_lowres_bwd")
+    return dlow
+
+
 class LovaszOptions(NamedTuple):
     """The constructor options of smp's LovaszLoss as the gdl_lovasz_* entry points take them: ``per_image`` (one sort per image
     and class, the loss averaged over images) and ``ignore_index`` (any int64, or None)."""

@@ -16,7 +16,8 @@ section 2) and are skipped with a log line.  Third-party classes that are absent
 ``segmentation_models_pytorch.losses.JaccardLoss`` -> ``gdlhip.nn.JaccardLoss``,
 ``segmentation_models_pytorch.losses.TverskyLoss`` -> ``gdlhip.nn.TverskyLoss``,
 ``segmentation_models_pytorch.losses.FocalLoss`` -> ``gdlhip.nn.FocalLoss``,
-``segmentation_models_pytorch.losses.LovaszLoss`` -> ``gdlhip.nn.LovaszLoss``.
+``segmentation_models_pytorch.losses.LovaszLoss`` -> ``gdlhip.nn.LovaszLoss``,
+``segmentation_models_pytorch.losses.SoftBCEWithLogitsLoss`` -> ``gdlhip.nn.SoftBCEWithLogitsLoss``.
 """
 
 from __future__ import annotations
@@ -42,7 +43,8 @@ CLASS_ALIASES = {"segmentation_models_pytorch.losses.DiceLoss": "gdlhip.nn.DiceL
                  "segmentation_models_pytorch.losses.JaccardLoss": "gdlhip.nn.JaccardLoss",
                  "segmentation_models_pytorch.losses.TverskyLoss": "gdlhip.nn.TverskyLoss",
                  "segmentation_models_pytorch.losses.FocalLoss": "gdlhip.nn.FocalLoss",
-                 "segmentation_models_pytorch.losses.LovaszLoss": "gdlhip.nn.LovaszLoss"}
+                 "segmentation_models_pytorch.losses.LovaszLoss": "gdlhip.nn.LovaszLoss",
+                 "segmentation_models_pytorch.losses.SoftBCEWithLogitsLoss": "gdlhip.nn.SoftBCEWithLogitsLoss"}
 CALLABLE_KEYS = ("optimizer", "scheduler")       # LightningCLI OptimizerCallable / LRSchedulerCallable arguments
 TRAINER_KEYS = ("max_epochs", "precision", "gradient_clip_val", "sync_batchnorm", "accumulate_grad_batches",
                 "limit_train_batches", "limit_val_batches", "limit_test_batches", "default_root_dir", "fast_dev_run")

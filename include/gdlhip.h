@@ -792,6 +792,49 @@ int gdl_focal_binary_lowres_bwd(const float* low, const int64_t* target, int B, 
                                 int mean, const float* norm, const float* upstream, float grad_scale, float* dlow, float* ws,
                                 int64_t ws_bytes, int form, gdl_stream_t stream);
 
+/* smp 0.5.0 SoftBCEWithLogitsLoss(weight, ignore_index, reduction, smooth_factor, pos_weight) (losses/soft_bce.py), which is
+ * F.binary_cross_entropy_with_logits(y_pred, t, weight, pos_weight=pos_weight, reduction="none") on the smoothed target, masked by
+ * y_true != ignore_index and reduced by mean() / sum().  NCHW f32 logits [B,C,HW], any C >= 1 (elementwise), and one target VALUE
+ * per logit in the type `target_type` names: GDL_BCE_TARGET_I64 (int64) or GDL_BCE_TARGET_F32 (f32, any fraction).  Per element,
+ * with w = weight[channel], p = pos_weight[channel] (device pointers, each null = 1, of weight_numel / pos_weight_numel = 1 or C
+ * values; channel = (i / HW) % C):
+ *   t = (1 - y) smooth + y (1 - smooth) (has_smooth; smooth in [0, 1]) or y;
+ *   l = w ((1 - t) x + (1 + (p - 1) t) softplus(-x));   dl/dx = w ((1 - t) - (1 + (p - 1) t) sigmoid(-x));
+ *   loss = scale * sum of l over the elements with y != ignore, tested on the RAW target: y == ignore as int64 for an int64
+ *   target, y == ignore_f as float for an f32 one (has_ignore).  scale = 1 / (B C HW) for "mean" -- smp divides by EVERY element,
+ *   ignored ones included -- or 1 for "sum"; the caller passes it, the kernels apply it on the device.
+ *   dlogits_i = upstream[0] (device scalar, may be null) * grad_scale * scale * dl/dx   (= or += with accumulate); an ignored
+ *   element is selected out: it adds exactly 0 and gets exactly 0 whatever its logit holds.
+ * fwd: f64 per-workgroup partials in `workspace` (gdl_soft_bce_workspace() bytes, 8-byte aligned), added in a fixed order: no
+ * float atomics, the same bits on every launch, nothing synchronises with the host. */
+#define GDL_BCE_TARGET_I64 0
+#define GDL_BCE_TARGET_F32 1
+int64_t gdl_soft_bce_workspace(int B, int C, int64_t HW);
+int gdl_soft_bce_fwd(const float* logits, const void* target, int target_type, int B, int C, int64_t HW, int has_smooth, float smooth,
+                     int has_ignore, int64_t ignore, float ignore_f, const float* weight, int weight_numel, const float* pos_weight,
+                     int pos_weight_numel, float scale, float* loss, void* workspace, int64_t workspace_bytes, gdl_stream_t stream);
+int gdl_soft_bce_bwd(const float* logits, const void* target, int target_type, int B, int C, int64_t HW, int has_smooth, float smooth,
+                     int has_ignore, int64_t ignore, float ignore_f, const float* weight, int weight_numel, const float* pos_weight,
+                     int pos_weight_numel, float scale, const float* upstream, float grad_scale, float* dlogits, int accumulate,
+                     gdl_stream_t stream);
+/* smp SoftBCEWithLogitsLoss / F.binary_cross_entropy_with_logits of F.interpolate(head(x), size=(Ho, Wo), mode="bilinear") for a
+ * one-class model WITHOUT the full-resolution logits: low = the [B, Hi, Wi, 1] f32 map of gdl_head_1x1, target [B, Ho, Wo] in
+ * either type; every output pixel's logit is evaluated on the fly with the expression of gdl_upsample_logits.  C = 1, so
+ * weight_numel / pos_weight_numel must be 1; an upsample by at most 64 per direction (as gdl_focal_binary_lowres_*); anything
+ * else is GDL_ERR_INVALID.  _fwd is a partial-sum pass (ws: gdl_soft_bce_lowres_workspace() bytes, 8-byte aligned); _bwd writes
+ * dlow [B, Hi, Wi, 1] = d loss / d low, scaled as above, in the form `form` selects (GDL_FOCAL_AUTO / _GATHER / _TILE as
+ * gdl_focal_lowres_bwd; the tile form needs gdl_binary_lowres_bwd_workspace() > 0 bytes in ws).  A low-resolution logit whose
+ * every contributing pixel is ignored gets exactly 0. */
+int64_t gdl_soft_bce_lowres_workspace(int B, int Ho, int Wo);
+int gdl_soft_bce_lowres_fwd(const float* low, const void* target, int target_type, int B, int Hi, int Wi, int Ho, int Wo,
+                            int has_smooth, float smooth, int has_ignore, int64_t ignore, float ignore_f, const float* weight,
+                            int weight_numel, const float* pos_weight, int pos_weight_numel, float scale, float* loss, void* ws,
+                            int64_t ws_bytes, gdl_stream_t stream);
+int gdl_soft_bce_lowres_bwd(const float* low, const void* target, int target_type, int B, int Hi, int Wi, int Ho, int Wo,
+                            int has_smooth, float smooth, int has_ignore, int64_t ignore, float ignore_f, const float* weight,
+                            int weight_numel, const float* pos_weight, int pos_weight_numel, float scale, const float* upstream,
+                            float grad_scale, float* dlow, float* ws, int64_t ws_bytes, int form, gdl_stream_t stream);
+
 /* Segmented stable sort, descending, of NON-NEGATIVE f32 keys (+0 only; NaN unspecified): keys [S][n] -> sorted [S][n] and perm
  * [S][n] (int32: the position inside the segment each sorted key came from), equal keys in ascending position order -- what
  * torch.sort(keys, dim=1, descending=True, stable=True) returns, bit for bit (smp 0.5.0 losses/lovasz.py sorts its errors with
