@@ -1,6 +1,7 @@
 // Index arithmetic of the bilinear (align_corners=False) logit resize, shared by the kernels that evaluate it on the fly
-// (misc.hip: gdl_upsample_logits, gdl_upsample_argmax; loss_dice.hip: gdl_dice_loss_lowres_*; loss_ce.hip: gdl_soft_ce_lowres_*; loss_focal.hip: gdl_focal_lowres_*; loss_bce.hip: gdl_soft_bce_lowres_*).  One
-// definition, so that every kernel forms the bits gdl_upsample_logits writes.
+// (misc.hip: gdl_upsample_logits, gdl_upsample_argmax; loss_dice.hip: gdl_dice_loss_lowres_* and the binary forward; lowres_tile.h:
+// the kernel skeletons behind gdl_soft_ce_lowres_*, gdl_focal_lowres_*, gdl_focal_binary_lowres_*, gdl_soft_bce_lowres_* and the
+// binary Dice family's backward).  One definition, so that every kernel evaluates the expression gdl_upsample_logits writes.
 #pragma once
 #include "gdl_common.h"
 

@@ -20,8 +20,8 @@
 //   full resolution -- NCHW f32 logits [B, C, H, W], any C >= 1 (elementwise), one element per thread-iteration, the channel of
 //                      element i is (i / HW) % C (only formed where weight or pos_weight vary over channels).
 //   low resolution  -- the one-class head's map [B, Hi, Wi, 1] and a target at [Ho, Wo], the bilinear logit evaluated on the fly
-//                      (bilinear_index.h); the forward is a partial-sum pass, the backward recomputes: the tile form of
-//                      lowres_tile.h or the gather kernel, as gdl_focal_binary_lowres_*.
+//                      (bilinear_index.h); the forward is a partial-sum pass, the backward recomputes in the tile or the gather
+//                      form: the skeletons of lowres_tile.h with the policy BcePix.
 // Every kernel is instantiated for an int64 and an f32 target (GDL_BCE_TARGET_*): neither task needs a conversion pass.
 #include "gdl_common.h"
 #include "bilinear_index.h"
@@ -118,106 +118,19 @@ __global__ __launch_bounds__(256) void bce_bwd_kernel(const float* __restrict__ 
 }
 
 // ------------------------------------------------------------------ low resolution, one class: low [B, Hi, Wi, 1]
+// the policy of lowres_tile.h; T = the target's element type
 template <typename T>
-__global__ __launch_bounds__(256) void bce_lowres_partial_kernel(const float* __restrict__ low, const T* __restrict__ target, int B, int Hi,
-                                                                 int Wi, int Ho, int Wo, double* __restrict__ ws, const BceOpt o) {
-  const int64_t total = (int64_t)B * Ho * Wo;
-  const float ry = (float)Hi / (float)Ho, rx = (float)Wi / (float)Wo;
-  float w, p;
-  bce_channel(o, 0, w, p);
-  double acc = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const T y = target[i];
-    if (!bce_valid(y, o)) continue;
-    const int ox = (int)(i % Wo);
-    const int64_t r = i / Wo;
-    const int oy = (int)(r % Ho), b = (int)(r / Ho);
-    int y0, y1, x0, x1; float ly, lx;
-    src_index2(ry, oy, Hi, y0, y1, ly);
-    src_index2(rx, ox, Wi, x0, x1, lx);
-    float x[1];
-    bilinear_logits<1>(low, b, Hi, Wi, y0, y1, x0, x1, ly, lx, x);
-    acc += (double)bce_elem<true>(x[0], (float)y, w, p, o);
-  }
-  block256_store_sum(acc, ws);
-}
-
-// gather form: one thread per LOW-resolution logit sums wy * wx * dl/dx over the full-resolution pixels that interpolate from it,
-// rows then columns in ascending order (focal_lowres_bwd_gather_kernel at K = 1)
-template <typename T>
-__global__ __launch_bounds__(256) void bce_lowres_bwd_gather_kernel(const float* __restrict__ low, const T* __restrict__ target, int B,
-                                                                    int Hi, int Wi, int Ho, int Wo, const float* __restrict__ upstream,
-                                                                    float grad_scale, float* __restrict__ dlow, const BceOpt o) {
-  const float cf = (upstream ? upstream[0] : 1.f) * grad_scale * o.scale;
-  const int64_t total = (int64_t)B * Hi * Wi;
-  const float ry = (float)Hi / (float)Ho, rx = (float)Wi / (float)Wo;
-  float w, p;
-  bce_channel(o, 0, w, p);
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int ix = (int)(i % Wi);
-    const int64_t r = i / Wi;
-    const int iy = (int)(r % Hi), b = (int)(r / Hi);
-    int ylo, yhi, xlo, xhi;
-    cand_range(iy, ry, Ho, ylo, yhi);
-    cand_range(ix, rx, Wo, xlo, xhi);
-    float acc = 0.f;
-    for (int oy = ylo; oy <= yhi; ++oy) {
-      int y0, y1; float ly;
-      src_index2(ry, oy, Hi, y0, y1, ly);
-      const float wy = (y0 == iy ? 1.f - ly : 0.f) + (y1 == iy ? ly : 0.f);
-      if (wy == 0.f) continue;
-      const int64_t trow = ((int64_t)b * Ho + oy) * Wo;
-#pragma unroll 1
-      for (int ox = xlo; ox <= xhi; ++ox) {
-        int x0, x1; float lx;
-        src_index2(rx, ox, Wi, x0, x1, lx);
-        const float wt = wy * ((x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f));
-        if (wt == 0.f) continue;
-        const T y = target[trow + ox];
-        if (!bce_valid(y, o)) continue;      // an ignored pixel adds nothing
-        float x[1];
-        bilinear_logits<1>(low, b, Hi, Wi, y0, y1, x0, x1, ly, lx, x);
-        acc += wt * bce_elem<false>(x[0], (float)y, w, p, o);
-      }
-    }
-    dlow[i] = cf * acc;
-  }
-}
-
-// tile form (lowres_tile.h): dl/dx of the tile's pixels (unscaled) -> LDS, then the shared transposed resize into the tile's
-// partial patch; lowres_reduce_kernel applies upstream * grad_scale * scale (LowresTile::scale holds the product of the two).
-struct BceTile : LowresTile {
-  const void* tgt;      // the target in its own type (LowresTile::target stays unused)
+struct BcePix {
+  typedef BceOpt Opt;
+  typedef T Target;
+  static constexpr bool ONE_CLASS = true, COUNTS = false;
   BceOpt o;
+  float w, p;      // the one channel's weight / pos_weight
+  __device__ BcePix(const BceOpt& opt, int) : o(opt) { bce_channel(o, 0, w, p); }
+  __device__ bool valid(T y) const { return bce_valid(y, o); }
+  __device__ void grad(const float (&x)[1], T y, float (&g)[1]) const { g[0] = bce_elem<false>(x[0], (float)y, w, p, o); }
+  __device__ float loss(const float (&x)[1], T y) const { return bce_elem<true>(x[0], (float)y, w, p, o); }
 };
-
-template <typename T>
-__global__ __launch_bounds__(CT_T) void bce_lowres_tile_kernel(const BceTile a) {
-  extern __shared__ __attribute__((aligned(16))) float csm[];
-  float* dl = csm;                                   // [CT_H][CT_W]
-  const T* __restrict__ target = (const T*)a.tgt;
-  const TileAt at = lowres_tile_at(a);
-  float w, p;
-  bce_channel(a.o, 0, w, p);
-  for (int i = threadIdx.x; i < CT_H * CT_W; i += CT_T) {
-    const int r = i / CT_W, c = i - r * CT_W;
-    float v = 0.f;
-    if (r < at.rows && c < at.cols) {
-      const int oy = at.oy0 + r, ox = at.ox0 + c;
-      const T y = target[((int64_t)at.b * a.Ho + oy) * a.Wo + ox];
-      if (bce_valid(y, a.o)) {
-        int y0, y1, x0, x1; float ly, lx;
-        src_index2(at.ry, oy, a.Hi, y0, y1, ly);
-        src_index2(at.rx, ox, a.Wi, x0, x1, lx);
-        float x[1];
-        bilinear_logits<1>(a.low, at.b, a.Hi, a.Wi, y0, y1, x0, x1, ly, lx, x);
-        v = bce_elem<false>(x[0], (float)y, w, p, a.o);
-      }
-    }
-    dl[r * CT_W + c] = v;
-  }
-  lowres_tile_patch<1>(a, at, csm, [] {});
-}
 
 }  // namespace
 
@@ -303,64 +216,37 @@ extern "C" int gdl_soft_bce_bwd(const float* logits, const void* target, int tar
   return GDL_OK;
 }
 
-// ---- low resolution, one class: the shape limits of gdl_focal_binary_lowres_*
-#define BCE_LOWRES_SHAPE(who)                                                                                                     \
-  GDL_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi, who ": bad sizes (an upsample is expected)");                  \
-  GDL_CHECK_ARG((Ho + Hi - 1) / Hi <= LOWRES_MAX_FACTOR && (Wo + Wi - 1) / Wi <= LOWRES_MAX_FACTOR,                               \
-                who ": upsampling factors above 64 are not supported")
-
-// (1024 pixels per workgroup, as gdl_focal_lowres_fwd: the scattered loads are latency bound)
+// ---- low resolution, one class: the shape limits of gdl_focal_binary_lowres_* (forward workspace: 1024 pixels per workgroup)
 extern "C" int64_t gdl_soft_bce_lowres_workspace(int B, int Ho, int Wo) {
   if (B <= 0 || Ho <= 0 || Wo <= 0) return 0;
-  return (int64_t)bce_blocks((int64_t)B * Ho * Wo, 1024) * (int64_t)sizeof(double);
+  return (int64_t)lowres_fwd_blocks((int64_t)B * Ho * Wo) * (int64_t)sizeof(double);
 }
 
 extern "C" int gdl_soft_bce_lowres_fwd(const float* low, const void* target, int target_type, int B, int Hi, int Wi, int Ho, int Wo,
                                        BCE_OPT_PARAMS, float* loss, void* ws, int64_t ws_bytes, gdl_stream_t stream) {
   GDL_CHECK_ARG(low && target && loss && ws, "gdl_soft_bce_lowres_fwd: null pointer");
-  BCE_LOWRES_SHAPE("gdl_soft_bce_lowres_fwd");
+  LOWRES_SHAPE("gdl_soft_bce_lowres_fwd", 1);
   BCE_TARGET_TYPE("gdl_soft_bce_lowres_fwd");
   GDL_CHECK_ARG(ws_bytes >= gdl_soft_bce_lowres_workspace(B, Ho, Wo) && (uintptr_t)ws % 8 == 0,
                 "gdl_soft_bce_lowres_fwd: workspace too small or misaligned");
   BCE_OPT("gdl_soft_bce_lowres_fwd", 1);
-  const int nblk = bce_blocks((int64_t)B * Ho * Wo, 1024);
   hipStream_t s = (hipStream_t)stream;
-  BCE_TYPE_SWITCH(hipLaunchKernelGGL((bce_lowres_partial_kernel<TT>), dim3(nblk), dim3(256), 0, s, low, (const TT*)target, B, Hi, Wi, Ho,
-                                     Wo, (double*)ws, o));
+  int nblk;
+  BCE_TYPE_SWITCH(lowres_launch_partial<BcePix<TT>>(low, target, B, 1, Hi, Wi, Ho, Wo, (double*)ws, o, nblk, s));
   hipLaunchKernelGGL(bce_final_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, nblk, o.scale, loss);
   GDL_CHECK_LAUNCH("gdl_soft_bce_lowres_fwd");
   return GDL_OK;
 }
 
+// the final factor is upstream * (grad_scale * scale): LowresTile::scale holds the product of the two
 extern "C" int gdl_soft_bce_lowres_bwd(const float* low, const void* target, int target_type, int B, int Hi, int Wi, int Ho, int Wo,
                                        BCE_OPT_PARAMS, const float* upstream, float grad_scale, float* dlow, float* ws,
                                        int64_t ws_bytes, int form, gdl_stream_t stream) {
   GDL_CHECK_ARG(low && target && dlow, "gdl_soft_bce_lowres_bwd: null pointer");
-  BCE_LOWRES_SHAPE("gdl_soft_bce_lowres_bwd");
+  LOWRES_SHAPE("gdl_soft_bce_lowres_bwd", 1);
   BCE_TARGET_TYPE("gdl_soft_bce_lowres_bwd");
-  GDL_CHECK_ARG(form == GDL_FOCAL_AUTO || form == GDL_FOCAL_GATHER || form == GDL_FOCAL_TILE, "gdl_soft_bce_lowres_bwd: unknown form %d", form);
   GDL_CHECK_ARG(!ws || (uintptr_t)ws % 4 == 0, "gdl_soft_bce_lowres_bwd: workspace misaligned");
   BCE_OPT("gdl_soft_bce_lowres_bwd", 1);
-  hipStream_t st = (hipStream_t)stream;
-  int ny, nx;
-  const int64_t need = gdl_binary_lowres_bwd_workspace(B, Hi, Wi, Ho, Wo);
-  const bool can_tile = need > 0 && ws && ws_bytes >= need && binary_tile_dims(Hi, Wi, Ho, Wo, ny, nx);
-  GDL_CHECK_ARG(form != GDL_FOCAL_TILE || can_tile, "gdl_soft_bce_lowres_bwd: this shape or workspace does not take the tile form");
-  if (can_tile && form != GDL_FOCAL_GATHER) {
-    BceTile a{};
-    a.low = low; a.tgt = target; a.upstream = upstream; a.patches = ws; a.dlow = dlow; a.norm = nullptr;
-    lowres_tile_shape(a, B, Hi, Wi, Ho, Wo, ny, nx);
-    a.scale = grad_scale * o.scale; a.o = o;
-    BCE_TYPE_SWITCH(hipLaunchKernelGGL((bce_lowres_tile_kernel<TT>), dim3((unsigned)lowres_tiles(B, Ho, Wo)), dim3(CT_T),
-                                       lowres_tile_lds(1, ny, nx), st, a));
-    const int rc = lowres_launch_reduce(a, 1, st);
-    if (rc != GDL_OK) return rc;
-    GDL_CHECK_LAUNCH("gdl_soft_bce_lowres_bwd");
-    return GDL_OK;
-  }
-  const int64_t total = (int64_t)B * Hi * Wi;
-  BCE_TYPE_SWITCH(hipLaunchKernelGGL((bce_lowres_bwd_gather_kernel<TT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, low,
-                                     (const TT*)target, B, Hi, Wi, Ho, Wo, upstream, grad_scale, dlow, o));
-  GDL_CHECK_LAUNCH("gdl_soft_bce_lowres_bwd");
-  return GDL_OK;
+  auto a = lowres_args(low, target, B, Hi, Wi, Ho, Wo, upstream, grad_scale * o.scale, nullptr, dlow, o);
+  BCE_TYPE_SWITCH(return lowres_bwd<BcePix<TT>>("gdl_soft_bce_lowres_bwd", a, 1, form, ws, ws_bytes, (hipStream_t)stream));
 }

@@ -20,7 +20,7 @@
 //                       needs no global sums (Dice's does), so a tile kernel can form the loss AND the unscaled partial patches
 //                       of d(low) in one pass ("fused" form: the backward is the fixed-order patch reduce times upstream); the
 //                       "recompute" form leaves the forward a plain partial-sum pass and runs the tile (K <= 8) or gather kernel
-//                       in the backward.
+//                       in the backward.  The kernels are the skeletons of lowres_tile.h with the policy CePix.
 #include <atomic>
 
 #include "gdl_common.h"
@@ -164,136 +164,37 @@ __global__ __launch_bounds__(256) void ce_bwd_any_kernel(const float* __restrict
   }
 }
 
-// ------------------------------------------------------------------ low resolution
-// forward of the recompute form: the partial sums of ce_partial_kernel over the on-the-fly bilinear logits
-template <int K>
-__global__ __launch_bounds__(256) void ce_lowres_partial_kernel(const float* __restrict__ low, const int64_t* __restrict__ target, int B,
-                                                                int Hi, int Wi, int Ho, int Wo, double* __restrict__ ws,
-                                                                const CeOpt o) {
-  const int64_t total = (int64_t)B * Ho * Wo;
-  const float ry = (float)Hi / (float)Ho, rx = (float)Wi / (float)Wo;
-  double acc = 0.0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int ox = (int)(i % Wo);
-    const int64_t r = i / Wo;
-    const int oy = (int)(r % Ho), b = (int)(r / Ho);
-    int y0, y1, x0, x1; float ly, lx;
-    src_index2(ry, oy, Hi, y0, y1, ly);
-    src_index2(rx, ox, Wi, x0, x1, lx);
-    const int64_t t = target[i];
-    float x[K], L;
-    bilinear_logits<K>(low, b, Hi, Wi, y0, y1, x0, x1, ly, lx, x);
-    ce_softmax<K, true>(x, (int)t, o, L);
-    if (ce_valid(t, K, o)) acc += (double)L;
-  }
-  block256_store_sum(acc, ws);
-}
-
-// gather form: one thread per LOW-resolution logit vector sums wy * wx * dL/dlogit over the full-resolution pixels that interpolate
-// from it, rows then columns in ascending order.  Every class count up to 16; each full-resolution softmax is evaluated once per
-// low-resolution neighbour (up to four times).
-template <int K>
-__global__ __launch_bounds__(256) void ce_lowres_bwd_gather_kernel(const float* __restrict__ low, const int64_t* __restrict__ target,
-                                                                   int B, int Hi, int Wi, int Ho, int Wo,
-                                                                   const float* __restrict__ upstream, float scale,
-                                                                   float* __restrict__ dlow, const CeOpt o) {
-  const float c = (upstream ? upstream[0] : 1.f) * scale;
-  const int64_t total = (int64_t)B * Hi * Wi;
-  const float ry = (float)Hi / (float)Ho, rx = (float)Wi / (float)Wo;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int ix = (int)(i % Wi);
-    const int64_t r = i / Wi;
-    const int iy = (int)(r % Hi), b = (int)(r / Hi);
-    int ylo, yhi, xlo, xhi;
-    cand_range(iy, ry, Ho, ylo, yhi);
-    cand_range(ix, rx, Wo, xlo, xhi);
-    float acc[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) acc[k] = 0.f;
-    for (int oy = ylo; oy <= yhi; ++oy) {
-      int y0, y1; float ly;
-      src_index2(ry, oy, Hi, y0, y1, ly);
-      const float wy = (y0 == iy ? 1.f - ly : 0.f) + (y1 == iy ? ly : 0.f);
-      if (wy == 0.f) continue;
-      const int64_t trow = ((int64_t)b * Ho + oy) * Wo;
-#pragma unroll 1
-      for (int ox = xlo; ox <= xhi; ++ox) {
-        int x0, x1; float lx;
-        src_index2(rx, ox, Wi, x0, x1, lx);
-        const float w = wy * ((x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f));
-        if (w == 0.f) continue;
-        const int64_t t = target[trow + ox];
-        const int y = (int)t;
-        float x[K], L;
-        bilinear_logits<K>(low, b, Hi, Wi, y0, y1, x0, x1, ly, lx, x);
-        const float inv = 1.f / ce_softmax<K, false>(x, y, o, L);
-        const bool valid = ce_valid(t, K, o);
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-          const float sum = acc[k] + w * (x[k] * inv - (k == y ? o.keep : 0.f) - o.uni);
-          acc[k] = valid ? sum : acc[k];      // an ignored pixel adds nothing
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) dlow[i * K + k] = c * acc[k];
-  }
-}
-
-// tile form (lowres_tile.h): dL/dlogit of the tile's pixels (unscaled) -> LDS; with LOSS also the tile's loss sum (f64) ->
-// tile_loss[tile]; then the shared transposed resize into the tile's partial patch.  Every full-resolution softmax is evaluated once.
-struct CeTile : LowresTile {
+// ------------------------------------------------------------------ low resolution: the policy of lowres_tile.h
+struct CePix {
+  typedef CeOpt Opt;
+  typedef int64_t Target;
+  static constexpr bool ONE_CLASS = false, COUNTS = false;
   CeOpt o;
+  int K;
+  __device__ CePix(const CeOpt& opt, int classes) : o(opt), K(classes) {}
+  __device__ bool valid(int64_t t) const { return ce_valid(t, K, o); }
+  // x -> dL/dlogit in g; returns the pixel's loss with WITH_LOSS (one softmax for both: the fused form)
+  template <bool WITH_LOSS, int KK>
+  __device__ float grad_loss_(float (&x)[KK], int64_t t, float (&g)[KK]) const {
+    const int y = (int)t;
+    float L = 0.f;
+    const float inv = 1.f / ce_softmax<KK, WITH_LOSS>(x, y, o, L);
+#pragma unroll
+    for (int k = 0; k < KK; ++k) g[k] = x[k] * inv - (k == y ? o.keep : 0.f) - o.uni;
+    return L;
+  }
+  template <int KK>
+  __device__ void grad(float (&x)[KK], int64_t t, float (&g)[KK]) const { grad_loss_<false>(x, t, g); }
+  template <int KK>
+  __device__ float grad_loss(float (&x)[KK], int64_t t, float (&g)[KK]) const { return grad_loss_<true>(x, t, g); }
+  template <int KK>
+  __device__ float loss(float (&x)[KK], int64_t t) const {
+    float L;
+    ce_softmax<KK, true>(x, (int)t, o, L);
+    return L;
+  }
 };
-
-template <int K, bool LOSS>
-__global__ __launch_bounds__(CT_T) void ce_lowres_tile_kernel(const CeTile a) {
-  extern __shared__ __attribute__((aligned(16))) float csm[];
-  __shared__ double lred[CT_T / 64];
-  float* dl = csm;                                   // [K][CT_H][CT_W]
-  const int tid = threadIdx.x;
-  const TileAt at = lowres_tile_at(a);
-  const int b = at.b, oy0 = at.oy0, ox0 = at.ox0, rows = at.rows, cols = at.cols;
-  const float ry = at.ry, rx = at.rx;
-  double lacc = 0.0;
-  // ---- 1. dL/dlogit of the tile (zeros outside the image and at ignored pixels)
-  for (int i = tid; i < CT_H * CT_W; i += CT_T) {
-    const int r = i / CT_W, c = i - r * CT_W;
-    float v[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = 0.f;
-    if (r < rows && c < cols) {
-      const int oy = oy0 + r, ox = ox0 + c;
-      int y0, y1, x0, x1; float ly, lx;
-      src_index2(ry, oy, a.Hi, y0, y1, ly);
-      src_index2(rx, ox, a.Wi, x0, x1, lx);
-      const int64_t t = a.target[((int64_t)b * a.Ho + oy) * a.Wo + ox];
-      const int y = (int)t;
-      float x[K], L = 0.f;
-      bilinear_logits<K>(a.low, b, a.Hi, a.Wi, y0, y1, x0, x1, ly, lx, x);
-      const float inv = 1.f / ce_softmax<K, LOSS>(x, y, a.o, L);
-      if (ce_valid(t, K, a.o)) {
-        if (LOSS) lacc += (double)L;
-#pragma unroll
-        for (int k = 0; k < K; ++k) v[k] = x[k] * inv - (k == y ? a.o.keep : 0.f) - a.o.uni;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) dl[(k * CT_H + r) * CT_W + c] = v[k];
-  }
-  if (LOSS) {
-    lacc = wave_sum_f64(lacc);
-    if ((tid & 63) == 0) lred[tid >> 6] = lacc;
-  }
-  lowres_tile_patch<K>(a, at, csm, [&] {
-    if (LOSS && tid == 0) {
-      double s = 0.0;
-#pragma unroll
-      for (int w = 0; w < CT_T / 64; ++w) s += lred[w];
-      a.tile_loss[blockIdx.x] = s;
-    }
-  });
-}
+typedef LowresArgs<CeOpt> CeTile;
 
 }  // namespace
 
@@ -360,38 +261,26 @@ extern "C" int gdl_soft_ce_bwd(const float* logits, const int64_t* target, int B
   return GDL_OK;
 }
 
-// ---- low resolution
-#define CE_LOWRES_SHAPE(who)                                                                                                      \
-  GDL_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi, who ": bad sizes (an upsample is expected)");                  \
-  GDL_CHECK_ARG((Ho + Hi - 1) / Hi <= LOWRES_MAX_FACTOR && (Wo + Wi - 1) / Wi <= LOWRES_MAX_FACTOR,                         \
-                who ": upsampling factors above 64 are not supported");                                                           \
-  GDL_CHECK_ARG(K >= 1 && K <= 16, who ": K=%d classes unsupported (1..16)", K)
-
-// (1024 pixels per workgroup, as the Dice low-resolution forward: the scattered loads of the on-the-fly logit are latency bound)
-static int ce_lowres_blocks(int64_t total) {
-  int64_t g = (total + 1023) / 1024;
-  return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
-}
-
+// ---- low resolution (forward workspace: 1024 pixels per workgroup)
 extern "C" int64_t gdl_soft_ce_lowres_workspace(int B, int K, int Ho, int Wo) {
   (void)K;
-  return (int64_t)ce_lowres_blocks((int64_t)B * Ho * Wo) * (int64_t)sizeof(double);
+  return (int64_t)lowres_fwd_blocks((int64_t)B * Ho * Wo) * (int64_t)sizeof(double);
 }
 
 extern "C" int gdl_soft_ce_lowres_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float smooth,
                                       int has_ignore, int64_t ignore, int mean, float* loss, void* ws, int64_t ws_bytes,
                                       gdl_stream_t stream) {
   GDL_CHECK_ARG(low && target && loss && ws, "gdl_soft_ce_lowres_fwd: null pointer");
-  CE_LOWRES_SHAPE("gdl_soft_ce_lowres_fwd");
+  LOWRES_SHAPE("gdl_soft_ce_lowres_fwd", K);
   GDL_CHECK_ARG(ws_bytes >= gdl_soft_ce_lowres_workspace(B, K, Ho, Wo) && (uintptr_t)ws % 8 == 0,
                 "gdl_soft_ce_lowres_fwd: workspace too small or misaligned");
   CE_OPT("gdl_soft_ce_lowres_fwd", K);
   const int64_t total = (int64_t)B * Ho * Wo;
-  const int nblk = ce_lowres_blocks(total);
   hipStream_t s = (hipStream_t)stream;
-  double* part = (double*)ws;
-  K_SWITCH(K, hipLaunchKernelGGL((ce_lowres_partial_kernel<KK>), dim3(nblk), dim3(256), 0, s, low, target, B, Hi, Wi, Ho, Wo, part, o));
-  hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(256), 0, s, (const double*)part, nblk, mean ? 1.0 / (double)total : 1.0, loss);
+  int nblk;
+  const int rc = lowres_launch_partial<CePix>(low, target, B, K, Hi, Wi, Ho, Wo, (double*)ws, o, nblk, s);
+  if (rc != GDL_OK) return rc;
+  hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, nblk, mean ? 1.0 / (double)total : 1.0, loss);
   GDL_CHECK_LAUNCH("gdl_soft_ce_lowres_fwd");
   return GDL_OK;
 }
@@ -399,53 +288,21 @@ extern "C" int gdl_soft_ce_lowres_fwd(const float* low, const int64_t* target, i
 static std::atomic<int> g_ce_tiled{1};
 extern "C" void gdl_debug_set_soft_ce_lowres_tiled(int on) { g_ce_tiled = on; }   // A/B hook: 0 = the gather kernel for every class count
 
-// launches the tile kernel (with or without the loss partials) into `patches`
-template <bool LOSS>
-static int ce_launch_tiles(CeTile& a, int K, int ny, int nx, hipStream_t st) {
-  const unsigned tiles = (unsigned)lowres_tiles(a.B, a.Ho, a.Wo);
-  K_SWITCH(K, if (KK <= 8) {
-                   constexpr int K8 = KK <= 8 ? KK : 8;
-                   const size_t lds = lowres_tile_lds(K8, ny, nx);
-                   GDL_SET_MAX_LDS_ONCE((ce_lowres_tile_kernel<K8, LOSS>), 159 * 1024);
-                   hipLaunchKernelGGL((ce_lowres_tile_kernel<K8, LOSS>), dim3(tiles), dim3(CT_T), lds, st, a);
-                 });
-  return GDL_OK;
-}
 // bytes of scratch gdl_soft_ce_lowres_bwd needs (0: none -- the gather kernel)
 extern "C" int64_t gdl_soft_ce_lowres_bwd_workspace(int B, int K, int Hi, int Wi, int Ho, int Wo) {
-  int ny, nx;
-  if (B <= 0 || K < 1 || Hi <= 0 || Wi <= 0 || Ho < Hi || Wo < Wi || !g_ce_tiled || !lowres_tile_dims(K, Hi, Wi, Ho, Wo, ny, nx)) return 0;
-  return lowres_tiles(B, Ho, Wo) * ny * nx * K * (int64_t)sizeof(float);
+  return g_ce_tiled ? lowres_bwd_need(K, false, B, Hi, Wi, Ho, Wo) : 0;
 }
 
 extern "C" int gdl_soft_ce_lowres_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo, float smooth,
                                       int has_ignore, int64_t ignore, int mean, const float* upstream, float grad_scale, float* dlow,
                                       float* ws, int64_t ws_bytes, gdl_stream_t stream) {
   GDL_CHECK_ARG(low && target && dlow, "gdl_soft_ce_lowres_bwd: null pointer");
-  CE_LOWRES_SHAPE("gdl_soft_ce_lowres_bwd");
+  LOWRES_SHAPE("gdl_soft_ce_lowres_bwd", K);
   CE_OPT("gdl_soft_ce_lowres_bwd", K);
   const int64_t npix = (int64_t)B * Ho * Wo;
   const float scale = (float)(mean ? (double)grad_scale / (double)npix : (double)grad_scale);
-  hipStream_t st = (hipStream_t)stream;
-  int ny, nx;
-  const int64_t need = gdl_soft_ce_lowres_bwd_workspace(B, K, Hi, Wi, Ho, Wo);
-  if (need > 0 && ws && ws_bytes >= need && lowres_tile_dims(K, Hi, Wi, Ho, Wo, ny, nx)) {
-    CeTile a{};
-    a.low = low; a.target = target; a.upstream = upstream; a.tile_loss = nullptr; a.patches = ws; a.dlow = dlow;
-    lowres_tile_shape(a, B, Hi, Wi, Ho, Wo, ny, nx);
-    a.scale = scale; a.o = o;
-    int rc = ce_launch_tiles<false>(a, K, ny, nx, st);
-    if (rc != GDL_OK) return rc;
-    rc = lowres_launch_reduce(a, K, st);
-    if (rc != GDL_OK) return rc;
-    GDL_CHECK_LAUNCH("gdl_soft_ce_lowres_bwd");
-    return GDL_OK;
-  }
-  const int64_t total = (int64_t)B * Hi * Wi;
-  K_SWITCH(K, hipLaunchKernelGGL((ce_lowres_bwd_gather_kernel<KK>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, low, target, B, Hi,
-                                    Wi, Ho, Wo, upstream, scale, dlow, o));
-  GDL_CHECK_LAUNCH("gdl_soft_ce_lowres_bwd");
-  return GDL_OK;
+  CeTile a = lowres_args(low, target, B, Hi, Wi, Ho, Wo, upstream, scale, nullptr, dlow, o);
+  return lowres_bwd<CePix>("gdl_soft_ce_lowres_bwd", a, K, g_ce_tiled ? GDL_FOCAL_AUTO : GDL_FOCAL_GATHER, ws, ws_bytes, (hipStream_t)stream);
 }
 
 // ---- fused form: the forward leaves the unscaled patches of d(low) in `state`; the backward only reduces them.
@@ -474,14 +331,14 @@ extern "C" int gdl_soft_ce_lowres_fused_fwd(const float* low, const int64_t* tar
                                             float smooth, int has_ignore, int64_t ignore, int mean, float* loss, void* state,
                                             int64_t state_bytes, gdl_stream_t stream) {
   GDL_CHECK_ARG(low && target && loss, "gdl_soft_ce_lowres_fused_fwd: null pointer");
-  CE_LOWRES_SHAPE("gdl_soft_ce_lowres_fused_fwd");
+  LOWRES_SHAPE("gdl_soft_ce_lowres_fused_fwd", K);
   CE_OPT("gdl_soft_ce_lowres_fused_fwd", K);
   CeTile a{};
   int rc = ce_fused_args("gdl_soft_ce_lowres_fused_fwd", state, state_bytes, B, K, Hi, Wi, Ho, Wo, a);
   if (rc != GDL_OK) return rc;
   a.low = low; a.target = target; a.upstream = nullptr; a.dlow = nullptr; a.scale = 1.f; a.o = o;
   hipStream_t st = (hipStream_t)stream;
-  rc = ce_launch_tiles<true>(a, K, a.ny_max, a.nx_max, st);
+  rc = lowres_launch_tiles<CePix, true>(a, K, st);
   if (rc != GDL_OK) return rc;
   const int64_t npix = (int64_t)B * Ho * Wo;
   hipLaunchKernelGGL(ce_final_kernel, dim3(1), dim3(256), 0, st, (const double*)a.tile_loss, (int)lowres_tiles(B, Ho, Wo),
@@ -493,7 +350,7 @@ extern "C" int gdl_soft_ce_lowres_fused_fwd(const float* low, const int64_t* tar
 extern "C" int gdl_soft_ce_lowres_fused_bwd(const void* state, int64_t state_bytes, int B, int K, int Hi, int Wi, int Ho, int Wo, int mean,
                                             const float* upstream, float grad_scale, float* dlow, gdl_stream_t stream) {
   GDL_CHECK_ARG(dlow, "gdl_soft_ce_lowres_fused_bwd: null pointer");
-  CE_LOWRES_SHAPE("gdl_soft_ce_lowres_fused_bwd");
+  LOWRES_SHAPE("gdl_soft_ce_lowres_fused_bwd", K);
   CeTile a{};
   const int rc = ce_fused_args("gdl_soft_ce_lowres_fused_bwd", const_cast<void*>(state), state_bytes, B, K, Hi, Wi, Ho, Wo, a);
   if (rc != GDL_OK) return rc;

@@ -580,9 +580,8 @@ __global__ __launch_bounds__(256) void dice_binary_bwd_kernel(const float* __res
 // weight:
 //   forward  -- the sums [I | S | N] in the K = 1 layout (dice_final_kernel<1> finishes them), workgroups and pixel order of
 //               dice_lowres_partial_kernel;
-//   backward -- dL/dx = (cb + ca y) p (1 - p) with dice_coeffs<1> at upstream 1, gathered per low-resolution logit (one thread each,
-//               rows then columns ascending) or tile by tile (lowres_tile.h at K = 1: every pixel evaluated once; lowres_reduce_kernel
-//               adds the patches in a fixed order).  Both forms multiply by upstream * grad_scale once, at the end.
+//   backward -- dL/dx = (cb + ca y) p (1 - p) with dice_coeffs<1> at upstream 1 (DiceBinaryPix), in the gather or the tile form of
+//               lowres_tile.h at K = 1.  Both forms multiply by upstream * grad_scale once, at the end.
 // No float atomics: the same input gives the same bits on every launch.
 template <bool IGN>
 __global__ __launch_bounds__(256) void dice_binary_lowres_partial_kernel(const float* __restrict__ low, const int64_t* __restrict__ target,
@@ -616,82 +615,27 @@ __global__ __launch_bounds__(256) void dice_binary_lowres_partial_kernel(const f
         (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-template <bool IGN>
-__global__ __launch_bounds__(256) void dice_binary_lowres_bwd_gather_kernel(const float* __restrict__ low, const int64_t* __restrict__ target,
-                                                                            int B, int Hi, int Wi, int Ho, int Wo,
-                                                                            const float* __restrict__ sums, float eps,
-                                                                            const float* __restrict__ upstream, float grad_scale,
-                                                                            float* __restrict__ dlow, int64_t ignore, const DiceCoef o) {
-  float ca[1], cb[1];  // dL/dp = ca * y + cb at upstream 1
-  dice_coeffs<1>(sums, eps, 1.f, o, ca, cb);
-  const float cf = (upstream ? upstream[0] : 1.f) * grad_scale;
-  const int64_t total = (int64_t)B * Hi * Wi;
-  const float ry = (float)Hi / (float)Ho, rx = (float)Wi / (float)Wo;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-    const int ix = (int)(i % Wi);
-    const int64_t r = i / Wi;
-    const int iy = (int)(r % Hi), b = (int)(r / Hi);
-    int ylo, yhi, xlo, xhi;
-    cand_range(iy, ry, Ho, ylo, yhi);
-    cand_range(ix, rx, Wo, xlo, xhi);
-    float acc = 0.f;
-    for (int oy = ylo; oy <= yhi; ++oy) {
-      int y0, y1; float ly;
-      src_index2(ry, oy, Hi, y0, y1, ly);
-      const float wy = (y0 == iy ? 1.f - ly : 0.f) + (y1 == iy ? ly : 0.f);
-      if (wy == 0.f) continue;
-      const int64_t trow = ((int64_t)b * Ho + oy) * Wo;
-#pragma unroll 1
-      for (int ox = xlo; ox <= xhi; ++ox) {
-        int x0, x1; float lx;
-        src_index2(rx, ox, Wi, x0, x1, lx);
-        const float w = wy * ((x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f));
-        if (w == 0.f) continue;
-        const int64_t t = target[trow + ox];
-        if (IGN && t == ignore) continue;      // an ignored pixel adds nothing
-        float x[1];
-        bilinear_logits<1>(low, b, Hi, Wi, y0, y1, x0, x1, ly, lx, x);
-        const float p = expf(fminf(x[0], 0.f) - log1pf(expf(-fabsf(x[0]))));
-        acc += w * ((cb[0] + ca[0] * (float)t) * p * (1.f - p));
-      }
-    }
-    dlow[i] = cf * acc;
-  }
-}
-
-struct DiceBinaryTile : LowresTile {
+// the backward's policy of lowres_tile.h
+struct DiceBinaryOpt {
   const float* sums;
   float eps;
   int64_t ignore;
   DiceCoef o;
 };
-
 template <bool IGN>
-__global__ __launch_bounds__(CT_T) void dice_binary_lowres_tile_kernel(const DiceBinaryTile a) {
-  extern __shared__ __attribute__((aligned(16))) float csm[];      // dl [1][CT_H][CT_W], then lowres_tile_patch's tables
-  const TileAt at = lowres_tile_at(a);
-  float ca[1], cb[1];
-  dice_coeffs<1>(a.sums, a.eps, 1.f, a.o, ca, cb);
-  for (int i = threadIdx.x; i < CT_H * CT_W; i += CT_T) {
-    const int r = i / CT_W, c = i - r * CT_W;
-    float v = 0.f;      // outside the image and at ignored pixels
-    if (r < at.rows && c < at.cols) {
-      const int oy = at.oy0 + r, ox = at.ox0 + c;
-      const int64_t t = a.target[((int64_t)at.b * a.Ho + oy) * a.Wo + ox];
-      if (!(IGN && t == a.ignore)) {
-        int y0, y1, x0, x1; float ly, lx;
-        src_index2(at.ry, oy, a.Hi, y0, y1, ly);
-        src_index2(at.rx, ox, a.Wi, x0, x1, lx);
-        float x[1];
-        bilinear_logits<1>(a.low, at.b, a.Hi, a.Wi, y0, y1, x0, x1, ly, lx, x);
-        const float p = expf(fminf(x[0], 0.f) - log1pf(expf(-fabsf(x[0]))));
-        v = (cb[0] + ca[0] * (float)t) * p * (1.f - p);
-      }
-    }
-    csm[r * CT_W + c] = v;
+struct DiceBinaryPix {
+  typedef DiceBinaryOpt Opt;
+  typedef int64_t Target;
+  static constexpr bool ONE_CLASS = true;
+  float ca[1], cb[1];      // dL/dp = ca * y + cb at upstream 1
+  int64_t ignore;
+  __device__ DiceBinaryPix(const DiceBinaryOpt& d, int) : ignore(d.ignore) { dice_coeffs<1>(d.sums, d.eps, 1.f, d.o, ca, cb); }
+  __device__ bool valid(int64_t t) const { return !(IGN && t == ignore); }
+  __device__ void grad(const float (&x)[1], int64_t t, float (&g)[1]) const {
+    const float p = expf(fminf(x[0], 0.f) - log1pf(expf(-fabsf(x[0]))));
+    g[0] = (cb[0] + ca[0] * (float)t) * p * (1.f - p);
   }
-  lowres_tile_patch<1>(a, at, csm, [] {});
-}
+};
 
 }  // namespace
 
@@ -1018,16 +962,11 @@ extern "C" int gdl_overlap_binary_loss_bwd(const float* logits, const int64_t* t
 
 // ---- binary, from the low-resolution map: low [B, Hi, Wi, 1], target [B, Ho, Wo]; forward workspace: gdl_dice_loss_lowres_workspace(B, 1,
 // Ho, Wo).  Shape limits of the multiclass low-resolution entry points: an upsample by at most 64 per direction.
-#define DICE_BINARY_LOWRES_SHAPE(who)                                                                                     \
-  GDL_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho >= Hi && Wo >= Wi, "%s: bad sizes (an upsample is expected)", who);       \
-  GDL_CHECK_ARG((Ho + Hi - 1) / Hi <= LOWRES_MAX_FACTOR && (Wo + Wi - 1) / Wi <= LOWRES_MAX_FACTOR,                       \
-                "%s: upsampling factors above 64 are not supported", who)
-
 static int dice_binary_lowres_fwd_run(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo, float eps,
                                       DiceFamilyOpt opt, const char* who, float* sums, float* loss, float* ws, int64_t ws_bytes,
                                       gdl_stream_t stream) {
   GDL_CHECK_ARG(low && target && sums && loss && ws, "%s: null pointer", who);
-  DICE_BINARY_LOWRES_SHAPE(who);
+  LOWRES_SHAPE(who, 1);
   GDL_CHECK_ARG(ws_bytes >= gdl_dice_loss_lowres_workspace(B, 1, Ho, Wo), "%s: workspace too small", who);
   DiceHostOpt h;
   if (const int st = opt.resolve(1, who, h); st != GDL_OK) return st;
@@ -1055,41 +994,18 @@ extern "C" int gdl_overlap_binary_loss_lowres_fwd(const float* low, const int64_
 
 // bytes of scratch the tile form of the binary low-resolution backwards needs (0: the shape takes the gather kernel only)
 extern "C" int64_t gdl_binary_lowres_bwd_workspace(int B, int Hi, int Wi, int Ho, int Wo) {
-  int ny, nx;
-  if (B <= 0 || Hi <= 0 || Wi <= 0 || Ho < Hi || Wo < Wi || !binary_tile_dims(Hi, Wi, Ho, Wo, ny, nx)) return 0;
-  return lowres_tiles(B, Ho, Wo) * ny * nx * (int64_t)sizeof(float);
+  return lowres_bwd_need(1, true, B, Hi, Wi, Ho, Wo);
 }
 
 static int dice_binary_lowres_bwd_run(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo, float eps,
                                       DiceFamilyOpt opt, const char* who, const float* sums, const float* upstream, float grad_scale,
                                       float* dlow, float* ws, int64_t ws_bytes, int form, gdl_stream_t stream) {
   GDL_CHECK_ARG(low && target && sums && dlow, "%s: null pointer", who);
-  DICE_BINARY_LOWRES_SHAPE(who);
-  GDL_CHECK_ARG(form == GDL_FOCAL_AUTO || form == GDL_FOCAL_GATHER || form == GDL_FOCAL_TILE, "%s: unknown form %d", who, form);
+  LOWRES_SHAPE(who, 1);
   DiceHostOpt h;
   if (const int st = opt.resolve(1, who, h); st != GDL_OK) return st;
-  hipStream_t st = (hipStream_t)stream;
-  int ny, nx;
-  const int64_t need = gdl_binary_lowres_bwd_workspace(B, Hi, Wi, Ho, Wo);
-  const bool can_tile = need > 0 && ws && ws_bytes >= need && binary_tile_dims(Hi, Wi, Ho, Wo, ny, nx);
-  GDL_CHECK_ARG(form != GDL_FOCAL_TILE || can_tile, "%s: this shape or workspace does not take the tile form", who);
-  if (can_tile && form != GDL_FOCAL_GATHER) {
-    DiceBinaryTile a{};
-    a.low = low; a.target = target; a.upstream = upstream; a.patches = ws; a.dlow = dlow;
-    lowres_tile_shape(a, B, Hi, Wi, Ho, Wo, ny, nx);
-    a.scale = grad_scale; a.sums = sums; a.eps = eps; a.ignore = h.ignore; a.o = h.o;
-    const unsigned tiles = (unsigned)lowres_tiles(B, Ho, Wo);
-    IGN_SWITCH(h.ign, hipLaunchKernelGGL((dice_binary_lowres_tile_kernel<IG>), dim3(tiles), dim3(CT_T), lowres_tile_lds(1, ny, nx), st, a));
-    const int rc = lowres_launch_reduce(a, 1, st);
-    if (rc != GDL_OK) return rc;
-    GDL_CHECK_LAUNCH(who);
-    return GDL_OK;
-  }
-  const int64_t total = (int64_t)B * Hi * Wi;
-  IGN_SWITCH(h.ign, hipLaunchKernelGGL((dice_binary_lowres_bwd_gather_kernel<IG>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, low, target,
-                                B, Hi, Wi, Ho, Wo, sums, eps, upstream, grad_scale, dlow, h.ignore, h.o));
-  GDL_CHECK_LAUNCH(who);
-  return GDL_OK;
+  auto a = lowres_args(low, target, B, Hi, Wi, Ho, Wo, upstream, grad_scale, nullptr, dlow, DiceBinaryOpt{sums, eps, h.ignore, h.o});
+  IGN_SWITCH(h.ign, return lowres_bwd<DiceBinaryPix<IG>>(who, a, 1, form, ws, ws_bytes, (hipStream_t)stream));
 }
 extern "C" int gdl_dice_binary_loss_lowres_opt_bwd(const float* low, const int64_t* target, int B, int Hi, int Wi, int Ho, int Wo,
                                                    float eps, const gdl_dice_options* opt, const float* sums, const float* upstream,

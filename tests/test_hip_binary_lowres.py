@@ -41,6 +41,10 @@ LOSS_TOL, LOSS_TOL_LOWRES, GRAD_TOL = 1e-6, 2e-6, 1e-4
 
 # (B, hi, wi, ho, wo): an integer factor, non-integer factors, a factor of 64, and 1:1 (gather form only)
 SHAPES = [(2, 16, 16, 64, 64), (1, 5, 7, 37, 41), (1, 2, 2, 128, 128), (3, 16, 16, 16, 16)]
+# the tile-edge and window cases of the kernel skeletons every low-resolution loss shares (csrc/lowres_tile.h; tiles are 32 x 64):
+# one partial tile; remainder tiles of one pixel in each direction at a non-integer ratio; the largest factor; 1:1 in one
+# direction only; 1:1 in both (gather form only)
+SKELETON_SHAPES = [(2, 4, 4, 8, 8), (2, 5, 7, 33, 65), (2, 1, 1, 64, 64), (2, 8, 8, 8, 16), (2, 8, 8, 8, 8)]
 
 # name -> (class, constructor arguments, the f64 reference of the loss on full-resolution logits [B,1,H,W])
 CASES = {
@@ -51,6 +55,8 @@ CASES = {
     "tversky": (gnn.TverskyLoss, dict(mode="binary", alpha=0.3, beta=0.7, gamma=0.75, ignore_index=-1),
                 lambda x, y: overlap_ref(x, y, "tversky", mode="binary", alpha=0.3, beta=0.7, gamma=0.75, ignore_index=-1)[0]),
 }
+CASES["focal-noignore"] = (gnn.FocalLoss, dict(mode="binary", alpha=0.25, gamma=2.0),
+                           lambda x, y: focal_ref(x, y, mode="binary", alpha=0.25, gamma=2.0))
 for _g in (0.0, 0.5, 2.0):
     for _r in ("mean", "sum"):
         CASES[f"focal-g{_g}-{_r}"] = (
@@ -68,12 +74,16 @@ def forms_of(shape):
 
 def make_inputs(shape, ignore, seed=0):
     """low [B,hi,wi,1] (randn * 2) and a 0/1 target; with ``ignore``: 10 % of the pixels at random plus the top-left ninth of
-    image 0 (so that some low-resolution logits have every contributing pixel ignored)."""
+    image 0 (so that some low-resolution logits have every contributing pixel ignored).  SKELETON_SHAPES: a quarter of the pixels
+    at random plus the whole first 32 x 64 tile of image 0."""
     B, hi, wi, ho, wo = shape
     g = torch.Generator().manual_seed(seed + sum(shape))
     low = torch.randn(B, hi, wi, 1, generator=g) * 2.0
     tgt = torch.randint(0, 2, (B, ho, wo), generator=g)
-    if ignore is not None:
+    if ignore is not None and shape in SKELETON_SHAPES:
+        tgt[torch.rand(tgt.shape, generator=g) < 0.25] = ignore
+        tgt[0, :32, :64] = ignore
+    elif ignore is not None:
         tgt[torch.rand(tgt.shape, generator=g) < 0.1] = ignore
         tgt[0, : ho // 3, : wo // 3] = ignore
         share = (tgt == ignore).float().mean().item()
@@ -127,7 +137,7 @@ def run_ops(crit, low, tgt, size, form, up=UP):
 
 
 @pytest.mark.parametrize("case", list(CASES))
-@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("shape", SHAPES + SKELETON_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_loss_and_gradient_from_the_low_resolution_map(shape, case):
     """Every backward form the shape admits, against the f64 reference and against the class's own materialised path; the class
     itself takes the low-resolution node (``upsample_logits`` is never called) and its first form, up to the factor at which that

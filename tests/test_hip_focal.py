@@ -61,12 +61,13 @@ def check_full(logits, target, mode="multiclass", closed=False, **kw):
     return loss, ld.grad
 
 
-def check_lowres(shape, form, **kw):
+def check_lowres(shape, form, tgt=None, **kw):
     """FocalLoss("multiclass", **kw) on LowresLogits with the ``form`` backward: against focal_ref on the interpolated logits and
     against the class's own materialised path."""
     B, K, hi, wi, ho, wo = shape
     low = rnd(B, hi, wi, K, seed=3) * 2.0
-    tgt = make_target((B, ho, wo), K, kw.get("ignore_index"), seed=4)
+    if tgt is None:
+        tgt = make_target((B, ho, wo), K, kw.get("ignore_index"), seed=4)
     lr = low.double().permute(0, 3, 1, 2).clone().requires_grad_(True)
     ref = focal_ref(F.interpolate(lr, size=(ho, wo), mode="bilinear", align_corners=False), tgt, **kw)
     (UP * ref).backward()
@@ -215,15 +216,26 @@ def test_binary(reduction):
 def test_low_resolution(shape, kw):
     """Every backward form the shape can take (K <= 8: tile and gather; K = 16: gather), each against the f64 reference and the
     materialised path, then against each other; the class itself takes the tile form where there is one."""
+    check_forms(shape, kw)
+
+
+@pytest.mark.parametrize("ignore", [255, None], ids=["ignored", "none_ignored"])
+@pytest.mark.parametrize("shape", _sce.SKELETON_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_low_resolution_at_the_tile_edges(shape, ignore):
+    """The shapes of tests/test_hip_soft_ce.py::test_low_resolution_at_the_tile_edges."""
+    check_forms(shape, dict(alpha=0.25, ignore_index=ignore), _sce.skeleton_target(shape, ignore))
+
+
+def check_forms(shape, kw, tgt=None):
     forms = forms_of(shape)
-    got = {f: check_lowres(shape, f, **kw) for f in forms}
+    got = {f: check_lowres(shape, f, tgt, **kw) for f in forms}
     base_loss, base_grad = got["gather"]
     for f in forms[:-1]:
         assert torch.equal(got[f][0], base_loss), "the forms share the forward"
         grad_close(got[f][1], base_grad, f"{shape} {f} vs gather backward")
     B, K, hi, wi, ho, wo = shape
     a = (rnd(B, hi, wi, K, seed=3) * 2.0).to(DEV).requires_grad_(True)
-    y = make_target((B, ho, wo), K, kw.get("ignore_index"), seed=4).to(DEV)
+    y = (make_target((B, ho, wo), K, kw.get("ignore_index"), seed=4) if tgt is None else tgt).to(DEV)
     loss = gnn.FocalLoss("multiclass", **kw)(gnn.LowresLogits(a, (ho, wo)), y[:, None])
     (UP * loss).backward()
     assert torch.equal(loss.detach(), base_loss) and torch.equal(a.grad, got[forms[0]][1])

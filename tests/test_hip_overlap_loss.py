@@ -35,6 +35,9 @@ GRID_IDS = ["jaccard-default", "jaccard-smooth", "jaccard-log", "jaccard-classes
 # change of shape across that condition.
 LOWRES = [(2, 4, 4, 5, 32, 32), (2, 2, 2, 5, 64, 64), (2, 3, 5, 3, 24, 40), (2, 3, 4, 8, 9, 10), (2, 3, 4, 9, 9, 10)]
 LOWRES_IDS = ["x8", "x32", "nonsquare", "K8-tiled", "K9-gather"]
+# the tile-edge and window cases of tests/test_hip_soft_ce.py::SKELETON_SIZES, at the class counts 5, 8 (the tile limit), 9 and 16
+EDGES = [(2, hi, wi, K, ho, wo) for hi, wi, ho, wo in [(4, 4, 8, 8), (5, 7, 33, 65), (1, 1, 64, 64), (8, 8, 8, 16), (8, 8, 8, 8)]
+         for K in (5, 8, 9, 16)]
 
 
 def make(kind, mode="multiclass", **kw):
@@ -67,11 +70,14 @@ def check_full(kind, logits, target, mode="multiclass", **kw):
     return loss, ld.grad
 
 
-def check_lowres(kind, shape, **kw):
-    """On LowresLogits: against overlap_ref on the interpolated logits, and against the same loss on materialise()d logits."""
+def check_lowres(kind, shape, tile_ignored=False, **kw):
+    """On LowresLogits: against overlap_ref on the interpolated logits, and against the same loss on materialise()d logits.
+    ``tile_ignored``: the whole first 32 x 64 tile of image 0 is ignored on top of the random quarter."""
     B, hi, wi, K, ho, wo = shape
     low = uniform(B, hi, wi, K, seed=3)
     tgt = make_target((B, ho, wo), K, kw.get("ignore_index"), frac=0.25, seed=4)
+    if tile_ignored:
+        tgt[0, :32, :64] = kw["ignore_index"]
     lr = low.double().permute(0, 3, 1, 2).clone().requires_grad_(True)
     ref, score, ysum, m = overlap_ref(F.interpolate(lr, size=(ho, wo), mode="bilinear", align_corners=False), tgt, kind, **kw)
     assert m.item() > 0.05
@@ -152,6 +158,14 @@ def test_low_resolution(shape, kind, kw):
             make(kind, **kw)(gnn.LowresLogits(low, shape[4:]), y)
         return
     assert check_lowres(kind, shape, **kw) == (K <= 8), "K <= 8 runs the tiled backward, K > 8 the gather kernel"
+
+
+@gpu
+@pytest.mark.parametrize("ignore", [255, None], ids=["ignored", "none_ignored"])
+@pytest.mark.parametrize("shape", EDGES, ids=lambda s: "x".join(map(str, s)))
+def test_low_resolution_at_the_tile_edges(shape, ignore):
+    kw = dict(alpha=0.3, beta=0.7, smooth=1.0, ignore_index=ignore)
+    assert check_lowres("tversky", shape, tile_ignored=ignore is not None, **kw) == (shape[3] <= 8)
 
 
 # ------------------------------------------------------------------------------------------------ ignored pixels

@@ -165,13 +165,15 @@ LOW_CASES = {
     "plain": dict(weight=None, pos_weight=None, smooth_factor=None, ignore_index=255, reduction="mean"),
     "smooth-weights": dict(weight=torch.tensor(0.7), pos_weight=torch.tensor([2.0]), smooth_factor=0.1, ignore_index=255, reduction="mean"),
     "smooth-sum": dict(weight=None, pos_weight=torch.tensor([[[0.5]]]), smooth_factor=0.1, ignore_index=255, reduction="sum"),
+    "no-ignore": dict(weight=None, pos_weight=torch.tensor([2.0]), smooth_factor=0.1, ignore_index=None, reduction="mean"),
 }
 
 
-def low_inputs(shape, float_target):
+def low_inputs(shape, float_target, ignore=255):
     """``make_inputs`` of tests/test_hip_binary_lowres.py (10 % ignored at random plus the top-left ninth of image 0; it asserts the
-    10-30 % share); the f32 target holds 0.25 / 0.75 in place of 0 / 1 and 255.0 at the ignored pixels."""
-    low, tgt = T.make_inputs(shape, 255)
+    10-30 % share; its other pattern on T.SKELETON_SHAPES; nothing ignored with ``ignore`` None); the f32 target holds 0.25 / 0.75
+    in place of 0 / 1 and 255.0 at the ignored pixels."""
+    low, tgt = T.make_inputs(shape, ignore)
     if float_target:
         tgt = torch.where(tgt == 255, torch.tensor(255.0), 0.25 + 0.5 * tgt.float())
     return low, tgt
@@ -182,7 +184,7 @@ def low_reference(shape, case, float_target):
     """(low, target, f64 loss, UP * d loss / d low [B,hi,wi,1], dead): computed once, never modified.  ``dead`` marks the
     low-resolution logits whose every contributing pixel is ignored (from the resize's own weights)."""
     kw = LOW_CASES[case]
-    low, tgt = low_inputs(shape, float_target)
+    low, tgt = low_inputs(shape, float_target, kw["ignore_index"])
     size = shape[3:]
     lr = low.double().permute(0, 3, 1, 2).clone().requires_grad_(True)
     ref = soft_bce_ref(F.interpolate(lr, size=size, mode="bilinear", align_corners=False), tgt, **kw)
@@ -201,7 +203,7 @@ def run_low(opt, low, tgt, size, form, up=UP):
 
 @pytest.mark.parametrize("float_target", [False, True], ids=["int64", "f32"])
 @pytest.mark.parametrize("case", list(LOW_CASES))
-@pytest.mark.parametrize("shape", T.SHAPES, ids=_ids)
+@pytest.mark.parametrize("shape", T.SHAPES + T.SKELETON_SHAPES, ids=_ids)
 def test_loss_and_gradient_from_the_low_resolution_map(shape, case, float_target):
     """Every backward form the shape admits, against the f64 reference and against the class's own materialised route; the class
     itself takes the low-resolution node (``upsample_logits`` is never called) up to factor 8 and materialises beyond it."""
@@ -226,7 +228,7 @@ def test_loss_and_gradient_from_the_low_resolution_map(shape, case, float_target
         if dead.any():
             assert (grad.cpu()[dead] == 0).all(), what + ": a logit whose every contributing pixel is ignored gets exactly 0"
         got[form] = (loss, grad)
-    if shape[1] >= 5:
+    if shape[1] >= 5 and kw["ignore_index"] is not None:
         assert dead.any()
     for form in forms[:-1]:
         assert torch.equal(got[form][0], got["gather"][0]), "the forms share the forward"

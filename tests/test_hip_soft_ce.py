@@ -90,12 +90,13 @@ class Form:
         self.lib.gdl_debug_set_soft_ce_lowres_tiled(1)
 
 
-def check_lowres(shape, form, **kw):
+def check_lowres(shape, form, tgt=None, **kw):
     """SoftCrossEntropyLoss(**kw) on LowresLogits through ``form``: against soft_ce_ref on the interpolated logits and against
     the class's own materialised path."""
     B, K, hi, wi, ho, wo = shape
     low = rnd(B, hi, wi, K, seed=3) * 2.0
-    tgt = make_target((B, ho, wo), K, kw.get("ignore_index", -100), seed=4)
+    if tgt is None:
+        tgt = make_target((B, ho, wo), K, kw.get("ignore_index", -100), seed=4)
     lr = low.double().permute(0, 3, 1, 2).clone().requires_grad_(True)
     ref = soft_ce_ref(F.interpolate(lr, size=(ho, wo), mode="bilinear", align_corners=False), tgt, kw.get("smooth_factor"),
                       kw.get("ignore_index", -100), kw.get("reduction", "mean"))
@@ -212,25 +213,51 @@ LOWRES_SHAPES = [(2, 5, 36, 36, 128, 128), (2, 5, 18, 18, 512, 512), (3, 16, 6, 
                  (2, 5, 144, 144, 512, 512)]
 
 
-@pytest.mark.parametrize("kw", [dict(), dict(smooth_factor=0.1, ignore_index=255), dict(smooth_factor=0.1, reduction="sum", ignore_index=None)],
-                         ids=["defaults", "smooth_ignore255", "smooth_sum_noignore"])
-@pytest.mark.parametrize("shape", LOWRES_SHAPES)
-def test_low_resolution(shape, kw):
-    """Every backward form the shape can take, each against the f64 reference and the materialised path, then against each
-    other.  K <= 8 takes the fused form by default and the tile kernel in the recompute form; K > 8 the gather kernel."""
+# The tile-edge and window cases of the kernel skeletons every low-resolution loss shares (csrc/lowres_tile.h; tiles are 32 x 64):
+# one partial tile; remainder tiles of one pixel in each direction at a non-integer ratio; the largest factor; 1:1 in one direction
+# only; 1:1 in both.  K = 8 is the tile limit, K = 9 and 16 take the gather kernel.
+SKELETON_SIZES = [(4, 4, 8, 8), (5, 7, 33, 65), (1, 1, 64, 64), (8, 8, 8, 16), (8, 8, 8, 8)]
+SKELETON_SHAPES = [(2, K, *size) for size in SKELETON_SIZES for K in (5, 8, 9, 16)]
+
+
+def skeleton_target(shape, ignore):
+    """With ``ignore``: a quarter of the pixels at random plus the whole first 32 x 64 tile of image 0."""
+    B, K, hi, wi, ho, wo = shape
+    tgt = make_target((B, ho, wo), K, ignore, frac=0.25, seed=4)
+    if ignore is not None:
+        tgt[0, :32, :64] = ignore
+    return tgt
+
+
+def check_forms(shape, kw, tgt=None):
     B, K, hi, wi, ho, wo = shape
     lib = gdlhip._lib.load()
     tiles = lib.gdl_soft_ce_lowres_fused_state(B, K, hi, wi, ho, wo) > 0
     assert tiles == (K <= 8)
     assert (lib.gdl_soft_ce_lowres_bwd_workspace(B, K, hi, wi, ho, wo) > 0) == tiles
     forms = ("fused", "tile", "gather") if tiles else ("gather",)
-    got = {f: check_lowres(shape, f, **kw) for f in forms}
+    got = {f: check_lowres(shape, f, tgt, **kw) for f in forms}
     base_loss, base_grad = got["gather"]
     for f in forms[:-1]:
         loss_close(got[f][0].item(), base_loss.item(), LOSS_TOL, f"{shape} {f} vs gather")
         grad_close(got[f][1], base_grad, f"{shape} {f} vs gather backward")
     if tiles:
         assert torch.equal(got["tile"][0], got["gather"][0]), "the two recompute forms share the forward"
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(smooth_factor=0.1, ignore_index=255), dict(smooth_factor=0.1, reduction="sum", ignore_index=None)],
+                         ids=["defaults", "smooth_ignore255", "smooth_sum_noignore"])
+@pytest.mark.parametrize("shape", LOWRES_SHAPES)
+def test_low_resolution(shape, kw):
+    """Every backward form the shape can take, each against the f64 reference and the materialised path, then against each
+    other.  K <= 8 takes the fused form by default and the tile kernel in the recompute form; K > 8 the gather kernel."""
+    check_forms(shape, kw)
+
+
+@pytest.mark.parametrize("ignore", [255, None], ids=["ignored", "none_ignored"])
+@pytest.mark.parametrize("shape", SKELETON_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_low_resolution_at_the_tile_edges(shape, ignore):
+    check_forms(shape, dict(smooth_factor=0.1, ignore_index=ignore), skeleton_target(shape, ignore))
 
 
 def test_low_resolution_out_of_range_target_and_unsqueezed_mask():
