@@ -23,6 +23,7 @@
 #include "gdl_common.h"
 #include "bilinear_index.h"
 #include "lowres_tile.h"
+#include "mean_final.h"
 
 namespace {
 
@@ -78,35 +79,6 @@ __global__ __launch_bounds__(256) void focal_partial_kernel(const float* __restr
   block256_store_sum(cnt, ws + gridDim.x);
 }
 
-// one workgroup: the two sums of n partials each in a fixed order (strided per thread, then a tree); the divisor
-// (mean: 1 / valid count, 0 without a valid pixel; sum: 1) -> norm[0], loss = sum * divisor
-__global__ __launch_bounds__(256) void focal_final_kernel(const double* __restrict__ ws, int n, int mean, float* __restrict__ loss,
-                                                          float* __restrict__ norm) {
-  __shared__ double part[256], pcnt[256];
-  const int t = threadIdx.x;
-  double acc = 0.0, cnt = 0.0;
-#pragma unroll 8
-  for (int i = t; i < n; i += 256) acc += ws[i];
-#pragma unroll 8
-  for (int i = t; i < n; i += 256) cnt += ws[n + i];
-  part[t] = acc;
-  pcnt[t] = cnt;
-  __syncthreads();
-#pragma unroll
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) {
-      part[t] += part[t + s];
-      pcnt[t] += pcnt[t + s];
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    const double inv = mean ? (pcnt[0] > 0.0 ? 1.0 / pcnt[0] : 0.0) : 1.0;
-    loss[0] = (float)(part[0] * inv);
-    norm[0] = (float)inv;
-  }
-}
-
 __global__ __launch_bounds__(256) void focal_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, int B, int K,
                                                         int64_t HW, const float* __restrict__ norm, const float* __restrict__ upstream,
                                                         float scale, float* __restrict__ dlogits, int accumulate, const FocalOpt o) {
@@ -138,6 +110,7 @@ struct FocalPix {
   FocalOpt o;
   __device__ FocalPix(const FocalOpt& opt, int) : o(opt) {}
   __device__ bool valid(int64_t t) const { return focal_valid(t, o); }
+  __device__ float count(int64_t) const { return 1.f; }
   template <int K>
   __device__ void grad(const float (&x)[K], int64_t t, float (&g)[K]) const {
 #pragma unroll
@@ -193,7 +166,7 @@ static int focal_fwd(const char* who, const float* logits, const int64_t* target
   const int nblk = focal_blocks((int64_t)B * HW, 2048);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(focal_partial_kernel, dim3(nblk), dim3(256), 0, s, logits, target, B, K, HW, (double*)ws, o);
-  hipLaunchKernelGGL(focal_final_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, nblk, mean, loss, norm);
+  hipLaunchKernelGGL(mean_final_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, nblk, mean, loss, norm);
   GDL_CHECK_LAUNCH(who);
   return GDL_OK;
 }
@@ -255,7 +228,7 @@ static int focal_lowres_fwd(const char* who, const float* low, const int64_t* ta
   int nblk;
   const int rc = lowres_launch_partial<FocalPix<BIN>>(low, target, B, K, Hi, Wi, Ho, Wo, (double*)ws, o, nblk, s);
   if (rc != GDL_OK) return rc;
-  hipLaunchKernelGGL(focal_final_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, nblk, mean, loss, norm);
+  hipLaunchKernelGGL(mean_final_kernel, dim3(1), dim3(256), 0, s, (const double*)ws, nblk, mean, loss, norm);
   GDL_CHECK_LAUNCH(who);
   return GDL_OK;
 }

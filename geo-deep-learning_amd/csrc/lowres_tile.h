@@ -1,6 +1,6 @@
-// What the per-pixel and one-class losses share (loss_ce.hip: soft cross-entropy; loss_focal.hip: focal, multiclass and binary;
-// loss_bce.hip: soft BCE; loss_dice.hip: the binary Dice family): the f64 partial-sum helpers and the three low-resolution kernel
-// skeletons, each parametrised by the class count K and the loss's per-pixel policy `Pix` -- the only part that differs:
+// What the per-pixel and one-class losses share (loss_ce.hip: soft cross-entropy; loss_xent.hip: weighted cross-entropy;
+// loss_focal.hip: focal, multiclass and binary; loss_bce.hip: soft BCE; loss_dice.hip: the binary Dice family): the f64
+// partial-sum helpers and the three low-resolution kernel skeletons, each parametrised by the class count K and the loss's per-pixel policy `Pix` -- the only part that differs:
 //   lowres_partial_kernel     forward: per-workgroup f64 partial sums of the loss over the on-the-fly bilinear logits
 //   lowres_gather_bwd_kernel  backward, gather form: one thread per low-resolution logit vector (K <= 16)
 //   lowres_tile_front_kernel  backward, tile form (K <= 8, LDS).  A per-pixel gradient needs no global sum, so a workgroup that
@@ -14,7 +14,9 @@
 // A policy is a trivially copyable struct built once per thread as Pix(opt, K); it holds what the loss hoists out of the pixel loop:
 //   Opt, Target        the loss's option struct (a kernel argument) and the target's element type
 //   ONE_CLASS          K is always 1 (the one-class losses): only that instantiation exists, and a 1:1 resize has no tile form
-//   COUNTS             the forward also stores the per-workgroup count of valid pixels at ws[gridDim.x ..)
+//   COUNTS             the forward also stores, at ws[gridDim.x ..), the per-workgroup sum of count(t) over the valid pixels: the
+//                      divisor of a mean the loss forms on the device (mean_final.h)
+//   count(t)           (COUNTS only) what a valid pixel adds to that divisor: 1 (focal), the target class's weight (cross-entropy)
 //   valid(t)           false: the pixel adds nothing (tested BEFORE its logits are evaluated)
 //   grad(x, t, g)      the K bilinear logits x (may be overwritten) and target t -> the unscaled dL/dlogit in g[K]
 //   loss(x, t)         the pixel's loss (forward)
@@ -49,7 +51,7 @@ struct LowresTile {
   const float* low;
   const void* target;     // [B, Ho, Wo] of the policy's Target
   const float* upstream; double* tile_loss; float* patches; float* dlow;
-  const float* norm;      // device scalar multiplied into the final factor (the focal loss's 1 / valid count); null: 1
+  const float* norm;      // device scalar multiplied into the final factor (the divisor mean_final.h left); null: 1
   int B, Hi, Wi, Ho, Wo, tiles_y, tiles_x, ny_max, nx_max;
   float scale;
 };
@@ -228,7 +230,7 @@ inline int lowres_launch_reduce(const LowresTile& a, int K, hipStream_t st) {
 
 // ------------------------------------------------------------------ the three skeletons
 // forward: ws[0 .. gridDim.x) = f64 partial sums of the loss over the valid pixels; with Pix::COUNTS, ws[gridDim.x .. 2 gridDim.x) =
-// the valid-pixel counts (exact in f64)
+// the sums of Pix::count() over them (a count of pixels is exact in f64)
 template <int K, typename Pix>
 __global__ __launch_bounds__(256) void lowres_partial_kernel(const float* __restrict__ low, const typename Pix::Target* __restrict__ target,
                                                              int B, int Hi, int Wi, int Ho, int Wo, double* __restrict__ ws,
@@ -249,7 +251,7 @@ __global__ __launch_bounds__(256) void lowres_partial_kernel(const float* __rest
     float x[K];
     bilinear_logits<K>(low, b, Hi, Wi, y0, y1, x0, x1, ly, lx, x);
     acc += (double)pix.loss(x, t);
-    cnt += 1.0;
+    if constexpr (Pix::COUNTS) cnt += (double)pix.count(t);
   }
   block256_store_sum(acc, ws);
   if constexpr (Pix::COUNTS) {

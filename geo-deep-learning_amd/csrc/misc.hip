@@ -875,6 +875,29 @@ __global__ __launch_bounds__(256) void upsample_logits_kernel(const float* __res
   }
 }
 
+// more than 16 classes: the same expression with the class dimension in a run-time loop (a loss whose low-resolution kernels stop
+// at 16 classes materialises its logits through this one)
+__global__ __launch_bounds__(256) void upsample_logits_any_kernel(const float* __restrict__ in, int B, int Hi, int Wi, int K,
+                                                                  float* __restrict__ out, int Ho, int Wo) {
+  const int64_t total = (int64_t)B * Ho * Wo;
+  const float ry = (float)Hi / (float)Ho, rx = (float)Wi / (float)Wo;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int ox = (int)(i % Wo);
+    const int64_t t = i / Wo;
+    const int oy = (int)(t % Ho), b = (int)(t / Ho);
+    int y0, y1, x0, x1; float ly, lx;
+    src_index2(ry, oy, Hi, y0, y1, ly);
+    src_index2(rx, ox, Wi, x0, x1, lx);
+    const float* p00 = in + (((int64_t)b * Hi + y0) * Wi + x0) * K;
+    const float* p01 = in + (((int64_t)b * Hi + y0) * Wi + x1) * K;
+    const float* p10 = in + (((int64_t)b * Hi + y1) * Wi + x0) * K;
+    const float* p11 = in + (((int64_t)b * Hi + y1) * Wi + x1) * K;
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    for (int k = 0; k < K; ++k)
+      out[(((int64_t)b * K + k) * Ho + oy) * Wo + ox] = hy * (hx * p00[k] + lx * p01[k]) + ly * (hx * p10[k] + lx * p11[k]);
+  }
+}
+
 // Backward of the logit upsample, separable (bilinear weights factor as wy*wx), gather form:
 //   pass 1: tmp[b,k,iy,ox] = sum_oy wy(oy->iy) * dout[b,k,oy,ox]      (coalesced along ox)
 //   pass 2: din[b,iy,ix,k] = sum_ox wx(ox->ix) * tmp[b,k,iy,ox]
@@ -903,6 +926,31 @@ __global__ __launch_bounds__(256) void upsample_logits_bwd_pass1(const float* __
 template <int K>
 __global__ __launch_bounds__(256) void upsample_logits_bwd_pass2(const float* __restrict__ tmp, int B, int Wo,
                                                                  float* __restrict__ din, int Hi, int Wi) {
+  const int64_t total = (int64_t)B * Hi * Wi * K;
+  const float rx = (float)Wi / (float)Wo;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int k = (int)(i % K);
+    int64_t t = i / K;
+    const int ix = (int)(t % Wi); t /= Wi;
+    const int iy = (int)(t % Hi);
+    const int b = (int)(t / Hi);
+    int lo, hi;
+    cand_range(ix, rx, Wo, lo, hi);
+    const float* row = tmp + (((int64_t)b * K + k) * Hi + iy) * Wo;
+    float acc = 0.f;
+    for (int ox = lo; ox <= hi; ++ox) {
+      int x0, x1; float lx;
+      src_index2(rx, ox, Wi, x0, x1, lx);
+      const float wx = (x0 == ix ? 1.f - lx : 0.f) + (x1 == ix ? lx : 0.f);
+      if (wx != 0.f) acc += wx * row[ox];
+    }
+    din[i] = acc;
+  }
+}
+
+// (pass 2 for more than 16 classes: K at run time)
+__global__ __launch_bounds__(256) void upsample_logits_bwd_pass2_any(const float* __restrict__ tmp, int B, int K, int Wo,
+                                                                     float* __restrict__ din, int Hi, int Wi) {
   const int64_t total = (int64_t)B * Hi * Wi * K;
   const float rx = (float)Wi / (float)Wo;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
@@ -1441,7 +1489,11 @@ extern "C" int gdl_upsample_logits(const float* in, int B, int Hi, int Wi, int K
                                    gdl_stream_t stream) {
   GDL_CHECK_ARG(in && out, "gdl_upsample_logits: null pointer");
   const int64_t total = (int64_t)B * Ho * Wo;
-  K_SWITCH(K, hipLaunchKernelGGL((upsample_logits_kernel<KK>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, B, Hi, Wi, out, Ho, Wo));
+  if (K > 16) {
+    hipLaunchKernelGGL(upsample_logits_any_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, B, Hi, Wi, K, out, Ho, Wo);
+  } else {
+    K_SWITCH(K, hipLaunchKernelGGL((upsample_logits_kernel<KK>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, in, B, Hi, Wi, out, Ho, Wo));
+  }
   GDL_CHECK_LAUNCH("gdl_upsample_logits");
   return GDL_OK;
 }
@@ -1456,7 +1508,11 @@ extern "C" int gdl_upsample_logits_bwd(const float* dout, int B, int Ho, int Wo,
   GDL_CHECK_ARG(ws_bytes >= gdl_upsample_logits_bwd_workspace(B, K, Hi, Wo), "gdl_upsample_logits_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(upsample_logits_bwd_pass1, dim3(grid_for((int64_t)B * K * Hi * Wo)), dim3(256), 0, s, dout, B * K, Ho, Wo, ws, Hi);
-  K_SWITCH(K, hipLaunchKernelGGL((upsample_logits_bwd_pass2<KK>), dim3(grid_for((int64_t)B * Hi * Wi * K)), dim3(256), 0, s, ws, B, Wo, din, Hi, Wi));
+  if (K > 16) {
+    hipLaunchKernelGGL(upsample_logits_bwd_pass2_any, dim3(grid_for((int64_t)B * Hi * Wi * K)), dim3(256), 0, s, ws, B, K, Wo, din, Hi, Wi);
+  } else {
+    K_SWITCH(K, hipLaunchKernelGGL((upsample_logits_bwd_pass2<KK>), dim3(grid_for((int64_t)B * Hi * Wi * K)), dim3(256), 0, s, ws, B, Wo, din, Hi, Wi));
+  }
   GDL_CHECK_LAUNCH("gdl_upsample_logits_bwd");
   return GDL_OK;
 }

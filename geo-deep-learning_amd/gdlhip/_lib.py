@@ -79,6 +79,8 @@ class OverlapOptions(C.Structure):
 FOCAL_AUTO, FOCAL_GATHER, FOCAL_TILE = 0, 1, 2
 # gamma, has_alpha, alpha, has_threshold, threshold, has_ignore, ignore, mean: the option arguments of every gdl_focal_* call
 _FOCAL_OPT = (c_f, c_i, c_f, c_i, c_f, c_i, c_l, c_i)
+# weight, smooth, has_ignore, ignore, mean: the option arguments of every gdl_cross_entropy_* call
+_XENT_OPT = (c_p, c_f, c_i, c_l, c_i)
 # has_smooth, smooth, has_ignore, ignore, ignore_f, weight, weight_numel, pos_weight, pos_weight_numel, scale: the option arguments
 # of every gdl_soft_bce_* call
 _BCE_OPT = (c_i, c_f, c_i, c_l, c_f, c_p, c_i, c_p, c_i, c_f)
@@ -229,6 +231,13 @@ SIGNATURES = {
     "gdl_soft_ce_lowres_fused_state": (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),
     "gdl_soft_ce_lowres_fused_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_l, c_i, c_p, c_p, c_l, c_p]),
     "gdl_soft_ce_lowres_fused_bwd": (c_i, [c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_f, c_p, c_p]),
+    "gdl_cross_entropy_workspace": (c_l, [c_i, c_i, c_l]),
+    "gdl_cross_entropy_fwd": (c_i, [c_p, c_p, c_i, c_i, c_l, *_XENT_OPT, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_cross_entropy_bwd": (c_i, [c_p, c_p, c_i, c_i, c_l, *_XENT_OPT, c_p, c_p, c_f, c_p, c_i, c_p]),
+    "gdl_cross_entropy_lowres_workspace": (c_l, [c_i, c_i, c_i, c_i]),
+    "gdl_cross_entropy_lowres_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, *_XENT_OPT, c_p, c_p, c_p, c_l, c_p]),
+    "gdl_cross_entropy_lowres_bwd_workspace": (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    "gdl_cross_entropy_lowres_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, *_XENT_OPT, c_p, c_p, c_f, c_p, c_p, c_l, c_i, c_p]),
     "gdl_focal_workspace": (c_l, [c_i, c_i, c_l]),
     "gdl_focal_fwd": (c_i, [c_p, c_p, c_i, c_i, c_l, *_FOCAL_OPT, c_p, c_p, c_p, c_l, c_p]),
     "gdl_focal_bwd": (c_i, [c_p, c_p, c_i, c_i, c_l, *_FOCAL_OPT, c_p, c_p, c_f, c_p, c_i, c_p]),

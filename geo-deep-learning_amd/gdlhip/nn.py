@@ -1683,6 +1683,125 @@ class SoftCrossEntropyLoss(nn.Module):
         return _SoftCE.apply(y_pred, y_true.long().contiguous(), self.options)
 
 
+class _CrossEntropy(Function):
+    """torch CrossEntropyLoss on full-resolution NCHW logits; the backward recomputes the softmax from the saved logits and reads
+    the divisor the forward left on the device."""
+
+    @staticmethod
+    def forward(ctx, logits, target, options):
+        loss, norm = ops.cross_entropy_fwd(logits, target, options)
+        ctx.save_for_backward(logits, target, norm)
+        ctx.options = options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, target, norm = ctx.saved_tensors
+        return ops.cross_entropy_bwd(logits, target, norm, g.contiguous().float(), 1.0, ctx.options), None, None
+
+
+class _CrossEntropyLowres(Function):
+    """torch CrossEntropyLoss of bilinear(low -> size), forward and backward from the low-resolution map."""
+
+    @staticmethod
+    def forward(ctx, low, target, size, options):
+        loss, norm = ops.cross_entropy_lowres_fwd(low, target, size, options)
+        ctx.save_for_backward(low, target, norm)
+        ctx.size, ctx.options = size, options
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        low, target, norm = ctx.saved_tensors
+        dlow = ops.cross_entropy_lowres_bwd(low, target, ctx.size, norm, g.contiguous().float(), 1.0, ctx.options)
+        return dlow, None, None, None
+
+
+class CrossEntropyLoss(nn.Module):
+    """``torch.nn.CrossEntropyLoss`` (argument names, order and defaults) for class-index targets, evaluated by the
+    gdl_cross_entropy_* HIP kernels; the reference of every number is ``F.cross_entropy`` itself.
+
+    With ``e = label_smoothing``, ``K`` classes, ``w_k = weight[k]`` (all 1 without ``weight``), ``W = sum_k w_k`` and
+    ``lse_i = logsumexp_k x_ik``, per valid pixel
+    ``L_i = (1 - e) w_{y_i} (lse_i - x_{i,y_i}) + (e / K) sum_k w_k (lse_i - x_ik)``; ``reduction="mean"`` is
+    ``sum_i L_i / D`` with ``D = sum_i w_{y_i}`` over the valid pixels, ``reduction="sum"`` is ``sum_i L_i``.  A pixel whose target
+    equals ``ignore_index`` (compared as int64) adds nothing and gets an exactly zero gradient.  A zero-weight class adds nothing
+    to ``D`` or to the first term; its pixels still carry the smoothing term, as in torch.  ``weight`` is a buffer under torch's
+    name (the same state-dict key), held as f32; the kernels read it through its device pointer at call time and ``D`` is formed
+    and applied on the device, so nothing is copied to the host in forward or backward.  Targets are int64 ``[B,H,W]`` or
+    ``[B,1,H,W]``.
+
+    Two deliberate deviations from torch:
+
+    1. A target outside ``0..K-1`` that is not ``ignore_index`` is treated as ignored (torch device-asserts on it): the target is
+       only ever compared, never used as an index -- the rule of ``SoftCrossEntropyLoss``.
+    2. With ``reduction="mean"`` and ``D == 0`` (every pixel ignored, or every valid pixel of a zero-weight class) the loss is 0
+       and every gradient is 0, where torch returns NaN: a NaN would poison the weights inside a captured step that cannot look
+       at it.  ``FocalLoss`` does the same.
+
+    ``reduction="none"``, class-probability (floating point) targets and a non-``None`` ``size_average`` / ``reduce`` raise
+    ``NotImplementedError``.
+
+    ``y_pred`` may be ``LowresLogits`` (a DOFA training / validation step): the loss and d(low) come straight from the head's own
+    map, the [B, K, H, W] tensor is never written (K <= 16, factor <= 64 as for SoftCrossEntropyLoss; other shapes materialise)."""
+
+    def __init__(self, weight: Tensor | None = None, size_average=None, ignore_index: int | None = -100, reduce=None,
+                 reduction: str = "mean", label_smoothing: float = 0.0) -> None:
+        super().__init__()
+        if size_average is not None or reduce is not None:
+            raise NotImplementedError("gdlhip CrossEntropyLoss implements reduction= only (size_average and reduce must be None)")
+        if reduction not in ("mean", "sum"):
+            if reduction == "none":
+                raise NotImplementedError("gdlhip CrossEntropyLoss implements reduction='mean' and 'sum' (got 'none')")
+            raise ValueError(f"CrossEntropyLoss: unknown reduction {reduction!r}")
+        label_smoothing = float(label_smoothing)
+        if not 0.0 <= label_smoothing <= 1.0:      # (NaN and the infinities fail the comparison)
+            raise ValueError(f"CrossEntropyLoss: label_smoothing must be a finite value in [0, 1] (got {label_smoothing})")
+        if ignore_index is not None:      # (None, which torch does not take: no pixel is ignored)
+            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
+                raise ValueError(f"CrossEntropyLoss: ignore_index must be an int64 value or None (got {ignore_index!r})")
+            ignore_index = int(ignore_index)
+        if weight is not None:
+            if not isinstance(weight, Tensor):      # a yaml config spells the weights as a list
+                weight = torch.as_tensor(weight, dtype=torch.float32)
+            if weight.dim() != 1 or weight.numel() < 1:
+                raise ValueError(f"CrossEntropyLoss: weight must be 1-D, one value per class (got shape {tuple(weight.shape)})")
+            weight = weight.detach().float().contiguous()
+            if not bool((torch.isfinite(weight) & (weight >= 0)).all()):
+                raise ValueError("CrossEntropyLoss: every weight must be finite and >= 0")
+        self.ignore_index, self.reduction, self.label_smoothing = ignore_index, reduction, label_smoothing
+        self.register_buffer("weight", weight)
+
+    def _options(self, K: int) -> ops.CrossEntropyOptions:
+        """The options with the buffer as it is now (a ``.to(device)`` moves it): f32 and contiguous, which it already is unless a
+        state dict or a cast changed it."""
+        w = self.weight
+        if w is not None:
+            if w.dim() != 1 or w.numel() != K:
+                raise ValueError(f"CrossEntropyLoss: weight holds {tuple(w.shape)} values for {K} classes")
+            w = w.detach().float().contiguous()
+        return ops.CrossEntropyOptions(self.label_smoothing, self.ignore_index, self.reduction == "mean", w)
+
+    def forward(self, y_pred, y_true: Tensor) -> Tensor:
+        if y_true.is_floating_point() or y_true.is_complex():
+            raise NotImplementedError("gdlhip CrossEntropyLoss implements class-index targets only (got class probabilities)")
+        if isinstance(y_pred, LowresLogits):
+            size = (int(y_pred.size[0]), int(y_pred.size[1]))
+            yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
+            if (FUSE_LOWRES_DICE and ops.cross_entropy_lowres_ok(y_pred.low, size) and y_pred.low.dtype == torch.float32
+                    and tuple(yt.shape[1:]) == size):
+                return _CrossEntropyLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size,
+                                                 self._options(y_pred.low.shape[3]))
+            y_pred = y_pred.materialise()
+        if y_pred.dim() != 4:
+            raise ValueError(f"CrossEntropyLoss: [B, K, H, W] logits expected (got {tuple(y_pred.shape)})")
+        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
+            y_pred = y_pred.float().contiguous()
+        if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
+            y_true = y_true[:, 0]
+        return _CrossEntropy.apply(y_pred, y_true.long().contiguous(), self._options(y_pred.shape[1]))
+
+
 class _Focal(Function):
     """smp FocalLoss(multiclass) on full-resolution NCHW logits; the backward recomputes from the saved logits and reads the
     divisor the forward left on the device."""
@@ -2046,13 +2165,13 @@ class LovaszLoss(nn.Module):
 def reads_lowres(loss, num_classes: int | None = None) -> bool:
     """True for a loss that evaluates itself (and its gradient) from ``LowresLogits``: a task may then ask the model for the heads'
     own maps instead of the resized [B, K, H, W] logits.  gdlhip's multiclass DiceLoss, JaccardLoss, TverskyLoss and FocalLoss,
-    and SoftCrossEntropyLoss; for a one-class model (``num_classes == 1``) also their binary modes, which read the head's
+    SoftCrossEntropyLoss and CrossEntropyLoss (gdlhip's, not torch's); for a one-class model (``num_classes == 1``) also their binary modes, which read the head's
     [B, h, w, 1] map, and SoftBCEWithLogitsLoss (which has no mode: its low-resolution kernels are the one-class ones)."""
     if isinstance(loss, (_DiceFamily, FocalLoss)):
         return loss.mode == "multiclass" or (loss.mode == "binary" and num_classes == 1)
     if isinstance(loss, SoftBCEWithLogitsLoss):
         return num_classes == 1
-    return isinstance(loss, SoftCrossEntropyLoss)
+    return isinstance(loss, (SoftCrossEntropyLoss, CrossEntropyLoss))
 
 
 def predict_mask(logits) -> Tensor:

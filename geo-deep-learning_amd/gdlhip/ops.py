@@ -2353,6 +2353,100 @@ def focal_binary_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], 
     return dlow
 
 
+class CrossEntropyOptions(NamedTuple):
+    """The constructor options of torch's CrossEntropyLoss as the gdl_cross_entropy_* entry points take them: ``label_smoothing`` in
+    [0, 1], ``ignore_index`` (any int64, or None), ``mean`` (reduction "mean": divide by the summed weights of the valid pixels'
+    classes) and the device tensor ``weight`` (f32, one value per class, or None), which the kernels read through its pointer at
+    call time."""
+
+    label_smoothing: float = 0.0
+    ignore_index: int | None = -100
+    mean: bool = True
+    weight: Tensor | None = None
+
+    def c_args(self) -> tuple:
+        """(weight, smooth, has_ignore, ignore, mean) in the order of the C calls"""
+        return (_p(self.weight), float(self.label_smoothing), int(self.ignore_index is not None), int(self.ignore_index or 0),
+                int(bool(self.mean)))
+
+
+def _cross_entropy_check(who: str, logits: Tensor, target: Tensor, want_target: tuple, layout: str, K: int,
+                         options: CrossEntropyOptions) -> None:
+    _soft_ce_check(who, logits, target, want_target, layout)
+    w = options.weight
+    if w is not None:
+        _need_cuda(w)
+        if w.dtype != torch.float32 or not w.is_contiguous() or w.dim() != 1 or w.numel() != K:
+            raise ValueError(f"{who}: weight must be a contiguous 1-D f32 tensor of {K} (classes) values, got {tuple(w.shape)} {w.dtype}")
+
+
+def cross_entropy_fwd(logits: Tensor, target: Tensor, options: CrossEntropyOptions = CrossEntropyOptions()):
+    """torch CrossEntropyLoss on NCHW f32 logits [B,K,H,W] and an int64 target [B,H,W]: ``(loss, norm)``, the 0-dim f32 loss and
+    the divisor the kernels formed on the device (1 / summed weights of the valid pixels, 0 where that sum is 0, or 1 for "sum"),
+    which cross_entropy_bwd reads."""
+    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
+    _cross_entropy_check("cross_entropy", logits, target, (B, H, W), "NCHW", K, options)
+    lib = _lib.load()
+    nbytes = lib.gdl_cross_entropy_workspace(B, K, H * W)
+    loss, norm, ws = _focal_out(logits, nbytes)
+    check(lib.gdl_cross_entropy_fwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
+                                    _stream()), "gdl_cross_entropy_fwd")
+    return loss, norm
+
+
+def cross_entropy_bwd(logits: Tensor, target: Tensor, norm: Tensor, upstream: Tensor | None, grad_scale: float = 1.0,
+                      options: CrossEntropyOptions = CrossEntropyOptions(), out: Tensor | None = None,
+                      accumulate: bool = False) -> Tensor:
+    """d loss / d logits * upstream[0] * grad_scale (softmax recomputed from ``logits``; ``norm`` from cross_entropy_fwd);
+    ``out``/``accumulate`` as soft_ce_bwd."""
+    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
+    _cross_entropy_check("cross_entropy", logits, target, (B, H, W), "NCHW", K, options)
+    _need_cuda(norm, upstream, out)
+    out = _focal_grad_out("cross_entropy_bwd", logits, out)
+    check(_lib.load().gdl_cross_entropy_bwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(norm), _p(upstream), grad_scale,
+                                            _p(out), int(accumulate), _stream()), "gdl_cross_entropy_bwd")
+    return out
+
+
+def cross_entropy_lowres_ok(low: Tensor, size: tuple[int, int]) -> bool:
+    """Shapes gdl_cross_entropy_lowres_* take: those of gdl_soft_ce_lowres_* (K <= 16, an upsample by at most 64 per direction)."""
+    return dice_lowres_ok(low, size)
+
+
+def cross_entropy_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int],
+                             options: CrossEntropyOptions = CrossEntropyOptions()):
+    """The cross-entropy of bilinear(low -> size) vs target [B, H, W] without the full-resolution logits: ``(loss, norm)`` as
+    cross_entropy_fwd."""
+    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
+    _cross_entropy_check("cross_entropy_lowres", low, target, (B, int(size[0]), int(size[1])), "NHWC low-resolution [B, h, w, K]", K,
+                         options)
+    lib = _lib.load()
+    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
+    nbytes = lib.gdl_cross_entropy_lowres_workspace(B, K, dims[4], dims[5])
+    loss, norm, ws = _focal_out(low, nbytes)
+    check(lib.gdl_cross_entropy_lowres_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
+                                           _stream()), "gdl_cross_entropy_lowres_fwd")
+    return loss, norm
+
+
+def cross_entropy_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], norm: Tensor, upstream: Tensor | None,
+                             grad_scale: float = 1.0, options: CrossEntropyOptions = CrossEntropyOptions(),
+                             form: str = "auto") -> Tensor:
+    """d loss / d low [B, h, w, K] * upstream[0] * grad_scale; ``form`` as focal_lowres_bwd."""
+    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
+    _cross_entropy_check("cross_entropy_lowres", low, target, (B, int(size[0]), int(size[1])), "NHWC low-resolution [B, h, w, K]", K,
+                         options)
+    _need_cuda(norm, upstream)
+    dlow = torch.empty_like(low)
+    lib = _lib.load()
+    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
+    nbytes = lib.gdl_cross_entropy_lowres_bwd_workspace(*dims) if form != "gather" else 0
+    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    check(lib.gdl_cross_entropy_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(norm), _p(upstream), grad_scale, _p(dlow),
+                                           _p(ws), nbytes, FOCAL_FORMS[form], _stream()), "gdl_cross_entropy_lowres_bwd")
+    return dlow
+
+
 class SoftBCEOptions(NamedTuple):
     """The constructor options of smp's SoftBCEWithLogitsLoss as the gdl_soft_bce_* entry points take them: ``smooth_factor`` in
     [0, 1] or None, ``ignore_index`` (any int64, or None), ``mean`` (reduction "mean": divide by EVERY element, ignored ones

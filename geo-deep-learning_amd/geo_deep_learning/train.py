@@ -18,6 +18,8 @@ section 2) and are skipped with a log line.  Third-party classes that are absent
 ``segmentation_models_pytorch.losses.FocalLoss`` -> ``gdlhip.nn.FocalLoss``,
 ``segmentation_models_pytorch.losses.LovaszLoss`` -> ``gdlhip.nn.LovaszLoss``,
 ``segmentation_models_pytorch.losses.SoftBCEWithLogitsLoss`` -> ``gdlhip.nn.SoftBCEWithLogitsLoss``.
+torch's own classes are present and are never aliased: a yaml that names ``torch.nn.CrossEntropyLoss`` or
+``torch.nn.BCEWithLogitsLoss`` gets torch's; the HIP losses are chosen by name (``class_path: gdlhip.nn.CrossEntropyLoss``).
 """
 
 from __future__ import annotations

@@ -510,7 +510,8 @@ int gdl_bn_head_bwd_reduce(const void* x, int dtype, const float* dlog, int64_t 
 int gdl_bn_head_bwd_dx(const void* x, int dtype, const float* dlog, void* dx, int64_t P, int C, int K, const float* w,
                        const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
                        const float* dgamma_sum, const float* dbeta_sum, int64_t P_total, gdl_stream_t stream);
-/* bilinear (align_corners=False) NHWC [B,Hi,Wi,K] -> NCHW f32 [B,K,Ho,Wo] logits (dofa.py:89-105) */
+/* bilinear (align_corners=False) NHWC [B,Hi,Wi,K] -> NCHW f32 [B,K,Ho,Wo] logits (dofa.py:89-105); any K >= 1 (up to 16 classes
+ * unrolled, more in a run-time loop), and its gradient */
 int gdl_upsample_logits(const float* in, int B, int Hi, int Wi, int K, float* out, int Ho, int Wo,
                         gdl_stream_t stream);
 int64_t gdl_upsample_logits_bwd_workspace(int B, int K, int Hi, int Wo);
@@ -730,6 +731,43 @@ int gdl_soft_ce_lowres_fused_fwd(const float* low, const int64_t* target, int B,
                                  gdl_stream_t stream);
 int gdl_soft_ce_lowres_fused_bwd(const void* state, int64_t state_bytes, int B, int K, int Hi, int Wi, int Ho, int Wo, int mean,
                                  const float* upstream, float grad_scale, float* dlow, gdl_stream_t stream);
+
+/* torch.nn.CrossEntropyLoss(weight, ignore_index, reduction, label_smoothing) on class-index targets, the loss the reference's own
+ * tests train with (tests/test_notebooks_00quickstart.py:63): NCHW f32 logits [B,K,HW], int64 target [B,HW], any K >= 1.
+ * With e = smooth (label_smoothing, in [0, 1]), w_k = weight[k] (a device pointer to K f32 values read at call time; null: all 1,
+ * and no load), W = sum_k w_k, lse_i = logsumexp_k x_ik and valid_i = (target_i != ignore when has_ignore) && 0 <= target_i < K
+ * (compared as int64; an out-of-range target is treated as ignored -- torch device-asserts -- and never used as an index):
+ *   L_i = (1-e) w_{y_i} (lse_i - x_{i,y_i}) + (e/K) sum_k w_k (lse_i - x_ik), evaluated max-shifted, every term of one sign;
+ *   D = sum_{valid i} w_{y_i};  loss = sum_i L_i * d,  d = 1 / D (mean != 0; d = 0 where D = 0 -- every pixel ignored or of a
+ *   zero-weight class: loss 0, gradient 0, where torch returns NaN) or 1 (mean == 0).  d is formed ON THE DEVICE and written to
+ *   norm[0] (f32), which _bwd reads: nothing synchronises with the host.
+ *   dlogits_ik = upstream[0] (device scalar, may be null) * grad_scale * norm[0] * valid_i *
+ *                (softmax_k(x_i) ((1-e) w_{y_i} + (e/K) W) - (1-e) w_{y_i} [k == y_i] - (e/K) w_k)   (= or += with accumulate).
+ * fwd: f64 per-workgroup partials of sum L_i and of D in `workspace` (gdl_cross_entropy_workspace() bytes, 8-byte aligned), added in
+ * a fixed order: no float atomics, the same bits on every launch.  bwd recomputes the softmax.  K <= 16 from registers. */
+int64_t gdl_cross_entropy_workspace(int B, int K, int64_t HW);
+int gdl_cross_entropy_fwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, const float* weight, float smooth,
+                          int has_ignore, int64_t ignore, int mean, float* loss, float* norm, void* workspace,
+                          int64_t workspace_bytes, gdl_stream_t stream);
+int gdl_cross_entropy_bwd(const float* logits, const int64_t* target, int B, int K, int64_t HW, const float* weight, float smooth,
+                          int has_ignore, int64_t ignore, int mean, const float* norm, const float* upstream, float grad_scale,
+                          float* dlogits, int accumulate, gdl_stream_t stream);
+/* torch.nn.CrossEntropyLoss (reference tests/test_notebooks_00quickstart.py:63; the formula above) of
+ * F.interpolate(head(x), size=(Ho, Wo), mode="bilinear") (dofa.py:89-105) WITHOUT the full-resolution logits: low = the
+ * [B, Hi, Wi, K] f32 map of gdl_head_1x1, target [B, Ho, Wo]; every output pixel's logits are evaluated on the fly with the
+ * expression of gdl_upsample_logits.  K <= 16, upsampling factors up to 64 per direction (as gdl_soft_ce_lowres_*).  _fwd is a
+ * partial-sum pass (ws: gdl_cross_entropy_lowres_workspace() bytes, 8-byte aligned) that also leaves norm[0] = 1 / D; _bwd writes
+ * dlow [B, Hi, Wi, K] = d loss / d low, scaled as above, in the form `form` selects (GDL_FOCAL_AUTO / _GATHER / _TILE as
+ * gdl_focal_lowres_bwd; the tile form: K <= 8 and gdl_cross_entropy_lowres_bwd_workspace() > 0 bytes in ws). */
+int64_t gdl_cross_entropy_lowres_workspace(int B, int K, int Ho, int Wo);
+int gdl_cross_entropy_lowres_fwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo,
+                                 const float* weight, float smooth, int has_ignore, int64_t ignore, int mean, float* loss, float* norm,
+                                 void* ws, int64_t ws_bytes, gdl_stream_t stream);
+int64_t gdl_cross_entropy_lowres_bwd_workspace(int B, int K, int Hi, int Wi, int Ho, int Wo);
+int gdl_cross_entropy_lowres_bwd(const float* low, const int64_t* target, int B, int K, int Hi, int Wi, int Ho, int Wo,
+                                 const float* weight, float smooth, int has_ignore, int64_t ignore, int mean, const float* norm,
+                                 const float* upstream, float grad_scale, float* dlow, float* ws, int64_t ws_bytes, int form,
+                                 gdl_stream_t stream);
 
 /* smp 0.5.0 FocalLoss(mode, alpha, gamma, ignore_index, reduction, reduced_threshold) (losses/focal.py; per-element arithmetic:
  * focal_loss_with_logits in losses/_functional.py), mode "multiclass": NCHW f32 logits [B,K,HW], int64 target [B,HW], any K >= 1.
