@@ -1369,72 +1369,49 @@ def logits_from_low(low: Tensor, size, lowres: bool = False):
     return _UpsampleLogits.apply(low, (int(size[0]), int(size[1])))
 
 
-class _DiceLoss(Function):
-    """smp DiceLoss(mode='multiclass') (configs/dofa_config_RGB.yaml:58-61), and Jaccard / Tversky on the same kernels;
-    ``options``: None (Dice defaults), ops.DiceOptions or ops.OverlapOptions."""
+# ------------------------------------------------------------------ losses
+# The routes of the loss modules below: op stem (ops.<stem>_fwd / ops.<stem>_bwd) -> (number of state tensors the forward returns
+# behind the loss and the backward takes again, what the route computes).  "low": bilinear(low -> size) of a head's NHWC map
+# [B, h, w, K] (one-class: K = 1), forward and backward from that map; every backward recomputes from the saved logits.
+# (SoftCrossEntropyLoss on a low-resolution map is the one route with a rule of its own: _SoftCELowres.)
+_LOSS_ROUTES = {
+    "dice_loss": (1, "smp DiceLoss / JaccardLoss / TverskyLoss (multiclass) on NCHW logits; state: the per-class sums"),
+    "dice_loss_lowres": (1, "the same losses, low"),
+    "dice_binary_loss": (1, "smp DiceLoss / JaccardLoss / TverskyLoss (binary): one logit per target entry"),
+    "dice_binary_lowres": (1, "the same losses, one-class low"),
+    "soft_ce": (0, "smp SoftCrossEntropyLoss on NCHW logits"),
+    "cross_entropy": (1, "torch CrossEntropyLoss on NCHW logits; state: the divisor the forward left on the device"),
+    "cross_entropy_lowres": (1, "torch CrossEntropyLoss, low"),
+    "focal": (1, "smp FocalLoss (multiclass) on NCHW logits; state: the divisor the forward left on the device"),
+    "focal_binary": (1, "smp FocalLoss (binary): one logit per target entry, positive where the target is 1"),
+    "focal_lowres": (1, "smp FocalLoss (multiclass), low"),
+    "focal_binary_lowres": (1, "smp FocalLoss (binary), one-class low"),
+    "soft_bce": (0, "smp SoftBCEWithLogitsLoss on NCHW logits and an int64 or f32 target of the same numel"),
+    "soft_bce_lowres": (0, "smp SoftBCEWithLogitsLoss, one-class low"),
+    "lovasz": (2, "smp LovaszLoss (multiclass) on NCHW logits; state: the Jaccard coefficients in pixel order, the segments' weights"),
+    "lovasz_binary": (2, "smp LovaszLoss (binary): one logit per target entry, positive where the target is 1"),
+}
+
+
+class _Loss(Function):
+    """The autograd node of every route in _LOSS_ROUTES: ``ops.<stem>_fwd(x, target[, size][, eps], options=)`` returns the loss
+    and the route's state tensors; ``ops.<stem>_bwd(x, target[, size], *state, g, 1.0[, eps], options=)`` is d loss / d x.
+    ``size`` (the low-resolution routes) and ``eps`` (the Dice family) are None where the ops do not take them."""
 
     @staticmethod
-    def forward(ctx, logits, target, eps, options=None):
-        loss, sums = ops.dice_loss_fwd(logits, target, eps, options=options)
-        ctx.save_for_backward(logits, target, sums)
-        ctx.eps, ctx.options = eps, options
+    def forward(ctx, stem, x, target, options, size, eps):
+        out = getattr(ops, stem + "_fwd")(x, target, *(a for a in (size, eps) if a is not None), options=options)
+        loss, *state = out if _LOSS_ROUTES[stem][0] else (out,)
+        ctx.save_for_backward(x, target, *state)
+        ctx.stem, ctx.options, ctx.size, ctx.eps = stem, options, size, eps
         return loss
 
     @staticmethod
     def backward(ctx, g):
-        logits, target, sums = ctx.saved_tensors
-        return ops.dice_loss_bwd(logits, target, sums, g.contiguous().float(), 1.0, ctx.eps, options=ctx.options), None, None, None
-
-
-class _DiceLowres(Function):
-    """The same losses of bilinear(low -> size), forward and backward from the low-resolution map."""
-
-    @staticmethod
-    def forward(ctx, low, target, size, eps, options=None):
-        loss, sums = ops.dice_loss_lowres_fwd(low, target, size, eps, options=options)
-        ctx.save_for_backward(low, target, sums)
-        ctx.size, ctx.eps, ctx.options = size, eps, options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        low, target, sums = ctx.saved_tensors
-        dlow = ops.dice_loss_lowres_bwd(low, target, ctx.size, sums, g.contiguous().float(), 1.0, ctx.eps, options=ctx.options)
-        return dlow, None, None, None, None
-
-
-class _DiceBinaryLoss(Function):
-    """smp DiceLoss(mode='binary') (configs/unetplus_config_RGB.yaml:40-47, num_classes 1), and Jaccard / Tversky (binary)."""
-
-    @staticmethod
-    def forward(ctx, logits, target, eps, options=None):
-        loss, sums = ops.dice_binary_loss_fwd(logits, target, eps, options=options)
-        ctx.save_for_backward(logits, target, sums)
-        ctx.eps, ctx.options = eps, options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, target, sums = ctx.saved_tensors
-        return (ops.dice_binary_loss_bwd(logits, target, sums, g.contiguous().float(), 1.0, ctx.eps, options=ctx.options),
-                None, None, None)
-
-
-class _DiceBinaryLowres(Function):
-    """The binary losses of bilinear(low -> size) for a one-class head's map [B, h, w, 1], forward and backward from that map."""
-
-    @staticmethod
-    def forward(ctx, low, target, size, eps, options=None):
-        loss, sums = ops.dice_binary_lowres_fwd(low, target, size, eps, options=options)
-        ctx.save_for_backward(low, target, sums)
-        ctx.size, ctx.eps, ctx.options = size, eps, options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        low, target, sums = ctx.saved_tensors
-        dlow = ops.dice_binary_lowres_bwd(low, target, ctx.size, sums, g.contiguous().float(), 1.0, ctx.eps, options=ctx.options)
-        return dlow, None, None, None, None
+        x, target, *state = ctx.saved_tensors
+        size, eps = (() if a is None else (a,) for a in (ctx.size, ctx.eps))
+        dx = getattr(ops, ctx.stem + "_bwd")(x, target, *size, *state, g.contiguous().float(), 1.0, *eps, options=ctx.options)
+        return None, dx, None, None, None, None
 
 
 def _binary_lowres_ok(low: Tensor, size, yt: Tensor) -> bool:
@@ -1442,6 +1419,56 @@ def _binary_lowres_ok(low: Tensor, size, yt: Tensor) -> bool:
     faster route (ops.binary_lowres_pays: the measured factors; a larger one materialises, as every other excluded case)."""
     return (FUSE_LOWRES_DICE and low.dim() == 4 and low.shape[3] == 1 and low.dtype == torch.float32 and ops.binary_lowres_pays(low, size)
             and yt.dim() == 3 and tuple(yt.shape[1:]) == size)
+
+
+def _loss_input(y_pred, y_true: Tensor, lowres: str | None, squeeze: bool):
+    """The start of every loss's forward: ``(x, target, size)``.  ``lowres``: the low-resolution kernels the loss has for this
+    call, "multiclass" ([B, h, w, K] maps), "binary" (the one-class head's [B, h, w, 1]) or None.  Where ``y_pred`` is a
+    LowresLogits those kernels take, ``x`` is its contiguous map, ``target`` the [B, H, W] view of ``y_true`` and ``size`` the
+    image size.  Everything else gets ``size`` None and ``x`` the contiguous f32 logits (a LowresLogits materialised), with an
+    un-squeezed [B, 1, H, W] ``y_true`` viewed as [B, H, W] if ``squeeze`` (smp views the target as [B, -1]: the same)."""
+    if isinstance(y_pred, LowresLogits):
+        # a training step's not-yet-resized logits: the loss (and its gradient) straight from the low-resolution map
+        low, size = y_pred.low, (int(y_pred.size[0]), int(y_pred.size[1]))
+        yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
+        if lowres == "multiclass":
+            ok = FUSE_LOWRES_DICE and ops.dice_lowres_ok(low, size) and low.dtype == torch.float32 and tuple(yt.shape[1:]) == size
+        else:
+            ok = lowres == "binary" and _binary_lowres_ok(low, size, yt) and low.shape[0] == yt.shape[0]
+        if ok:
+            return low.contiguous(), yt, size
+        y_pred = y_pred.materialise()
+    if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
+        y_pred = y_pred.float().contiguous()
+    if squeeze and y_true.dim() == y_pred.dim() >= 2 and y_true.shape[1] == 1:
+        y_true = y_true[:, 0]
+    return y_pred, y_true, None
+
+
+def _checked_ignore_index(name: str, ignore_index):
+    """``ignore_index`` as an int, or None (no pixel is ignored)."""
+    if ignore_index is None:
+        return None
+    if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
+        raise ValueError(f"{name}: ignore_index must be an int64 value or None (got {ignore_index!r})")
+    return int(ignore_index)
+
+
+def _check_mode(name: str, mode, unimplemented: tuple | None = ("multilabel",)) -> None:
+    """A mode smp has and gdlhip does not (``unimplemented``; None: any other) is a NotImplementedError, an unknown one a
+    ValueError."""
+    if mode not in ("multiclass", "binary"):
+        if unimplemented is None or mode in unimplemented:
+            raise NotImplementedError(f"gdlhip {name} implements mode='multiclass' and mode='binary' (got {mode!r})")
+        raise ValueError(f"{name}: unknown mode {mode!r}")
+
+
+def _check_reduction(name: str, reduction, unimplemented: tuple = ("none",)) -> None:
+    """As _check_mode, for ``reduction``."""
+    if reduction not in ("mean", "sum"):
+        if reduction in unimplemented:
+            raise NotImplementedError(f"gdlhip {name} implements reduction='mean' and 'sum' (got {reduction!r})")
+        raise ValueError(f"{name}: unknown reduction {reduction!r}")
 
 
 class _DiceFamily(nn.Module):
@@ -1452,9 +1479,7 @@ class _DiceFamily(nn.Module):
     def _check_common(self, mode, classes, from_logits, ignore_index, **floats):
         """The validated (classes, ignore_index); ``floats``: named values that must be finite."""
         name = type(self).__name__
-        if mode not in ("multiclass", "binary"):
-            msg = f"gdlhip {name} implements mode='multiclass' and mode='binary' (got {mode!r})"
-            raise NotImplementedError(msg)
+        _check_mode(name, mode, None)
         if not from_logits:
             raise NotImplementedError(f"gdlhip {name} takes logits (from_logits=True); from_logits=False is not implemented")
         if classes is not None:
@@ -1463,10 +1488,7 @@ class _DiceFamily(nn.Module):
                 raise ValueError(f"{name}: classes must be a non-empty list of distinct class indices >= 0 (got {classes})")
             if mode == "binary" and classes != (0,):
                 raise ValueError(f"{name}(binary) has the single class 0: classes must be None or [0] (got {list(classes)})")
-        if ignore_index is not None:
-            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
-                raise ValueError(f"{name}: ignore_index must be an int64 value or None (got {ignore_index!r})")
-            ignore_index = int(ignore_index)
+        ignore_index = _checked_ignore_index(name, ignore_index)
         for key, v in floats.items():
             if not math.isfinite(v):
                 raise ValueError(f"{name}: {key} must be finite (got {v})")
@@ -1477,28 +1499,18 @@ class _DiceFamily(nn.Module):
             raise ValueError(f"{type(self).__name__}: classes {list(self.classes)} out of range for {K} classes")
 
     def forward(self, y_pred, y_true: Tensor) -> Tensor:
-        if isinstance(y_pred, LowresLogits):
-            # a training step's not-yet-resized logits: the loss (and its gradient) straight from the low-resolution map
-            size = (int(y_pred.size[0]), int(y_pred.size[1]))
-            yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
-            if (self.mode == "multiclass" and FUSE_LOWRES_DICE and ops.dice_lowres_ok(y_pred.low, size)
-                    and y_pred.low.dtype == torch.float32 and tuple(yt.shape[1:]) == size):
-                self._check_classes(y_pred.low.shape[3])
-                return _DiceLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.eps, self.options)
-            if self.mode == "binary" and _binary_lowres_ok(y_pred.low, size, yt) and y_pred.low.shape[0] == yt.shape[0]:
-                return _DiceBinaryLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.eps, self.options)
-            y_pred = y_pred.materialise()
-        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
-            y_pred = y_pred.float().contiguous()
-        if self.mode == "binary":
-            if y_pred.shape[0] != y_true.shape[0] or y_pred.numel() != y_true.numel():
-                msg = f"{type(self).__name__}(binary): y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} do not match"
-                raise ValueError(msg)
-            return _DiceBinaryLoss.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
-        if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
-            y_true = y_true[:, 0]          # smp views the target as [B, -1]: an un-squeezed [B,1,H,W] mask is the same
-        self._check_classes(y_pred.shape[1])
-        return _DiceLoss.apply(y_pred, y_true.long().contiguous(), self.eps, self.options)
+        binary = self.mode == "binary"
+        x, y_true, size = _loss_input(y_pred, y_true, self.mode, squeeze=not binary)
+        if not binary:
+            self._check_classes(x.shape[1 if size is None else 3])
+        elif size is None and (x.shape[0] != y_true.shape[0] or x.numel() != y_true.numel()):
+            msg = f"{type(self).__name__}(binary): y_pred {tuple(x.shape)} and y_true {tuple(y_true.shape)} do not match"
+            raise ValueError(msg)
+        if binary:
+            stem = "dice_binary_loss" if size is None else "dice_binary_lowres"
+        else:
+            stem = "dice_loss" if size is None else "dice_loss_lowres"
+        return _Loss.apply(stem, x, y_true.long().contiguous(), self.options, size, self.eps)
 
 
 class DiceLoss(_DiceFamily):
@@ -1590,22 +1602,6 @@ class TverskyLoss(_DiceFamily):
         self.options = ops.OverlapOptions("tversky", ignore_index, smooth, self.log_loss, classes, alpha, beta, gamma)
 
 
-class _SoftCE(Function):
-    """smp SoftCrossEntropyLoss on full-resolution NCHW logits; the backward recomputes the softmax from the saved logits."""
-
-    @staticmethod
-    def forward(ctx, logits, target, options):
-        loss = ops.soft_ce_fwd(logits, target, options)
-        ctx.save_for_backward(logits, target)
-        ctx.options = options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, target = ctx.saved_tensors
-        return ops.soft_ce_bwd(logits, target, g.contiguous().float(), 1.0, ctx.options), None, None
-
-
 class _SoftCELowres(Function):
     """smp SoftCrossEntropyLoss of bilinear(low -> size) from the low-resolution map.  ``fused``: the forward also leaves the
     unscaled patches of d(low) behind and the backward only reduces them (ops.soft_ce_lowres_fwd)."""
@@ -1650,71 +1646,23 @@ class SoftCrossEntropyLoss(nn.Module):
     def __init__(self, reduction: str = "mean", smooth_factor: float | None = None, ignore_index: int | None = -100,
                  dim: int = 1) -> None:
         super().__init__()
-        if reduction not in ("mean", "sum"):
-            if reduction == "none":
-                raise NotImplementedError("gdlhip SoftCrossEntropyLoss implements reduction='mean' and 'sum' (got 'none')")
-            raise ValueError(f"SoftCrossEntropyLoss: unknown reduction {reduction!r}")
+        _check_reduction("SoftCrossEntropyLoss", reduction)
         if dim != 1:
             raise NotImplementedError(f"gdlhip SoftCrossEntropyLoss takes the class dimension at dim=1 (got dim={dim})")
         eps = 0.0 if smooth_factor is None else float(smooth_factor)
         if not math.isfinite(eps) or not 0.0 <= eps <= 1.0:
             raise ValueError(f"SoftCrossEntropyLoss: smooth_factor must be a finite value in [0, 1] (got {smooth_factor!r})")
-        if ignore_index is not None:
-            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
-                raise ValueError(f"SoftCrossEntropyLoss: ignore_index must be an int64 value or None (got {ignore_index!r})")
-            ignore_index = int(ignore_index)
+        ignore_index = _checked_ignore_index("SoftCrossEntropyLoss", ignore_index)
         self.reduction, self.smooth_factor, self.ignore_index, self.dim = reduction, smooth_factor, ignore_index, dim
         self.options = ops.SoftCEOptions(eps, ignore_index, reduction == "mean")
 
     def forward(self, y_pred, y_true: Tensor) -> Tensor:
-        if isinstance(y_pred, LowresLogits):
-            size = (int(y_pred.size[0]), int(y_pred.size[1]))
-            yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
-            if (FUSE_LOWRES_DICE and ops.soft_ce_lowres_ok(y_pred.low, size) and y_pred.low.dtype == torch.float32
-                    and tuple(yt.shape[1:]) == size):
-                return _SoftCELowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.options, SOFT_CE_LOWRES_FUSED)
-            y_pred = y_pred.materialise()
-        if y_pred.dim() != 4:
-            raise ValueError(f"SoftCrossEntropyLoss: [B, K, H, W] logits expected (got {tuple(y_pred.shape)})")
-        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
-            y_pred = y_pred.float().contiguous()
-        if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
-            y_true = y_true[:, 0]
-        return _SoftCE.apply(y_pred, y_true.long().contiguous(), self.options)
-
-
-class _CrossEntropy(Function):
-    """torch CrossEntropyLoss on full-resolution NCHW logits; the backward recomputes the softmax from the saved logits and reads
-    the divisor the forward left on the device."""
-
-    @staticmethod
-    def forward(ctx, logits, target, options):
-        loss, norm = ops.cross_entropy_fwd(logits, target, options)
-        ctx.save_for_backward(logits, target, norm)
-        ctx.options = options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, target, norm = ctx.saved_tensors
-        return ops.cross_entropy_bwd(logits, target, norm, g.contiguous().float(), 1.0, ctx.options), None, None
-
-
-class _CrossEntropyLowres(Function):
-    """torch CrossEntropyLoss of bilinear(low -> size), forward and backward from the low-resolution map."""
-
-    @staticmethod
-    def forward(ctx, low, target, size, options):
-        loss, norm = ops.cross_entropy_lowres_fwd(low, target, size, options)
-        ctx.save_for_backward(low, target, norm)
-        ctx.size, ctx.options = size, options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        low, target, norm = ctx.saved_tensors
-        dlow = ops.cross_entropy_lowres_bwd(low, target, ctx.size, norm, g.contiguous().float(), 1.0, ctx.options)
-        return dlow, None, None, None
+        x, y_true, size = _loss_input(y_pred, y_true, "multiclass", squeeze=True)
+        if size is not None:
+            return _SoftCELowres.apply(x, y_true.long().contiguous(), size, self.options, SOFT_CE_LOWRES_FUSED)
+        if x.dim() != 4:
+            raise ValueError(f"SoftCrossEntropyLoss: [B, K, H, W] logits expected (got {tuple(x.shape)})")
+        return _Loss.apply("soft_ce", x, y_true.long().contiguous(), self.options, None, None)
 
 
 class CrossEntropyLoss(nn.Module):
@@ -1750,17 +1698,11 @@ class CrossEntropyLoss(nn.Module):
         super().__init__()
         if size_average is not None or reduce is not None:
             raise NotImplementedError("gdlhip CrossEntropyLoss implements reduction= only (size_average and reduce must be None)")
-        if reduction not in ("mean", "sum"):
-            if reduction == "none":
-                raise NotImplementedError("gdlhip CrossEntropyLoss implements reduction='mean' and 'sum' (got 'none')")
-            raise ValueError(f"CrossEntropyLoss: unknown reduction {reduction!r}")
+        _check_reduction("CrossEntropyLoss", reduction)
         label_smoothing = float(label_smoothing)
         if not 0.0 <= label_smoothing <= 1.0:      # (NaN and the infinities fail the comparison)
             raise ValueError(f"CrossEntropyLoss: label_smoothing must be a finite value in [0, 1] (got {label_smoothing})")
-        if ignore_index is not None:      # (None, which torch does not take: no pixel is ignored)
-            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
-                raise ValueError(f"CrossEntropyLoss: ignore_index must be an int64 value or None (got {ignore_index!r})")
-            ignore_index = int(ignore_index)
+        ignore_index = _checked_ignore_index("CrossEntropyLoss", ignore_index)      # (None, which torch does not take: no pixel is ignored)
         if weight is not None:
             if not isinstance(weight, Tensor):      # a yaml config spells the weights as a list
                 weight = torch.as_tensor(weight, dtype=torch.float32)
@@ -1785,86 +1727,11 @@ class CrossEntropyLoss(nn.Module):
     def forward(self, y_pred, y_true: Tensor) -> Tensor:
         if y_true.is_floating_point() or y_true.is_complex():
             raise NotImplementedError("gdlhip CrossEntropyLoss implements class-index targets only (got class probabilities)")
-        if isinstance(y_pred, LowresLogits):
-            size = (int(y_pred.size[0]), int(y_pred.size[1]))
-            yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
-            if (FUSE_LOWRES_DICE and ops.cross_entropy_lowres_ok(y_pred.low, size) and y_pred.low.dtype == torch.float32
-                    and tuple(yt.shape[1:]) == size):
-                return _CrossEntropyLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size,
-                                                 self._options(y_pred.low.shape[3]))
-            y_pred = y_pred.materialise()
-        if y_pred.dim() != 4:
-            raise ValueError(f"CrossEntropyLoss: [B, K, H, W] logits expected (got {tuple(y_pred.shape)})")
-        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
-            y_pred = y_pred.float().contiguous()
-        if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
-            y_true = y_true[:, 0]
-        return _CrossEntropy.apply(y_pred, y_true.long().contiguous(), self._options(y_pred.shape[1]))
-
-
-class _Focal(Function):
-    """smp FocalLoss(multiclass) on full-resolution NCHW logits; the backward recomputes from the saved logits and reads the
-    divisor the forward left on the device."""
-
-    @staticmethod
-    def forward(ctx, logits, target, options):
-        loss, norm = ops.focal_fwd(logits, target, options)
-        ctx.save_for_backward(logits, target, norm)
-        ctx.options = options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, target, norm = ctx.saved_tensors
-        return ops.focal_bwd(logits, target, norm, g.contiguous().float(), 1.0, ctx.options), None, None
-
-
-class _FocalBinary(Function):
-    """smp FocalLoss(binary): one logit per target entry, positive where the target is 1."""
-
-    @staticmethod
-    def forward(ctx, logits, target, options):
-        loss, norm = ops.focal_binary_fwd(logits, target, options)
-        ctx.save_for_backward(logits, target, norm)
-        ctx.options = options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, target, norm = ctx.saved_tensors
-        return ops.focal_binary_bwd(logits, target, norm, g.contiguous().float(), 1.0, ctx.options), None, None
-
-
-class _FocalLowres(Function):
-    """smp FocalLoss(multiclass) of bilinear(low -> size), forward and backward from the low-resolution map."""
-
-    @staticmethod
-    def forward(ctx, low, target, size, options):
-        loss, norm = ops.focal_lowres_fwd(low, target, size, options)
-        ctx.save_for_backward(low, target, norm)
-        ctx.size, ctx.options = size, options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        low, target, norm = ctx.saved_tensors
-        return ops.focal_lowres_bwd(low, target, ctx.size, norm, g.contiguous().float(), 1.0, ctx.options), None, None, None
-
-
-class _FocalBinaryLowres(Function):
-    """smp FocalLoss(binary) of bilinear(low -> size) for a one-class head's map [B, h, w, 1], forward and backward from that map."""
-
-    @staticmethod
-    def forward(ctx, low, target, size, options):
-        loss, norm = ops.focal_binary_lowres_fwd(low, target, size, options)
-        ctx.save_for_backward(low, target, norm)
-        ctx.size, ctx.options = size, options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        low, target, norm = ctx.saved_tensors
-        return ops.focal_binary_lowres_bwd(low, target, ctx.size, norm, g.contiguous().float(), 1.0, ctx.options), None, None, None
+        x, y_true, size = _loss_input(y_pred, y_true, "multiclass", squeeze=True)
+        if size is None and x.dim() != 4:
+            raise ValueError(f"CrossEntropyLoss: [B, K, H, W] logits expected (got {tuple(x.shape)})")
+        stem, K = ("cross_entropy", x.shape[1]) if size is None else ("cross_entropy_lowres", x.shape[3])
+        return _Loss.apply(stem, x, y_true.long().contiguous(), self._options(K), size, None)
 
 
 class FocalLoss(nn.Module):
@@ -1896,16 +1763,10 @@ class FocalLoss(nn.Module):
     def __init__(self, mode: str, alpha: float | None = None, gamma: float | None = 2.0, ignore_index: int | None = None,
                  reduction: str | None = "mean", normalized: bool = False, reduced_threshold: float | None = None) -> None:
         super().__init__()
-        if mode not in ("multiclass", "binary"):
-            if mode == "multilabel":
-                raise NotImplementedError("gdlhip FocalLoss implements mode='multiclass' and mode='binary' (got 'multilabel')")
-            raise ValueError(f"FocalLoss: unknown mode {mode!r}")
+        _check_mode("FocalLoss", mode)
         if normalized:
             raise NotImplementedError("gdlhip FocalLoss implements normalized=False only")
-        if reduction not in ("mean", "sum"):
-            if reduction in ("none", "batchwise_mean"):
-                raise NotImplementedError(f"gdlhip FocalLoss implements reduction='mean' and 'sum' (got {reduction!r})")
-            raise ValueError(f"FocalLoss: unknown reduction {reduction!r}")
+        _check_reduction("FocalLoss", reduction, ("none", "batchwise_mean"))
         gamma = float(gamma)
         if not math.isfinite(gamma) or gamma < 0.0:
             raise ValueError(f"FocalLoss: gamma must be finite and >= 0 (got {gamma})")
@@ -1917,69 +1778,21 @@ class FocalLoss(nn.Module):
             reduced_threshold = float(reduced_threshold)
             if not 0.0 < reduced_threshold <= 1.0:
                 raise ValueError(f"FocalLoss: reduced_threshold must be None or in (0, 1] (got {reduced_threshold})")
-        if ignore_index is not None:
-            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
-                raise ValueError(f"FocalLoss: ignore_index must be an int64 value or None (got {ignore_index!r})")
-            ignore_index = int(ignore_index)
+        ignore_index = _checked_ignore_index("FocalLoss", ignore_index)
         self.mode, self.alpha, self.gamma, self.ignore_index = mode, alpha, gamma, ignore_index
         self.reduction, self.normalized, self.reduced_threshold = reduction, False, reduced_threshold
         self.options = ops.FocalOptions(gamma, alpha, ignore_index, reduction == "mean", reduced_threshold)
 
     def forward(self, y_pred, y_true: Tensor) -> Tensor:
-        if isinstance(y_pred, LowresLogits):
-            size = (int(y_pred.size[0]), int(y_pred.size[1]))
-            yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
-            if (self.mode == "multiclass" and FUSE_LOWRES_DICE and ops.focal_lowres_ok(y_pred.low, size)
-                    and y_pred.low.dtype == torch.float32 and tuple(yt.shape[1:]) == size):
-                return _FocalLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.options)
-            if self.mode == "binary" and _binary_lowres_ok(y_pred.low, size, yt) and y_pred.low.shape[0] == yt.shape[0]:
-                return _FocalBinaryLowres.apply(y_pred.low.contiguous(), yt.long().contiguous(), size, self.options)
-            y_pred = y_pred.materialise()
-        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
-            y_pred = y_pred.float().contiguous()
-        if self.mode == "binary":
-            if y_pred.shape[0] != y_true.shape[0] or y_pred.numel() != y_true.numel():
-                raise ValueError(f"FocalLoss(binary): y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} do not match")
-            return _FocalBinary.apply(y_pred, y_true.long().contiguous(), self.options)
-        if y_pred.dim() != 4:
-            raise ValueError(f"FocalLoss(multiclass): [B, K, H, W] logits expected (got {tuple(y_pred.shape)})")
-        if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
-            y_true = y_true[:, 0]
-        return _Focal.apply(y_pred, y_true.long().contiguous(), self.options)
-
-
-class _SoftBCE(Function):
-    """smp SoftBCEWithLogitsLoss on full-resolution NCHW logits and an int64 or f32 target of the same numel; the backward
-    recomputes from the saved logits and target."""
-
-    @staticmethod
-    def forward(ctx, logits, target, options):
-        loss = ops.soft_bce_fwd(logits, target, options)
-        ctx.save_for_backward(logits, target)
-        ctx.options = options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, target = ctx.saved_tensors
-        return ops.soft_bce_bwd(logits, target, g.contiguous().float(), 1.0, ctx.options), None, None
-
-
-class _SoftBCELowres(Function):
-    """smp SoftBCEWithLogitsLoss of bilinear(low -> size) for a one-class head's map [B, h, w, 1], forward and backward from that
-    map."""
-
-    @staticmethod
-    def forward(ctx, low, target, size, options):
-        loss = ops.soft_bce_lowres_fwd(low, target, size, options)
-        ctx.save_for_backward(low, target)
-        ctx.size, ctx.options = size, options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        low, target = ctx.saved_tensors
-        return ops.soft_bce_lowres_bwd(low, target, ctx.size, g.contiguous().float(), 1.0, ctx.options), None, None, None
+        binary = self.mode == "binary"
+        x, y_true, size = _loss_input(y_pred, y_true, self.mode, squeeze=not binary)
+        if size is None:
+            if binary and (x.shape[0] != y_true.shape[0] or x.numel() != y_true.numel()):
+                raise ValueError(f"FocalLoss(binary): y_pred {tuple(x.shape)} and y_true {tuple(y_true.shape)} do not match")
+            if not binary and x.dim() != 4:
+                raise ValueError(f"FocalLoss(multiclass): [B, K, H, W] logits expected (got {tuple(x.shape)})")
+        stem = ("focal_binary" if binary else "focal") + ("" if size is None else "_lowres")
+        return _Loss.apply(stem, x, y_true.long().contiguous(), self.options, size, None)
 
 
 class SoftBCEWithLogitsLoss(nn.Module):
@@ -2013,18 +1826,12 @@ class SoftBCEWithLogitsLoss(nn.Module):
     def __init__(self, weight: Tensor | None = None, ignore_index: int | None = -100, reduction: str = "mean",
                  smooth_factor: float | None = None, pos_weight: Tensor | None = None) -> None:
         super().__init__()
-        if reduction not in ("mean", "sum"):
-            if reduction == "none":
-                raise NotImplementedError("gdlhip SoftBCEWithLogitsLoss implements reduction='mean' and 'sum' (got 'none')")
-            raise ValueError(f"SoftBCEWithLogitsLoss: unknown reduction {reduction!r}")
+        _check_reduction("SoftBCEWithLogitsLoss", reduction)
         if smooth_factor is not None:
             smooth_factor = float(smooth_factor)
             if not 0.0 <= smooth_factor <= 1.0:      # (NaN and the infinities fail the comparison)
                 raise ValueError(f"SoftBCEWithLogitsLoss: smooth_factor must be None or in [0, 1] (got {smooth_factor})")
-        if ignore_index is not None:
-            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
-                raise ValueError(f"SoftBCEWithLogitsLoss: ignore_index must be an int64 value or None (got {ignore_index!r})")
-            ignore_index = int(ignore_index)
+        ignore_index = _checked_ignore_index("SoftBCEWithLogitsLoss", ignore_index)
         for name, t in (("weight", weight), ("pos_weight", pos_weight)):
             if t is None:
                 continue
@@ -2052,53 +1859,14 @@ class SoftBCEWithLogitsLoss(nn.Module):
         return y_true.contiguous()
 
     def forward(self, y_pred, y_true: Tensor) -> Tensor:
-        options = self._options()
-        if isinstance(y_pred, LowresLogits):
-            size = (int(y_pred.size[0]), int(y_pred.size[1]))
-            yt = y_true[:, 0] if y_true.dim() == 4 and y_true.shape[1] == 1 else y_true
-            if _binary_lowres_ok(y_pred.low, size, yt) and y_pred.low.shape[0] == yt.shape[0]:
-                return _SoftBCELowres.apply(y_pred.low.contiguous(), self._target(yt), size, options)
-            y_pred = y_pred.materialise()
-        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
-            y_pred = y_pred.float().contiguous()
-        if y_pred.dim() < 1 or y_pred.shape[0] != y_true.shape[0] or y_pred.numel() != y_true.numel():
-            raise ValueError(f"SoftBCEWithLogitsLoss: y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} do not match")
-        if y_pred.dim() != 4:      # no channel dimension to speak of: one "channel" of everything behind the batch
-            y_pred = y_pred.reshape(y_pred.shape[0], 1, 1, -1)
-        return _SoftBCE.apply(y_pred, self._target(y_true), options)
-
-
-class _Lovasz(Function):
-    """smp LovaszLoss(multiclass) on full-resolution NCHW logits; the forward leaves the Jaccard coefficients in pixel order and the
-    segments' weights on the device, the backward recomputes the softmax from the saved logits."""
-
-    @staticmethod
-    def forward(ctx, logits, target, options):
-        loss, coef, norm = ops.lovasz_fwd(logits, target, options)
-        ctx.save_for_backward(logits, target, coef, norm)
-        ctx.options = options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, target, coef, norm = ctx.saved_tensors
-        return ops.lovasz_bwd(logits, target, coef, norm, g.contiguous().float(), 1.0, ctx.options), None, None
-
-
-class _LovaszBinary(Function):
-    """smp LovaszLoss(binary): one logit per target entry, positive where the target is 1."""
-
-    @staticmethod
-    def forward(ctx, logits, target, options):
-        loss, coef, norm = ops.lovasz_binary_fwd(logits, target, options)
-        ctx.save_for_backward(logits, target, coef, norm)
-        ctx.options = options
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        logits, target, coef, norm = ctx.saved_tensors
-        return ops.lovasz_binary_bwd(logits, target, coef, norm, g.contiguous().float(), 1.0, ctx.options), None, None
+        x, y_true, size = _loss_input(y_pred, y_true, "binary", squeeze=False)
+        if size is not None:
+            return _Loss.apply("soft_bce_lowres", x, self._target(y_true), self._options(), size, None)
+        if x.dim() < 1 or x.shape[0] != y_true.shape[0] or x.numel() != y_true.numel():
+            raise ValueError(f"SoftBCEWithLogitsLoss: y_pred {tuple(x.shape)} and y_true {tuple(y_true.shape)} do not match")
+        if x.dim() != 4:      # no channel dimension to speak of: one "channel" of everything behind the batch
+            x = x.reshape(x.shape[0], 1, 1, -1)
+        return _Loss.apply("soft_bce", x, self._target(y_true), self._options(), None, None)
 
 
 class LovaszLoss(nn.Module):
@@ -2133,33 +1901,21 @@ class LovaszLoss(nn.Module):
 
     def __init__(self, mode: str, per_image: bool = False, ignore_index: int | None = None, from_logits: bool = True) -> None:
         super().__init__()
-        if mode not in ("multiclass", "binary"):
-            if mode == "multilabel":
-                raise NotImplementedError("gdlhip LovaszLoss implements mode='multiclass' and mode='binary' (got 'multilabel')")
-            raise ValueError(f"LovaszLoss: unknown mode {mode!r}")
+        _check_mode("LovaszLoss", mode)
         if not from_logits:
             raise NotImplementedError("gdlhip LovaszLoss implements from_logits=True only")
-        if ignore_index is not None:
-            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not -2**63 <= int(ignore_index) < 2**63:
-                raise ValueError(f"LovaszLoss: ignore_index must be an int64 value or None (got {ignore_index!r})")
-            ignore_index = int(ignore_index)
+        ignore_index = _checked_ignore_index("LovaszLoss", ignore_index)
         self.mode, self.per_image, self.ignore_index, self.from_logits = mode, bool(per_image), ignore_index, True
         self.options = ops.LovaszOptions(self.per_image, ignore_index)
 
     def forward(self, y_pred, y_true: Tensor) -> Tensor:
-        if isinstance(y_pred, LowresLogits):
-            y_pred = y_pred.materialise()
-        if y_pred.dtype != torch.float32 or not y_pred.is_contiguous():
-            y_pred = y_pred.float().contiguous()
-        if self.mode == "binary":
-            if y_pred.dim() < 1 or y_pred.shape[0] != y_true.shape[0] or y_pred.numel() != y_true.numel():
-                raise ValueError(f"LovaszLoss(binary): y_pred {tuple(y_pred.shape)} and y_true {tuple(y_true.shape)} do not match")
-            return _LovaszBinary.apply(y_pred, y_true.long().contiguous(), self.options)
-        if y_pred.dim() != 4:
-            raise ValueError(f"LovaszLoss(multiclass): [B, K, H, W] logits expected (got {tuple(y_pred.shape)})")
-        if y_true.dim() == y_pred.dim() and y_true.shape[1] == 1:
-            y_true = y_true[:, 0]
-        return _Lovasz.apply(y_pred, y_true.long().contiguous(), self.options)
+        binary = self.mode == "binary"
+        x, y_true, _ = _loss_input(y_pred, y_true, None, squeeze=not binary)      # (no low-resolution kernels: always the logits)
+        if binary and (x.dim() < 1 or x.shape[0] != y_true.shape[0] or x.numel() != y_true.numel()):
+            raise ValueError(f"LovaszLoss(binary): y_pred {tuple(x.shape)} and y_true {tuple(y_true.shape)} do not match")
+        if not binary and x.dim() != 4:
+            raise ValueError(f"LovaszLoss(multiclass): [B, K, H, W] logits expected (got {tuple(x.shape)})")
+        return _Loss.apply("lovasz_binary" if binary else "lovasz", x, y_true.long().contiguous(), self.options, None, None)
 
 
 def reads_lowres(loss, num_classes: int | None = None) -> bool:

@@ -1961,7 +1961,55 @@ class OverlapOptions(NamedTuple):
 
 
 # the `form` argument of the low-resolution backwards that have two
-FOCAL_FORMS = {"auto": _lib.FOCAL_AUTO, "gather": _lib.FOCAL_GATHER, "tile": _lib.FOCAL_TILE}
+LOWRES_BWD_FORMS = {"auto": _lib.FOCAL_AUTO, "gather": _lib.FOCAL_GATHER, "tile": _lib.FOCAL_TILE}
+FOCAL_FORMS = LOWRES_BWD_FORMS      # (the name it had while FocalLoss was its only user)
+
+
+def _logits_target_check(who: str, logits: Tensor, target: Tensor, want_target: tuple, layout: str) -> None:
+    _need_cuda(logits, target)
+    if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 4:
+        raise ValueError(f"{who}: contiguous f32 {layout} logits expected")
+    if target.dtype != torch.int64 or not target.is_contiguous() or tuple(target.shape) != want_target:
+        raise ValueError(f"{who}: contiguous int64 target {list(want_target)} expected, got {tuple(target.shape)}")
+
+
+def _nchw_check(who: str, logits: Tensor, target: Tensor) -> tuple:
+    """(B, K, HW) of contiguous f32 NCHW logits [B, K, H, W] with a contiguous int64 target [B, H, W]."""
+    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
+    _logits_target_check(who, logits, target, (B, H, W), "NCHW")
+    return B, K, H * W
+
+
+def _lowres_check(who: str, low: Tensor, target: Tensor, size: tuple[int, int]) -> tuple:
+    """``dims`` = (B, K, h, w, H, W), as the low-resolution entry points take them, of a contiguous f32 NHWC map [B, h, w, K] with a
+    contiguous int64 target [B, H, W] at ``size``."""
+    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
+    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
+    _logits_target_check(who, low, target, (B, dims[4], dims[5]), "NHWC low-resolution [B, h, w, K]")
+    return dims
+
+
+def _loss_buffers(like: Tensor, nbytes: int, norm: bool = False):
+    """(loss [], norm [1] or None, f64 workspace of ``nbytes``) for a forward, on ``like``'s device."""
+    return (torch.empty((), device=like.device, dtype=torch.float32),
+            torch.empty(1, device=like.device, dtype=torch.float32) if norm else None,
+            torch.empty(nbytes // 8, device=like.device, dtype=torch.float64))
+
+
+def _grad_out(who: str, logits: Tensor, out: Tensor | None) -> Tensor:
+    """``out`` (the caller's buffer for a full-resolution gradient) checked, or a new one."""
+    if out is None:
+        return torch.empty_like(logits)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.shape != logits.shape:
+        raise ValueError(f"{who}: out must be a contiguous f32 tensor of the logits' shape")
+    return out
+
+
+def _bwd_workspace(query, dims: tuple, like: Tensor, form: str = "auto"):
+    """(f32 workspace or None, its bytes) of a low-resolution backward: what ``query(*dims)`` asks for -- only the tile kernels
+    need one, so nothing with ``form`` "gather"."""
+    nbytes = query(*dims) if form != "gather" else 0
+    return (torch.empty(nbytes // 4, device=like.device, dtype=torch.float32) if nbytes else None), nbytes
 
 
 def _dice_entry(stem: str, way: str, options):
@@ -2021,6 +2069,10 @@ def dice_lowres_ok(low: Tensor, size: tuple[int, int]) -> bool:
     return size[0] >= hi and size[1] >= wi and -(-size[0] // hi) <= 64 and -(-size[1] // wi) <= 64
 
 
+# gdl_soft_ce_lowres_*, gdl_focal_lowres_* and gdl_cross_entropy_lowres_* take the same shapes
+soft_ce_lowres_ok = focal_lowres_ok = cross_entropy_lowres_ok = dice_lowres_ok
+
+
 def dice_loss_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], eps: float = 1e-7,
                          options: DiceOptions | OverlapOptions | None = None):
     """Dice(multiclass) -- or the family member ``options`` selects -- of bilinear(low -> size) vs target [B, H, W] without the
@@ -2043,8 +2095,7 @@ def dice_loss_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], sum
                          options: DiceOptions | OverlapOptions | None = None) -> Tensor:
     B, Hi, Wi, K = low.shape
     dlow = torch.empty_like(low)
-    nbytes = _lib.load().gdl_dice_loss_lowres_bwd_workspace(B, K, Hi, Wi, size[0], size[1])
-    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    ws, nbytes = _bwd_workspace(_lib.load().gdl_dice_loss_lowres_bwd_workspace, (B, K, Hi, Wi, size[0], size[1]), low)
     name, fn, opt, keep = _dice_entry("loss_lowres", "bwd", options)
     check(fn(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, *opt, _p(sums), _p(upstream), grad_scale, _p(dlow), _p(ws),
              nbytes, _stream()), name)
@@ -2097,11 +2148,10 @@ def dice_binary_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], s
     _need_cuda(sums, upstream)
     dlow = torch.empty_like(low)
     lib = _lib.load()
-    nbytes = lib.gdl_binary_lowres_bwd_workspace(B, Hi, Wi, Ho, Wo) if form != "gather" else 0
-    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    ws, nbytes = _bwd_workspace(lib.gdl_binary_lowres_bwd_workspace, (B, Hi, Wi, Ho, Wo), low, form)
     name, fn, opt, keep = _dice_entry("binary_loss_lowres", "bwd", options)
     check(fn(_p(low), _p(target), B, Hi, Wi, Ho, Wo, eps, *opt, _p(sums), _p(upstream), grad_scale, _p(dlow), _p(ws), nbytes,
-             FOCAL_FORMS[form], _stream()), name)
+             LOWRES_BWD_FORMS[form], _stream()), name)
     return dlow
 
 
@@ -2118,23 +2168,13 @@ class SoftCEOptions(NamedTuple):
         return (float(self.smooth_factor), int(self.ignore_index is not None), int(self.ignore_index or 0), int(bool(self.mean)))
 
 
-def _soft_ce_check(who: str, logits: Tensor, target: Tensor, want_target: tuple, layout: str) -> None:
-    _need_cuda(logits, target)
-    if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 4:
-        raise ValueError(f"{who}: contiguous f32 {layout} logits expected")
-    if target.dtype != torch.int64 or not target.is_contiguous() or tuple(target.shape) != want_target:
-        raise ValueError(f"{who}: contiguous int64 target {list(want_target)} expected, got {tuple(target.shape)}")
-
-
 def soft_ce_fwd(logits: Tensor, target: Tensor, options: SoftCEOptions = SoftCEOptions()) -> Tensor:
     """smp SoftCrossEntropyLoss on NCHW f32 logits [B,K,H,W] and an int64 target [B,H,W]: the loss (0-dim f32)."""
-    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
-    _soft_ce_check("soft_ce", logits, target, (B, H, W), "NCHW")
-    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    B, K, HW = _nchw_check("soft_ce", logits, target)
     lib = _lib.load()
-    nbytes = lib.gdl_soft_ce_workspace(B, K, H * W)
-    ws = torch.empty(nbytes // 8, device=logits.device, dtype=torch.float64)
-    check(lib.gdl_soft_ce_fwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(loss), _p(ws), nbytes, _stream()),
+    nbytes = lib.gdl_soft_ce_workspace(B, K, HW)
+    loss, _, ws = _loss_buffers(logits, nbytes)
+    check(lib.gdl_soft_ce_fwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(loss), _p(ws), nbytes, _stream()),
           "gdl_soft_ce_fwd")
     return loss
 
@@ -2142,21 +2182,12 @@ def soft_ce_fwd(logits: Tensor, target: Tensor, options: SoftCEOptions = SoftCEO
 def soft_ce_bwd(logits: Tensor, target: Tensor, upstream: Tensor | None, grad_scale: float = 1.0,
                 options: SoftCEOptions = SoftCEOptions(), out: Tensor | None = None, accumulate: bool = False) -> Tensor:
     """d loss / d logits * upstream[0] * grad_scale (softmax recomputed from ``logits``); ``out``/``accumulate`` as dice_loss_bwd."""
-    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
-    _soft_ce_check("soft_ce", logits, target, (B, H, W), "NCHW")
+    B, K, HW = _nchw_check("soft_ce", logits, target)
     _need_cuda(upstream, out)
-    if out is None:
-        out = torch.empty_like(logits)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.shape != logits.shape:
-        raise ValueError("soft_ce_bwd: out must be a contiguous f32 tensor of the logits' shape")
-    check(_lib.load().gdl_soft_ce_bwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(upstream), grad_scale, _p(out),
+    out = _grad_out("soft_ce_bwd", logits, out)
+    check(_lib.load().gdl_soft_ce_bwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(upstream), grad_scale, _p(out),
                                       int(accumulate), _stream()), "gdl_soft_ce_bwd")
     return out
-
-
-def soft_ce_lowres_ok(low: Tensor, size: tuple[int, int]) -> bool:
-    """Shapes gdl_soft_ce_lowres_* take: those of gdl_dice_loss_lowres_* (K <= 16, an upsample by at most 64 per direction)."""
-    return dice_lowres_ok(low, size)
 
 
 def soft_ce_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], options: SoftCEOptions = SoftCEOptions(),
@@ -2164,18 +2195,16 @@ def soft_ce_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], optio
     """The loss of bilinear(low -> size) vs target [B, H, W] without the full-resolution logits: ``(loss, state)``.  ``fused``: the
     same pass also leaves the unscaled partial patches of d(low) in ``state`` (for soft_ce_lowres_bwd); where the shape does not
     take that form (K > 8, resize close to 1:1), and without ``fused``, ``state`` is None and the backward recomputes."""
-    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
-    _soft_ce_check("soft_ce_lowres", low, target, (B, int(size[0]), int(size[1])), "NHWC low-resolution [B, h, w, K]")
+    dims = _lowres_check("soft_ce_lowres", low, target, size)
     loss = torch.empty((), device=low.device, dtype=torch.float32)
     lib = _lib.load()
-    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
     nstate = lib.gdl_soft_ce_lowres_fused_state(*dims) if fused else 0
     if nstate:
         state = torch.empty(nstate // 8 + 1, device=low.device, dtype=torch.float64)
         check(lib.gdl_soft_ce_lowres_fused_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(state), state.numel() * 8,
                                                _stream()), "gdl_soft_ce_lowres_fused_fwd")
         return loss, state
-    nbytes = lib.gdl_soft_ce_lowres_workspace(B, K, dims[4], dims[5])
+    nbytes = lib.gdl_soft_ce_lowres_workspace(*dims[:2], *dims[4:])
     ws = torch.empty(nbytes // 8, device=low.device, dtype=torch.float64)
     check(lib.gdl_soft_ce_lowres_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(ws), nbytes, _stream()),
           "gdl_soft_ce_lowres_fwd")
@@ -2186,18 +2215,15 @@ def soft_ce_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], upstr
                        options: SoftCEOptions = SoftCEOptions(), state: Tensor | None = None) -> Tensor:
     """d loss / d low [B, h, w, K] * upstream[0] * grad_scale: the reduce of the forward's patches (``state`` of a fused forward)
     or the recompute form (tile kernel for K <= 8, gather kernel otherwise)."""
-    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
-    _soft_ce_check("soft_ce_lowres", low, target, (B, int(size[0]), int(size[1])), "NHWC low-resolution [B, h, w, K]")
+    dims = _lowres_check("soft_ce_lowres", low, target, size)
     _need_cuda(upstream, state)
     dlow = torch.empty_like(low)
     lib = _lib.load()
-    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
     if state is not None:
         check(lib.gdl_soft_ce_lowres_fused_bwd(_p(state), state.numel() * state.element_size(), *dims, int(bool(options.mean)),
                                                _p(upstream), grad_scale, _p(dlow), _stream()), "gdl_soft_ce_lowres_fused_bwd")
         return dlow
-    nbytes = lib.gdl_soft_ce_lowres_bwd_workspace(*dims)
-    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    ws, nbytes = _bwd_workspace(lib.gdl_soft_ce_lowres_bwd_workspace, dims, low)
     check(lib.gdl_soft_ce_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(upstream), grad_scale, _p(dlow), _p(ws), nbytes,
                                      _stream()), "gdl_soft_ce_lowres_bwd")
     return dlow
@@ -2221,29 +2247,14 @@ class FocalOptions(NamedTuple):
                 int(bool(self.mean)))
 
 
-def _focal_out(like: Tensor, nbytes: int):
-    """(loss [], norm [1], workspace of ``nbytes``) for a focal forward, on ``like``'s device."""
-    return (torch.empty((), device=like.device, dtype=torch.float32), torch.empty(1, device=like.device, dtype=torch.float32),
-            torch.empty(nbytes // 8, device=like.device, dtype=torch.float64))
-
-
-def _focal_grad_out(who: str, logits: Tensor, out: Tensor | None) -> Tensor:
-    if out is None:
-        return torch.empty_like(logits)
-    if out.dtype != torch.float32 or not out.is_contiguous() or out.shape != logits.shape:
-        raise ValueError(f"{who}: out must be a contiguous f32 tensor of the logits' shape")
-    return out
-
-
 def focal_fwd(logits: Tensor, target: Tensor, options: FocalOptions = FocalOptions()):
     """smp FocalLoss(mode="multiclass") on NCHW f32 logits [B,K,H,W] and an int64 target [B,H,W]: ``(loss, norm)``, the 0-dim f32
     loss and the divisor the kernels formed on the device (1 / valid pixels, or 1 for "sum"), which focal_bwd reads."""
-    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
-    _soft_ce_check("focal", logits, target, (B, H, W), "NCHW")
+    B, K, HW = _nchw_check("focal", logits, target)
     lib = _lib.load()
-    nbytes = lib.gdl_focal_workspace(B, K, H * W)
-    loss, norm, ws = _focal_out(logits, nbytes)
-    check(lib.gdl_focal_fwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes, _stream()),
+    nbytes = lib.gdl_focal_workspace(B, K, HW)
+    loss, norm, ws = _loss_buffers(logits, nbytes, norm=True)
+    check(lib.gdl_focal_fwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes, _stream()),
           "gdl_focal_fwd")
     return loss, norm
 
@@ -2252,11 +2263,10 @@ def focal_bwd(logits: Tensor, target: Tensor, norm: Tensor, upstream: Tensor | N
               options: FocalOptions = FocalOptions(), out: Tensor | None = None, accumulate: bool = False) -> Tensor:
     """d loss / d logits * upstream[0] * grad_scale (recomputed from ``logits``; ``norm`` from focal_fwd); ``out``/``accumulate``
     as soft_ce_bwd."""
-    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
-    _soft_ce_check("focal", logits, target, (B, H, W), "NCHW")
+    B, K, HW = _nchw_check("focal", logits, target)
     _need_cuda(norm, upstream, out)
-    out = _focal_grad_out("focal_bwd", logits, out)
-    check(_lib.load().gdl_focal_bwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(norm), _p(upstream), grad_scale,
+    out = _grad_out("focal_bwd", logits, out)
+    check(_lib.load().gdl_focal_bwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(norm), _p(upstream), grad_scale,
                                     _p(out), int(accumulate), _stream()), "gdl_focal_bwd")
     return out
 
@@ -2275,7 +2285,7 @@ def focal_binary_fwd(logits: Tensor, target: Tensor, options: FocalOptions = Foc
     _focal_binary_check(logits, target)
     lib = _lib.load()
     nbytes = lib.gdl_focal_workspace(1, 1, logits.numel())
-    loss, norm, ws = _focal_out(logits, nbytes)
+    loss, norm, ws = _loss_buffers(logits, nbytes, norm=True)
     check(lib.gdl_focal_binary_fwd(_p(logits), _p(target), logits.numel(), *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
                                    _stream()), "gdl_focal_binary_fwd")
     return loss, norm
@@ -2285,26 +2295,19 @@ def focal_binary_bwd(logits: Tensor, target: Tensor, norm: Tensor, upstream: Ten
                      options: FocalOptions = FocalOptions(), out: Tensor | None = None, accumulate: bool = False) -> Tensor:
     _focal_binary_check(logits, target)
     _need_cuda(norm, upstream, out)
-    out = _focal_grad_out("focal_binary_bwd", logits, out)
+    out = _grad_out("focal_binary_bwd", logits, out)
     check(_lib.load().gdl_focal_binary_bwd(_p(logits), _p(target), logits.numel(), *options.c_args(), _p(norm), _p(upstream),
                                            grad_scale, _p(out), int(accumulate), _stream()), "gdl_focal_binary_bwd")
     return out
 
 
-def focal_lowres_ok(low: Tensor, size: tuple[int, int]) -> bool:
-    """Shapes gdl_focal_lowres_* take: those of gdl_dice_loss_lowres_* (K <= 16, an upsample by at most 64 per direction)."""
-    return dice_lowres_ok(low, size)
-
-
 def focal_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], options: FocalOptions = FocalOptions()):
     """The multiclass focal loss of bilinear(low -> size) vs target [B, H, W] without the full-resolution logits:
     ``(loss, norm)`` as focal_fwd."""
-    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
-    _soft_ce_check("focal_lowres", low, target, (B, int(size[0]), int(size[1])), "NHWC low-resolution [B, h, w, K]")
+    dims = _lowres_check("focal_lowres", low, target, size)
     lib = _lib.load()
-    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
-    nbytes = lib.gdl_focal_lowres_workspace(B, K, dims[4], dims[5])
-    loss, norm, ws = _focal_out(low, nbytes)
+    nbytes = lib.gdl_focal_lowres_workspace(*dims[:2], *dims[4:])
+    loss, norm, ws = _loss_buffers(low, nbytes, norm=True)
     check(lib.gdl_focal_lowres_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes, _stream()),
           "gdl_focal_lowres_fwd")
     return loss, norm
@@ -2314,16 +2317,13 @@ def focal_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], norm: T
                      grad_scale: float = 1.0, options: FocalOptions = FocalOptions(), form: str = "auto") -> Tensor:
     """d loss / d low [B, h, w, K] * upstream[0] * grad_scale.  ``form``: "tile" (K <= 8: every full-resolution element once),
     "gather" (every K <= 16) or "auto" (the tile kernel where the shape takes it, the default -- DESIGN.md section 2)."""
-    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
-    _soft_ce_check("focal_lowres", low, target, (B, int(size[0]), int(size[1])), "NHWC low-resolution [B, h, w, K]")
+    dims = _lowres_check("focal_lowres", low, target, size)
     _need_cuda(norm, upstream)
     dlow = torch.empty_like(low)
     lib = _lib.load()
-    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
-    nbytes = lib.gdl_focal_lowres_bwd_workspace(*dims) if form != "gather" else 0
-    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    ws, nbytes = _bwd_workspace(lib.gdl_focal_lowres_bwd_workspace, dims, low, form)
     check(lib.gdl_focal_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(norm), _p(upstream), grad_scale, _p(dlow), _p(ws),
-                                   nbytes, FOCAL_FORMS[form], _stream()), "gdl_focal_lowres_bwd")
+                                   nbytes, LOWRES_BWD_FORMS[form], _stream()), "gdl_focal_lowres_bwd")
     return dlow
 
 
@@ -2333,7 +2333,7 @@ def focal_binary_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], 
     B, Hi, Wi, Ho, Wo = _binary_lowres_check("focal_binary_lowres", low, size, target)
     lib = _lib.load()
     nbytes = lib.gdl_focal_lowres_workspace(B, 1, Ho, Wo)
-    loss, norm, ws = _focal_out(low, nbytes)
+    loss, norm, ws = _loss_buffers(low, nbytes, norm=True)
     check(lib.gdl_focal_binary_lowres_fwd(_p(low), _p(target), B, Hi, Wi, Ho, Wo, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
                                           _stream()), "gdl_focal_binary_lowres_fwd")
     return loss, norm
@@ -2346,10 +2346,9 @@ def focal_binary_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], 
     _need_cuda(norm, upstream)
     dlow = torch.empty_like(low)
     lib = _lib.load()
-    nbytes = lib.gdl_binary_lowres_bwd_workspace(B, Hi, Wi, Ho, Wo) if form != "gather" else 0
-    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    ws, nbytes = _bwd_workspace(lib.gdl_binary_lowres_bwd_workspace, (B, Hi, Wi, Ho, Wo), low, form)
     check(lib.gdl_focal_binary_lowres_bwd(_p(low), _p(target), B, Hi, Wi, Ho, Wo, *options.c_args(), _p(norm), _p(upstream), grad_scale,
-                                          _p(dlow), _p(ws), nbytes, FOCAL_FORMS[form], _stream()), "gdl_focal_binary_lowres_bwd")
+                                          _p(dlow), _p(ws), nbytes, LOWRES_BWD_FORMS[form], _stream()), "gdl_focal_binary_lowres_bwd")
     return dlow
 
 
@@ -2370,9 +2369,7 @@ class CrossEntropyOptions(NamedTuple):
                 int(bool(self.mean)))
 
 
-def _cross_entropy_check(who: str, logits: Tensor, target: Tensor, want_target: tuple, layout: str, K: int,
-                         options: CrossEntropyOptions) -> None:
-    _soft_ce_check(who, logits, target, want_target, layout)
+def _cross_entropy_weight_check(who: str, options: CrossEntropyOptions, K: int) -> None:
     w = options.weight
     if w is not None:
         _need_cuda(w)
@@ -2384,12 +2381,12 @@ def cross_entropy_fwd(logits: Tensor, target: Tensor, options: CrossEntropyOptio
     """torch CrossEntropyLoss on NCHW f32 logits [B,K,H,W] and an int64 target [B,H,W]: ``(loss, norm)``, the 0-dim f32 loss and
     the divisor the kernels formed on the device (1 / summed weights of the valid pixels, 0 where that sum is 0, or 1 for "sum"),
     which cross_entropy_bwd reads."""
-    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
-    _cross_entropy_check("cross_entropy", logits, target, (B, H, W), "NCHW", K, options)
+    B, K, HW = _nchw_check("cross_entropy", logits, target)
+    _cross_entropy_weight_check("cross_entropy", options, K)
     lib = _lib.load()
-    nbytes = lib.gdl_cross_entropy_workspace(B, K, H * W)
-    loss, norm, ws = _focal_out(logits, nbytes)
-    check(lib.gdl_cross_entropy_fwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
+    nbytes = lib.gdl_cross_entropy_workspace(B, K, HW)
+    loss, norm, ws = _loss_buffers(logits, nbytes, norm=True)
+    check(lib.gdl_cross_entropy_fwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
                                     _stream()), "gdl_cross_entropy_fwd")
     return loss, norm
 
@@ -2399,31 +2396,24 @@ def cross_entropy_bwd(logits: Tensor, target: Tensor, norm: Tensor, upstream: Te
                       accumulate: bool = False) -> Tensor:
     """d loss / d logits * upstream[0] * grad_scale (softmax recomputed from ``logits``; ``norm`` from cross_entropy_fwd);
     ``out``/``accumulate`` as soft_ce_bwd."""
-    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
-    _cross_entropy_check("cross_entropy", logits, target, (B, H, W), "NCHW", K, options)
+    B, K, HW = _nchw_check("cross_entropy", logits, target)
+    _cross_entropy_weight_check("cross_entropy", options, K)
     _need_cuda(norm, upstream, out)
-    out = _focal_grad_out("cross_entropy_bwd", logits, out)
-    check(_lib.load().gdl_cross_entropy_bwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(norm), _p(upstream), grad_scale,
+    out = _grad_out("cross_entropy_bwd", logits, out)
+    check(_lib.load().gdl_cross_entropy_bwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(norm), _p(upstream), grad_scale,
                                             _p(out), int(accumulate), _stream()), "gdl_cross_entropy_bwd")
     return out
-
-
-def cross_entropy_lowres_ok(low: Tensor, size: tuple[int, int]) -> bool:
-    """Shapes gdl_cross_entropy_lowres_* take: those of gdl_soft_ce_lowres_* (K <= 16, an upsample by at most 64 per direction)."""
-    return dice_lowres_ok(low, size)
 
 
 def cross_entropy_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int],
                              options: CrossEntropyOptions = CrossEntropyOptions()):
     """The cross-entropy of bilinear(low -> size) vs target [B, H, W] without the full-resolution logits: ``(loss, norm)`` as
     cross_entropy_fwd."""
-    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
-    _cross_entropy_check("cross_entropy_lowres", low, target, (B, int(size[0]), int(size[1])), "NHWC low-resolution [B, h, w, K]", K,
-                         options)
+    dims = _lowres_check("cross_entropy_lowres", low, target, size)
+    _cross_entropy_weight_check("cross_entropy_lowres", options, dims[1])
     lib = _lib.load()
-    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
-    nbytes = lib.gdl_cross_entropy_lowres_workspace(B, K, dims[4], dims[5])
-    loss, norm, ws = _focal_out(low, nbytes)
+    nbytes = lib.gdl_cross_entropy_lowres_workspace(*dims[:2], *dims[4:])
+    loss, norm, ws = _loss_buffers(low, nbytes, norm=True)
     check(lib.gdl_cross_entropy_lowres_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
                                            _stream()), "gdl_cross_entropy_lowres_fwd")
     return loss, norm
@@ -2433,17 +2423,14 @@ def cross_entropy_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int],
                              grad_scale: float = 1.0, options: CrossEntropyOptions = CrossEntropyOptions(),
                              form: str = "auto") -> Tensor:
     """d loss / d low [B, h, w, K] * upstream[0] * grad_scale; ``form`` as focal_lowres_bwd."""
-    B, Hi, Wi, K = low.shape if low.dim() == 4 else (0, 0, 0, 0)
-    _cross_entropy_check("cross_entropy_lowres", low, target, (B, int(size[0]), int(size[1])), "NHWC low-resolution [B, h, w, K]", K,
-                         options)
+    dims = _lowres_check("cross_entropy_lowres", low, target, size)
+    _cross_entropy_weight_check("cross_entropy_lowres", options, dims[1])
     _need_cuda(norm, upstream)
     dlow = torch.empty_like(low)
     lib = _lib.load()
-    dims = (B, K, Hi, Wi, int(size[0]), int(size[1]))
-    nbytes = lib.gdl_cross_entropy_lowres_bwd_workspace(*dims) if form != "gather" else 0
-    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    ws, nbytes = _bwd_workspace(lib.gdl_cross_entropy_lowres_bwd_workspace, dims, low, form)
     check(lib.gdl_cross_entropy_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(norm), _p(upstream), grad_scale, _p(dlow),
-                                           _p(ws), nbytes, FOCAL_FORMS[form], _stream()), "gdl_cross_entropy_lowres_bwd")
+                                           _p(ws), nbytes, LOWRES_BWD_FORMS[form], _stream()), "gdl_cross_entropy_lowres_bwd")
     return dlow
 
 
@@ -2498,8 +2485,7 @@ def soft_bce_fwd(logits: Tensor, target: Tensor, options: SoftBCEOptions = SoftB
     B, C_, HW = _soft_bce_check("soft_bce", logits, target, options)
     lib = _lib.load()
     nbytes = lib.gdl_soft_bce_workspace(B, C_, HW)
-    loss = torch.empty((), device=logits.device, dtype=torch.float32)
-    ws = torch.empty(nbytes // 8, device=logits.device, dtype=torch.float64)
+    loss, _, ws = _loss_buffers(logits, nbytes)
     check(lib.gdl_soft_bce_fwd(_p(logits), _p(target), BCE_TARGET_TYPES[target.dtype], B, C_, HW, *options.c_args(logits.numel()),
                                _p(loss), _p(ws), nbytes, _stream()), "gdl_soft_bce_fwd")
     return loss
@@ -2510,7 +2496,7 @@ def soft_bce_bwd(logits: Tensor, target: Tensor, upstream: Tensor | None, grad_s
     """d loss / d logits * upstream[0] * grad_scale (recomputed from ``logits``); ``out``/``accumulate`` as soft_ce_bwd."""
     B, C_, HW = _soft_bce_check("soft_bce", logits, target, options)
     _need_cuda(upstream, out)
-    out = _focal_grad_out("soft_bce_bwd", logits, out)
+    out = _grad_out("soft_bce_bwd", logits, out)
     check(_lib.load().gdl_soft_bce_bwd(_p(logits), _p(target), BCE_TARGET_TYPES[target.dtype], B, C_, HW,
                                        *options.c_args(logits.numel()), _p(upstream), grad_scale, _p(out), int(accumulate), _stream()),
           "gdl_soft_bce_bwd")
@@ -2533,8 +2519,7 @@ def soft_bce_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], opti
     B, Hi, Wi, Ho, Wo = _soft_bce_lowres_check(low, target, size, options)
     lib = _lib.load()
     nbytes = lib.gdl_soft_bce_lowres_workspace(B, Ho, Wo)
-    loss = torch.empty((), device=low.device, dtype=torch.float32)
-    ws = torch.empty(nbytes // 8, device=low.device, dtype=torch.float64)
+    loss, _, ws = _loss_buffers(low, nbytes)
     check(lib.gdl_soft_bce_lowres_fwd(_p(low), _p(target), BCE_TARGET_TYPES[target.dtype], B, Hi, Wi, Ho, Wo,
                                       *options.c_args(target.numel()), _p(loss), _p(ws), nbytes, _stream()), "gdl_soft_bce_lowres_fwd")
     return loss
@@ -2547,11 +2532,10 @@ def soft_bce_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], upst
     _need_cuda(upstream)
     dlow = torch.empty_like(low)
     lib = _lib.load()
-    nbytes = lib.gdl_binary_lowres_bwd_workspace(B, Hi, Wi, Ho, Wo) if form != "gather" else 0
-    ws = torch.empty(nbytes // 4, device=low.device, dtype=torch.float32) if nbytes else None
+    ws, nbytes = _bwd_workspace(lib.gdl_binary_lowres_bwd_workspace, (B, Hi, Wi, Ho, Wo), low, form)
     check(lib.gdl_soft_bce_lowres_bwd(_p(low), _p(target), BCE_TARGET_TYPES[target.dtype], B, Hi, Wi, Ho, Wo,
                                       *options.c_args(target.numel()), _p(upstream), grad_scale, _p(dlow), _p(ws), nbytes,
-                                      FOCAL_FORMS[form], _stream()), "gdl_soft_bce_lowres_bwd")
+                                      LOWRES_BWD_FORMS[form], _stream()), "gdl_soft_bce_lowres_bwd")
     return dlow
 
 
@@ -2594,12 +2578,11 @@ def lovasz_fwd(logits: Tensor, target: Tensor, options: LovaszOptions = LovaszOp
     """smp LovaszLoss(mode="multiclass") on NCHW f32 logits [B,K,H,W] and an int64 target [B,H,W]: ``(loss, coef, norm)``, the 0-dim
     f32 loss, the Jaccard coefficient of every (class, pixel) in pixel order and the weight of every segment in the loss (formed on
     the device), both of which lovasz_bwd reads."""
-    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
-    _soft_ce_check("lovasz", logits, target, (B, H, W), "NCHW")
+    B, K, HW = _nchw_check("lovasz", logits, target)
     lib = _lib.load()
-    segs, n = (B * K, H * W) if options.per_image else (K, B * H * W)
+    segs, n = (B * K, HW) if options.per_image else (K, B * HW)
     loss, coef, norm, ws, nbytes = _lovasz_out(logits, lib, segs, n, K)
-    check(lib.gdl_lovasz_fwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(loss), _p(coef), _p(norm), _p(ws), nbytes,
+    check(lib.gdl_lovasz_fwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(loss), _p(coef), _p(norm), _p(ws), nbytes,
                              _stream()), "gdl_lovasz_fwd")
     return loss, coef, norm
 
@@ -2608,13 +2591,12 @@ def lovasz_bwd(logits: Tensor, target: Tensor, coef: Tensor, norm: Tensor, upstr
                options: LovaszOptions = LovaszOptions(), out: Tensor | None = None, accumulate: bool = False) -> Tensor:
     """d loss / d logits * upstream[0] * grad_scale (softmax recomputed from ``logits``; ``coef``, ``norm`` from lovasz_fwd with the
     same options); ``out``/``accumulate`` as focal_bwd."""
-    B, K, H, W = logits.shape if logits.dim() == 4 else (0, 0, 0, 0)
-    _soft_ce_check("lovasz", logits, target, (B, H, W), "NCHW")
+    B, K, HW = _nchw_check("lovasz", logits, target)
     _need_cuda(coef, norm, upstream, out)
     _f32vec(coef, logits.numel(), "lovasz_bwd: coef")
     _f32vec(norm, B * K if options.per_image else K, "lovasz_bwd: norm")
-    out = _focal_grad_out("lovasz_bwd", logits, out)
-    check(_lib.load().gdl_lovasz_bwd(_p(logits), _p(target), B, K, H * W, *options.c_args(), _p(coef), _p(norm), _p(upstream), grad_scale,
+    out = _grad_out("lovasz_bwd", logits, out)
+    check(_lib.load().gdl_lovasz_bwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(coef), _p(norm), _p(upstream), grad_scale,
                                      _p(out), int(accumulate), _stream()), "gdl_lovasz_bwd")
     return out
 
@@ -2646,7 +2628,7 @@ def lovasz_binary_bwd(logits: Tensor, target: Tensor, coef: Tensor, norm: Tensor
     _need_cuda(coef, norm, upstream, out)
     _f32vec(coef, logits.numel(), "lovasz_binary_bwd: coef")
     _f32vec(norm, B if options.per_image else 1, "lovasz_binary_bwd: norm")
-    out = _focal_grad_out("lovasz_binary_bwd", logits, out)
+    out = _grad_out("lovasz_binary_bwd", logits, out)
     check(_lib.load().gdl_lovasz_binary_bwd(_p(logits), _p(target), B, per, *options.c_args(), _p(coef), _p(norm), _p(upstream),
                                             grad_scale, _p(out), int(accumulate), _stream()), "gdl_lovasz_binary_bwd")
     return out

@@ -141,10 +141,10 @@ def test_argument_errors_are_raised_before_the_device_is_touched():
 
 def test_losses_materialise_what_the_binary_kernels_do_not_take(monkeypatch):
     """The routing of _DiceFamily.forward / FocalLoss.forward: a one-class f32 map within the shape limits goes to the
-    low-resolution node, everything else (K != 1, a downsample, the switch off, a target at another size) is materialised."""
+    low-resolution ops, everything else (K != 1, a downsample, the switch off, a target at another size) is materialised."""
     taken = []
-    monkeypatch.setattr(gnn._DiceBinaryLowres, "apply", staticmethod(lambda *a: taken.append("dice") or torch.zeros(())))
-    monkeypatch.setattr(gnn._FocalBinaryLowres, "apply", staticmethod(lambda *a: taken.append("focal") or torch.zeros(())))
+    monkeypatch.setattr(ops, "dice_binary_lowres_fwd", lambda *a, **k: taken.append("dice") or (torch.zeros(()), torch.zeros(3)))
+    monkeypatch.setattr(ops, "focal_binary_lowres_fwd", lambda *a, **k: taken.append("focal") or (torch.zeros(()), torch.zeros(1)))
 
     class Materialised(Exception):
         pass

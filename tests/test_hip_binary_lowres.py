@@ -388,9 +388,9 @@ def test_one_class_dofa_task_with_the_path_on_and_off(monkeypatch, loss):
 def test_graphed_binary_dice_step_reproduces_the_eager_losses_bit_for_bit():
     """GraphedTrainStep (hipGraph capture of forward + DiceLoss(binary) from the one-class low-resolution maps + backward + Adam):
     one capture and two replays against the same steps run eagerly, bit for bit.  In a fresh child process
-    (tests/_binary_lowres_graph_worker.py) under its own time limit, one capture scenario per process."""
-    worker = Path(__file__).with_name("_binary_lowres_graph_worker.py")
-    run = subprocess.run(["timeout", "-k", "10", "300", sys.executable, str(worker)], capture_output=True, text=True)
+    (tests/_loss_graph_worker.py, scenario "binary_lowres") under its own time limit, one capture scenario per process."""
+    worker = Path(__file__).with_name("_loss_graph_worker.py")
+    run = subprocess.run(["timeout", "-k", "10", "300", sys.executable, str(worker), "binary_lowres"], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     res = json.loads(run.stdout.strip().splitlines()[-1])
     print(res)

@@ -449,10 +449,10 @@ def test_graphed_train_step_reproduces_the_eager_losses_bit_for_bit():
     """GraphedTrainStep (hipGraph capture of forward + weighted mean CrossEntropyLoss from low-resolution logits + backward + Adam)
     on the tiny DOFA task: one capture and three replays on batches whose ignored fraction differs, so the divisor D changes from
     replay to replay, against the same steps run eagerly, bit for bit -- a divisor baked in at capture time fails this.  In a
-    process of its own (tests/_cross_entropy_graph_worker.py), one capture scenario per process as
+    process of its own (tests/_loss_graph_worker.py, scenario "cross_entropy"), one capture scenario per process as
     tests/_graph_interleave_worker.py explains."""
-    worker = Path(__file__).with_name("_cross_entropy_graph_worker.py")
-    run = subprocess.run([sys.executable, str(worker)], capture_output=True, text=True, timeout=600)
+    worker = Path(__file__).with_name("_loss_graph_worker.py")
+    run = subprocess.run([sys.executable, str(worker), "cross_entropy"], capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     res = json.loads(run.stdout.strip().splitlines()[-1])
     print(res)

@@ -347,9 +347,9 @@ def test_dofa_training_step_from_low_resolution_logits_equals_the_materialised_s
 def test_graphed_train_step_reproduces_the_eager_losses_bit_for_bit():
     """GraphedTrainStep (hipGraph capture of forward + FocalLoss from low-resolution logits + backward + Adam) on the tiny DOFA
     task: one capture and two replays against the same steps run eagerly, bit for bit.  In a process of its own
-    (tests/_focal_graph_worker.py), one capture scenario per process as tests/_graph_interleave_worker.py explains."""
-    worker = Path(__file__).with_name("_focal_graph_worker.py")
-    run = subprocess.run([sys.executable, str(worker)], capture_output=True, text=True, timeout=600)
+    (tests/_loss_graph_worker.py, scenario "focal"), one capture scenario per process as tests/_graph_interleave_worker.py explains."""
+    worker = Path(__file__).with_name("_loss_graph_worker.py")
+    run = subprocess.run([sys.executable, str(worker), "focal"], capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     res = json.loads(run.stdout.strip().splitlines()[-1])
     print(res)

@@ -306,9 +306,9 @@ def test_c_entry_points_return_error_codes():
 # ------------------------------------------------------------------------------------------------ 7. captured step
 def test_graphed_train_step_reproduces_the_eager_losses_bit_for_bit():
     """GraphedTrainStep (hipGraph capture of forward + LovaszLoss + backward + Adam) on the toy task: one capture and three replays
-    against the same steps run eagerly, bit for bit.  In a process of its own (tests/_lovasz_graph_worker.py)."""
-    worker = Path(__file__).with_name("_lovasz_graph_worker.py")
-    run = subprocess.run([sys.executable, str(worker)], capture_output=True, text=True, timeout=600)
+    against the same steps run eagerly, bit for bit.  In a process of its own (tests/_loss_graph_worker.py, scenario "lovasz")."""
+    worker = Path(__file__).with_name("_loss_graph_worker.py")
+    run = subprocess.run([sys.executable, str(worker), "lovasz"], capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     res = json.loads(run.stdout.strip().splitlines()[-1])
     print(res)

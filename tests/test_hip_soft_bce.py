@@ -504,9 +504,9 @@ def test_one_class_unetplus_step_with_the_float_mask_matches_the_oracle():
 def test_graphed_soft_bce_step_reproduces_the_eager_losses_bit_for_bit():
     """GraphedTrainStep (hipGraph capture of forward + SoftBCEWithLogitsLoss from the one-class low-resolution maps + backward +
     Adam): one capture and three replays against the same steps run eagerly, bit for bit.  In a fresh child process
-    (tests/_soft_bce_graph_worker.py) under its own time limit; nothing follows a non-zero exit status."""
-    worker = Path(__file__).with_name("_soft_bce_graph_worker.py")
-    run = subprocess.run(["timeout", "-k", "10", "300", sys.executable, str(worker)], capture_output=True, text=True)
+    (tests/_loss_graph_worker.py, scenario "soft_bce") under its own time limit; nothing follows a non-zero exit status."""
+    worker = Path(__file__).with_name("_loss_graph_worker.py")
+    run = subprocess.run(["timeout", "-k", "10", "300", sys.executable, str(worker), "soft_bce"], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
     res = json.loads(run.stdout.strip().splitlines()[-1])
     print(res)
