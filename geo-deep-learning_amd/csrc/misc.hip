@@ -197,6 +197,40 @@ __global__ __launch_bounds__(256) void normalize_raw_kernel(const TI* __restrict
   }
 }
 
+// The caller's sensor range instead of 0..255 -> 0..1 (tools/script_model.py:45-52 with any image_min / image_max / norm_min /
+// norm_max): ((d * (x - image_min)) / span + norm_min - mean[c]) / std[c] with d = norm_max - norm_min and span = image_max -
+// image_min, every step rounded to f32 in the order utils/tensors.py:19-21,34 takes them on an f32 tensor (not folded into one scale
+// and offset: that form differs from the reference by up to a few ulp).  V elements of the flat NCHW tile per thread (V == 4: one
+// vector load and one 16-byte store; a group may straddle a channel when H*W % 4 != 0, so the channel advances per element); the
+// total % V elements behind the last whole group are done one per thread by the first threads of the grid.
+template <typename TI, int V>
+__global__ __launch_bounds__(256) void normalize_range_kernel(const TI* __restrict__ in, float* __restrict__ out, int C, int64_t HW,
+                                                              int64_t total, float imin, float span, float d, float nmin,
+                                                              const float* __restrict__ mean, const float* __restrict__ stdv) {
+  struct alignas(sizeof(TI) * V) Vec { TI v[V]; };
+  struct alignas(sizeof(float) * V) VecF { float v[V]; };
+  const int64_t groups = total / V;
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  for (int64_t g = tid; g < groups; g += (int64_t)gridDim.x * 256) {
+    const int64_t i0 = g * V, q = i0 / HW;
+    int64_t r = i0 - q * HW;
+    int c = (int)(q % C);
+    const Vec x = *(const Vec*)(in + i0);
+    VecF o;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      o.v[e] = ((d * ((float)x.v[e] - imin)) / span + nmin - mean[c]) / stdv[c];
+      if (++r == HW) { r = 0; if (++c == C) c = 0; }
+    }
+    *(VecF*)(out + i0) = o;
+  }
+  const int64_t i = groups * V + tid;
+  if (i < total) {
+    const int c = (int)((i / HW) % C);
+    out[i] = ((d * ((float)in[i] - imin)) / span + nmin - mean[c]) / stdv[c];
+  }
+}
+
 // ------------------------------------------------------------------ IoU counts (torchmetrics MeanIoU update)
 // per sample b and class k: intersection |pred==k & target==k|, |pred==k|, |target==k| as exact 64-bit counts.
 // LDS histogram per block, integer atomics only (deterministic).
@@ -1015,6 +1049,21 @@ __global__ __launch_bounds__(256) void class_probs_kernel(const float* __restric
   }
 }
 
+// more than 16 classes: the same softmax with the class dimension in run-time loops (the logits are read three times; the
+// inference wrapper's route for a head wider than the unrolled kernels)
+__global__ __launch_bounds__(256) void class_probs_any_kernel(const float* __restrict__ logits, int B, int K, int64_t HW,
+                                                              float* __restrict__ probs) {
+  const int64_t total = (int64_t)B * HW;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t b = i / HW, p = i - b * HW;
+    const float* x = logits + b * K * HW + p;
+    float mx = -INFINITY, s = 0.f;
+    for (int k = 0; k < K; ++k) mx = fmaxf(mx, x[k * HW]);
+    for (int k = 0; k < K; ++k) s += expf(x[k * HW] - mx);
+    for (int k = 0; k < K; ++k) probs[(b * K + k) * HW + p] = expf(x[k * HW] - mx) / s;
+  }
+}
+
 // ------------------------------------------------------------------ mask prediction from the LOW-resolution logits
 // softmax(dim=1).argmax(dim=1) of the resized logits straight from the head's low-resolution map (validation / test / inference:
 // `outputs.out.softmax(dim=1).argmax(dim=1)`, segmentation_dofa.py:278-281): the bilinear logits of a pixel with the expression of
@@ -1072,6 +1121,53 @@ __global__ __launch_bounds__(256) void upsample_threshold_kernel(const float* __
     float x[1];
     bilinear_logits<1>(low, b, Hi, Wi, y0, y1, x0, x1, ly, lx, x);
     mask[i] = sigmoid_over(x[0], th);
+  }
+}
+
+// Class probabilities of the exported inference model straight from a head's low-resolution map (tools/script_model.py:53-58 over
+// dofa.py:89-95): the bilinear logits of a pixel with the expression of upsample_logits_kernel, then class_probs_kernel's softmax
+// (K > 1) or sigmoid (K == 1) -- the probabilities of gdl_upsample_logits + gdl_class_probs with one store per value instead of a
+// store, a load and a store of [B, K, Ho, Wo] f32.  The kernel is store-bound (K * 4 bytes per pixel against a few cached reads of
+// the map): a thread owns V consecutive pixels of an output row, so every class plane is written along Wo, 256 contiguous bytes
+// per wave-instruction with V == 1 and 1 KiB (16 bytes per lane, the widest store there is) with V == 4, which needs Wo % 4 == 0.
+template <int K, int V>
+__global__ __launch_bounds__(256) void upsample_probs_kernel(const float* __restrict__ low, int B, int Hi, int Wi, int Ho, int Wo,
+                                                             float* __restrict__ probs) {
+  struct alignas(sizeof(float) * V) VecF { float v[V]; };
+  const int Wv = Wo / V;
+  const int64_t total = (int64_t)B * Ho * Wv;
+  const float ry = (float)Hi / (float)Ho, rx = (float)Wi / (float)Wo;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int ox0 = (int)(i % Wv) * V;
+    const int64_t t = i / Wv;
+    const int oy = (int)(t % Ho), b = (int)(t / Ho);
+    int y0, y1; float ly;
+    src_index2(ry, oy, Hi, y0, y1, ly);
+    float x[V][K];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      int x0, x1; float lx;
+      src_index2(rx, ox0 + e, Wi, x0, x1, lx);
+      bilinear_logits<K>(low, b, Hi, Wi, y0, y1, x0, x1, ly, lx, x[e]);
+      if constexpr (K == 1) {
+        x[e][0] = 1.0f / (1.0f + expf(-x[e][0]));
+      } else {
+        float mx = -INFINITY, s = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) mx = fmaxf(mx, x[e][k]);
+#pragma unroll
+        for (int k = 0; k < K; ++k) { x[e][k] = expf(x[e][k] - mx); s += x[e][k]; }
+#pragma unroll
+        for (int k = 0; k < K; ++k) x[e][k] = x[e][k] / s;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      VecF o;
+#pragma unroll
+      for (int e = 0; e < V; ++e) o.v[e] = x[e][k];
+      *(VecF*)(probs + (((int64_t)b * K + k) * Ho + oy) * Wo + ox0) = o;
+    }
   }
 }
 
@@ -1320,6 +1416,32 @@ extern "C" int gdl_normalize_raw(const void* in, int kind, float* out, int B, in
   return GDL_OK;
 }
 
+extern "C" int gdl_normalize_range(const void* in, int kind, float* out, int B, int C, int64_t HW, int image_min, int image_max,
+                                   double norm_min, double norm_max, const float* mean, const float* stdv, gdl_stream_t stream) {
+  GDL_CHECK_ARG(in && out && mean && stdv, "gdl_normalize_range: null pointer");
+  GDL_CHECK_ARG(kind >= GDL_RAW_U8 && kind <= GDL_RAW_F32, "gdl_normalize_range: bad sample kind %d", kind);
+  GDL_CHECK_ARG(B > 0 && C > 0 && HW > 0, "gdl_normalize_range: bad sizes");
+  GDL_CHECK_ARG(image_max != image_min, "gdl_normalize_range: image_max == image_min (%d): the range is empty", image_min);
+  const int64_t total = (int64_t)B * C * HW;
+  // the scalars as Python forms them before they meet the f32 tensor: differences in int / double, one rounding to f32 each
+  const float imin = (float)image_min, span = (float)((int64_t)image_max - (int64_t)image_min);
+  const float d = (float)(norm_max - norm_min), nmin = (float)norm_min;
+  const bool vec = (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0;
+  hipStream_t s = (hipStream_t)stream;
+#define NR(T)                                                                                                                      \
+  if (vec) hipLaunchKernelGGL((normalize_range_kernel<T, 4>), dim3(grid_for(total / 4)), dim3(256), 0, s, (const T*)in, out, C, HW,  \
+                              total, imin, span, d, nmin, mean, stdv);                                                             \
+  else hipLaunchKernelGGL((normalize_range_kernel<T, 1>), dim3(grid_for(total)), dim3(256), 0, s, (const T*)in, out, C, HW, total, \
+                          imin, span, d, nmin, mean, stdv)
+  if (kind == GDL_RAW_U8) { NR(uint8_t); }
+  else if (kind == GDL_RAW_U16) { NR(uint16_t); }
+  else if (kind == GDL_RAW_I16) { NR(int16_t); }
+  else { NR(float); }
+#undef NR
+  GDL_CHECK_LAUNCH("gdl_normalize_range");
+  return GDL_OK;
+}
+
 extern "C" int gdl_scale_outer(void* x, int dtype, const float* s, int64_t outer, int64_t inner, gdl_stream_t stream) {
   GDL_CHECK_ARG(x && s, "gdl_scale_outer: null pointer");
   const int64_t total = outer * inner;
@@ -1554,8 +1676,27 @@ extern "C" int gdl_upsample_threshold(const float* low, int B, int Hi, int Wi, i
 extern "C" int gdl_class_probs(const float* logits, int B, int K, int64_t HW, float* probs, gdl_stream_t stream) {
   GDL_CHECK_ARG(logits && probs, "gdl_class_probs: null pointer");
   const int64_t total = (int64_t)B * HW;
-  K_SWITCH(K, hipLaunchKernelGGL((class_probs_kernel<KK>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, logits, B, HW, probs));
+  if (K > 16) {
+    hipLaunchKernelGGL(class_probs_any_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, logits, B, K, HW, probs);
+  } else {
+    K_SWITCH(K, hipLaunchKernelGGL((class_probs_kernel<KK>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, logits, B, HW, probs));
+  }
   GDL_CHECK_LAUNCH("gdl_class_probs");
+  return GDL_OK;
+}
+
+// every size pair gdl_upsample_logits takes (an upsample, a downsample or the identity, any factor); K up to the 16 unrolled classes
+extern "C" int gdl_upsample_probs(const float* low, int B, int Hi, int Wi, int K, float* probs, int Ho, int Wo, gdl_stream_t stream) {
+  GDL_CHECK_ARG(low && probs, "gdl_upsample_probs: null pointer");
+  GDL_CHECK_ARG(B > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "gdl_upsample_probs: bad sizes %d x %d x %d -> %d x %d", B, Hi, Wi, Ho, Wo);
+  GDL_CHECK_ARG(K >= 1 && K <= 16, "gdl_upsample_probs: 1..16 classes, got %d (more: gdl_upsample_logits + gdl_class_probs)", K);
+  hipStream_t s = (hipStream_t)stream;
+  if (Wo % 4 == 0 && (uintptr_t)probs % 16 == 0) {
+    K_SWITCH(K, hipLaunchKernelGGL((upsample_probs_kernel<KK, 4>), dim3(grid_for((int64_t)B * Ho * (Wo / 4))), dim3(256), 0, s, low, B, Hi, Wi, Ho, Wo, probs));
+  } else {
+    K_SWITCH(K, hipLaunchKernelGGL((upsample_probs_kernel<KK, 1>), dim3(grid_for((int64_t)B * Ho * Wo)), dim3(256), 0, s, low, B, Hi, Wi, Ho, Wo, probs));
+  }
+  GDL_CHECK_LAUNCH("gdl_upsample_probs");
   return GDL_OK;
 }
 

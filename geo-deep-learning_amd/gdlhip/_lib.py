@@ -177,6 +177,7 @@ SIGNATURES = {
     "gdl_add_rows": (c_i, [c_p, c_l, c_l, c_p, c_l, c_l, c_p, c_l, c_l, c_i, c_p]),
     "gdl_normalize_u8": (c_i, [c_p, c_p, c_i, c_i, c_l, c_p, c_p, c_p]),
     "gdl_normalize_raw": (c_i, [c_p, c_i, c_p, c_i, c_i, c_l, c_p, c_p, c_p]),
+    "gdl_normalize_range": (c_i, [c_p, c_i, c_p, c_i, c_i, c_l, c_i, c_i, C.c_double, C.c_double, c_p, c_p, c_p]),
     "gdl_augment": (c_i, [c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     "gdl_scale_outer": (c_i, [c_p, c_i, c_p, c_l, c_l, c_p]),
     "gdl_head_1x1": (c_i, [c_p, c_i, c_l, c_i, c_l, c_p, c_p, c_p, c_l, c_p, c_i, c_p]),
@@ -199,6 +200,7 @@ SIGNATURES = {
     "gdl_sigmoid_threshold": (c_i, [c_p, c_l, c_f, c_p, c_p]),
     "gdl_upsample_threshold": (c_i, [c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_f, c_p]),
     "gdl_class_probs": (c_i, [c_p, c_i, c_i, c_l, c_p, c_p]),
+    "gdl_upsample_probs": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_p]),
     "gdl_iou_counts": (c_i, [c_p, c_p, c_i, c_l, c_i, c_p, c_p]),
     "gdl_dice_loss_workspace": (c_l, [c_i, c_i, c_l]),
     "gdl_dice_loss_fwd": (c_i, [c_p, c_p, c_i, c_i, c_l, c_f, c_p, c_p, c_p, c_l, c_p]),

@@ -1961,6 +1961,20 @@ def predict_binary_mask(logits, threshold: float = 0.5) -> Tensor:
     return ops.sigmoid_threshold(logits.float().contiguous(), threshold)
 
 
+@torch.no_grad()
+def predict_probs(logits) -> Tensor:
+    """``f.softmax(output, dim=1)`` (more than one class) / ``f.sigmoid(output)`` (one class) of the exported inference model
+    (tools/script_model.py:54-58): f32 [B, K, H, W].  For not-yet-resized f32 logits (LowresLogits) with 1..16 classes the resize
+    is evaluated per pixel inside the kernel: the same probabilities without the [B, K, H, W] logits.  Any other LowresLogits is
+    resized first (``materialise()``), as ``predict_mask`` does for its shapes.  Inference only: no gradient."""
+    if isinstance(logits, LowresLogits):
+        low = logits.low
+        if low.dtype == torch.float32 and low.dim() == 4 and 1 <= low.shape[3] <= 16:
+            return ops.upsample_probs(low.contiguous(), (int(logits.size[0]), int(logits.size[1])))
+        logits = LowresLogits(low.float().contiguous(), logits.size).materialise()      # (the resize kernel reads f32)
+    return ops.class_probs(logits.float().contiguous())
+
+
 # ------------------------------------------------------------------ optimizer
 class _FusedOptimizer(torch.optim.Optimizer):
     """What the fused optimizers share: one chunk table per param group (rows {param, grad, buf0, buf1, count, shadow}, cached on

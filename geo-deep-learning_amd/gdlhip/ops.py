@@ -1659,6 +1659,24 @@ def normalize_raw(raw: Tensor, mean: Tensor, std: Tensor) -> Tensor:
     return out
 
 
+def normalize_range(raw: Tensor, mean: Tensor, std: Tensor, image_min: int = 0, image_max: int = 255, norm_min: float = 0.0,
+                    norm_max: float = 1.0) -> Tensor:
+    """Raw NCHW samples (uint8 / uint16 / int16 / f32) -> ((norm_max - norm_min) * (float(x) - image_min) / (image_max - image_min)
+    + norm_min - mean[c]) / std[c] f32: ``normalization`` with the caller's sensor range, then ``standardization``
+    (utils/tensors.py:10-35), every step in f32 in the reference's order."""
+    if raw.dtype not in _RAW_KIND or not raw.is_contiguous() or raw.dim() != 4:
+        raise ValueError(f"normalize_range: contiguous NCHW uint8/uint16/int16/float32 expected, got {raw.dtype}")
+    if int(image_max) == int(image_min):
+        raise ValueError(f"normalize_range: image_max == image_min ({int(image_min)}): the range is empty")
+    _need_cuda(raw)
+    B, Cc, H, W = raw.shape
+    out = torch.empty((B, Cc, H, W), device=raw.device, dtype=torch.float32)
+    check(_lib.load().gdl_normalize_range(_p(raw), _RAW_KIND[raw.dtype], _p(out), B, Cc, H * W, int(image_min), int(image_max),
+                                          float(norm_min), float(norm_max), _p(_f32vec(mean, Cc, "mean")),
+                                          _p(_f32vec(std, Cc, "std")), _stream()), "gdl_normalize_range")
+    return out
+
+
 def augment(img: Tensor, mask: Tensor | None, params: Tensor, mean: Tensor | None = None,
             std: Tensor | None = None) -> tuple[Tensor, Tensor | None]:
     """Per-sample flip / rot90 / resized-crop of an NCHW tile (+ its int64 mask), optionally fused with the
@@ -1900,6 +1918,21 @@ def class_probs(logits: Tensor) -> Tensor:
     B, K, H, W = logits.shape
     out = torch.empty_like(logits)
     check(_lib.load().gdl_class_probs(_p(logits), B, K, H * W, _p(out), _stream()), "gdl_class_probs")
+    return out
+
+
+def upsample_probs(low: Tensor, size: tuple[int, int]) -> Tensor:
+    """softmax(dim=1) (2..16 classes) or sigmoid (one class) of bilinear(low -> size) for a head's NHWC f32 map [B, h, w, K] -> f32
+    [B, K, H, W], without the resized logits (gdl_upsample_probs; the probabilities of upsample_logits + class_probs)."""
+    _need_cuda(low)
+    if low.dtype != torch.float32 or not low.is_contiguous() or low.dim() != 4 or not 1 <= low.shape[3] <= 16:
+        raise ValueError("upsample_probs: contiguous f32 NHWC logits [B, h, w, K] with 1..16 classes expected")
+    B, Hi, Wi, K = low.shape
+    Ho, Wo = int(size[0]), int(size[1])
+    if min(B, Hi, Wi, Ho, Wo) < 1:
+        raise ValueError(f"upsample_probs: bad sizes {tuple(low.shape)} -> {Ho} x {Wo}")
+    out = torch.empty((B, K, Ho, Wo), device=low.device, dtype=torch.float32)
+    check(_lib.load().gdl_upsample_probs(_p(low), B, Hi, Wi, K, _p(out), Ho, Wo, _stream()), "gdl_upsample_probs")
     return out
 
 

@@ -465,6 +465,11 @@ int gdl_normalize_u8(const uint8_t* in, float* out, int B, int C, int64_t HW, co
 enum { GDL_RAW_U8 = 0, GDL_RAW_U16 = 1, GDL_RAW_I16 = 2, GDL_RAW_F32 = 3 };
 int gdl_normalize_raw(const void* in, int kind, float* out, int B, int C, int64_t HW, const float* mean,
                       const float* stdv, gdl_stream_t stream);
+/* `normalization` with the caller's sensor range + `standardization` (utils/tensors.py:10-35 as tools/script_model.py:45-52 and
+ * :71-78 call them): ((norm_max - norm_min) * (x - image_min) / (image_max - image_min) + norm_min - mean[c]) / std[c] on a raw
+ * NCHW tile of `kind` (GDL_RAW_*), each step rounded to f32 in the reference's order.  image_max == image_min is an error. */
+int gdl_normalize_range(const void* in, int kind, float* out, int B, int C, int64_t HW, int image_min, int image_max,
+                        double norm_min, double norm_max, const float* mean, const float* stdv, gdl_stream_t stream);
 /* x[o, :inner] *= s[o]  (per-sample DropPath scaling, timm DropPath) */
 int gdl_scale_outer(void* x, int dtype, const float* s, int64_t outer, int64_t inner,
                     gdl_stream_t stream);
@@ -534,8 +539,13 @@ int gdl_sigmoid_threshold(const float* logits, int64_t total, float threshold, i
  * every pixel.  An upsample by at most 64 per direction. */
 int gdl_upsample_threshold(const float* low, int B, int Hi, int Wi, int64_t* mask, int Ho, int Wo, float threshold,
                            gdl_stream_t stream);
-/* f.softmax(output, dim=1) (K > 1) / f.sigmoid (K == 1) of the exported inference model (tools/script_model.py:55-59) */
+/* f.softmax(output, dim=1) (K > 1) / f.sigmoid (K == 1) of the exported inference model (tools/script_model.py:55-59); any K >= 1
+ * (up to 16 classes unrolled, more in a run-time loop) */
 int gdl_class_probs(const float* logits, int B, int K, int64_t HW, float* probs, gdl_stream_t stream);
+/* the same probabilities [B,K,Ho,Wo] from a head's own NHWC f32 map [B,Hi,Wi,K]: f.softmax(dim=1) (2 <= K <= 16) / f.sigmoid
+ * (K == 1) of F.interpolate(logits, (Ho, Wo)) (tools/script_model.py:53-58, :79-85 over dofa.py:89-95) without the resized tensor;
+ * the expressions of gdl_upsample_logits and gdl_class_probs per pixel.  Any positive sizes (as gdl_upsample_logits); other K fail. */
+int gdl_upsample_probs(const float* low, int B, int Hi, int Wi, int K, float* probs, int Ho, int Wo, gdl_stream_t stream);
 /* The constructor options of smp 0.5.0 DiceLoss (losses/dice.py) for the gdl_dice_*_opt_* entry points below; a null pointer
  * means smp's defaults (the plain gdl_dice_* entry points).  Read on the host when the call is made.  With `valid` = (target !=
  * ignore_index), compared as int64 (any value, negative ones included; all true without has_ignore_index):
