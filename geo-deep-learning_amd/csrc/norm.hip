@@ -93,18 +93,27 @@ __device__ __forceinline__ LaneMap lane_map(int lane, int C, int block_x) {
 // index into a per-wave [64 lanes][4] scratch row of the value lane-group `sub` holds for channel t of the block
 __device__ __forceinline__ int lane_slot(const LaneMap& m, int sub, int t) { return (sub * m.lpp + (t >> 2)) * 4 + (t & 3); }
 
+// Two pairs of sums per channel.  The PLAIN pair, sum x and sum x^2, is what var = E[x^2] - mean^2 has always been formed from here:
+// exact to f32 round-off while kappa = |mean| / std is small, but its f32 partials lose digits as kappa^2 (measured: 2e-4 of the
+// variance at kappa = 30, 2e-2 at 300, 17 % at 1000).  The PIVOTED pair, sum (x - p) and sum (x - p)^2 about the channel's value p at
+// pixel 0 (every block loads it; it lies within a few standard deviations of the mean), loses digits as ((mean - p) / std)^2 only.
+// bn_stats_final keeps the plain result where kappa <= 4 -- the well-conditioned channels keep the bits they have always had --
+// and takes the pivoted one beyond.  All partial rows of a launch share the pivot, so both pairs are added the same way:
+// ws[nsplit][2][C] plain, then ws[nsplit][2][C] pivoted.
 template <typename T>
 __global__ __launch_bounds__(256) void bn_stats_partial(const void* __restrict__ x, int64_t P, int C,
                                                         int64_t x_sP, float* __restrict__ ws) {
-  __shared__ float red[2][4][256];
+  __shared__ float red[4][4][256];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const LaneMap lm = lane_map(lane, C, blockIdx.x);
   const int c = lm.c, st = 4 * lm.nsub;
   const int nsplit = gridDim.y;
   const int64_t per = (P + nsplit - 1) / nsplit;
   const int64_t p0 = per * blockIdx.y, p1 = p0 + per < P ? p0 + per : P;
-  float s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
+  float s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, sp[4] = {0, 0, 0, 0}, qp[4] = {0, 0, 0, 0};
   if (c < C) {
+    float pv[4];
+    load4<T>(x, c, pv);
     int64_t p = p0 + w * lm.nsub + lm.sub;
     for (; p + 3 * st < p1; p += 4 * st) {      // four independent loads in flight per lane
       float v[4][4];
@@ -113,29 +122,45 @@ __global__ __launch_bounds__(256) void bn_stats_partial(const void* __restrict__
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) { s[j] += v[u][j]; q[j] += v[u][j] * v[u][j]; }
+        for (int j = 0; j < 4; ++j) {
+          s[j] += v[u][j]; q[j] += v[u][j] * v[u][j];
+          const float d = v[u][j] - pv[j];
+          sp[j] += d; qp[j] += d * d;
+        }
     }
     for (; p < p1; p += st) {
       float v[4];
       load4<T>(x, p * x_sP + c, v);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { s[j] += v[j]; q[j] += v[j] * v[j]; }
+      for (int j = 0; j < 4; ++j) {
+        s[j] += v[j]; q[j] += v[j] * v[j];
+        const float d = v[j] - pv[j];
+        sp[j] += d; qp[j] += d * d;
+      }
     }
   }
 #pragma unroll
-  for (int j = 0; j < 4; ++j) { red[0][w][lane * 4 + j] = s[j]; red[1][w][lane * 4 + j] = q[j]; }
+  for (int j = 0; j < 4; ++j) {
+    red[0][w][lane * 4 + j] = s[j]; red[1][w][lane * 4 + j] = q[j];
+    red[2][w][lane * 4 + j] = sp[j]; red[3][w][lane * 4 + j] = qp[j];
+  }
   __syncthreads();
   const int t = threadIdx.x;
   const int cc = blockIdx.x * 256 + t;
   if (cc < C) {
-    float ss = 0.f, qq = 0.f;
+    float ss = 0.f, qq = 0.f, ssp = 0.f, qqp = 0.f;
     for (int sub = 0; sub < lm.nsub; ++sub) {
       const int i = lane_slot(lm, sub, t);
       ss += (red[0][0][i] + red[0][1][i]) + (red[0][2][i] + red[0][3][i]);
       qq += (red[1][0][i] + red[1][1][i]) + (red[1][2][i] + red[1][3][i]);
+      ssp += (red[2][0][i] + red[2][1][i]) + (red[2][2][i] + red[2][3][i]);
+      qqp += (red[3][0][i] + red[3][1][i]) + (red[3][2][i] + red[3][3][i]);
     }
+    float* wsp = ws + (int64_t)nsplit * 2 * C;
     ws[((int64_t)blockIdx.y * 2 + 0) * C + cc] = ss;
     ws[((int64_t)blockIdx.y * 2 + 1) * C + cc] = qq;
+    wsp[((int64_t)blockIdx.y * 2 + 0) * C + cc] = ssp;
+    wsp[((int64_t)blockIdx.y * 2 + 1) * C + cc] = qqp;
   }
 }
 
@@ -182,18 +207,37 @@ __device__ __forceinline__ bool bn_final_reduce(double (&ps)[BN_FINAL_G][4], dou
   return true;
 }
 
+// `wsp` / `pivot`: the pivoted partial sums and the row of the tensor they were taken about (bn_stats_partial: pixel 0 of x, in x's
+// dtype), or NULL for producers that emit plain sums of x and x^2 only (the GEMM epilogue, the resized-conv forward sums)
+constexpr double BN_PLAIN_KAPPA2 = 16.0;     // (mean / std)^2 up to which the plain sums are kept
+
 __global__ __launch_bounds__(BN_FINAL_T) void bn_stats_final(const float* __restrict__ ws, int nsplit, int C, int64_t P,
                                                              float* __restrict__ mean, float* __restrict__ var, float* running_mean,
-                                                             float* running_var, float momentum) {
+                                                             float* running_var, float momentum, const float* __restrict__ wsp,
+                                                             const void* __restrict__ pivot, int pivot_dtype) {
   __shared__ double ps[BN_FINAL_G][4], pq[BN_FINAL_G][4];
   const int cl = threadIdx.x & 3, grp = threadIdx.x >> 2;
   const int c = blockIdx.x * 4 + cl;
-  double s = 0, q = 0;
+  double s = 0, q = 0, sp = 0, qp = 0;
   if (c < C) ordered_sum8_pair(ws, grp, nsplit, BN_FINAL_G, C, c, s, q);
-  if (!bn_final_reduce(ps, pq, cl, grp, s, q) || c >= C) return;
-  const double m = s / (double)P;
+  bool last = bn_final_reduce(ps, pq, cl, grp, s, q);
+  if (wsp) {
+    if (c < C) ordered_sum8_pair(wsp, grp, nsplit, BN_FINAL_G, C, c, sp, qp);
+    __syncthreads();
+    last = bn_final_reduce(ps, pq, cl, grp, sp, qp);
+  }
+  if (!last || c >= C) return;
+  double m = s / (double)P;
   double v = q / (double)P - m * m;
   v = v > 0 ? v : 0;
+  if (wsp) {
+    const double d = sp / (double)P;
+    double vp = qp / (double)P - d * d;
+    vp = vp > 0 ? vp : 0;
+    const double mp = d + (pivot_dtype == GDL_BF16 ? (double)__uint_as_float((uint32_t)((const uint16_t*)pivot)[c] << 16)
+                                                   : (double)((const float*)pivot)[c]);
+    if (mp * mp > BN_PLAIN_KAPPA2 * vp) { m = mp; v = vp; }
+  }
   mean[c] = (float)m;
   var[c] = (float)v;
   if (running_mean) {  // nn.BatchNorm2d: unbiased variance for the running estimate
@@ -779,11 +823,11 @@ __global__ __launch_bounds__(BNG_T) void bn_gelu_bwd_dx_kernel(const void* __res
 // 450 vs 461 tiles/s at batch 4, profiles/r05c_*).
 constexpr int BNS_T = 1024;      // threads per workgroup of the small-map kernels (16 waves: 5 pixels per thread at 36 x 36 x 4)
 
-// block-wide sum of 8 values per thread (4 channels x {first, second} sum): f32 butterflies inside each wave (what the
-// multi-workgroup kernels do inside a workgroup), then the 16 wave results in f64 through LDS in a fixed order -- deterministic.
-// Result valid in every thread.
-__device__ __forceinline__ void bns_block_sum(const float (&s)[4], const float (&q)[4], double (&out)[8], float (*red)[8]) {
-  float v[8] = {s[0], s[1], s[2], s[3], q[0], q[1], q[2], q[3]};
+// block-wide sum of 8 values per thread (4 channels x {first, second} sum): f64 butterflies inside each wave (a thread of a small
+// map holds a handful of pixels: f32 here would round the sums once per level for nothing), then the 16 wave results through LDS
+// in a fixed order -- deterministic.  Result valid in every thread.
+__device__ __forceinline__ void bns_block_sum(const float (&s)[4], const float (&q)[4], double (&out)[8], double (*red)[8]) {
+  double v[8] = {s[0], s[1], s[2], s[3], q[0], q[1], q[2], q[3]};
 #pragma unroll
   for (int j = 0; j < 8; ++j)
 #pragma unroll
@@ -798,7 +842,7 @@ __device__ __forceinline__ void bns_block_sum(const float (&s)[4], const float (
   for (int j = 0; j < 8; ++j) {
     double t = 0;
 #pragma unroll 1
-    for (int k = 0; k < BNS_T / 64; ++k) t += (double)red[k][j];
+    for (int k = 0; k < BNS_T / 64; ++k) t += red[k][j];
     out[j] = t;
   }
 }
@@ -809,9 +853,10 @@ __global__ __launch_bounds__(BNS_T) void bn_small_fwd_kernel(const void* __restr
                                                              const float* __restrict__ beta, float eps, int relu,
                                                              float* __restrict__ mean, float* __restrict__ var, float* running_mean,
                                                              float* running_var, float momentum) {
-  __shared__ float red[BNS_T / 64][8];
+  __shared__ double red[BNS_T / 64][8];
   const int t = threadIdx.x, c = blockIdx.x * 4;
-  float s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
+  float s[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0}, pv[4];
+  load4<T>(x, c, pv);                                  // sums about the value at pixel 0, as bn_stats_partial
   int64_t p = t;
   for (; p + 3 * BNS_T < P; p += 4 * BNS_T) {
     float v[4][4];
@@ -820,21 +865,21 @@ __global__ __launch_bounds__(BNS_T) void bn_small_fwd_kernel(const void* __restr
 #pragma unroll
     for (int u = 0; u < 4; ++u)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { s[j] += v[u][j]; q[j] += v[u][j] * v[u][j]; }
+      for (int j = 0; j < 4; ++j) { const float d = v[u][j] - pv[j]; s[j] += d; q[j] += d * d; }
   }
   for (; p < P; p += BNS_T) {
     float v[4];
     load4<T>(x, p * x_sP + c, v);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) { s[j] += v[j]; q[j] += v[j] * v[j]; }
+    for (int j = 0; j < 4; ++j) { const float d = v[j] - pv[j]; s[j] += d; q[j] += d * d; }
   }
   double acc[8];
   bns_block_sum(s, q, acc, red);
   float mu[4], sc[4], be[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const double m = acc[j] / (double)P;
-    double v = acc[4 + j] / (double)P - m * m;
+    const double d = acc[j] / (double)P, m = (double)pv[j] + d;
+    double v = acc[4 + j] / (double)P - d * d;
     v = v > 0 ? v : 0;
     if (t == 0) {
       mean[c + j] = (float)m;
@@ -884,7 +929,7 @@ __global__ __launch_bounds__(BNS_T) void bn_small_bwd_kernel(const void* __restr
                                                              const float* __restrict__ mean, const float* __restrict__ var,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                              int relu, float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  __shared__ float red[BNS_T / 64][8];
+  __shared__ double red[BNS_T / 64][8];
   const int t = threadIdx.x, c = blockIdx.x * 4;
   float mu[4], rs[4], ga[4], be[4];
 #pragma unroll
@@ -957,30 +1002,34 @@ __global__ __launch_bounds__(BNS_T) void bn_small_bwd_kernel(const void* __restr
 }
 
 // ---------------------------------------------------------------- SyncBatchNorm message (round 5)
-// One rank's statistics as the count-weighted message that is summed over the ranks: [n mean | n E[x^2] | n] (2 C + 1 floats),
+// One rank's statistics as the count-weighted message that is summed over the ranks: [n (mean - r) | n E[(x - r)^2] | n]
+// (2 C + 1 floats) about a per-channel pivot r that is the SAME on every rank (the layer's running_mean; NULL: r = 0) -- the f32
+// message then cancels digits in proportion to ((global mean - r) / std)^2 instead of (mean / std)^2 --
 // and the global statistics back out of the summed message (+ the running-estimate update with the unbiased variance and the
 // global count, which never leaves the device).  Replaces ~5 + ~10 one-line torch kernels per layer: with 21 train-mode
 // BatchNorms that was ~300 launches of a DDP + SyncBatchNorm step (configs/dofa_config_RGB.yaml:5-13).
 __global__ __launch_bounds__(256) void syncbn_pack_kernel(const float* __restrict__ mean, const float* __restrict__ var, float n, int C,
-                                                          float* __restrict__ out) {
+                                                          const float* __restrict__ pivot, float* __restrict__ out) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c < C) {
-    const float m = mean[c];
+    const float m = mean[c] - (pivot ? pivot[c] : 0.f);
     out[c] = m * n;
     out[C + c] = (var[c] + m * m) * n;
   }
   if (c == 0) out[2 * C] = n;
 }
 
-__global__ __launch_bounds__(256) void syncbn_unpack_kernel(const float* __restrict__ packed, int C, float* __restrict__ mean,
-                                                            float* __restrict__ var, float* running_mean, float* running_var,
-                                                            float momentum) {
+// (pivot may be running_mean itself: a thread reads its channel's pivot before it writes the running estimate)
+__global__ __launch_bounds__(256) void syncbn_unpack_kernel(const float* __restrict__ packed, int C, const float* pivot,
+                                                            float* __restrict__ mean, float* __restrict__ var, float* running_mean,
+                                                            float* running_var, float momentum) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
   const float total = packed[2 * C];
-  const float m = packed[c] / total;
-  float v = packed[C + c] / total - m * m;
+  const float d = packed[c] / total;
+  float v = packed[C + c] / total - d * d;
   v = v > 0.f ? v : 0.f;
+  const float m = d + (pivot ? pivot[c] : 0.f);
   mean[c] = m;
   var[c] = v;
   if (running_mean) {
@@ -1051,7 +1100,7 @@ extern "C" int gdl_layernorm_fwd(const float* x, int64_t x_stride, const float* 
 }
 
 extern "C" int64_t gdl_bn_stats_workspace(int64_t P, int C) {
-  return (int64_t)bn_nsplit(P, C) * 2 * C * sizeof(float);
+  return (int64_t)bn_nsplit(P, C) * 4 * C * sizeof(float);      // [nsplit][2][C] plain + [nsplit][2][C] pivoted sums
 }
 
 // One-launch train-mode BatchNorm(+ReLU) for small maps (see bn_small_fwd_kernel): statistics, running-estimate update and the
@@ -1090,18 +1139,19 @@ extern "C" int gdl_bn_small_bwd(const void* x, const void* dy, void* dx, int dty
   return GDL_OK;
 }
 
-extern "C" int gdl_syncbn_pack(const float* mean, const float* var, double count, int C, float* out, gdl_stream_t stream) {
+extern "C" int gdl_syncbn_pack(const float* mean, const float* var, double count, int C, const float* pivot, float* out,
+                               gdl_stream_t stream) {
   GDL_CHECK_ARG(mean && var && out && C > 0 && count > 0, "gdl_syncbn_pack: bad arguments");
-  hipLaunchKernelGGL(syncbn_pack_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, mean, var, (float)count, C, out);
+  hipLaunchKernelGGL(syncbn_pack_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, mean, var, (float)count, C, pivot, out);
   GDL_CHECK_LAUNCH("gdl_syncbn_pack");
   return GDL_OK;
 }
 
-extern "C" int gdl_syncbn_unpack(const float* packed, int C, float* mean, float* var, float* running_mean, float* running_var,
-                                 float momentum, gdl_stream_t stream) {
+extern "C" int gdl_syncbn_unpack(const float* packed, int C, const float* pivot, float* mean, float* var, float* running_mean,
+                                 float* running_var, float momentum, gdl_stream_t stream) {
   GDL_CHECK_ARG(packed && mean && var && C > 0 && (!running_mean == !running_var), "gdl_syncbn_unpack: bad arguments");
-  hipLaunchKernelGGL(syncbn_unpack_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, packed, C, mean, var, running_mean,
-                     running_var, momentum);
+  hipLaunchKernelGGL(syncbn_unpack_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, packed, C, pivot, mean, var,
+                     running_mean, running_var, momentum);
   GDL_CHECK_LAUNCH("gdl_syncbn_unpack");
   return GDL_OK;
 }
@@ -1117,7 +1167,8 @@ extern "C" int gdl_bn_stats(const void* x, int dtype, int64_t P, int C, int64_t 
   dim3 grid((C + 255) / 256, nsplit);
   if (dtype == GDL_BF16) hipLaunchKernelGGL(bn_stats_partial<uint16_t>, grid, dim3(256), 0, s, x, P, C, x_sP, ws);
   else hipLaunchKernelGGL(bn_stats_partial<float>, grid, dim3(256), 0, s, x, P, C, x_sP, ws);
-  hipLaunchKernelGGL(bn_stats_final, dim3((C + 3) / 4), dim3(BN_FINAL_T), 0, s, ws, nsplit, C, P, mean, var, running_mean, running_var, momentum);
+  hipLaunchKernelGGL(bn_stats_final, dim3((C + 3) / 4), dim3(BN_FINAL_T), 0, s, ws, nsplit, C, P, mean, var, running_mean, running_var, momentum,
+                     (const float*)(ws + (int64_t)nsplit * 2 * C), x, dtype);
   GDL_CHECK_LAUNCH("gdl_bn_stats");
   return GDL_OK;
 }
@@ -1128,7 +1179,7 @@ extern "C" int gdl_bn_stats_finalize(const float* ws, int nsplit, int C, int64_t
                                      float* running_var, float momentum, gdl_stream_t stream) {
   GDL_CHECK_ARG(ws && mean && var && nsplit > 0 && C > 0 && P > 0, "gdl_bn_stats_finalize: bad arguments");
   hipLaunchKernelGGL(bn_stats_final, dim3((C + 3) / 4), dim3(BN_FINAL_T), 0, (hipStream_t)stream, ws, nsplit, C, P, mean, var, running_mean,
-                     running_var, momentum);
+                     running_var, momentum, (const float*)nullptr, (const void*)nullptr, GDL_F32);
   GDL_CHECK_LAUNCH("gdl_bn_stats_finalize");
   return GDL_OK;
 }

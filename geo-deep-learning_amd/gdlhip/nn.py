@@ -298,31 +298,71 @@ _EVAL_BN_GRAD_MSG = ("gdlhip: autograd through eval-mode BatchNorm is not implem
 
 # ------------------------------------------------------------------ SyncBatchNorm exchange
 FUSE_SYNC_MESSAGE = os.environ.get("GDL_SYNC_MESSAGE_KERNELS", "1") != "0"   # A/B switch: 0 = the message is built by torch expressions
+# 1 = every statistics exchange first checks that its pivot (running_mean) is the same on all ranks: two more all-reduces per message
+SYNC_CHECK_PIVOT = os.environ.get("GDL_SYNC_CHECK_PIVOT", "0") == "1"
 
 
-def sync_batch_stats(mean: Tensor, var: Tensor, group=None, count: int | None = None):
+def check_sync_pivot(pivot: Tensor | None, group=None) -> None:
+    """The pivoted message is only right if every rank subtracts the SAME pivot (SyncBatchNorm without DDP, or with
+    broadcast_buffers=False after divergent loads, breaks that silently).  With GDL_SYNC_CHECK_PIVOT=1: raise if not."""
+    if not SYNC_CHECK_PIVOT or pivot is None:
+        return
+    lo, hi = pivot.clone(), pivot.clone()
+    dist.all_reduce(lo, op=dist.ReduceOp.MIN, group=group)
+    dist.all_reduce(hi, op=dist.ReduceOp.MAX, group=group)
+    if not torch.equal(lo, hi):
+        raise RuntimeError("gdlhip: running_mean differs between the ranks: the SyncBatchNorm statistics message needs identical "
+                           "buffers on every rank (DDP with broadcast_buffers=True, or load the same state everywhere)")
+
+
+def sync_message(mean: Tensor, var: Tensor, n: float, pivot: Tensor | None = None) -> list[Tensor]:
+    """One rank's share of the statistics message as torch expressions (what ops.syncbn_pack writes): the sums are taken about
+    ``pivot``, per-channel values that every rank holds identically (the layer's running_mean; None = 0), so that the f32
+    message cancels digits in proportion to ((global mean - pivot) / std)^2 and not to (mean / std)^2."""
+    d = mean if pivot is None else mean - pivot
+    return [d * n, (var + d * d) * n, mean.new_full((1,), n)]
+
+
+def sync_message_stats(packed: Tensor, c: int, pivot: Tensor | None = None):
+    """(global mean, global biased variance, global count) out of the summed message of sync_message (ops.syncbn_unpack)."""
+    total = packed[2 * c]
+    d = packed[:c] / total
+    gvar = (packed[c:2 * c] / total - d * d).clamp_min_(0).contiguous()
+    gmean = (d if pivot is None else d + pivot).contiguous()
+    return gmean, gvar, total
+
+
+def _sync_pivot(running_mean: Tensor | None, c: int) -> Tensor | None:
+    """The message pivot of a layer with c (possibly padded) channels: its running_mean (identical on every rank under DDP, which
+    broadcasts the buffers, and under SyncBatchNorm, which updates them alike), zero-padded; None (pivot 0) without buffers."""
+    if running_mean is None:
+        return None
+    rm = running_mean.detach()
+    return (rm if rm.numel() == c else nn.functional.pad(rm, (0, c - rm.numel()))).contiguous()
+
+
+def sync_batch_stats(mean: Tensor, var: Tensor, group=None, count: int | None = None, pivot: Tensor | None = None):
     """Merge per-rank batch statistics into global ones (nn.SyncBatchNorm forward): count-weighted, so a
     ragged last batch (ranks with different pixel counts) merges exactly like torch's all_gather of
-    [mean, invstd, count] does -- in ONE small all-reduce of 2C + 1 floats: sum_r n_r * [mean_r, E_r[x^2], 1].
+    [mean, invstd, count] does -- in ONE small all-reduce of 2C + 1 floats: sum_r n_r * [mean_r - r, E_r[(x - r)^2], 1]
+    about the pivot r = ``pivot`` (see sync_message; it must be identical on every rank).
     Returns (global mean, global biased variance, global count); the count stays a 0-dim DEVICE tensor (no host
     read-back: 21 layers per step would mean 21 stream syncs)."""
     n = float(count if count is not None else 1)
     c = mean.numel()
+    check_sync_pivot(pivot, group)
     if mean.is_cuda and FUSE_SYNC_MESSAGE:
         # one pack kernel, the all-reduce, one unpack kernel (the torch expressions below are ~12 one-line launches per layer)
         packed = torch.empty(2 * c + 1, device=mean.device, dtype=torch.float32)
-        ops.syncbn_pack(mean, var, n, packed)
+        ops.syncbn_pack(mean, var, n, packed, pivot)
         dist.all_reduce(packed, group=group)
         SYNC_MESSAGES[0] += 1
-        gmean, gvar = ops.syncbn_unpack(packed, c)
+        gmean, gvar = ops.syncbn_unpack(packed, c, pivot=pivot)
         return gmean, gvar, packed[2 * c]
-    packed = torch.cat([mean * n, (var + mean * mean) * n, mean.new_full((1,), n)])
+    packed = torch.cat(sync_message(mean, var, n, pivot))
     dist.all_reduce(packed, group=group)
     SYNC_MESSAGES[0] += 1
-    total = packed[2 * c]
-    gmean = (packed[:c] / total).contiguous()
-    gvar = (packed[c:2 * c] / total - gmean * gmean).clamp_min_(0).contiguous()
-    return gmean, gvar, total
+    return sync_message_stats(packed, c, pivot)
 
 
 def update_running_stats(running_mean, running_var, mean, var, momentum: float, count) -> None:
@@ -361,7 +401,7 @@ def _bn_train_stats(y, n, running_mean, running_var, momentum, sync_group, stats
     in_kernel = world == 1 and y.shape[-1] == n
     mean, var = _bn_local_stats(y, stats_done, *((running_mean, running_var) if in_kernel else (None, None)), momentum)
     if world > 1:
-        mean, var, total = sync_batch_stats(mean, var, sync_group or None, count=p_local)
+        mean, var, total = sync_batch_stats(mean, var, sync_group or None, count=p_local, pivot=_sync_pivot(running_mean, mean.numel()))
     if in_kernel:
         _mark_running(running_mean, running_var)
     elif running_mean is not None:
@@ -573,29 +613,30 @@ class _ConvBNActGroupTrain(Function):
             ys.append(y)
             locals_.append(_bn_local_stats(y, stats_done))
             counts.append(y.numel() // weight.shape[0])
-        # one message: per member [n * mean, n * E[x^2], n]  (count-weighted merge, see sync_batch_stats)
+        # one message: per member [n * (mean - r), n * E[(x - r)^2], n] about its running_mean r  (count-weighted merge, see sync_batch_stats)
         fused = FUSE_SYNC_MESSAGE and ys[0].is_cuda
+        pivots = [_sync_pivot(m[5], m[1].shape[0]) for m in mem]
+        for piv in pivots:
+            check_sync_pivot(piv, sync_group or None)
         if fused:      # every member packs its share straight into its slice of the message: no torch arithmetic, no cat
             packed = torch.empty(sum(2 * w.shape[0] + 1 for (_, w, *_r) in mem), device=ys[0].device, dtype=torch.float32)
             off = 0
-            for (mean, var), n in zip(locals_, counts):
-                ops.syncbn_pack(mean, var, float(n), packed[off:off + 2 * mean.numel() + 1])
+            for (mean, var), n, piv in zip(locals_, counts, pivots):
+                ops.syncbn_pack(mean, var, float(n), packed[off:off + 2 * mean.numel() + 1], piv)
                 off += 2 * mean.numel() + 1
         else:
-            packed = torch.cat([t for (mean, var), n in zip(locals_, counts)
-                                for t in (mean * float(n), (var + mean * mean) * float(n), mean.new_full((1,), float(n)))])
+            packed = torch.cat([t for (mean, var), n, piv in zip(locals_, counts, pivots) for t in sync_message(mean, var, float(n), piv)])
         dist.all_reduce(packed, group=sync_group or None)
         SYNC_MESSAGES[0] += 1
         outs, saved, cfg, off = [], [], [], 0
-        for (x, weight, conv_bias, gamma, beta, rm, rv), (momentum, eps, pad, relu, up4), y, n in zip(mem, metas, ys, counts):
+        for (x, weight, conv_bias, gamma, beta, rm, rv), (momentum, eps, pad, relu, up4), y, n, piv in zip(mem, metas, ys, counts, pivots):
             c = weight.shape[0]
             total = packed[off + 2 * c]
-            if fused:  # global statistics + the running-estimate update in one kernel
-                gmean, gvar = ops.syncbn_unpack(packed[off:off + 2 * c + 1], c, rm, rv, momentum)
+            if fused:  # global statistics + the running-estimate update in one kernel (it reads the pivot, rm, before it writes rm)
+                gmean, gvar = ops.syncbn_unpack(packed[off:off + 2 * c + 1], c, rm, rv, momentum, pivot=piv)
                 _mark_running(rm, rv)
             else:
-                gmean = (packed[off:off + c] / total).contiguous()
-                gvar = (packed[off + c:off + 2 * c] / total - gmean * gmean).clamp_min_(0).contiguous()
+                gmean, gvar, _ = sync_message_stats(packed[off:off + 2 * c + 1], c, piv)
                 if rm is not None:
                     update_running_stats(rm, rv, gmean, gvar, momentum, total)
             off += 2 * c + 1

@@ -413,25 +413,34 @@ def bn_apply(x: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, beta: Tensor, 
     return out
 
 
-def syncbn_pack(mean: Tensor, var: Tensor, count: float, out: Tensor) -> None:
-    """out[0:C] = count * mean, out[C:2C] = count * (var + mean^2), out[2C] = count: one rank's share of the SyncBatchNorm message
-    (out: a contiguous f32 slice of 2 C + 1 elements of the message buffer)."""
+def _syncbn_pivot(pivot: Tensor | None, c: int, what: str) -> Tensor | None:
+    if pivot is not None and (pivot.numel() != c or pivot.dtype != torch.float32 or not pivot.is_contiguous()):
+        raise ValueError(f"{what}: pivot must be a contiguous f32 tensor of C elements")
+    return pivot
+
+
+def syncbn_pack(mean: Tensor, var: Tensor, count: float, out: Tensor, pivot: Tensor | None = None) -> None:
+    """With d = mean - pivot: out[0:C] = count * d, out[C:2C] = count * (var + d^2), out[2C] = count: one rank's share of the
+    SyncBatchNorm message (out: a contiguous f32 slice of 2 C + 1 elements of the message buffer).  ``pivot`` [C]: values that are
+    identical on every rank (the layer's running_mean), None = 0; syncbn_unpack must be given the same."""
     c = mean.numel()
     if out.numel() != 2 * c + 1 or out.dtype != torch.float32 or not out.is_contiguous():
         raise ValueError("syncbn_pack: out must be a contiguous f32 slice of 2 C + 1 elements")
-    check(_lib.load().gdl_syncbn_pack(_p(mean), _p(var), float(count), c, _p(out), _stream()), "gdl_syncbn_pack")
+    check(_lib.load().gdl_syncbn_pack(_p(mean), _p(var), float(count), c, _p(_syncbn_pivot(pivot, c, "syncbn_pack")), _p(out), _stream()),
+          "gdl_syncbn_pack")
 
 
 def syncbn_unpack(packed: Tensor, channels: int, running_mean: Tensor | None = None, running_var: Tensor | None = None,
-                  momentum: float = 0.1):
-    """(global mean, global biased var) from the all-reduced message slice [sum n mean | sum n E[x^2] | sum n]; the running
-    estimates are updated with the unbiased variance over the global count (which stays on the device)."""
+                  momentum: float = 0.1, pivot: Tensor | None = None):
+    """(global mean, global biased var) from the all-reduced message slice [sum n (mean - pivot) | sum n E[(x - pivot)^2] | sum n];
+    the running estimates are updated with the unbiased variance over the global count (which stays on the device).  ``pivot``: what
+    syncbn_pack was given (it may be ``running_mean`` itself: it is read before the update)."""
     if packed.numel() != 2 * channels + 1 or packed.dtype != torch.float32 or not packed.is_contiguous():
         raise ValueError("syncbn_unpack: packed must be a contiguous f32 slice of 2 C + 1 elements")
     mean = torch.empty(channels, device=packed.device, dtype=torch.float32)
     var = torch.empty_like(mean)
-    check(_lib.load().gdl_syncbn_unpack(_p(packed), channels, _p(mean), _p(var), _p(running_mean), _p(running_var), momentum, _stream()),
-          "gdl_syncbn_unpack")
+    check(_lib.load().gdl_syncbn_unpack(_p(packed), channels, _p(_syncbn_pivot(pivot, channels, "syncbn_unpack")), _p(mean), _p(var),
+                                        _p(running_mean), _p(running_var), momentum, _stream()), "gdl_syncbn_unpack")
     return mean, var
 
 

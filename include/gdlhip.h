@@ -136,7 +136,9 @@ int gdl_layernorm_fwd(const float* x, int64_t x_stride, const float* gamma, cons
                       void* y, int y_dtype, int64_t rows, int D, float eps, gdl_stream_t stream);
 
 /* BatchNorm2d, training mode, NHWC [P pixels][C] (F.batch_norm(training=True)).
- * stats: per-channel sum and sum of squares in f64-free two-level f32 (deterministic). */
+ * stats: per-channel f32 partial sums, finished in f64 in a fixed order (deterministic, no atomics), of x and x^2 AND of
+ * (x - pivot) and (x - pivot)^2 about the channel's value at pixel 0: channels with |mean| / std <= 4 get E[x^2] - mean^2 from
+ * the plain sums, the others E[(x - pivot)^2] - E[x - pivot]^2, which stays accurate at any |mean| / std. */
 int gdl_bn_stats(const void* x, int dtype, int64_t P, int C, int64_t x_sP, float* mean,
                  float* var_biased, float* running_mean, float* running_var, float momentum,
                  float* workspace, int64_t workspace_bytes, gdl_stream_t stream);
@@ -159,14 +161,16 @@ int gdl_bn_bwd_dx(const void* x, const void* dy, void* dx, int dtype, int64_t P,
                   const float* dgamma_sum, const float* dbeta_sum, int64_t P_total,
                   gdl_stream_t stream);
 /* SyncBatchNorm (torch.nn.SyncBatchNorm under `sync_batchnorm: true`, configs/dofa_config_RGB.yaml:13): the cross-rank exchange is
- * ONE all-reduce(SUM) of a count-weighted message per direction.  gdl_syncbn_pack writes this rank's [count * mean | count * E[x^2] |
- * count] (2 C + 1 floats) into `out` (a slice of the message buffer); gdl_syncbn_unpack reads the summed message back into the
- * GLOBAL mean / biased variance and updates the running estimates with the unbiased variance over the global count (which stays
- * on the device).  gdl_bn_bwd_dx_sync = gdl_bn_bwd_dx with the all-reduced sums and that device-side count (`total_count` points
+ * ONE all-reduce(SUM) of a count-weighted message per direction.  gdl_syncbn_pack writes this rank's [count * (mean - pivot) | count *
+ * E[(x - pivot)^2] | count] (2 C + 1 floats) into `out` (a slice of the message buffer); gdl_syncbn_unpack reads the summed message
+ * back into the GLOBAL mean / biased variance and updates the running estimates with the unbiased variance over the global count
+ * (which stays on the device).  `pivot` [C]: any per-channel values that are IDENTICAL on every rank and the same in both calls
+ * (the layer's running_mean before this step's update -- unpack may be given running_mean as pivot and as output); NULL = 0.  The
+ * f32 message loses digits of the variance in proportion to ((global mean - pivot) / std)^2.  gdl_bn_bwd_dx_sync = gdl_bn_bwd_dx with the all-reduced sums and that device-side count (`total_count` points
  * at entry 2 C of the forward message). */
-int gdl_syncbn_pack(const float* mean, const float* var, double count, int C, float* out, gdl_stream_t stream);
-int gdl_syncbn_unpack(const float* packed, int C, float* mean, float* var, float* running_mean, float* running_var, float momentum,
-                      gdl_stream_t stream);
+int gdl_syncbn_pack(const float* mean, const float* var, double count, int C, const float* pivot, float* out, gdl_stream_t stream);
+int gdl_syncbn_unpack(const float* packed, int C, const float* pivot, float* mean, float* var, float* running_mean, float* running_var,
+                      float momentum, gdl_stream_t stream);
 int gdl_bn_bwd_dx_sync(const void* x, const void* dy, void* dx, int dtype, int64_t P, int C, int64_t x_sP, int64_t dy_sP, int64_t dx_sP,
                        const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
                        const float* dgamma_sum, const float* dbeta_sum, const float* total_count, gdl_stream_t stream);
