@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/gdlhip.h"
+#include "../../include/gdlhip_debug.h"   // the gdl_debug_* hooks: declared once, so a definition that drifts does not compile
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;

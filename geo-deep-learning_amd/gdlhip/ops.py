@@ -337,11 +337,11 @@ def conv_wgrad(x: Tensor, dy: Tensor, *, R: int, S: int, stride: int = 1, pad: i
     a.dy_sB, a.dy_sH, a.dy_sW = dy4.stride(0), dy4.stride(1), dy4.stride(2)
     a.dw, a.dw_sN, a.accumulate = dw.data_ptr(), dw.stride(0), int(accumulate)
     a.nz, a.nz_inner = 1, 1
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_conv_wgrad_workspace(C.byref(a))
     ws = torch.empty(max(nbytes, 4) // 4, device=x.device, dtype=torch.float32)
     a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
-    check(lib.gdl_conv_wgrad(C.byref(a), _stream()), "gdl_conv_wgrad")
+    lib.gdl_conv_wgrad(C.byref(a), _stream())
     return dw
 
 
@@ -353,9 +353,9 @@ def layernorm(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, out_dtype: tor
     D = x.shape[-1]
     x2 = x.reshape(-1, D)
     y = torch.empty((x2.shape[0], D), device=x.device, dtype=out_dtype)
-    check(_lib.load().gdl_layernorm_fwd(_p(x2), x2.stride(0), _p(_f32vec(gamma, D, "gamma")),
-                                        _p(_f32vec(beta, D, "beta")), _p(y), dt(y), x2.shape[0], D,
-                                        eps, _stream()), "gdl_layernorm_fwd")
+    _lib.checked().gdl_layernorm_fwd(_p(x2), x2.stride(0), _p(_f32vec(gamma, D, "gamma")),
+                                     _p(_f32vec(beta, D, "beta")), _p(y), dt(y), x2.shape[0], D,
+                                     eps, _stream())
     return y.reshape(x.shape)
 
 
@@ -382,11 +382,11 @@ def bn_stats(x: Tensor, running_mean: Tensor | None = None, running_var: Tensor 
     P, Cc, sP = _pix(x, "bn_stats x")
     mean = torch.empty(Cc, device=x.device, dtype=torch.float32)
     var = torch.empty_like(mean)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_bn_stats_workspace(P, Cc)
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
-    check(lib.gdl_bn_stats(_p(x), dt(x), P, Cc, sP, _p(mean), _p(var), _p(running_mean),
-                           _p(running_var), momentum, _p(ws), nbytes, _stream()), "gdl_bn_stats")
+    lib.gdl_bn_stats(_p(x), dt(x), P, Cc, sP, _p(mean), _p(var), _p(running_mean),
+                     _p(running_var), momentum, _p(ws), nbytes, _stream())
     return mean, var
 
 
@@ -397,8 +397,8 @@ def bn_stats_finalize(partials: Tensor, rows: int, channels: int, pixels: int, r
     _need_cuda(partials)
     mean = torch.empty(channels, device=partials.device, dtype=torch.float32)
     var = torch.empty_like(mean)
-    check(_lib.load().gdl_bn_stats_finalize(_p(partials), rows, channels, pixels, _p(mean), _p(var), _p(running_mean),
-                                            _p(running_var), momentum, _stream()), "gdl_bn_stats_finalize")
+    _lib.checked().gdl_bn_stats_finalize(_p(partials), rows, channels, pixels, _p(mean), _p(var), _p(running_mean),
+                                         _p(running_var), momentum, _stream())
     return mean, var
 
 
@@ -408,8 +408,8 @@ def bn_apply(x: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, beta: Tensor, 
     if out is None:
         out = torch.empty(x.shape, device=x.device, dtype=x.dtype)
     Po, Co, sPo = _pix(out, "bn_apply out")
-    check(_lib.load().gdl_bn_apply(_p(x), _p(out), dt(x), P, Cc, sP, sPo, _p(mean), _p(var),
-                                   _p(gamma), _p(beta), eps, int(relu), _stream()), "gdl_bn_apply")
+    _lib.checked().gdl_bn_apply(_p(x), _p(out), dt(x), P, Cc, sP, sPo, _p(mean), _p(var),
+                                _p(gamma), _p(beta), eps, int(relu), _stream())
     return out
 
 
@@ -426,8 +426,7 @@ def syncbn_pack(mean: Tensor, var: Tensor, count: float, out: Tensor, pivot: Ten
     c = mean.numel()
     if out.numel() != 2 * c + 1 or out.dtype != torch.float32 or not out.is_contiguous():
         raise ValueError("syncbn_pack: out must be a contiguous f32 slice of 2 C + 1 elements")
-    check(_lib.load().gdl_syncbn_pack(_p(mean), _p(var), float(count), c, _p(_syncbn_pivot(pivot, c, "syncbn_pack")), _p(out), _stream()),
-          "gdl_syncbn_pack")
+    _lib.checked().gdl_syncbn_pack(_p(mean), _p(var), float(count), c, _p(_syncbn_pivot(pivot, c, "syncbn_pack")), _p(out), _stream())
 
 
 def syncbn_unpack(packed: Tensor, channels: int, running_mean: Tensor | None = None, running_var: Tensor | None = None,
@@ -439,8 +438,8 @@ def syncbn_unpack(packed: Tensor, channels: int, running_mean: Tensor | None = N
         raise ValueError("syncbn_unpack: packed must be a contiguous f32 slice of 2 C + 1 elements")
     mean = torch.empty(channels, device=packed.device, dtype=torch.float32)
     var = torch.empty_like(mean)
-    check(_lib.load().gdl_syncbn_unpack(_p(packed), channels, _p(_syncbn_pivot(pivot, channels, "syncbn_unpack")), _p(mean), _p(var),
-                                        _p(running_mean), _p(running_var), momentum, _stream()), "gdl_syncbn_unpack")
+    _lib.checked().gdl_syncbn_unpack(_p(packed), channels, _p(_syncbn_pivot(pivot, channels, "syncbn_unpack")), _p(mean), _p(var),
+                                     _p(running_mean), _p(running_var), momentum, _stream())
     return mean, var
 
 
@@ -453,8 +452,8 @@ def bn_bwd_dx_sync(x, dy, mean, var, gamma, beta, eps, relu, dgamma_sum, dbeta_s
     _, _, sPx = _pix(dx, "bn_bwd dx")
     if total_count.dtype != torch.float32 or total_count.numel() != 1:
         raise ValueError("bn_bwd_dx_sync: total_count must be one f32 element on the device")
-    check(_lib.load().gdl_bn_bwd_dx_sync(_p(x), _p(dy), _p(dx), dt(x), P, Cc, sP, sPd, sPx, _p(mean), _p(var), _p(gamma), _p(beta), eps,
-                                         int(relu), _p(dgamma_sum), _p(dbeta_sum), _p(total_count), _stream()), "gdl_bn_bwd_dx_sync")
+    _lib.checked().gdl_bn_bwd_dx_sync(_p(x), _p(dy), _p(dx), dt(x), P, Cc, sP, sPd, sPx, _p(mean), _p(var), _p(gamma), _p(beta), eps,
+                                      int(relu), _p(dgamma_sum), _p(dbeta_sum), _p(total_count), _stream())
     return dx
 
 
@@ -488,8 +487,8 @@ def bn_small_fwd(x: Tensor, gamma: Tensor, beta: Tensor, eps: float, relu: bool,
     _, _, sPo = _pix(out, "bn_small_fwd out")
     mean = torch.empty(Cc, device=x.device, dtype=torch.float32)
     var = torch.empty_like(mean)
-    check(_lib.load().gdl_bn_small_fwd(_p(x), _p(out), dt(x), P, Cc, sP, sPo, _p(gamma), _p(beta), eps, int(relu), _p(mean), _p(var),
-                                       _p(running_mean), _p(running_var), momentum, _stream()), "gdl_bn_small_fwd")
+    _lib.checked().gdl_bn_small_fwd(_p(x), _p(out), dt(x), P, Cc, sP, sPo, _p(gamma), _p(beta), eps, int(relu), _p(mean), _p(var),
+                                    _p(running_mean), _p(running_var), momentum, _stream())
     return out, mean, var
 
 
@@ -503,8 +502,8 @@ def bn_small_bwd(x: Tensor, dy: Tensor, mean, var, gamma, beta, eps, relu, out: 
     _, _, sPx = _pix(dx, "bn_small_bwd dx")
     dgamma = torch.empty(Cc, device=x.device, dtype=torch.float32)
     dbeta = torch.empty_like(dgamma)
-    check(_lib.load().gdl_bn_small_bwd(_p(x), _p(dy), _p(dx), dt(x), P, Cc, sP, sPd, sPx, _p(mean), _p(var), _p(gamma), _p(beta), eps,
-                                       int(relu), _p(dgamma), _p(dbeta), _stream()), "gdl_bn_small_bwd")
+    _lib.checked().gdl_bn_small_bwd(_p(x), _p(dy), _p(dx), dt(x), P, Cc, sP, sPd, sPx, _p(mean), _p(var), _p(gamma), _p(beta), eps,
+                                    int(relu), _p(dgamma), _p(dbeta), _stream())
     return dx, dgamma, dbeta
 
 
@@ -515,12 +514,12 @@ def bn_bwd_reduce(x, dy, mean, var, gamma, beta, eps, relu):
         raise ValueError("bn_bwd: dy dtype must match x")
     dgamma = torch.empty(Cc, device=x.device, dtype=torch.float32)
     dbeta = torch.empty_like(dgamma)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_bn_stats_workspace(P, Cc)
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
-    check(lib.gdl_bn_bwd_reduce(_p(x), _p(dy), dt(x), P, Cc, sP, sPd, _p(mean), _p(var), _p(gamma),
-                                _p(beta), eps, int(relu), _p(dgamma), _p(dbeta), _p(ws), nbytes,
-                                _stream()), "gdl_bn_bwd_reduce")
+    lib.gdl_bn_bwd_reduce(_p(x), _p(dy), dt(x), P, Cc, sP, sPd, _p(mean), _p(var), _p(gamma),
+                          _p(beta), eps, int(relu), _p(dgamma), _p(dbeta), _p(ws), nbytes,
+                          _stream())
     return dgamma, dbeta
 
 
@@ -530,9 +529,9 @@ def bn_bwd_dx(x, dy, mean, var, gamma, beta, eps, relu, dgamma_sum, dbeta_sum, p
     _, _, sPd = _pix(dy, "bn_bwd dy")
     dx = out if out is not None else torch.empty(x.shape, device=x.device, dtype=x.dtype)
     _, _, sPx = _pix(dx, "bn_bwd dx")
-    check(_lib.load().gdl_bn_bwd_dx(_p(x), _p(dy), _p(dx), dt(x), P, Cc, sP, sPd, sPx, _p(mean),
-                                    _p(var), _p(gamma), _p(beta), eps, int(relu), _p(dgamma_sum),
-                                    _p(dbeta_sum), p_total, _stream()), "gdl_bn_bwd_dx")
+    _lib.checked().gdl_bn_bwd_dx(_p(x), _p(dy), _p(dx), dt(x), P, Cc, sP, sPd, sPx, _p(mean),
+                                 _p(var), _p(gamma), _p(beta), eps, int(relu), _p(dgamma_sum),
+                                 _p(dbeta_sum), p_total, _stream())
     return dx
 
 
@@ -545,8 +544,8 @@ def bn_gelu_apply(x: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, beta: Ten
     if out is None:
         out = torch.empty(x.shape, device=x.device, dtype=x.dtype)
     _, _, sPo = _pix(out, "bn_gelu_apply out")
-    check(_lib.load().gdl_bn_gelu_apply(_p(x), _p(out), dt(x), P, Cc, sP, sPo, _p(_f32vec(mean, Cc, "mean")), _p(_f32vec(var, Cc, "var")),
-                                        _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")), eps, _stream()), "gdl_bn_gelu_apply")
+    _lib.checked().gdl_bn_gelu_apply(_p(x), _p(out), dt(x), P, Cc, sP, sPo, _p(_f32vec(mean, Cc, "mean")), _p(_f32vec(var, Cc, "var")),
+                                     _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")), eps, _stream())
     return out
 
 
@@ -559,11 +558,11 @@ def bn_gelu_bwd_reduce(x: Tensor, dy: Tensor, mean, var, gamma, beta, eps):
         raise ValueError("bn_gelu_bwd: dy must match x in shape and dtype")
     dgamma = torch.empty(Cc, device=x.device, dtype=torch.float32)
     dbeta = torch.empty_like(dgamma)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_bn_stats_workspace(P, Cc)
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
-    check(lib.gdl_bn_gelu_bwd_reduce(_p(x), _p(dy), dt(x), P, Cc, sP, sPd, _p(mean), _p(var), _p(gamma), _p(beta), eps, _p(dgamma),
-                                     _p(dbeta), _p(ws), nbytes, _stream()), "gdl_bn_gelu_bwd_reduce")
+    lib.gdl_bn_gelu_bwd_reduce(_p(x), _p(dy), dt(x), P, Cc, sP, sPd, _p(mean), _p(var), _p(gamma), _p(beta), eps, _p(dgamma),
+                               _p(dbeta), _p(ws), nbytes, _stream())
     return dgamma, dbeta
 
 
@@ -580,8 +579,8 @@ def bn_gelu_bwd_dx(x: Tensor, dy: Tensor, mean, var, gamma, beta, eps, dgamma_su
     _, _, sPx = _pix(dx, "bn_gelu_bwd dx")
     if total_count is not None and (total_count.dtype != torch.float32 or total_count.numel() != 1):
         raise ValueError("bn_gelu_bwd_dx: total_count must be one f32 element on the device")
-    check(_lib.load().gdl_bn_gelu_bwd_dx(_p(x), _p(dy), _p(dx), dt(x), P, Cc, sP, sPd, sPx, _p(mean), _p(var), _p(gamma), _p(beta), eps,
-                                         _p(dgamma_sum), _p(dbeta_sum), int(p_total), _p(total_count), _stream()), "gdl_bn_gelu_bwd_dx")
+    _lib.checked().gdl_bn_gelu_bwd_dx(_p(x), _p(dy), _p(dx), dt(x), P, Cc, sP, sPd, sPx, _p(mean), _p(var), _p(gamma), _p(beta), eps,
+                                      _p(dgamma_sum), _p(dbeta_sum), int(p_total), _p(total_count), _stream())
     return dx
 
 
@@ -603,7 +602,7 @@ def convt2x2_pack(weight: Tensor, dtype: torch.dtype) -> tuple[Tensor, Tensor]:
     _convt_channels(cin, cout, dtype)
     fwd = torch.empty((4, cout, cin), device=weight.device, dtype=dtype)
     dgrad = torch.empty((cin, 4 * cout), device=weight.device, dtype=dtype)
-    check(_lib.load().gdl_convt2x2_pack(_p(weight), cin, cout, dt(dtype), _p(fwd), _p(dgrad), _stream()), "gdl_convt2x2_pack")
+    _lib.checked().gdl_convt2x2_pack(_p(weight), cin, cout, dt(dtype), _p(fwd), _p(dgrad), _stream())
     return fwd, dgrad
 
 
@@ -657,7 +656,7 @@ def convt2x2_wgrad(x: Tensor, dy: Tensor, out: Tensor | None = None, accumulate:
         out, accumulate = torch.empty((cin, cout, 2, 2), device=x.device, dtype=torch.float32), False
     elif tuple(out.shape) != (cin, cout, 2, 2) or out.dtype != torch.float32 or not out.is_contiguous():
         raise ValueError("convt2x2_wgrad: out must be a contiguous f32 [Cin, Cout, 2, 2] tensor")
-    check(_lib.load().gdl_convt2x2_unpack_grad(_p(dw), cin, cout, _p(out), int(accumulate), _stream()), "gdl_convt2x2_unpack_grad")
+    _lib.checked().gdl_convt2x2_unpack_grad(_p(dw), cin, cout, _p(out), int(accumulate), _stream())
     return out
 
 
@@ -675,10 +674,9 @@ def bilinear(x: Tensor, size: tuple[int, int], out: Tensor | None = None,
     o4 = _nhwc4(out, "bilinear out")
     if tuple(o4.shape) != (B, Ho, Wo, Cc):
         raise ValueError(f"bilinear: out shape {tuple(o4.shape)} != {(B, Ho, Wo, Cc)}")
-    check(_lib.load().gdl_bilinear_fwd(_p(x4), dt(x4), B, Hi, Wi, Cc, x4.stride(0), x4.stride(1),
-                                       x4.stride(2), _p(o4), dt(o4), Ho, Wo, o4.stride(0),
-                                       o4.stride(1), o4.stride(2), int(accumulate), _stream()),
-          "gdl_bilinear_fwd")
+    _lib.checked().gdl_bilinear_fwd(_p(x4), dt(x4), B, Hi, Wi, Cc, x4.stride(0), x4.stride(1),
+                                    x4.stride(2), _p(o4), dt(o4), Ho, Wo, o4.stride(0),
+                                    o4.stride(1), o4.stride(2), int(accumulate), _stream())
     return out
 
 
@@ -692,9 +690,8 @@ def bilinear_add(base: Tensor, x: Tensor) -> Tensor:
         raise ValueError(f"bilinear_add: {tuple(x4.shape)} {x4.dtype} does not resize onto {tuple(b4.shape)} {b4.dtype}")
     b4 = b4 if b4.is_contiguous() else b4.contiguous()
     out = torch.empty((B, Ho, Wo, Cc), device=base.device, dtype=base.dtype)
-    check(_lib.load().gdl_bilinear_fwd_add(_p(x4), dt(x4), B, x4.shape[1], x4.shape[2], Cc, x4.stride(0), x4.stride(1), x4.stride(2),
-                                           _p(b4), _p(out), dt(out), Ho, Wo, out.stride(0), out.stride(1), out.stride(2), _stream()),
-          "gdl_bilinear_fwd_add")
+    _lib.checked().gdl_bilinear_fwd_add(_p(x4), dt(x4), B, x4.shape[1], x4.shape[2], Cc, x4.stride(0), x4.stride(1), x4.stride(2),
+                                        _p(b4), _p(out), dt(out), Ho, Wo, out.stride(0), out.stride(1), out.stride(2), _stream())
     return out
 
 
@@ -708,9 +705,9 @@ def bilinear_add_bn(x_pre: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, bet
     if x4.shape[0] != B or x4.shape[3] != Cc or x4.dtype != b4.dtype or not b4.is_contiguous() or not x4.is_contiguous():
         raise ValueError(f"bilinear_add_bn: dense maps of one dtype expected, {tuple(x4.shape)} {x4.dtype} onto {tuple(b4.shape)} {b4.dtype}")
     out = torch.empty((B, Ho, Wo, Cc), device=x_pre.device, dtype=x_pre.dtype)
-    check(_lib.load().gdl_bilinear_fwd_add_bn(_p(x4), dt(x4), B, x4.shape[1], x4.shape[2], Cc, _p(b4), _p(_f32vec(mean, Cc, "mean")),
-                                              _p(_f32vec(var, Cc, "var")), _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")),
-                                              eps, int(relu), _p(out), Ho, Wo, _stream()), "gdl_bilinear_fwd_add_bn")
+    _lib.checked().gdl_bilinear_fwd_add_bn(_p(x4), dt(x4), B, x4.shape[1], x4.shape[2], Cc, _p(b4), _p(_f32vec(mean, Cc, "mean")),
+                                           _p(_f32vec(var, Cc, "var")), _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")),
+                                           eps, int(relu), _p(out), Ho, Wo, _stream())
     return out
 
 
@@ -727,16 +724,14 @@ def resize_conv3x3_bwd_gather(dy: Tensor, in_size: tuple[int, int]) -> Tensor:
     B, Ho, Wo, N = d4.shape
     Hi, Wi = in_size
     g = torch.empty((B, Hi, Wi, 9 * N), device=dy.device, dtype=dy.dtype)
-    lib = _lib.load()
+    lib = _lib.checked()
     one_pass = lib.gdl_resize_conv3x3_bwd_gather_one_pass(dt(d4), B, Ho, Wo, N, Hi, Wi)     # matrix-core form (bf16, x2 / x4)
     if GATHER_TWO_PASS and Ho >= 2 * Hi and not one_pass:      # upsampling factors >= 2: the single VALU pass is multiply-add bound
         nbytes = lib.gdl_resize_conv3x3_bwd_gather_workspace(dt(d4), B, Wo, N, Hi)
         ws = torch.empty(nbytes // d4.element_size(), device=dy.device, dtype=dy.dtype)
-        check(lib.gdl_resize_conv3x3_bwd_gather2(_p(d4), dt(d4), B, Ho, Wo, N, _p(g), Hi, Wi, _p(ws), nbytes, _stream()),
-              "gdl_resize_conv3x3_bwd_gather2")
+        lib.gdl_resize_conv3x3_bwd_gather2(_p(d4), dt(d4), B, Ho, Wo, N, _p(g), Hi, Wi, _p(ws), nbytes, _stream())
     else:
-        check(lib.gdl_resize_conv3x3_bwd_gather(_p(d4), dt(d4), B, Ho, Wo, N, _p(g), Hi, Wi, _stream()),
-              "gdl_resize_conv3x3_bwd_gather")
+        lib.gdl_resize_conv3x3_bwd_gather(_p(d4), dt(d4), B, Ho, Wo, N, _p(g), Hi, Wi, _stream())
     return g
 
 
@@ -759,9 +754,9 @@ def resize_conv3x3_bwd_gather_bn(dz: Tensor, y: Tensor, in_size: tuple[int, int]
     Hi, Wi = in_size
     g = torch.empty((B, Hi, Wi, 9 * N), device=dz.device, dtype=dz.dtype)
     coef = torch.empty(4 * N, device=dz.device, dtype=torch.float32)
-    check(_lib.load().gdl_resize_conv3x3_bwd_gather_bn(_p(dz), _p(y), dt(dz), B, Ho, Wo, N, _p(g), Hi, Wi, _p(mean), _p(var), _p(gamma),
-                                                       _p(beta), eps, int(relu), _p(dgamma_sum), _p(dbeta_sum), p_total, _p(coef),
-                                                       _stream()), "gdl_resize_conv3x3_bwd_gather_bn")
+    _lib.checked().gdl_resize_conv3x3_bwd_gather_bn(_p(dz), _p(y), dt(dz), B, Ho, Wo, N, _p(g), Hi, Wi, _p(mean), _p(var), _p(gamma),
+                                                    _p(beta), eps, int(relu), _p(dgamma_sum), _p(dbeta_sum), p_total, _p(coef),
+                                                    _stream())
     return g
 
 
@@ -803,7 +798,7 @@ def resize_conv3x3_fwd_sum(zs: list[Tensor], size: tuple[int, int], addvec: Tens
     out = torch.empty((B, size[0], size[1], N), device=zs[0].device, dtype=zs[0].dtype)
     cell = [z for z in z4 if resize_conv3x3_fwd_ok((z.shape[1], z.shape[2]), size, B)]
     other = [z for z in z4 if not resize_conv3x3_fwd_ok((z.shape[1], z.shape[2]), size, B)]
-    lib = _lib.load()
+    lib = _lib.checked()
     av = _f32vec(addvec, N, "addvec")
     if cell:
         n = len(cell)
@@ -811,14 +806,12 @@ def resize_conv3x3_fwd_sum(zs: list[Tensor], size: tuple[int, int], addvec: Tens
         hs = (C.c_int * 3)(*([z.shape[1] for z in cell] + [1] * (3 - n)))
         ws = (C.c_int * 3)(*([z.shape[2] for z in cell] + [1] * (3 - n)))
         # (addvec and the ReLU belong to the LAST pass over `out`)
-        check(lib.gdl_resize_conv3x3_fwd_sum(ptrs, hs, ws, n, dt(cell[0]), B, N, _p(out), size[0], size[1],
-                                             _p(None if other else av), int(relu and not other), _stream()),
-              "gdl_resize_conv3x3_fwd_sum")
+        lib.gdl_resize_conv3x3_fwd_sum(ptrs, hs, ws, n, dt(cell[0]), B, N, _p(out), size[0], size[1],
+                                       _p(None if other else av), int(relu and not other), _stream())
     for i, z in enumerate(other):
         last = i == len(other) - 1
-        check(lib.gdl_resize_conv3x3_fwd_sum_any(_p(z), z.shape[1], z.shape[2], dt(z), B, N, _p(out), size[0], size[1],
-                                                 int(bool(cell) or i > 0), _p(av if last else None), int(relu and last), _stream()),
-              "gdl_resize_conv3x3_fwd_sum_any")
+        lib.gdl_resize_conv3x3_fwd_sum_any(_p(z), z.shape[1], z.shape[2], dt(z), B, N, _p(out), size[0], size[1],
+                                           int(bool(cell) or i > 0), _p(av if last else None), int(relu and last), _stream())
     return out
 
 
@@ -836,17 +829,16 @@ def resize_conv3x3_fwd_sum_bn(zs: list[Tensor], size: tuple[int, int], addvec: T
     out = torch.empty((B, size[0], size[1], N), device=zs[0].device, dtype=zs[0].dtype)
     mean = torch.empty(N, device=out.device, dtype=torch.float32)
     var = torch.empty_like(mean)
-    lib = _lib.load()
+    lib = _lib.checked()
     rows = lib.gdl_resize_conv3x3_fwd_sum_bn_rows(B, size[0], size[1])
     wsp = torch.empty(rows * 2 * N, device=out.device, dtype=torch.float32)
     n = len(z4)
     ptrs = (C.c_void_p * 3)(*([z.data_ptr() for z in z4] + [None] * (3 - n)))
     hs = (C.c_int * 3)(*([z.shape[1] for z in z4] + [1] * (3 - n)))
     ws = (C.c_int * 3)(*([z.shape[2] for z in z4] + [1] * (3 - n)))
-    check(lib.gdl_resize_conv3x3_fwd_sum_bn(ptrs, hs, ws, n, dt(z4[0]), B, N, _p(out), size[0], size[1],
-                                            _p(_f32vec(addvec, N, "addvec")), _p(wsp), wsp.numel() * 4, _p(mean), _p(var),
-                                            _p(running_mean), _p(running_var), momentum, _stream()),
-          "gdl_resize_conv3x3_fwd_sum_bn")
+    lib.gdl_resize_conv3x3_fwd_sum_bn(ptrs, hs, ws, n, dt(z4[0]), B, N, _p(out), size[0], size[1],
+                                      _p(_f32vec(addvec, N, "addvec")), _p(wsp), wsp.numel() * 4, _p(mean), _p(var),
+                                      _p(running_mean), _p(running_var), momentum, _stream())
     return out, mean, var
 
 
@@ -886,8 +878,8 @@ def copy_cast(x: Tensor, out: Tensor | None = None, out_dtype: torch.dtype | Non
         raise ValueError(f"copy_cast: out shape {tuple(o4.shape)} != {(B, H, W, Cc)}")
     if B * H > 65535 or Cc % 4:        # very tall batches / odd channel counts: the identity resample handles any layout
         return bilinear(x, (H, W), out=out)      # (same HBM-bound copy through the flat-index kernel: no slow path to warn about)
-    check(_lib.load().gdl_copy_cast(_p(x4), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1), x4.stride(2), _p(o4), dt(o4),
-                                    o4.stride(0), o4.stride(1), o4.stride(2), _stream()), "gdl_copy_cast")
+    _lib.checked().gdl_copy_cast(_p(x4), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1), x4.stride(2), _p(o4), dt(o4),
+                                 o4.stride(0), o4.stride(1), o4.stride(2), _stream())
     return out
 
 
@@ -906,8 +898,7 @@ def bilinear_sum(xs: list[Tensor], size: tuple[int, int]) -> Tensor:
     ptrs = (C.c_void_p * 3)(*([x.data_ptr() for x in x4s] + [None] * (3 - n)))
     hs = (C.c_int * 3)(*([x.shape[1] for x in x4s] + [1] * (3 - n)))
     ws = (C.c_int * 3)(*([x.shape[2] for x in x4s] + [1] * (3 - n)))
-    check(_lib.load().gdl_bilinear_sum_fwd(ptrs, hs, ws, n, dt(x4s[0]), B, Cc, _p(out), size[0], size[1], _stream()),
-          "gdl_bilinear_sum_fwd")
+    _lib.checked().gdl_bilinear_sum_fwd(ptrs, hs, ws, n, dt(x4s[0]), B, Cc, _p(out), size[0], size[1], _stream())
     return out
 
 
@@ -919,10 +910,9 @@ def bilinear_bwd(dout: Tensor, in_size: tuple[int, int], din: Tensor | None = No
     if din is None:
         din = torch.empty((B, Hi, Wi, Cc), device=dout.device, dtype=din_dtype or dout.dtype)
     i4 = _nhwc4(din, "bilinear_bwd din")
-    check(_lib.load().gdl_bilinear_bwd(_p(d4), dt(d4), B, Ho, Wo, Cc, d4.stride(0), d4.stride(1),
-                                       d4.stride(2), _p(i4), dt(i4), Hi, Wi, i4.stride(0),
-                                       i4.stride(1), i4.stride(2), int(accumulate), _stream()),
-          "gdl_bilinear_bwd")
+    _lib.checked().gdl_bilinear_bwd(_p(d4), dt(d4), B, Ho, Wo, Cc, d4.stride(0), d4.stride(1),
+                                    d4.stride(2), _p(i4), dt(i4), Hi, Wi, i4.stride(0),
+                                    i4.stride(1), i4.stride(2), int(accumulate), _stream())
     return din
 
 
@@ -930,9 +920,9 @@ def adaptive_avgpool(x: Tensor, s: int, out_dtype: torch.dtype | None = None) ->
     x4 = _nhwc4(x, "avgpool x")
     B, Hi, Wi, Cc = x4.shape
     out = torch.empty((B, s, s, Cc), device=x.device, dtype=out_dtype or x.dtype)
-    check(_lib.load().gdl_adaptive_avgpool_fwd(_p(x4), dt(x4), B, Hi, Wi, Cc, x4.stride(0),
-                                               x4.stride(1), x4.stride(2), _p(out), dt(out), s,
-                                               _stream()), "gdl_adaptive_avgpool_fwd")
+    _lib.checked().gdl_adaptive_avgpool_fwd(_p(x4), dt(x4), B, Hi, Wi, Cc, x4.stride(0),
+                                            x4.stride(1), x4.stride(2), _p(out), dt(out), s,
+                                            _stream())
     return out
 
 
@@ -945,10 +935,9 @@ def adaptive_avgpool_bwd(dout: Tensor, in_size: tuple[int, int], din: Tensor | N
     if din is None:
         din = torch.empty((B, Hi, Wi, Cc), device=dout.device, dtype=dout.dtype)
     i4 = _nhwc4(din, "avgpool_bwd din")
-    check(_lib.load().gdl_adaptive_avgpool_bwd(_p(dout), dt(dout), B, s, Cc, _p(i4), dt(i4), Hi, Wi,
-                                               i4.stride(0), i4.stride(1), i4.stride(2),
-                                               int(accumulate), _stream()),
-          "gdl_adaptive_avgpool_bwd")
+    _lib.checked().gdl_adaptive_avgpool_bwd(_p(dout), dt(dout), B, s, Cc, _p(i4), dt(i4), Hi, Wi,
+                                            i4.stride(0), i4.stride(1), i4.stride(2),
+                                            int(accumulate), _stream())
     return din
 
 
@@ -959,8 +948,8 @@ def pad_nhwc(x: Tensor, pad_h: int, pad_w: int, zero: bool = False) -> Tensor:
     x4 = _nhwc4(x, "pad_nhwc x")
     B, H, W, Cc = x4.shape
     out = torch.empty((B, H + 2 * pad_h, W + 2 * pad_w, Cc), device=x.device, dtype=x.dtype)
-    check(_lib.load().gdl_pad_nhwc(_p(x4), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1), x4.stride(2), _p(out),
-                                   pad_h, pad_w, int(zero), _stream()), "gdl_pad_nhwc")
+    _lib.checked().gdl_pad_nhwc(_p(x4), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1), x4.stride(2), _p(out),
+                                pad_h, pad_w, int(zero), _stream())
     return out
 
 
@@ -972,8 +961,8 @@ def subpix4_weights(w32: Tensor, Cc: int, out_dtype: torch.dtype) -> dict:
         raise ValueError("subpix4_weights: contiguous f32 [N, 9*C] expected")
     mk = lambda taps: torch.empty((4, N, taps * Cc), device=w32.device, dtype=out_dtype)  # noqa: E731
     out = {"g22": mk(4), "g23": mk(6), "g32": mk(6), "g33": mk(9), "lines": mk(3)}
-    check(_lib.load().gdl_subpix4_weights(_p(w32), N, Cc, dt(out["g22"]), _p(out["g22"]), _p(out["g23"]), _p(out["g32"]),
-                                          _p(out["g33"]), _p(out["lines"]), _stream()), "gdl_subpix4_weights")
+    _lib.checked().gdl_subpix4_weights(_p(w32), N, Cc, dt(out["g22"]), _p(out["g22"]), _p(out["g23"]), _p(out["g32"]),
+                                       _p(out["g33"]), _p(out["lines"]), _stream())
     return out
 
 
@@ -1051,8 +1040,8 @@ def _attn_check(q: Tensor, k: Tensor, v: Tensor, num_heads: int):
 def _v_transposed(v: Tensor, num_heads: int, hd: int, npad: int) -> Tensor:
     B, Nkv, _ = v.shape
     vt = torch.empty((B, num_heads, hd, npad), device=v.device, dtype=v.dtype)
-    check(_lib.load().gdl_v_transpose(_p(v), dt(v), B, Nkv, num_heads, hd, v.stride(0), v.stride(1), _p(vt),
-                                      npad, _stream()), "gdl_v_transpose")
+    _lib.checked().gdl_v_transpose(_p(v), dt(v), B, Nkv, num_heads, hd, v.stride(0), v.stride(1), _p(vt),
+                                   npad, _stream())
     return vt
 
 
@@ -1066,7 +1055,7 @@ def attention_unfused(q: Tensor, k: Tensor, v: Tensor, num_heads: int) -> Tensor
     if hd % al != 0:
         raise ValueError(f"attention: head_dim {hd} must be a multiple of {al} for {q.dtype}")
     npad = (Nkv + 63) // 64 * 64
-    lib = _lib.load()
+    lib = _lib.checked()
     vt = _v_transposed(v, num_heads, hd, npad)
     scores = torch.empty((B, num_heads, Nq, npad), device=q.device, dtype=q.dtype)
     a = ConvArgs()
@@ -1083,8 +1072,8 @@ def attention_unfused(q: Tensor, k: Tensor, v: Tensor, num_heads: int) -> Tensor
     a.w_sZ0, a.w_sZ1 = k.stride(0), hd
     a.out_sZ0, a.out_sZ1 = num_heads * Nq * npad, Nq * npad
     batched_gemm_raw(a)
-    check(lib.gdl_softmax_rows(_p(scores), _p(scores), dt(scores), B * num_heads * Nq, Nkv, npad,
-                               _stream()), "gdl_softmax_rows")
+    lib.gdl_softmax_rows(_p(scores), _p(scores), dt(scores), B * num_heads * Nq, Nkv, npad,
+                         _stream())
     out = torch.empty((B, Nq, D), device=q.device, dtype=q.dtype)
     a = ConvArgs()
     a.inp, a.dtype = scores.data_ptr(), dt(scores)
@@ -1112,10 +1101,9 @@ def attention_flash(q: Tensor, k: Tensor, v: Tensor, num_heads: int, return_lse:
         raise ValueError("attention_flash: needs bf16 and head_dim 64")
     out = torch.empty((B, Nq, D), device=q.device, dtype=q.dtype)
     lse = torch.empty((B, num_heads, Nq), device=q.device, dtype=torch.float32) if return_lse else None
-    check(_lib.load().gdl_flash_attn_fwd2(_p(q), q.stride(0), q.stride(1), _p(k), k.stride(0), k.stride(1),
-                                          _p(v), v.stride(0), v.stride(1), _p(out), out.stride(0), out.stride(1),
-                                          _p(lse), B, num_heads, Nq, Nkv, float(hd) ** -0.5, _stream()),
-          "gdl_flash_attn_fwd2")
+    _lib.checked().gdl_flash_attn_fwd2(_p(q), q.stride(0), q.stride(1), _p(k), k.stride(0), k.stride(1),
+                                       _p(v), v.stride(0), v.stride(1), _p(out), out.stride(0), out.stride(1),
+                                       _p(lse), B, num_heads, Nq, Nkv, float(hd) ** -0.5, _stream())
     return (out, lse) if return_lse else out
 
 
@@ -1125,9 +1113,9 @@ def attention_flash_v1(q: Tensor, k: Tensor, v: Tensor, num_heads: int) -> Tenso
     npad = (Nkv + 63) // 64 * 64
     vt = _v_transposed(v, num_heads, hd, npad)
     out = torch.empty((B, Nq, D), device=q.device, dtype=q.dtype)
-    check(_lib.load().gdl_flash_attn_fwd(_p(q), q.stride(0), q.stride(1), _p(k), k.stride(0), k.stride(1),
-                                         _p(vt), _p(out), B, num_heads, Nq, Nkv, npad, float(hd) ** -0.5,
-                                         _stream()), "gdl_flash_attn_fwd")
+    _lib.checked().gdl_flash_attn_fwd(_p(q), q.stride(0), q.stride(1), _p(k), k.stride(0), k.stride(1),
+                                      _p(vt), _p(out), B, num_heads, Nq, Nkv, npad, float(hd) ** -0.5,
+                                      _stream())
     return out
 
 
@@ -1155,11 +1143,11 @@ def attention_flash_bwd(q: Tensor, k: Tensor, v: Tensor, o: Tensor, do: Tensor, 
     dvec = torch.empty_like(lse)
     nbytes = _lib.load().gdl_flash_attn_bwd_workspace(B, num_heads, Nq, Nkv)
     ws = torch.empty(nbytes // 4, device=q.device, dtype=torch.float32) if nbytes else None
-    check(_lib.load().gdl_flash_attn_bwd(
+    _lib.checked().gdl_flash_attn_bwd(
         _p(q), q.stride(0), q.stride(1), _p(k), k.stride(0), k.stride(1), _p(v), v.stride(0), v.stride(1),
         _p(o), o.stride(0), o.stride(1), _p(do), do.stride(0), do.stride(1), _p(lse), _p(dvec),
         _p(dq), dq.stride(0), dq.stride(1), _p(dk), dk.stride(0), dk.stride(1), _p(dv), dv.stride(0), dv.stride(1),
-        B, num_heads, Nq, Nkv, float(hd) ** -0.5, _p(ws), nbytes, _stream()), "gdl_flash_attn_bwd")
+        B, num_heads, Nq, Nkv, float(hd) ** -0.5, _p(ws), nbytes, _stream())
 
 
 def split_qkv(qkv: Tensor):
@@ -1177,8 +1165,8 @@ def dwconv3x3(x: Tensor, w9: Tensor, bias: Tensor, gelu: bool, out_dtype: torch.
     if w9.shape != (9, Cc) or w9.dtype != torch.float32 or not w9.is_contiguous():
         raise ValueError("dwconv3x3: w9 must be contiguous f32 [9, C]")
     out = torch.empty(x.shape, device=x.device, dtype=out_dtype or x.dtype)
-    check(_lib.load().gdl_dwconv3x3(_p(x), dt(x), B, H, W, Cc, _p(w9), _p(_f32vec(bias, Cc, "bias")), int(gelu),
-                                    _p(out), dt(out), _stream()), "gdl_dwconv3x3")
+    _lib.checked().gdl_dwconv3x3(_p(x), dt(x), B, H, W, Cc, _p(w9), _p(_f32vec(bias, Cc, "bias")), int(gelu),
+                                 _p(out), dt(out), _stream())
     return out
 
 
@@ -1206,9 +1194,9 @@ def layernorm_bwd(x: Tensor, dy: Tensor, gamma: Tensor, eps: float, dres: Tensor
     dgamma = torch.empty(D, device=x.device, dtype=torch.float32) if dgamma is None else dgamma
     dbeta = torch.empty(D, device=x.device, dtype=torch.float32) if dbeta is None else dbeta
     ws, nbytes = _colreduce_ws(rows, D, 2, x.device)
-    check(_lib.load().gdl_layernorm_bwd(_p(x2), x2.stride(0), _p(dy), dt(dy), _p(_f32vec(gamma, D, "gamma")), _p(r2),
-                                        0 if r2 is None else r2.stride(0), _p(dx), D, rows, D, eps, _p(dgamma),
-                                        _p(dbeta), int(accumulate), _p(ws), nbytes, _stream()), "gdl_layernorm_bwd")
+    _lib.checked().gdl_layernorm_bwd(_p(x2), x2.stride(0), _p(dy), dt(dy), _p(_f32vec(gamma, D, "gamma")), _p(r2),
+                                     0 if r2 is None else r2.stride(0), _p(dx), D, rows, D, eps, _p(dgamma),
+                                     _p(dbeta), int(accumulate), _p(ws), nbytes, _stream())
     return dx.reshape(x.shape), dgamma, dbeta
 
 
@@ -1222,8 +1210,8 @@ def colsum(x: Tensor, out: Tensor | None = None, accumulate: bool = False) -> Te
     if out is None:
         out = torch.empty(Cc, device=x.device, dtype=torch.float32)
     ws, nbytes = _colreduce_ws(x2.shape[0], Cc, 1, x.device)
-    check(_lib.load().gdl_colsum(_p(x2), dt(x2), x2.shape[0], Cc, x2.stride(0), _p(out), int(accumulate), _p(ws),
-                                 nbytes, _stream()), "gdl_colsum")
+    _lib.checked().gdl_colsum(_p(x2), dt(x2), x2.shape[0], Cc, x2.stride(0), _p(out), int(accumulate), _p(ws),
+                              nbytes, _stream())
     return out
 
 
@@ -1242,11 +1230,11 @@ def layerscale_bwd(g: Tensor, z: Tensor | None, gamma: Tensor | None, batch_scal
         dgamma = torch.empty(Cc, device=g.device, dtype=torch.float32) if dgamma is None else dgamma
         ws, nbytes = _colreduce_ws(B * N, Cc, 1, g.device)
     zz = z if gamma is not None else None
-    check(_lib.load().gdl_layerscale_bwd(_p(g), _p(zz), F32 if zz is None else dt(zz),
-                                         _p(None if gamma is None else _f32vec(gamma, Cc, "gamma")),
-                                         _p(None if batch_scale is None else _f32vec(batch_scale, B, "batch_scale")),
-                                         B * N, N, Cc, _p(dz), dt(dz), _p(dgamma if gamma is not None else None),
-                                         int(accumulate), _p(ws), nbytes, _stream()), "gdl_layerscale_bwd")
+    _lib.checked().gdl_layerscale_bwd(_p(g), _p(zz), F32 if zz is None else dt(zz),
+                                      _p(None if gamma is None else _f32vec(gamma, Cc, "gamma")),
+                                      _p(None if batch_scale is None else _f32vec(batch_scale, B, "batch_scale")),
+                                      B * N, N, Cc, _p(dz), dt(dz), _p(dgamma if gamma is not None else None),
+                                      int(accumulate), _p(ws), nbytes, _stream())
     return dz, (dgamma if gamma is not None else None)
 
 
@@ -1260,9 +1248,8 @@ def dwconv3x3_gelu_bwd(u: Tensor, dy: Tensor, w9: Tensor, bias: Tensor):
     dw9 = torch.empty((9, Cc), device=u.device, dtype=torch.float32)
     db = torch.empty(Cc, device=u.device, dtype=torch.float32)
     ws, nbytes = _colreduce_ws(B * H * W, Cc, 10, u.device)
-    check(_lib.load().gdl_dwconv3x3_gelu_bwd(_p(u), _p(dy), dt(u), B, H, W, Cc, _p(w9), _p(_f32vec(bias, Cc, "bias")),
-                                             _p(dpre), _p(dw9), _p(db), 0, _p(ws), nbytes, _stream()),
-          "gdl_dwconv3x3_gelu_bwd")
+    _lib.checked().gdl_dwconv3x3_gelu_bwd(_p(u), _p(dy), dt(u), B, H, W, Cc, _p(w9), _p(_f32vec(bias, Cc, "bias")),
+                                          _p(dpre), _p(dw9), _p(db), 0, _p(ws), nbytes, _stream())
     zero_b = torch.zeros(Cc, device=u.device, dtype=torch.float32)
     du = dwconv3x3(dpre, w9.flip(0).contiguous(), zero_b, False)
     return du, dw9, db
@@ -1287,10 +1274,10 @@ def chan_weights(pos: Tensor, W0: Tensor, b0: Tensor, W2: Tensor, b2: Tensor, W1
     cw = torch.empty((Cn, E), device=pos.device, dtype=torch.float32)
     hb = torch.empty((Cn, H1), device=pos.device, dtype=torch.float32)
     w1b = W1[:, E:]
-    check(_lib.load().gdl_chan_weights_fwd(_p(pos), Cn, PD, HD, E, H1, _p(W0), _p(_f32vec(b0, HD, "weight_gen.0.bias")),
-                                           _p(W2), _p(_f32vec(b2, E, "weight_gen.2.bias")), _p(w1b), W1.stride(0),
-                                           _p(_f32vec(b1, H1, "channel_attention.0.bias")), _p(hid), _p(cw), _p(hb),
-                                           _stream()), "gdl_chan_weights_fwd")
+    _lib.checked().gdl_chan_weights_fwd(_p(pos), Cn, PD, HD, E, H1, _p(W0), _p(_f32vec(b0, HD, "weight_gen.0.bias")),
+                                        _p(W2), _p(_f32vec(b2, E, "weight_gen.2.bias")), _p(w1b), W1.stride(0),
+                                        _p(_f32vec(b1, H1, "channel_attention.0.bias")), _p(hid), _p(cw), _p(hb),
+                                        _stream())
     return hid, cw, hb
 
 
@@ -1302,8 +1289,8 @@ def chan_weights_bwd(pos: Tensor, W2: Tensor, hid: Tensor, cw: Tensor, dcw: Tens
     _f32c(dcw, (Cn, E), "dcw"), _f32c(dhb, (Cn, H1), "dhb"), _f32c(W2, (E, HD), "weight_gen.2.weight")
     dev = pos.device
     outs = [torch.empty(sh, device=dev, dtype=torch.float32) for sh in ((HD, PD), (HD,), (E, HD), (E,), (H1, PD), (H1,))]
-    check(_lib.load().gdl_chan_weights_bwd(_p(pos), Cn, PD, HD, E, H1, _p(W2), _p(hid), _p(cw), _p(dcw), _p(dhb),
-                                           *[_p(o) for o in outs], _stream()), "gdl_chan_weights_bwd")
+    _lib.checked().gdl_chan_weights_bwd(_p(pos), Cn, PD, HD, E, H1, _p(W2), _p(hid), _p(cw), _p(dcw), _p(dhb),
+                                        *[_p(o) for o in outs], _stream())
     return tuple(outs)
 
 
@@ -1317,9 +1304,9 @@ def chan_pool(conv: Tensor, cw: Tensor, W1: Tensor, hb: Tensor, w2: Tensor, b2s:
         raise ValueError("chan_pool: W1 must be f32 [H1, >= E] with unit column stride")
     agg = torch.empty((B, P, E), device=conv.device, dtype=torch.float32)
     attn = torch.empty((B, P, Cn), device=conv.device, dtype=torch.float32)
-    check(_lib.load().gdl_chan_pool_fwd(_p(conv), B, Cn, P, E, H1, _p(cw), _p(W1), W1.stride(0), _p(hb),
-                                        _p(_f32vec(w2, H1, "channel_attention.2.weight")), float(b2s), _p(agg), _p(attn),
-                                        _stream()), "gdl_chan_pool_fwd")
+    _lib.checked().gdl_chan_pool_fwd(_p(conv), B, Cn, P, E, H1, _p(cw), _p(W1), W1.stride(0), _p(hb),
+                                     _p(_f32vec(w2, H1, "channel_attention.2.weight")), float(b2s), _p(agg), _p(attn),
+                                     _stream())
     return agg, attn
 
 
@@ -1329,13 +1316,13 @@ def chan_pool_bwd(conv: Tensor, cw: Tensor, W1: Tensor, hb: Tensor, w2: Tensor, 
     B, Cn, P, E = conv.shape
     H1 = hb.shape[1]
     _f32c(dagg, (B, P, E), "dagg")
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_chan_pool_workspace(B, Cn, P, E, H1)
     ws = torch.empty(max(nbytes, 4) // 4, device=conv.device, dtype=torch.float32)
     dconv = torch.empty_like(conv)
     grads = torch.empty(H1 * E + Cn * H1 + H1 + Cn * E, device=conv.device, dtype=torch.float32)
-    check(lib.gdl_chan_pool_bwd(_p(conv), B, Cn, P, E, H1, _p(cw), _p(W1), W1.stride(0), _p(hb), _p(w2), float(b2s),
-                                _p(dagg), _p(dconv), _p(grads), _p(ws), nbytes, _stream()), "gdl_chan_pool_bwd")
+    lib.gdl_chan_pool_bwd(_p(conv), B, Cn, P, E, H1, _p(cw), _p(W1), W1.stride(0), _p(hb), _p(w2), float(b2s),
+                          _p(dagg), _p(dconv), _p(grads), _p(ws), nbytes, _stream())
     o1, o2, o3 = H1 * E, H1 * E + Cn * H1, H1 * E + Cn * H1 + H1
     return dconv, grads[:o1].view(H1, E), grads[o1:o2].view(Cn, H1), grads[o2:o3], grads[o3:].view(Cn, E)
 
@@ -1347,8 +1334,8 @@ def col2im(cols: Tensor, B: int, Ho: int, Wo: int, R: int, S: int, Cc: int, stri
     if not cols.is_contiguous() or cols.numel() != B * Ho * Wo * R * S * Cc:
         raise ValueError("col2im: contiguous [B*Ho*Wo, R*S*C] expected")
     dx = torch.empty((B, H, W, Cc), device=cols.device, dtype=out_dtype)
-    check(_lib.load().gdl_col2im(_p(cols), dt(cols), B, Ho, Wo, R, S, Cc, stride, pad, H, W, _p(dx), dt(dx),
-                                 dx.stride(0), dx.stride(1), dx.stride(2), _stream()), "gdl_col2im")
+    _lib.checked().gdl_col2im(_p(cols), dt(cols), B, Ho, Wo, R, S, Cc, stride, pad, H, W, _p(dx), dt(dx),
+                              dx.stride(0), dx.stride(1), dx.stride(2), _stream())
     return dx
 
 
@@ -1416,19 +1403,18 @@ def attention_bwd(q: Tensor, k: Tensor, v: Tensor, do: Tensor, num_heads: int, d
             raise ValueError("attention_bwd: gradient tensor shape / dtype / stride mismatch")
     Hh = num_heads
     npad = (Nkv + 63) // 64 * 64
-    lib = _lib.load()
+    lib = _lib.checked()
     nz = B * Hh
     sc_z = (Hh * Nq * npad, Nq * npad)
     scale = float(hd) ** -0.5
     P = torch.empty((B, Hh, Nq, npad), device=q.device, dtype=cdt)
     _bgemm(q, q.stride(1), (q.stride(0), hd), k, k.stride(1), (k.stride(0), hd), P, npad, sc_z, Nq, hd, Nkv, nz, Hh,
            scale)
-    check(lib.gdl_softmax_rows(_p(P), _p(P), dt(P), nz * Nq, Nkv, npad, _stream()), "gdl_softmax_rows")
+    lib.gdl_softmax_rows(_p(P), _p(P), dt(P), nz * Nq, Nkv, npad, _stream())
     dS = torch.empty_like(P)
     _bgemm(do, do.stride(1), (do.stride(0), hd), v, v.stride(1), (v.stride(0), hd), dS, npad, sc_z, Nq, hd, Nkv, nz, Hh,
            1.0)
-    check(lib.gdl_softmax_bwd_rows(_p(P), _p(dS), _p(dS), dt(P), nz * Nq, Nkv, npad, scale, _stream()),
-          "gdl_softmax_bwd_rows")
+    lib.gdl_softmax_bwd_rows(_p(P), _p(dS), _p(dS), dt(P), nz * Nq, Nkv, npad, scale, _stream())
     kt = _v_transposed(k, Hh, hd, npad)                                    # K^T [B,H,hd,npad]
     _bgemm(dS, npad, sc_z, kt, npad, (Hh * hd * npad, hd * npad), dq, dq.stride(1), (dq.stride(0), hd), Nq, npad, hd,
            nz, Hh, 1.0)
@@ -1448,8 +1434,8 @@ def maxpool3x3s2(x: Tensor) -> Tensor:
     x4 = _nhwc4(x, "maxpool x")
     B, H, W, Cc = x4.shape
     out = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc), device=x.device, dtype=x.dtype)
-    check(_lib.load().gdl_maxpool3x3s2_fwd(_p(x4), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1), x4.stride(2), _p(out),
-                                           out.stride(0), out.stride(1), out.stride(2), _stream()), "gdl_maxpool3x3s2_fwd")
+    _lib.checked().gdl_maxpool3x3s2_fwd(_p(x4), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1), x4.stride(2), _p(out),
+                                        out.stride(0), out.stride(1), out.stride(2), _stream())
     return out
 
 
@@ -1457,9 +1443,9 @@ def maxpool3x3s2_bwd(x: Tensor, dout: Tensor) -> Tensor:
     x4, d4 = _nhwc4(x, "maxpool_bwd x"), _nhwc4(dout, "maxpool_bwd dout")
     B, H, W, Cc = x4.shape
     din = torch.empty((B, H, W, Cc), device=x.device, dtype=x.dtype)
-    check(_lib.load().gdl_maxpool3x3s2_bwd(_p(x4), _p(d4), _p(din), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1),
-                                           x4.stride(2), d4.stride(0), d4.stride(1), d4.stride(2), din.stride(0),
-                                           din.stride(1), din.stride(2), _stream()), "gdl_maxpool3x3s2_bwd")
+    _lib.checked().gdl_maxpool3x3s2_bwd(_p(x4), _p(d4), _p(din), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1),
+                                        x4.stride(2), d4.stride(0), d4.stride(1), d4.stride(2), din.stride(0),
+                                        din.stride(1), din.stride(2), _stream())
     return din
 
 
@@ -1471,8 +1457,8 @@ def maxpool2x2s2(x: Tensor) -> Tensor:
     if H < 2 or W < 2:
         raise ValueError(f"maxpool2x2s2: the map must be at least 2 x 2, got {H} x {W}")
     out = torch.empty((B, H // 2, W // 2, Cc), device=x.device, dtype=x.dtype)
-    check(_lib.load().gdl_maxpool2x2s2_fwd(_p(x4), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1), x4.stride(2), _p(out),
-                                           out.stride(0), out.stride(1), out.stride(2), _stream()), "gdl_maxpool2x2s2_fwd")
+    _lib.checked().gdl_maxpool2x2s2_fwd(_p(x4), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1), x4.stride(2), _p(out),
+                                        out.stride(0), out.stride(1), out.stride(2), _stream())
     return out
 
 
@@ -1484,9 +1470,9 @@ def maxpool2x2s2_bwd(x: Tensor, dout: Tensor) -> Tensor:
     if tuple(d4.shape) != (B, H // 2, W // 2, Cc) or d4.dtype != x4.dtype:
         raise ValueError(f"maxpool2x2s2_bwd: dout {tuple(d4.shape)} {d4.dtype} does not match x {tuple(x4.shape)} {x4.dtype}")
     din = torch.empty((B, H, W, Cc), device=x.device, dtype=x.dtype)
-    check(_lib.load().gdl_maxpool2x2s2_bwd(_p(x4), _p(d4), _p(din), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1),
-                                           x4.stride(2), d4.stride(0), d4.stride(1), d4.stride(2), din.stride(0),
-                                           din.stride(1), din.stride(2), _stream()), "gdl_maxpool2x2s2_bwd")
+    _lib.checked().gdl_maxpool2x2s2_bwd(_p(x4), _p(d4), _p(din), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1),
+                                        x4.stride(2), d4.stride(0), d4.stride(1), d4.stride(2), din.stride(0),
+                                        din.stride(1), din.stride(2), _stream())
     return din
 
 
@@ -1500,8 +1486,8 @@ def nearest2x(x: Tensor, out: Tensor | None = None) -> Tensor:
     o4 = _nhwc4(out, "nearest2x out")
     if tuple(o4.shape) != (B, 2 * H, 2 * W, Cc) or o4.dtype != x4.dtype:
         raise ValueError("nearest2x: out shape / dtype mismatch")
-    check(_lib.load().gdl_nearest2x_fwd(_p(x4), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1), x4.stride(2), _p(o4),
-                                        o4.stride(0), o4.stride(1), o4.stride(2), _stream()), "gdl_nearest2x_fwd")
+    _lib.checked().gdl_nearest2x_fwd(_p(x4), dt(x4), B, H, W, Cc, x4.stride(0), x4.stride(1), x4.stride(2), _p(o4),
+                                     o4.stride(0), o4.stride(1), o4.stride(2), _stream())
     return out
 
 
@@ -1509,9 +1495,8 @@ def nearest2x_bwd(dout: Tensor) -> Tensor:
     d4 = _nhwc4(dout, "nearest2x_bwd dout")
     B, H2, W2, Cc = d4.shape
     din = torch.empty((B, H2 // 2, W2 // 2, Cc), device=dout.device, dtype=dout.dtype)
-    check(_lib.load().gdl_nearest2x_bwd(_p(d4), dt(d4), B, H2 // 2, W2 // 2, Cc, d4.stride(0), d4.stride(1), d4.stride(2),
-                                        _p(din), din.stride(0), din.stride(1), din.stride(2), _stream()),
-          "gdl_nearest2x_bwd")
+    _lib.checked().gdl_nearest2x_bwd(_p(d4), dt(d4), B, H2 // 2, W2 // 2, Cc, d4.stride(0), d4.stride(1), d4.stride(2),
+                                     _p(din), din.stride(0), din.stride(1), din.stride(2), _stream())
     return din
 
 
@@ -1519,7 +1504,7 @@ def add_relu(a: Tensor, b: Tensor) -> Tensor:
     if a.shape != b.shape or a.dtype != b.dtype or not a.is_contiguous() or not b.is_contiguous():
         raise ValueError("add_relu: two contiguous tensors of one shape / dtype expected")
     out = torch.empty_like(a)
-    check(_lib.load().gdl_add_relu(_p(a), _p(b), _p(out), dt(a), a.numel(), _stream()), "gdl_add_relu")
+    _lib.checked().gdl_add_relu(_p(a), _p(b), _p(out), dt(a), a.numel(), _stream())
     return out
 
 
@@ -1530,8 +1515,7 @@ def pad_channels(x: Tensor, cpad: int, out_dtype: torch.dtype) -> Tensor:
         raise ValueError("pad_channels: contiguous input expected")
     Cc = x.shape[-1]
     out = torch.empty((*x.shape[:-1], cpad), device=x.device, dtype=out_dtype)
-    check(_lib.load().gdl_pad_channels(_p(x), dt(x), x.numel() // Cc, Cc, _p(out), dt(out), cpad, _stream()),
-          "gdl_pad_channels")
+    _lib.checked().gdl_pad_channels(_p(x), dt(x), x.numel() // Cc, Cc, _p(out), dt(out), cpad, _stream())
     return out
 
 
@@ -1539,7 +1523,7 @@ def relu_bwd(y: Tensor, dy: Tensor) -> Tensor:
     if y.shape != dy.shape or y.dtype != dy.dtype or not y.is_contiguous() or not dy.is_contiguous():
         raise ValueError("relu_bwd: two contiguous tensors of one shape / dtype expected")
     dx = torch.empty_like(y)
-    check(_lib.load().gdl_relu_bwd(_p(y), _p(dy), _p(dx), dt(y), y.numel(), _stream()), "gdl_relu_bwd")
+    _lib.checked().gdl_relu_bwd(_p(y), _p(dy), _p(dx), dt(y), y.numel(), _stream())
     return dx
 
 
@@ -1551,8 +1535,8 @@ def patchify(img: Tensor, P: int, pad: int, gh: int, gw: int, kpad: int,
         raise ValueError("patchify: image must be contiguous f32 NCHW")
     B, Cc, H, W = img.shape
     cols = torch.empty((B * gh * gw, kpad), device=img.device, dtype=out_dtype)
-    check(_lib.load().gdl_patchify(_p(img), B, Cc, H, W, P, P if stride is None else stride, pad, gh, gw,
-                                   _p(cols), dt(cols), kpad, _stream()), "gdl_patchify")
+    _lib.checked().gdl_patchify(_p(img), B, Cc, H, W, P, P if stride is None else stride, pad, gh, gw,
+                                _p(cols), dt(cols), kpad, _stream())
     return cols
 
 
@@ -1561,8 +1545,8 @@ def dofa_pack_kernel(g: Tensor, Cc: int, PP: int, D: int, scaler: float, kpad: i
     if g.dtype != torch.float32 or not g.is_contiguous() or g.numel() != Cc * PP * D:
         raise ValueError("dofa_pack_kernel: g must be contiguous f32 [C, P*P*D]")
     out = torch.empty((D, kpad), device=g.device, dtype=out_dtype)
-    check(_lib.load().gdl_dofa_pack_kernel(_p(g), Cc, PP, D, scaler, _p(out), dt(out), kpad,
-                                           _stream()), "gdl_dofa_pack_kernel")
+    _lib.checked().gdl_dofa_pack_kernel(_p(g), Cc, PP, D, scaler, _p(out), dt(out), kpad,
+                                        _stream())
     return out
 
 
@@ -1574,8 +1558,7 @@ def dofa_unpack_grad(dw: Tensor, Cc: int, PP: int, D: int, scaler: float) -> Ten
     if dw.dtype != torch.float32 or not dw.is_contiguous() or dw.shape[0] != D:
         raise ValueError("dofa_unpack_grad: contiguous f32 [D, Kpad] expected")
     dg = torch.empty((Cc, PP * D), device=dw.device, dtype=torch.float32)
-    check(_lib.load().gdl_dofa_unpack_grad(_p(dw), Cc, PP, D, scaler, dw.shape[1], _p(dg), _stream()),
-          "gdl_dofa_unpack_grad")
+    _lib.checked().gdl_dofa_unpack_grad(_p(dw), Cc, PP, D, scaler, dw.shape[1], _p(dg), _stream())
     return dg
 
 
@@ -1589,8 +1572,7 @@ def sincos_embed(pos: Tensor, D: int) -> Tensor:
         omega /= D / 2.0
         _OMEGA[key] = (1.0 / 10000**omega).to(pos.device)
     out = torch.empty((pos.numel(), D), device=pos.device, dtype=torch.float32)
-    check(_lib.load().gdl_sincos_embed(_p(pos), _p(_OMEGA[key]), pos.numel(), D, _p(out), _stream()),
-          "gdl_sincos_embed")
+    _lib.checked().gdl_sincos_embed(_p(pos), _p(_OMEGA[key]), pos.numel(), D, _p(out), _stream())
     return out
 
 
@@ -1598,8 +1580,8 @@ def bn_fold(gamma: Tensor, beta: Tensor, mean: Tensor, var: Tensor, eps: float):
     Cc = gamma.numel()
     scale = torch.empty(Cc, device=gamma.device, dtype=torch.float32)
     shift = torch.empty_like(scale)
-    check(_lib.load().gdl_bn_fold(_p(gamma), _p(beta), _p(mean), _p(var), eps, Cc, _p(scale),
-                                  _p(shift), _stream()), "gdl_bn_fold")
+    _lib.checked().gdl_bn_fold(_p(gamma), _p(beta), _p(mean), _p(var), eps, Cc, _p(scale),
+                               _p(shift), _stream())
     return scale, shift
 
 
@@ -1608,8 +1590,7 @@ def pack_dgrad(w: Tensor, N: int, T: int, Cc: int, out_dtype: torch.dtype) -> Te
     if not w.is_contiguous() or w.numel() != N * T * Cc:
         raise ValueError("pack_dgrad: contiguous [N, T*C] weights expected")
     out = torch.empty((Cc, T * N), device=w.device, dtype=out_dtype)
-    check(_lib.load().gdl_pack_dgrad(_p(w), dt(w), N, T, Cc, _p(out), dt(out), _stream()),
-          "gdl_pack_dgrad")
+    _lib.checked().gdl_pack_dgrad(_p(w), dt(w), N, T, Cc, _p(out), dt(out), _stream())
     return out
 
 
@@ -1620,22 +1601,22 @@ def cast(x: Tensor, dtype: torch.dtype, out: Tensor | None = None) -> Tensor:
         raise ValueError("cast: contiguous input required")
     if out is None:
         out = torch.empty(x.shape, device=x.device, dtype=dtype)
-    check(_lib.load().gdl_cast(_p(x), dt(x), _p(out), dt(out), x.numel(), _stream()), "gdl_cast")
+    _lib.checked().gdl_cast(_p(x), dt(x), _p(out), dt(out), x.numel(), _stream())
     return out
 
 
 def scale_f32(x: Tensor, s: float) -> Tensor:
     out = torch.empty_like(x)
-    check(_lib.load().gdl_scale_f32(_p(x), _p(out), x.numel(), s, _stream()), "gdl_scale_f32")
+    _lib.checked().gdl_scale_f32(_p(x), _p(out), x.numel(), s, _stream())
     return out
 
 
 def add_rows(a: Tensor, b: Tensor | None, out: Tensor, rows: int) -> Tensor:
     """out[r,:] = a[r % a_rows,:] + (b[r % b_rows,:] if b is given); 2-D f32 tensors."""
     D = a.shape[-1]
-    check(_lib.load().gdl_add_rows(_p(a), a.shape[0], a.stride(0), _p(b),
-                                   0 if b is None else b.shape[0], 0 if b is None else b.stride(0),
-                                   _p(out), out.stride(0), rows, D, _stream()), "gdl_add_rows")
+    _lib.checked().gdl_add_rows(_p(a), a.shape[0], a.stride(0), _p(b),
+                                0 if b is None else b.shape[0], 0 if b is None else b.stride(0),
+                                _p(out), out.stride(0), rows, D, _stream())
     return out
 
 
@@ -1646,8 +1627,8 @@ def normalize_u8(u8: Tensor, mean: Tensor, std: Tensor) -> Tensor:
         raise ValueError("normalize_u8: contiguous uint8 NCHW expected")
     B, Cc, H, W = u8.shape
     out = torch.empty((B, Cc, H, W), device=u8.device, dtype=torch.float32)
-    check(_lib.load().gdl_normalize_u8(_p(u8), _p(out), B, Cc, H * W, _p(_f32vec(mean, Cc, "mean")),
-                                       _p(_f32vec(std, Cc, "std")), _stream()), "gdl_normalize_u8")
+    _lib.checked().gdl_normalize_u8(_p(u8), _p(out), B, Cc, H * W, _p(_f32vec(mean, Cc, "mean")),
+                                    _p(_f32vec(std, Cc, "std")), _stream())
     return out
 
 
@@ -1662,9 +1643,8 @@ def normalize_raw(raw: Tensor, mean: Tensor, std: Tensor) -> Tensor:
         raise ValueError(f"normalize_raw: contiguous NCHW uint8/uint16/int16/float32 expected, got {raw.dtype}")
     B, Cc, H, W = raw.shape
     out = torch.empty((B, Cc, H, W), device=raw.device, dtype=torch.float32)
-    check(_lib.load().gdl_normalize_raw(_p(raw), _RAW_KIND[raw.dtype], _p(out), B, Cc, H * W,
-                                        _p(_f32vec(mean, Cc, "mean")), _p(_f32vec(std, Cc, "std")), _stream()),
-          "gdl_normalize_raw")
+    _lib.checked().gdl_normalize_raw(_p(raw), _RAW_KIND[raw.dtype], _p(out), B, Cc, H * W,
+                                     _p(_f32vec(mean, Cc, "mean")), _p(_f32vec(std, Cc, "std")), _stream())
     return out
 
 
@@ -1680,9 +1660,9 @@ def normalize_range(raw: Tensor, mean: Tensor, std: Tensor, image_min: int = 0, 
     _need_cuda(raw)
     B, Cc, H, W = raw.shape
     out = torch.empty((B, Cc, H, W), device=raw.device, dtype=torch.float32)
-    check(_lib.load().gdl_normalize_range(_p(raw), _RAW_KIND[raw.dtype], _p(out), B, Cc, H * W, int(image_min), int(image_max),
-                                          float(norm_min), float(norm_max), _p(_f32vec(mean, Cc, "mean")),
-                                          _p(_f32vec(std, Cc, "std")), _stream()), "gdl_normalize_range")
+    _lib.checked().gdl_normalize_range(_p(raw), _RAW_KIND[raw.dtype], _p(out), B, Cc, H * W, int(image_min), int(image_max),
+                                       float(norm_min), float(norm_max), _p(_f32vec(mean, Cc, "mean")),
+                                       _p(_f32vec(std, Cc, "std")), _stream())
     return out
 
 
@@ -1703,10 +1683,9 @@ def augment(img: Tensor, mask: Tensor | None, params: Tensor, mean: Tensor | Non
             raise ValueError("augment: int64 mask of B*H*W elements expected")
         m2 = mask.contiguous()
         om = torch.empty_like(m2)
-    check(_lib.load().gdl_augment(_p(img), _RAW_KIND[img.dtype], _p(out), _p(m2), _p(om), B, Cc, H, W,
-                                  _p(None if mean is None else _f32vec(mean, Cc, "mean")),
-                                  _p(None if std is None else _f32vec(std, Cc, "std")), _p(params), _stream()),
-          "gdl_augment")
+    _lib.checked().gdl_augment(_p(img), _RAW_KIND[img.dtype], _p(out), _p(m2), _p(om), B, Cc, H, W,
+                               _p(None if mean is None else _f32vec(mean, Cc, "mean")),
+                               _p(None if std is None else _f32vec(std, Cc, "std")), _p(params), _stream())
     return out, om
 
 
@@ -1715,8 +1694,8 @@ def scale_outer(x: Tensor, s: Tensor) -> Tensor:
     if not x.is_contiguous():
         raise ValueError("scale_outer: contiguous tensor required")
     outer = x.shape[0]
-    check(_lib.load().gdl_scale_outer(_p(x), dt(x), _p(_f32vec(s, outer, "s")), outer,
-                                      x.numel() // outer, _stream()), "gdl_scale_outer")
+    _lib.checked().gdl_scale_outer(_p(x), dt(x), _p(_f32vec(s, outer, "s")), outer,
+                                   x.numel() // outer, _stream())
     return x
 
 
@@ -1731,8 +1710,8 @@ def head_1x1(feat: Tensor, w: Tensor, bias: Tensor | None, chan_scale: Tensor | 
     if w2.dtype != torch.float32 or not w2.is_contiguous():
         raise ValueError("head_1x1: weight must be contiguous f32 [K, C]")
     out = torch.empty((B, H, W, K), device=feat.device, dtype=torch.float32)
-    check(_lib.load().gdl_head_1x1(_p(f4), dt(f4), P, Cc, sP, _p(w2), _p(bias), _p(chan_scale),
-                                   H * W, _p(out), K, _stream()), "gdl_head_1x1")
+    _lib.checked().gdl_head_1x1(_p(f4), dt(f4), P, Cc, sP, _p(w2), _p(bias), _p(chan_scale),
+                                H * W, _p(out), K, _stream())
     return out
 
 
@@ -1746,12 +1725,11 @@ def head_1x1_bwd(feat: Tensor, dlog: Tensor, w: Tensor, chan_scale: Tensor | Non
     dfeat = torch.empty((B, H, W, Cc), device=feat.device, dtype=feat.dtype) if need_dfeat else None
     dw = torch.empty((K, Cc), device=feat.device, dtype=torch.float32)
     db = torch.empty(K, device=feat.device, dtype=torch.float32)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_head_1x1_bwd_workspace(P, Cc, K)
     ws = torch.empty(nbytes // 4, device=feat.device, dtype=torch.float32)
-    check(lib.gdl_head_1x1_bwd(_p(f4), dt(f4), _p(dlog), P, Cc, sP, _p(w2), _p(chan_scale), H * W,
-                               _p(dfeat), Cc, _p(dw), _p(db), K, _p(ws), nbytes, _stream()),
-          "gdl_head_1x1_bwd")
+    lib.gdl_head_1x1_bwd(_p(f4), dt(f4), _p(dlog), P, Cc, sP, _p(w2), _p(chan_scale), H * W,
+                         _p(dfeat), Cc, _p(dw), _p(db), K, _p(ws), nbytes, _stream())
     return dfeat, dw, db
 
 
@@ -1774,9 +1752,9 @@ def head_1x1_bn(x: Tensor, mean: Tensor, var: Tensor, gamma: Tensor, beta: Tenso
     _need_cuda(x, w)
     x4, P, Cc, K, w2 = _head_bn_args(x, w, "head_1x1_bn x")
     out = torch.empty((*x4.shape[:3], K), device=x.device, dtype=torch.float32)
-    check(_lib.load().gdl_head_1x1_bn(_p(x4), dt(x4), P, Cc, _p(_f32vec(mean, Cc, "mean")), _p(_f32vec(var, Cc, "var")),
-                                      _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")), eps, int(relu), _p(w2),
-                                      _p(bias), _p(out), K, _stream()), "gdl_head_1x1_bn")
+    _lib.checked().gdl_head_1x1_bn(_p(x4), dt(x4), P, Cc, _p(_f32vec(mean, Cc, "mean")), _p(_f32vec(var, Cc, "var")),
+                                   _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")), eps, int(relu), _p(w2),
+                                   _p(bias), _p(out), K, _stream())
     return out
 
 
@@ -1791,13 +1769,12 @@ def bn_head_bwd_reduce(x: Tensor, dlog: Tensor, w: Tensor, mean, var, gamma, bet
     dbeta = torch.empty_like(dgamma)
     dw = torch.empty((K, Cc), device=x.device, dtype=torch.float32)
     db = torch.empty(K, device=x.device, dtype=torch.float32)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_bn_head_bwd_workspace(P, Cc, K)
     ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
-    check(lib.gdl_bn_head_bwd_reduce(_p(x4), dt(x4), _p(dlog), P, Cc, K, _p(w2), _p(_f32vec(mean, Cc, "mean")), _p(_f32vec(var, Cc, "var")),
-                                     _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")), eps,
-                                     int(relu), _p(dgamma), _p(dbeta), _p(dw), _p(db), _p(ws), nbytes, _stream()),
-          "gdl_bn_head_bwd_reduce")
+    lib.gdl_bn_head_bwd_reduce(_p(x4), dt(x4), _p(dlog), P, Cc, K, _p(w2), _p(_f32vec(mean, Cc, "mean")), _p(_f32vec(var, Cc, "var")),
+                               _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")), eps,
+                               int(relu), _p(dgamma), _p(dbeta), _p(dw), _p(db), _p(ws), nbytes, _stream())
     return dgamma, dbeta, dw, db
 
 
@@ -1811,10 +1788,10 @@ def bn_head_bwd_dx(x: Tensor, dlog: Tensor, w: Tensor, mean, var, gamma, beta, e
     dx = out if out is not None else torch.empty(x.shape, device=x.device, dtype=x.dtype)
     if dx.dtype != x.dtype or dx.shape != x.shape or not dx.is_contiguous():
         raise ValueError("bn_head_bwd_dx: out must be a dense map of x's shape and dtype")
-    check(_lib.load().gdl_bn_head_bwd_dx(_p(x4), dt(x4), _p(dlog), _p(dx), P, Cc, K, _p(w2), _p(_f32vec(mean, Cc, "mean")),
-                                         _p(_f32vec(var, Cc, "var")), _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")),
-                                         eps, int(relu), _p(_f32vec(dgamma_sum, Cc, "dgamma_sum")), _p(_f32vec(dbeta_sum, Cc, "dbeta_sum")),
-                                         p_total, _stream()), "gdl_bn_head_bwd_dx")
+    _lib.checked().gdl_bn_head_bwd_dx(_p(x4), dt(x4), _p(dlog), _p(dx), P, Cc, K, _p(w2), _p(_f32vec(mean, Cc, "mean")),
+                                      _p(_f32vec(var, Cc, "var")), _p(_f32vec(gamma, Cc, "gamma")), _p(_f32vec(beta, Cc, "beta")),
+                                      eps, int(relu), _p(_f32vec(dgamma_sum, Cc, "dgamma_sum")), _p(_f32vec(dbeta_sum, Cc, "dbeta_sum")),
+                                      p_total, _stream())
     return dx
 
 
@@ -1822,8 +1799,7 @@ def upsample_logits(x: Tensor, size: tuple[int, int]) -> Tensor:
     """f32 NHWC [B,Hi,Wi,K] -> NCHW f32 [B,K,Ho,Wo] (bilinear, align_corners=False)."""
     B, Hi, Wi, K = x.shape
     out = torch.empty((B, K, size[0], size[1]), device=x.device, dtype=torch.float32)
-    check(_lib.load().gdl_upsample_logits(_p(x), B, Hi, Wi, K, _p(out), size[0], size[1], _stream()),
-          "gdl_upsample_logits")
+    _lib.checked().gdl_upsample_logits(_p(x), B, Hi, Wi, K, _p(out), size[0], size[1], _stream())
     return out
 
 
@@ -1832,11 +1808,11 @@ def upsample_logits_bwd(dout: Tensor, in_size: tuple[int, int]) -> Tensor:
         raise ValueError("upsample_logits_bwd: contiguous f32 NCHW grad expected")
     B, K, Ho, Wo = dout.shape
     din = torch.empty((B, in_size[0], in_size[1], K), device=dout.device, dtype=torch.float32)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_upsample_logits_bwd_workspace(B, K, in_size[0], Wo)
     ws = torch.empty(nbytes // 4, device=dout.device, dtype=torch.float32)
-    check(lib.gdl_upsample_logits_bwd(_p(dout), B, Ho, Wo, K, _p(din), in_size[0], in_size[1], _p(ws),
-                                      nbytes, _stream()), "gdl_upsample_logits_bwd")
+    lib.gdl_upsample_logits_bwd(_p(dout), B, Ho, Wo, K, _p(din), in_size[0], in_size[1], _p(ws),
+                                nbytes, _stream())
     return din
 
 
@@ -1847,8 +1823,7 @@ def softmax_argmax(logits: Tensor) -> Tensor:
         raise ValueError("softmax_argmax: contiguous f32 NCHW logits expected")
     B, K, H, W = logits.shape
     mask = torch.empty((B, H, W), device=logits.device, dtype=torch.int64)
-    check(_lib.load().gdl_softmax_argmax(_p(logits), B, K, H * W, _p(mask), _stream()),
-          "gdl_softmax_argmax")
+    _lib.checked().gdl_softmax_argmax(_p(logits), B, K, H * W, _p(mask), _stream())
     return mask
 
 
@@ -1860,7 +1835,7 @@ def upsample_argmax(low: Tensor, size: tuple[int, int]) -> Tensor:
         raise ValueError("upsample_argmax: contiguous f32 NHWC logits [B, h, w, K] with 2..16 classes expected")
     B, Hi, Wi, K = low.shape
     mask = torch.empty((B, int(size[0]), int(size[1])), device=low.device, dtype=torch.int64)
-    check(_lib.load().gdl_upsample_argmax(_p(low), B, Hi, Wi, K, _p(mask), int(size[0]), int(size[1]), _stream()), "gdl_upsample_argmax")
+    _lib.checked().gdl_upsample_argmax(_p(low), B, Hi, Wi, K, _p(mask), int(size[0]), int(size[1]), _stream())
     return mask
 
 
@@ -1872,7 +1847,7 @@ def sigmoid_threshold(logits: Tensor, threshold: float = 0.5) -> Tensor:
         raise ValueError("sigmoid_threshold: contiguous f32 logits expected")
     shape = (logits.shape[0], *logits.shape[2:]) if logits.dim() == 4 and logits.shape[1] == 1 else tuple(logits.shape)
     mask = torch.empty(shape, device=logits.device, dtype=torch.int64)
-    check(_lib.load().gdl_sigmoid_threshold(_p(logits), logits.numel(), float(threshold), _p(mask), _stream()), "gdl_sigmoid_threshold")
+    _lib.checked().gdl_sigmoid_threshold(_p(logits), logits.numel(), float(threshold), _p(mask), _stream())
     return mask
 
 
@@ -1915,7 +1890,7 @@ def upsample_threshold(low: Tensor, size: tuple[int, int], threshold: float = 0.
     [B, H, W], without the resized logits (gdl_upsample_threshold; the same mask as upsample_logits + sigmoid_threshold)."""
     B, Hi, Wi, Ho, Wo = _binary_lowres_check("upsample_threshold", low, size)
     mask = torch.empty((B, Ho, Wo), device=low.device, dtype=torch.int64)
-    check(_lib.load().gdl_upsample_threshold(_p(low), B, Hi, Wi, _p(mask), Ho, Wo, float(threshold), _stream()), "gdl_upsample_threshold")
+    _lib.checked().gdl_upsample_threshold(_p(low), B, Hi, Wi, _p(mask), Ho, Wo, float(threshold), _stream())
     return mask
 
 
@@ -1926,7 +1901,7 @@ def class_probs(logits: Tensor) -> Tensor:
         raise ValueError("class_probs: contiguous f32 NCHW logits expected")
     B, K, H, W = logits.shape
     out = torch.empty_like(logits)
-    check(_lib.load().gdl_class_probs(_p(logits), B, K, H * W, _p(out), _stream()), "gdl_class_probs")
+    _lib.checked().gdl_class_probs(_p(logits), B, K, H * W, _p(out), _stream())
     return out
 
 
@@ -1941,7 +1916,7 @@ def upsample_probs(low: Tensor, size: tuple[int, int]) -> Tensor:
     if min(B, Hi, Wi, Ho, Wo) < 1:
         raise ValueError(f"upsample_probs: bad sizes {tuple(low.shape)} -> {Ho} x {Wo}")
     out = torch.empty((B, K, Ho, Wo), device=low.device, dtype=torch.float32)
-    check(_lib.load().gdl_upsample_probs(_p(low), B, Hi, Wi, K, _p(out), Ho, Wo, _stream()), "gdl_upsample_probs")
+    _lib.checked().gdl_upsample_probs(_p(low), B, Hi, Wi, K, _p(out), Ho, Wo, _stream())
     return out
 
 
@@ -1953,8 +1928,7 @@ def iou_counts(pred: Tensor, target: Tensor, num_classes: int) -> Tensor:
     B = pred.shape[0]
     p2, t2 = pred.reshape(B, -1).contiguous(), target.reshape(B, -1).contiguous()
     counts = torch.empty((B, 3, num_classes), device=pred.device, dtype=torch.int64)
-    check(_lib.load().gdl_iou_counts(_p(p2), _p(t2), B, p2.shape[1], num_classes, _p(counts), _stream()),
-          "gdl_iou_counts")
+    _lib.checked().gdl_iou_counts(_p(p2), _p(t2), B, p2.shape[1], num_classes, _p(counts), _stream())
     return counts
 
 
@@ -2055,8 +2029,8 @@ def _bwd_workspace(query, dims: tuple, like: Tensor, form: str = "auto"):
 
 
 def _dice_entry(stem: str, way: str, options):
-    """The C entry point of the Dice / Jaccard / Tversky family for ``options``: (symbol, function, the option arguments that
-    follow ``eps`` in its signature, objects to keep alive during the call).  None: the plain ``gdl_dice_<stem>_<way>`` (no option
+    """The C entry point of the Dice / Jaccard / Tversky family for ``options``: (function of the checked view, the option arguments
+    that follow ``eps`` in its signature, objects to keep alive during the call).  None: the plain ``gdl_dice_<stem>_<way>`` (no option
     argument); DiceOptions: ``gdl_dice_<stem>_opt_<way>``; OverlapOptions: ``gdl_overlap_<stem>_<way>``."""
     if options is None:
         name, opt, keep = f"gdl_dice_{stem}_{way}", (), None
@@ -2064,7 +2038,7 @@ def _dice_entry(stem: str, way: str, options):
         name = f"gdl_overlap_{stem}_{way}" if isinstance(options, OverlapOptions) else f"gdl_dice_{stem}_opt_{way}"
         addr, keep = options.c_arg()
         opt = (addr,)
-    return name, getattr(_lib.load(), name), opt, keep
+    return getattr(_lib.checked(), name), opt, keep
 
 
 def _dice_buffers(like: Tensor, K: int, nbytes: int):
@@ -2085,8 +2059,8 @@ def dice_loss_fwd(logits: Tensor, target: Tensor, eps: float = 1e-7, options: Di
     B, K, H, W = logits.shape
     nbytes = _lib.load().gdl_dice_loss_workspace(B, K, H * W)
     sums, loss, ws = _dice_buffers(logits, K, nbytes)
-    name, fn, opt, keep = _dice_entry("loss", "fwd", options)
-    check(fn(_p(logits), _p(target), B, K, H * W, eps, *opt, _p(sums), _p(loss), _p(ws), nbytes, _stream()), name)
+    fn, opt, keep = _dice_entry("loss", "fwd", options)
+    fn(_p(logits), _p(target), B, K, H * W, eps, *opt, _p(sums), _p(loss), _p(ws), nbytes, _stream())
     return loss, sums
 
 
@@ -2096,9 +2070,9 @@ def dice_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream: Tensor
     B, K, H, W = logits.shape
     if out is None:
         out = torch.empty_like(logits)
-    name, fn, opt, keep = _dice_entry("loss", "bwd", options)
-    check(fn(_p(logits), _p(target), B, K, H * W, eps, *opt, _p(sums), _p(upstream), grad_scale, _p(out), int(accumulate),
-             _stream()), name)
+    fn, opt, keep = _dice_entry("loss", "bwd", options)
+    fn(_p(logits), _p(target), B, K, H * W, eps, *opt, _p(sums), _p(upstream), grad_scale, _p(out), int(accumulate),
+       _stream())
     return out
 
 
@@ -2127,8 +2101,8 @@ def dice_loss_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], eps
         raise ValueError(f"dice_loss_lowres: contiguous int64 target [B, {size[0]}, {size[1]}] expected, got {tuple(target.shape)}")
     nbytes = _lib.load().gdl_dice_loss_lowres_workspace(B, K, size[0], size[1])
     sums, loss, ws = _dice_buffers(low, K, nbytes)
-    name, fn, opt, keep = _dice_entry("loss_lowres", "fwd", options)
-    check(fn(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, *opt, _p(sums), _p(loss), _p(ws), nbytes, _stream()), name)
+    fn, opt, keep = _dice_entry("loss_lowres", "fwd", options)
+    fn(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, *opt, _p(sums), _p(loss), _p(ws), nbytes, _stream())
     return loss, sums
 
 
@@ -2138,9 +2112,9 @@ def dice_loss_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], sum
     B, Hi, Wi, K = low.shape
     dlow = torch.empty_like(low)
     ws, nbytes = _bwd_workspace(_lib.load().gdl_dice_loss_lowres_bwd_workspace, (B, K, Hi, Wi, size[0], size[1]), low)
-    name, fn, opt, keep = _dice_entry("loss_lowres", "bwd", options)
-    check(fn(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, *opt, _p(sums), _p(upstream), grad_scale, _p(dlow), _p(ws),
-             nbytes, _stream()), name)
+    fn, opt, keep = _dice_entry("loss_lowres", "bwd", options)
+    fn(_p(low), _p(target), B, K, Hi, Wi, size[0], size[1], eps, *opt, _p(sums), _p(upstream), grad_scale, _p(dlow), _p(ws),
+       nbytes, _stream())
     return dlow
 
 
@@ -2155,8 +2129,8 @@ def dice_binary_loss_fwd(logits: Tensor, target: Tensor, eps: float = 1e-7, opti
     total = logits.numel()
     nbytes = _lib.load().gdl_dice_loss_workspace(1, 1, total)
     sums, loss, ws = _dice_buffers(logits, 1, nbytes)
-    name, fn, opt, keep = _dice_entry("binary_loss", "fwd", options)
-    check(fn(_p(logits), _p(target), total, eps, *opt, _p(sums), _p(loss), _p(ws), nbytes, _stream()), name)
+    fn, opt, keep = _dice_entry("binary_loss", "fwd", options)
+    fn(_p(logits), _p(target), total, eps, *opt, _p(sums), _p(loss), _p(ws), nbytes, _stream())
     return loss, sums
 
 
@@ -2164,8 +2138,8 @@ def dice_binary_loss_bwd(logits: Tensor, target: Tensor, sums: Tensor, upstream:
                          grad_scale: float = 1.0, eps: float = 1e-7,
                          options: DiceOptions | OverlapOptions | None = None) -> Tensor:
     out = torch.empty_like(logits)
-    name, fn, opt, keep = _dice_entry("binary_loss", "bwd", options)
-    check(fn(_p(logits), _p(target), logits.numel(), eps, *opt, _p(sums), _p(upstream), grad_scale, _p(out), 0, _stream()), name)
+    fn, opt, keep = _dice_entry("binary_loss", "bwd", options)
+    fn(_p(logits), _p(target), logits.numel(), eps, *opt, _p(sums), _p(upstream), grad_scale, _p(out), 0, _stream())
     return out
 
 
@@ -2176,8 +2150,8 @@ def dice_binary_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], e
     B, Hi, Wi, Ho, Wo = _binary_lowres_check("dice_binary_lowres", low, size, target)
     nbytes = _lib.load().gdl_dice_loss_lowres_workspace(B, 1, Ho, Wo)
     sums, loss, ws = _dice_buffers(low, 1, nbytes)
-    name, fn, opt, keep = _dice_entry("binary_loss_lowres", "fwd", options)
-    check(fn(_p(low), _p(target), B, Hi, Wi, Ho, Wo, eps, *opt, _p(sums), _p(loss), _p(ws), nbytes, _stream()), name)
+    fn, opt, keep = _dice_entry("binary_loss_lowres", "fwd", options)
+    fn(_p(low), _p(target), B, Hi, Wi, Ho, Wo, eps, *opt, _p(sums), _p(loss), _p(ws), nbytes, _stream())
     return loss, sums
 
 
@@ -2189,11 +2163,11 @@ def dice_binary_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], s
     B, Hi, Wi, Ho, Wo = _binary_lowres_check("dice_binary_lowres", low, size, target)
     _need_cuda(sums, upstream)
     dlow = torch.empty_like(low)
-    lib = _lib.load()
+    lib = _lib.checked()
     ws, nbytes = _bwd_workspace(lib.gdl_binary_lowres_bwd_workspace, (B, Hi, Wi, Ho, Wo), low, form)
-    name, fn, opt, keep = _dice_entry("binary_loss_lowres", "bwd", options)
-    check(fn(_p(low), _p(target), B, Hi, Wi, Ho, Wo, eps, *opt, _p(sums), _p(upstream), grad_scale, _p(dlow), _p(ws), nbytes,
-             LOWRES_BWD_FORMS[form], _stream()), name)
+    fn, opt, keep = _dice_entry("binary_loss_lowres", "bwd", options)
+    fn(_p(low), _p(target), B, Hi, Wi, Ho, Wo, eps, *opt, _p(sums), _p(upstream), grad_scale, _p(dlow), _p(ws), nbytes,
+       LOWRES_BWD_FORMS[form], _stream())
     return dlow
 
 
@@ -2213,11 +2187,10 @@ class SoftCEOptions(NamedTuple):
 def soft_ce_fwd(logits: Tensor, target: Tensor, options: SoftCEOptions = SoftCEOptions()) -> Tensor:
     """smp SoftCrossEntropyLoss on NCHW f32 logits [B,K,H,W] and an int64 target [B,H,W]: the loss (0-dim f32)."""
     B, K, HW = _nchw_check("soft_ce", logits, target)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_soft_ce_workspace(B, K, HW)
     loss, _, ws = _loss_buffers(logits, nbytes)
-    check(lib.gdl_soft_ce_fwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(loss), _p(ws), nbytes, _stream()),
-          "gdl_soft_ce_fwd")
+    lib.gdl_soft_ce_fwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(loss), _p(ws), nbytes, _stream())
     return loss
 
 
@@ -2227,8 +2200,8 @@ def soft_ce_bwd(logits: Tensor, target: Tensor, upstream: Tensor | None, grad_sc
     B, K, HW = _nchw_check("soft_ce", logits, target)
     _need_cuda(upstream, out)
     out = _grad_out("soft_ce_bwd", logits, out)
-    check(_lib.load().gdl_soft_ce_bwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(upstream), grad_scale, _p(out),
-                                      int(accumulate), _stream()), "gdl_soft_ce_bwd")
+    _lib.checked().gdl_soft_ce_bwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(upstream), grad_scale, _p(out),
+                                   int(accumulate), _stream())
     return out
 
 
@@ -2239,17 +2212,16 @@ def soft_ce_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], optio
     take that form (K > 8, resize close to 1:1), and without ``fused``, ``state`` is None and the backward recomputes."""
     dims = _lowres_check("soft_ce_lowres", low, target, size)
     loss = torch.empty((), device=low.device, dtype=torch.float32)
-    lib = _lib.load()
+    lib = _lib.checked()
     nstate = lib.gdl_soft_ce_lowres_fused_state(*dims) if fused else 0
     if nstate:
         state = torch.empty(nstate // 8 + 1, device=low.device, dtype=torch.float64)
-        check(lib.gdl_soft_ce_lowres_fused_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(state), state.numel() * 8,
-                                               _stream()), "gdl_soft_ce_lowres_fused_fwd")
+        lib.gdl_soft_ce_lowres_fused_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(state), state.numel() * 8,
+                                         _stream())
         return loss, state
     nbytes = lib.gdl_soft_ce_lowres_workspace(*dims[:2], *dims[4:])
     ws = torch.empty(nbytes // 8, device=low.device, dtype=torch.float64)
-    check(lib.gdl_soft_ce_lowres_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(ws), nbytes, _stream()),
-          "gdl_soft_ce_lowres_fwd")
+    lib.gdl_soft_ce_lowres_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(ws), nbytes, _stream())
     return loss, None
 
 
@@ -2260,14 +2232,14 @@ def soft_ce_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], upstr
     dims = _lowres_check("soft_ce_lowres", low, target, size)
     _need_cuda(upstream, state)
     dlow = torch.empty_like(low)
-    lib = _lib.load()
+    lib = _lib.checked()
     if state is not None:
-        check(lib.gdl_soft_ce_lowres_fused_bwd(_p(state), state.numel() * state.element_size(), *dims, int(bool(options.mean)),
-                                               _p(upstream), grad_scale, _p(dlow), _stream()), "gdl_soft_ce_lowres_fused_bwd")
+        lib.gdl_soft_ce_lowres_fused_bwd(_p(state), state.numel() * state.element_size(), *dims, int(bool(options.mean)),
+                                         _p(upstream), grad_scale, _p(dlow), _stream())
         return dlow
     ws, nbytes = _bwd_workspace(lib.gdl_soft_ce_lowres_bwd_workspace, dims, low)
-    check(lib.gdl_soft_ce_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(upstream), grad_scale, _p(dlow), _p(ws), nbytes,
-                                     _stream()), "gdl_soft_ce_lowres_bwd")
+    lib.gdl_soft_ce_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(upstream), grad_scale, _p(dlow), _p(ws), nbytes,
+                               _stream())
     return dlow
 
 
@@ -2293,11 +2265,10 @@ def focal_fwd(logits: Tensor, target: Tensor, options: FocalOptions = FocalOptio
     """smp FocalLoss(mode="multiclass") on NCHW f32 logits [B,K,H,W] and an int64 target [B,H,W]: ``(loss, norm)``, the 0-dim f32
     loss and the divisor the kernels formed on the device (1 / valid pixels, or 1 for "sum"), which focal_bwd reads."""
     B, K, HW = _nchw_check("focal", logits, target)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_focal_workspace(B, K, HW)
     loss, norm, ws = _loss_buffers(logits, nbytes, norm=True)
-    check(lib.gdl_focal_fwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes, _stream()),
-          "gdl_focal_fwd")
+    lib.gdl_focal_fwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes, _stream())
     return loss, norm
 
 
@@ -2308,8 +2279,8 @@ def focal_bwd(logits: Tensor, target: Tensor, norm: Tensor, upstream: Tensor | N
     B, K, HW = _nchw_check("focal", logits, target)
     _need_cuda(norm, upstream, out)
     out = _grad_out("focal_bwd", logits, out)
-    check(_lib.load().gdl_focal_bwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(norm), _p(upstream), grad_scale,
-                                    _p(out), int(accumulate), _stream()), "gdl_focal_bwd")
+    _lib.checked().gdl_focal_bwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(norm), _p(upstream), grad_scale,
+                                 _p(out), int(accumulate), _stream())
     return out
 
 
@@ -2325,11 +2296,11 @@ def focal_binary_fwd(logits: Tensor, target: Tensor, options: FocalOptions = Foc
     """smp FocalLoss(mode="binary"): f32 logits of any shape, int64 target of the same numel (1 = positive; any other value that
     is not ``ignore_index`` = negative): ``(loss, norm)`` as focal_fwd."""
     _focal_binary_check(logits, target)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_focal_workspace(1, 1, logits.numel())
     loss, norm, ws = _loss_buffers(logits, nbytes, norm=True)
-    check(lib.gdl_focal_binary_fwd(_p(logits), _p(target), logits.numel(), *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
-                                   _stream()), "gdl_focal_binary_fwd")
+    lib.gdl_focal_binary_fwd(_p(logits), _p(target), logits.numel(), *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
+                             _stream())
     return loss, norm
 
 
@@ -2338,8 +2309,8 @@ def focal_binary_bwd(logits: Tensor, target: Tensor, norm: Tensor, upstream: Ten
     _focal_binary_check(logits, target)
     _need_cuda(norm, upstream, out)
     out = _grad_out("focal_binary_bwd", logits, out)
-    check(_lib.load().gdl_focal_binary_bwd(_p(logits), _p(target), logits.numel(), *options.c_args(), _p(norm), _p(upstream),
-                                           grad_scale, _p(out), int(accumulate), _stream()), "gdl_focal_binary_bwd")
+    _lib.checked().gdl_focal_binary_bwd(_p(logits), _p(target), logits.numel(), *options.c_args(), _p(norm), _p(upstream),
+                                        grad_scale, _p(out), int(accumulate), _stream())
     return out
 
 
@@ -2347,11 +2318,10 @@ def focal_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], options
     """The multiclass focal loss of bilinear(low -> size) vs target [B, H, W] without the full-resolution logits:
     ``(loss, norm)`` as focal_fwd."""
     dims = _lowres_check("focal_lowres", low, target, size)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_focal_lowres_workspace(*dims[:2], *dims[4:])
     loss, norm, ws = _loss_buffers(low, nbytes, norm=True)
-    check(lib.gdl_focal_lowres_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes, _stream()),
-          "gdl_focal_lowres_fwd")
+    lib.gdl_focal_lowres_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes, _stream())
     return loss, norm
 
 
@@ -2362,10 +2332,10 @@ def focal_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], norm: T
     dims = _lowres_check("focal_lowres", low, target, size)
     _need_cuda(norm, upstream)
     dlow = torch.empty_like(low)
-    lib = _lib.load()
+    lib = _lib.checked()
     ws, nbytes = _bwd_workspace(lib.gdl_focal_lowres_bwd_workspace, dims, low, form)
-    check(lib.gdl_focal_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(norm), _p(upstream), grad_scale, _p(dlow), _p(ws),
-                                   nbytes, LOWRES_BWD_FORMS[form], _stream()), "gdl_focal_lowres_bwd")
+    lib.gdl_focal_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(norm), _p(upstream), grad_scale, _p(dlow), _p(ws),
+                             nbytes, LOWRES_BWD_FORMS[form], _stream())
     return dlow
 
 
@@ -2373,11 +2343,11 @@ def focal_binary_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], 
     """The binary focal loss (z = [y == 1]) of bilinear(low -> size) vs target [B, H, W] for the one-class head's map [B, h, w, 1],
     without the full-resolution logits: ``(loss, norm)`` as focal_fwd."""
     B, Hi, Wi, Ho, Wo = _binary_lowres_check("focal_binary_lowres", low, size, target)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_focal_lowres_workspace(B, 1, Ho, Wo)
     loss, norm, ws = _loss_buffers(low, nbytes, norm=True)
-    check(lib.gdl_focal_binary_lowres_fwd(_p(low), _p(target), B, Hi, Wi, Ho, Wo, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
-                                          _stream()), "gdl_focal_binary_lowres_fwd")
+    lib.gdl_focal_binary_lowres_fwd(_p(low), _p(target), B, Hi, Wi, Ho, Wo, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
+                                    _stream())
     return loss, norm
 
 
@@ -2387,10 +2357,10 @@ def focal_binary_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], 
     B, Hi, Wi, Ho, Wo = _binary_lowres_check("focal_binary_lowres", low, size, target)
     _need_cuda(norm, upstream)
     dlow = torch.empty_like(low)
-    lib = _lib.load()
+    lib = _lib.checked()
     ws, nbytes = _bwd_workspace(lib.gdl_binary_lowres_bwd_workspace, (B, Hi, Wi, Ho, Wo), low, form)
-    check(lib.gdl_focal_binary_lowres_bwd(_p(low), _p(target), B, Hi, Wi, Ho, Wo, *options.c_args(), _p(norm), _p(upstream), grad_scale,
-                                          _p(dlow), _p(ws), nbytes, LOWRES_BWD_FORMS[form], _stream()), "gdl_focal_binary_lowres_bwd")
+    lib.gdl_focal_binary_lowres_bwd(_p(low), _p(target), B, Hi, Wi, Ho, Wo, *options.c_args(), _p(norm), _p(upstream), grad_scale,
+                                    _p(dlow), _p(ws), nbytes, LOWRES_BWD_FORMS[form], _stream())
     return dlow
 
 
@@ -2425,11 +2395,11 @@ def cross_entropy_fwd(logits: Tensor, target: Tensor, options: CrossEntropyOptio
     which cross_entropy_bwd reads."""
     B, K, HW = _nchw_check("cross_entropy", logits, target)
     _cross_entropy_weight_check("cross_entropy", options, K)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_cross_entropy_workspace(B, K, HW)
     loss, norm, ws = _loss_buffers(logits, nbytes, norm=True)
-    check(lib.gdl_cross_entropy_fwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
-                                    _stream()), "gdl_cross_entropy_fwd")
+    lib.gdl_cross_entropy_fwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
+                              _stream())
     return loss, norm
 
 
@@ -2442,8 +2412,8 @@ def cross_entropy_bwd(logits: Tensor, target: Tensor, norm: Tensor, upstream: Te
     _cross_entropy_weight_check("cross_entropy", options, K)
     _need_cuda(norm, upstream, out)
     out = _grad_out("cross_entropy_bwd", logits, out)
-    check(_lib.load().gdl_cross_entropy_bwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(norm), _p(upstream), grad_scale,
-                                            _p(out), int(accumulate), _stream()), "gdl_cross_entropy_bwd")
+    _lib.checked().gdl_cross_entropy_bwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(norm), _p(upstream), grad_scale,
+                                         _p(out), int(accumulate), _stream())
     return out
 
 
@@ -2453,11 +2423,11 @@ def cross_entropy_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int],
     cross_entropy_fwd."""
     dims = _lowres_check("cross_entropy_lowres", low, target, size)
     _cross_entropy_weight_check("cross_entropy_lowres", options, dims[1])
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_cross_entropy_lowres_workspace(*dims[:2], *dims[4:])
     loss, norm, ws = _loss_buffers(low, nbytes, norm=True)
-    check(lib.gdl_cross_entropy_lowres_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
-                                           _stream()), "gdl_cross_entropy_lowres_fwd")
+    lib.gdl_cross_entropy_lowres_fwd(_p(low), _p(target), *dims, *options.c_args(), _p(loss), _p(norm), _p(ws), nbytes,
+                                     _stream())
     return loss, norm
 
 
@@ -2469,10 +2439,10 @@ def cross_entropy_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int],
     _cross_entropy_weight_check("cross_entropy_lowres", options, dims[1])
     _need_cuda(norm, upstream)
     dlow = torch.empty_like(low)
-    lib = _lib.load()
+    lib = _lib.checked()
     ws, nbytes = _bwd_workspace(lib.gdl_cross_entropy_lowres_bwd_workspace, dims, low, form)
-    check(lib.gdl_cross_entropy_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(norm), _p(upstream), grad_scale, _p(dlow),
-                                           _p(ws), nbytes, LOWRES_BWD_FORMS[form], _stream()), "gdl_cross_entropy_lowres_bwd")
+    lib.gdl_cross_entropy_lowres_bwd(_p(low), _p(target), *dims, *options.c_args(), _p(norm), _p(upstream), grad_scale, _p(dlow),
+                                     _p(ws), nbytes, LOWRES_BWD_FORMS[form], _stream())
     return dlow
 
 
@@ -2525,11 +2495,11 @@ def _soft_bce_check(who: str, logits: Tensor, target: Tensor, options: SoftBCEOp
 def soft_bce_fwd(logits: Tensor, target: Tensor, options: SoftBCEOptions = SoftBCEOptions()) -> Tensor:
     """smp SoftBCEWithLogitsLoss on NCHW f32 logits [B,C,H,W] and an int64 or f32 target of the same numel: the loss (0-dim f32)."""
     B, C_, HW = _soft_bce_check("soft_bce", logits, target, options)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_soft_bce_workspace(B, C_, HW)
     loss, _, ws = _loss_buffers(logits, nbytes)
-    check(lib.gdl_soft_bce_fwd(_p(logits), _p(target), BCE_TARGET_TYPES[target.dtype], B, C_, HW, *options.c_args(logits.numel()),
-                               _p(loss), _p(ws), nbytes, _stream()), "gdl_soft_bce_fwd")
+    lib.gdl_soft_bce_fwd(_p(logits), _p(target), BCE_TARGET_TYPES[target.dtype], B, C_, HW, *options.c_args(logits.numel()),
+                         _p(loss), _p(ws), nbytes, _stream())
     return loss
 
 
@@ -2539,9 +2509,8 @@ def soft_bce_bwd(logits: Tensor, target: Tensor, upstream: Tensor | None, grad_s
     B, C_, HW = _soft_bce_check("soft_bce", logits, target, options)
     _need_cuda(upstream, out)
     out = _grad_out("soft_bce_bwd", logits, out)
-    check(_lib.load().gdl_soft_bce_bwd(_p(logits), _p(target), BCE_TARGET_TYPES[target.dtype], B, C_, HW,
-                                       *options.c_args(logits.numel()), _p(upstream), grad_scale, _p(out), int(accumulate), _stream()),
-          "gdl_soft_bce_bwd")
+    _lib.checked().gdl_soft_bce_bwd(_p(logits), _p(target), BCE_TARGET_TYPES[target.dtype], B, C_, HW,
+                                    *options.c_args(logits.numel()), _p(upstream), grad_scale, _p(out), int(accumulate), _stream())
     return out
 
 
@@ -2559,11 +2528,11 @@ def soft_bce_lowres_fwd(low: Tensor, target: Tensor, size: tuple[int, int], opti
     """The loss of bilinear(low -> size) vs target [B, H, W] for the one-class head's map [B, h, w, 1], without the full-resolution
     logits: the loss (0-dim f32)."""
     B, Hi, Wi, Ho, Wo = _soft_bce_lowres_check(low, target, size, options)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_soft_bce_lowres_workspace(B, Ho, Wo)
     loss, _, ws = _loss_buffers(low, nbytes)
-    check(lib.gdl_soft_bce_lowres_fwd(_p(low), _p(target), BCE_TARGET_TYPES[target.dtype], B, Hi, Wi, Ho, Wo,
-                                      *options.c_args(target.numel()), _p(loss), _p(ws), nbytes, _stream()), "gdl_soft_bce_lowres_fwd")
+    lib.gdl_soft_bce_lowres_fwd(_p(low), _p(target), BCE_TARGET_TYPES[target.dtype], B, Hi, Wi, Ho, Wo,
+                                *options.c_args(target.numel()), _p(loss), _p(ws), nbytes, _stream())
     return loss
 
 
@@ -2573,11 +2542,11 @@ def soft_bce_lowres_bwd(low: Tensor, target: Tensor, size: tuple[int, int], upst
     B, Hi, Wi, Ho, Wo = _soft_bce_lowres_check(low, target, size, options)
     _need_cuda(upstream)
     dlow = torch.empty_like(low)
-    lib = _lib.load()
+    lib = _lib.checked()
     ws, nbytes = _bwd_workspace(lib.gdl_binary_lowres_bwd_workspace, (B, Hi, Wi, Ho, Wo), low, form)
-    check(lib.gdl_soft_bce_lowres_bwd(_p(low), _p(target), BCE_TARGET_TYPES[target.dtype], B, Hi, Wi, Ho, Wo,
-                                      *options.c_args(target.numel()), _p(upstream), grad_scale, _p(dlow), _p(ws), nbytes,
-                                      LOWRES_BWD_FORMS[form], _stream()), "gdl_soft_bce_lowres_bwd")
+    lib.gdl_soft_bce_lowres_bwd(_p(low), _p(target), BCE_TARGET_TYPES[target.dtype], B, Hi, Wi, Ho, Wo,
+                                *options.c_args(target.numel()), _p(upstream), grad_scale, _p(dlow), _p(ws), nbytes,
+                                LOWRES_BWD_FORMS[form], _stream())
     return dlow
 
 
@@ -2601,10 +2570,10 @@ def sort_desc_f32(keys: Tensor):
         raise ValueError("sort_desc_f32: contiguous f32 keys [S, n] expected")
     S, n = keys.shape
     out, perm = torch.empty_like(keys), torch.empty(S, n, device=keys.device, dtype=torch.int32)
-    lib = _lib.load()
+    lib = _lib.checked()
     nbytes = lib.gdl_sort_desc_workspace(S, n)
     ws = torch.empty(nbytes // 8, device=keys.device, dtype=torch.float64)
-    check(lib.gdl_sort_desc_f32(_p(keys), S, n, _p(out), _p(perm), _p(ws), nbytes, _stream()), "gdl_sort_desc_f32")
+    lib.gdl_sort_desc_f32(_p(keys), S, n, _p(out), _p(perm), _p(ws), nbytes, _stream())
     return out, perm
 
 
@@ -2621,11 +2590,11 @@ def lovasz_fwd(logits: Tensor, target: Tensor, options: LovaszOptions = LovaszOp
     f32 loss, the Jaccard coefficient of every (class, pixel) in pixel order and the weight of every segment in the loss (formed on
     the device), both of which lovasz_bwd reads."""
     B, K, HW = _nchw_check("lovasz", logits, target)
-    lib = _lib.load()
+    lib = _lib.checked()
     segs, n = (B * K, HW) if options.per_image else (K, B * HW)
     loss, coef, norm, ws, nbytes = _lovasz_out(logits, lib, segs, n, K)
-    check(lib.gdl_lovasz_fwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(loss), _p(coef), _p(norm), _p(ws), nbytes,
-                             _stream()), "gdl_lovasz_fwd")
+    lib.gdl_lovasz_fwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(loss), _p(coef), _p(norm), _p(ws), nbytes,
+                       _stream())
     return loss, coef, norm
 
 
@@ -2638,8 +2607,8 @@ def lovasz_bwd(logits: Tensor, target: Tensor, coef: Tensor, norm: Tensor, upstr
     _f32vec(coef, logits.numel(), "lovasz_bwd: coef")
     _f32vec(norm, B * K if options.per_image else K, "lovasz_bwd: norm")
     out = _grad_out("lovasz_bwd", logits, out)
-    check(_lib.load().gdl_lovasz_bwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(coef), _p(norm), _p(upstream), grad_scale,
-                                     _p(out), int(accumulate), _stream()), "gdl_lovasz_bwd")
+    _lib.checked().gdl_lovasz_bwd(_p(logits), _p(target), B, K, HW, *options.c_args(), _p(coef), _p(norm), _p(upstream), grad_scale,
+                                  _p(out), int(accumulate), _stream())
     return out
 
 
@@ -2656,11 +2625,11 @@ def lovasz_binary_fwd(logits: Tensor, target: Tensor, options: LovaszOptions = L
     """smp LovaszLoss(mode="binary"): f32 logits [B, ...], int64 target of the same numel (1 = positive; any other value that is not
     ``ignore_index`` = negative): ``(loss, coef, norm)`` as lovasz_fwd."""
     B, per = _lovasz_binary_check(logits, target)
-    lib = _lib.load()
+    lib = _lib.checked()
     segs, n = (B, per) if options.per_image else (1, B * per)
     loss, coef, norm, ws, nbytes = _lovasz_out(logits, lib, segs, n, 1)
-    check(lib.gdl_lovasz_binary_fwd(_p(logits), _p(target), B, per, *options.c_args(), _p(loss), _p(coef), _p(norm), _p(ws), nbytes,
-                                    _stream()), "gdl_lovasz_binary_fwd")
+    lib.gdl_lovasz_binary_fwd(_p(logits), _p(target), B, per, *options.c_args(), _p(loss), _p(coef), _p(norm), _p(ws), nbytes,
+                              _stream())
     return loss, coef, norm
 
 
@@ -2671,78 +2640,78 @@ def lovasz_binary_bwd(logits: Tensor, target: Tensor, coef: Tensor, norm: Tensor
     _f32vec(coef, logits.numel(), "lovasz_binary_bwd: coef")
     _f32vec(norm, B if options.per_image else 1, "lovasz_binary_bwd: norm")
     out = _grad_out("lovasz_binary_bwd", logits, out)
-    check(_lib.load().gdl_lovasz_binary_bwd(_p(logits), _p(target), B, per, *options.c_args(), _p(coef), _p(norm), _p(upstream),
-                                            grad_scale, _p(out), int(accumulate), _stream()), "gdl_lovasz_binary_bwd")
+    _lib.checked().gdl_lovasz_binary_bwd(_p(logits), _p(target), B, per, *options.c_args(), _p(coef), _p(norm), _p(upstream),
+                                         grad_scale, _p(out), int(accumulate), _stream())
     return out
 
 
 # ------------------------------------------------------------------ optimizer
 def sumsq_accum(x: Tensor, acc: Tensor) -> None:
-    check(_lib.load().gdl_sumsq(_p(x), x.numel(), _p(acc), _stream()), "gdl_sumsq")
+    _lib.checked().gdl_sumsq(_p(x), x.numel(), _p(acc), _stream())
 
 
 def clip_coef(sumsq: Tensor, max_norm: float, coef: Tensor) -> None:
-    check(_lib.load().gdl_clip_coef(_p(sumsq), max_norm, _p(coef), _stream()), "gdl_clip_coef")
+    _lib.checked().gdl_clip_coef(_p(sumsq), max_norm, _p(coef), _stream())
 
 
 def multi_sumsq(table: Tensor, acc: Tensor) -> None:
     """acc += sum of squares of every gradient chunk listed in the device table [nchunks, 5]."""
-    check(_lib.load().gdl_multi_sumsq(_p(table), table.shape[0], _p(acc), _stream()), "gdl_multi_sumsq")
+    _lib.checked().gdl_multi_sumsq(_p(table), table.shape[0], _p(acc), _stream())
 
 
 def multi_adam(table: Tensor, lr: float, b1: float, b2: float, eps: float, wd: float, step: int,
                clip: Tensor | None) -> None:
     bc1, bc2 = 1.0 - b1**step, 1.0 - b2**step
-    check(_lib.load().gdl_multi_adam(_p(table), table.shape[0], lr, b1, b2, eps, wd, bc1, bc2, _p(clip),
-                                     _stream()), "gdl_multi_adam")
+    _lib.checked().gdl_multi_adam(_p(table), table.shape[0], lr, b1, b2, eps, wd, bc1, bc2, _p(clip),
+                                  _stream())
 
 
 def adam_tick(state: Tensor, b1: float, b2: float) -> None:
     """state[0] += 1 and the two bias corrections refreshed, on the device (capturable Adam, see gdl_adam_tick)."""
-    check(_lib.load().gdl_adam_tick(_p(state), float(b1), float(b2), _stream()), "gdl_adam_tick")
+    _lib.checked().gdl_adam_tick(_p(state), float(b1), float(b2), _stream())
 
 
 def multi_adam_dev(table: Tensor, state: Tensor, clip: Tensor | None) -> None:
-    check(_lib.load().gdl_multi_adam_dev(_p(table), table.shape[0], _p(state), _p(clip), _stream()), "gdl_multi_adam_dev")
+    _lib.checked().gdl_multi_adam_dev(_p(table), table.shape[0], _p(state), _p(clip), _stream())
 
 
 def multi_adamw(table: Tensor, lr: float, b1: float, b2: float, eps: float, wd: float, step: int,
                 clip: Tensor | None) -> None:
     """torch.optim.AdamW (decoupled weight decay) over the chunk table, see gdl_multi_adamw."""
     bc1, bc2 = 1.0 - b1**step, 1.0 - b2**step
-    check(_lib.load().gdl_multi_adamw(_p(table), table.shape[0], lr, b1, b2, eps, wd, bc1, bc2, _p(clip),
-                                      _stream()), "gdl_multi_adamw")
+    _lib.checked().gdl_multi_adamw(_p(table), table.shape[0], lr, b1, b2, eps, wd, bc1, bc2, _p(clip),
+                                   _stream())
 
 
 def multi_adamw_dev(table: Tensor, state: Tensor, clip: Tensor | None) -> None:
-    check(_lib.load().gdl_multi_adamw_dev(_p(table), table.shape[0], _p(state), _p(clip), _stream()), "gdl_multi_adamw_dev")
+    _lib.checked().gdl_multi_adamw_dev(_p(table), table.shape[0], _p(state), _p(clip), _stream())
 
 
 def multi_sgd(table: Tensor, lr: float, momentum: float, dampening: float, nesterov: bool, wd: float, step: int,
               clip: Tensor | None) -> None:
     """torch.optim.SGD over the chunk table, see gdl_multi_sgd; ``step`` = the step count of the table's parameters (the
     momentum buffer is the gradient itself at step 1)."""
-    check(_lib.load().gdl_multi_sgd(_p(table), table.shape[0], lr, momentum, dampening, int(bool(nesterov)), wd, int(step == 1),
-                                    _p(clip), _stream()), "gdl_multi_sgd")
+    _lib.checked().gdl_multi_sgd(_p(table), table.shape[0], lr, momentum, dampening, int(bool(nesterov)), wd, int(step == 1),
+                                 _p(clip), _stream())
 
 
 def sgd_tick(state: Tensor) -> None:
     """state[0] += 1 and the first-step flag refreshed, on the device (capturable SGD, see gdl_sgd_tick)."""
-    check(_lib.load().gdl_sgd_tick(_p(state), _stream()), "gdl_sgd_tick")
+    _lib.checked().gdl_sgd_tick(_p(state), _stream())
 
 
 def multi_sgd_dev(table: Tensor, state: Tensor, clip: Tensor | None) -> None:
-    check(_lib.load().gdl_multi_sgd_dev(_p(table), table.shape[0], _p(state), _p(clip), _stream()), "gdl_multi_sgd_dev")
+    _lib.checked().gdl_multi_sgd_dev(_p(table), table.shape[0], _p(state), _p(clip), _stream())
 
 
 def multi_repack(table: Tensor, total_tiles: int) -> None:
     """Rebuild the bf16 operands derived from 3x3 conv parameters (channel-slice, tap-major, data-gradient layouts) listed in
     ``table`` (device int64 [rows, 10], see gdl_multi_repack) in one launch."""
-    check(_lib.load().gdl_multi_repack(_p(table), table.shape[0], int(total_tiles), _stream()), "gdl_multi_repack")
+    _lib.checked().gdl_multi_repack(_p(table), table.shape[0], int(total_tiles), _stream())
 
 
 def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, b1: float, b2: float,
               eps: float, wd: float, step: int, clip: Tensor | None) -> None:
     bc1, bc2 = 1.0 - b1**step, 1.0 - b2**step
-    check(_lib.load().gdl_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, b1, b2, eps, wd, bc1,
-                                    bc2, _p(clip), _stream()), "gdl_adam_step")
+    _lib.checked().gdl_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, b1, b2, eps, wd, bc1,
+                                 bc2, _p(clip), _stream())

@@ -72,26 +72,32 @@ ROUTES = [(None, "gdl_dice_{}_{}"), (ops.DiceOptions(255), "gdl_dice_{}_opt_{}")
 def test_ops_route_options_to_the_entry_point_and_argument_positions(monkeypatch, options, pattern):
     """As tests/test_overlap_loss_host.py holds the existing stems: ``options`` picks the C symbol, the option pointer follows
     ``eps``, ``eps`` / ``grad_scale`` land on the float positions, the backward's ``form`` is the last int.  No library is loaded."""
-    calls, checked = [], []
+    calls = []
 
     class Recorder:
+        """Either view of the library: a size query may go through both, a launch only through the one that checks its status."""
+
+        def __init__(self, checks_status):
+            self.checks_status = checks_status
+
         def __getattr__(self, name):
             if name.endswith("_workspace"):
                 return lambda *a: 48
+            assert self.checks_status and name in _lib.STATUS_FUNCTIONS, f"{name}: launched through the view that drops its status"
             return lambda *a: calls.append((name, a)) or 0
 
-    monkeypatch.setattr(_lib, "load", lambda: Recorder())
+    monkeypatch.setattr(_lib, "load", lambda: Recorder(False))
+    monkeypatch.setattr(_lib, "checked", lambda: Recorder(True))
     monkeypatch.setattr(ops, "_need_cuda", lambda *ts: None)
     monkeypatch.setattr(ops, "_stream", lambda: 7)
-    monkeypatch.setattr(ops, "check", lambda status, what: checked.append((status, what)))
     EPS, GS = 3e-5, 0.25
     low, y, sums, up = torch.zeros(1, 2, 2, 1), torch.zeros(1, 4, 4, dtype=torch.int64), torch.zeros(3), torch.ones(())
     for way, run in (("fwd", lambda: ops.dice_binary_lowres_fwd(low, y, (4, 4), EPS, options=options)),
                      ("bwd", lambda: ops.dice_binary_lowres_bwd(low, y, (4, 4), sums, up, GS, EPS, options=options, form="tile"))):
-        calls.clear(), checked.clear()
+        calls.clear()
         run()
         want = pattern.format("binary_loss_lowres", way)
-        assert [c[0] for c in calls] == [want] and checked == [(0, want)]
+        assert [c[0] for c in calls] == [want]
         args, types = calls[0][1], _lib.SIGNATURES[want][1]
         assert len(args) == len(types) and args[-1] == 7
         floats = [i for i, t in enumerate(types) if t is C.c_float]

@@ -45,7 +45,8 @@ def test_struct_layout_matches_header():
     """ctypes mirrors must have the header's field order and count."""
     from gdlhip import _lib
     text = (ROOT / "include" / "gdlhip.h").read_text()
-    for cname, struct in (("gdl_conv_args", _lib.ConvArgs), ("gdl_wgrad_args", _lib.WgradArgs)):
+    for cname, struct in (("gdl_conv_args", _lib.ConvArgs), ("gdl_wgrad_args", _lib.WgradArgs),
+                          ("gdl_dice_options", _lib.DiceOptions), ("gdl_overlap_options", _lib.OverlapOptions)):
         body = re.search(r"typedef struct \{([^}]*)\} " + cname + ";", text).group(1)
         body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
         fields = []
@@ -58,6 +59,151 @@ def test_struct_layout_matches_header():
         mine = [f[0] for f in struct._fields_]
         assert len(mine) == len(fields), (cname, mine, fields)
         assert [m.replace("inp", "in") for m in mine] == fields
+
+
+def test_parsed_signatures_spot_checks():
+    """The binding is read from include/gdlhip.h: literal expectations for one entry point of every type kind the header uses
+    (written out from the C declarations, not derived from the parser) and for the longest argument list."""
+    import ctypes as C
+    from gdlhip import _lib
+    i, l, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
+    sig = _lib.SIGNATURES
+    assert len(sig) == 187 and not any(n.startswith("gdl_debug_") for n in sig)
+    tensor = [p, l, l]                  # a pointer with its batch and token strides
+    want = [*tensor * 5, p, p, *tensor * 3, i, i, i, i, f, p, l, p]
+    assert len(want) == 34 and sig["gdl_flash_attn_bwd"] == (i, want)
+    assert sig["gdl_syncbn_pack"] == (i, [p, p, d, i, p, p, p])
+    assert sig["gdl_adam_tick"] == (i, [p, d, d, p])
+    assert sig["gdl_normalize_range"] == (i, [p, i, p, i, i, l, i, i, d, d, p, p, p])
+    assert sig["gdl_normalize_u8"] == (i, [p, p, i, i, l, p, p, p])                              # const uint8_t*
+    assert sig["gdl_sort_desc_f32"] == (i, [p, i, l, p, p, p, l, p])                             # int32_t*
+    assert sig["gdl_bilinear_sum_fwd"] == (i, [p, p, p, i, i, i, i, p, i, i, p])                 # const void* const*
+    assert sig["gdl_last_error"] == (C.c_char_p, []) and sig["gdl_version"] == (i, [])
+    res, args = sig["gdl_conv_gemm"]
+    assert res is i and args[1] is p and args[0]._type_ is _lib.ConvArgs                       # POINTER(ConvArgs): callers pass byref
+    res, args = sig["gdl_conv_gemm_plan"]
+    assert res is i and args[0]._type_ is _lib.ConvArgs and args[1]._type_ is l
+    assert sig["gdl_conv_wgrad_workspace"][0] is l and sig["gdl_conv_wgrad_workspace"][1][0]._type_ is _lib.WgradArgs
+    assert sig["gdl_dice_loss_opt_fwd"] == (i, [p, p, i, i, l, f, p, p, p, p, l, p])             # the options pointer: an address
+    assert sig["gdl_overlap_loss_fwd"] == sig["gdl_dice_loss_opt_fwd"]
+    assert sig["gdl_dice_loss_workspace"] == (l, [i, i, l])
+    assert sig["gdl_resize_conv3x3_bwd_gather_one_pass"] == (i, [i] * 7)
+    # struct fields: `in` is spelled inp, a run `int B, H, W, C` is four fields, `classes` is a typed host pointer
+    conv = dict(_lib.ConvArgs._fields_)
+    assert [n for n, _ in _lib.ConvArgs._fields_][:6] == ["inp", "dtype", "B", "H", "W", "C"]
+    assert conv["inp"] is p and conv["in_sB"] is l and conv["alpha"] is f and conv["stats_partial"] is p and len(conv) == 44
+    assert _lib.DiceOptions._fields_ == [("has_ignore_index", i), ("ignore_index", l), ("smooth", f), ("log_loss", i),
+                                         ("classes", C.POINTER(i)), ("num_classes", i)]
+    assert _lib.OverlapOptions._fields_[-2:] == [("classes", C.POINTER(i)), ("nclasses", i)] and len(_lib.OverlapOptions._fields_) == 10
+    assert (_lib.F32, _lib.BF16, _lib.ACT_RESID_RELU, _lib.FOCAL_TILE, _lib.BCE_TARGET_F32, _lib.OVERLAP_TVERSKY) == (0, 1, 4, 2, 1, 2)
+    # the hooks of include/gdlhip_debug.h: bound, typed, and not part of the public set
+    dbg = _lib.DEBUG_SIGNATURES
+    assert len(dbg) == 30 and all(n.startswith("gdl_debug_") for n in dbg)
+    assert dbg["gdl_debug_set_flash_fwd"] == (None, [i, f]) and dbg["gdl_debug_set_conv_probe"] == (None, [p])
+    assert all(sig_ == (None, [i]) for n, sig_ in dbg.items() if n not in ("gdl_debug_set_flash_fwd", "gdl_debug_set_conv_probe"))
+    assert set(_lib.ENV_HOOKS.values()) <= set(dbg) and _lib.ENV_HOOKS["GDL_WGRAD_MODE"] == "gdl_debug_force_wgrad_small"
+
+
+def test_every_debug_hook_is_exported(lib):
+    from gdlhip import _lib
+    for n in _lib.DEBUG_SIGNATURES:
+        assert hasattr(lib, n), f"{n} declared in include/gdlhip_debug.h but not exported by libgdlhip.so"
+        assert getattr(lib, n).argtypes == _lib.DEBUG_SIGNATURES[n][1]
+
+
+def test_header_parser_is_strict():
+    """Anything outside the header's dialect raises at import and names the line: no entry point binds with a guessed type."""
+    from gdlhip import _lib
+    good = "typedef void* gdl_stream_t;\n/* two\n lines */\nint gdl_a(const float* x, int64_t n, gdl_stream_t stream);\nint64_t gdl_b(int n);\n"
+    h = _lib.Header(good)
+    assert h.functions == {"gdl_a": (_lib.c_i, [_lib.c_p, _lib.c_l, _lib.c_p]), "gdl_b": (_lib.c_l, [_lib.c_i])}
+    assert h.status == {"gdl_a"}
+    bad = {"unknown type": (good + "int gdl_c(unsigned n, gdl_stream_t stream);\n", "line 6.*unsigned n"),
+           "two-word type": (good + "\nint gdl_c(long long n);\n", "line 7.*long long n"),
+           "unparsable declarator": (good + "int gdl_c(void (*cb)(int), gdl_stream_t stream);\n", r"line 6.*gdl_c\(void \(\*cb\)"),
+           "array of arrays": (good + "int gdl_c(float m[4][4]);\n", r"line 6.*float m\[4\]\[4\]"),
+           "unnamed parameter": (good + "int gdl_c(int);\n", "line 6.*'int'"),
+           "unknown return type": (good + "size_t gdl_c(int n);\n", "line 6.*size_t"),
+           "unknown struct": (good + "typedef struct {\n  int n;\n} gdl_new_args;\n", "line 6.*gdl_new_args"),
+           "macro with arguments": (good + "#define GDL_MAX(a, b) ((a) > (b) ? (a) : (b))\n", "line 6.*GDL_MAX"),
+           "unknown preprocessor line": (good + "#pragma pack(1)\n", "line 6.*#pragma pack"),
+           "enumerator without a value": (good + "enum { GDL_X, GDL_Y };\n", "line 6.*GDL_X"),
+           "declared twice": (good + "int gdl_b(int n);\n", "line 6.*gdl_b")}
+    for what, (text, match) in bad.items():
+        with pytest.raises(_lib.HeaderError, match=match):
+            _lib.Header(text)
+            pytest.fail(f"{what}: parsed")
+
+
+def test_checked_view_raises_what_check_raises(monkeypatch):
+    """_lib.checked(): exactly the int-returning functions that take a stream carry the errcheck; it raises check()'s errors with
+    the symbol as the label and hands a zero status through.  (No library call: gdl_last_error is a fake.)"""
+    import ctypes as C
+    from gdlhip import _lib
+    queries = {"gdl_version", "gdl_conv_gemm_plan", "gdl_resize_conv3x3_bwd_gather_one_pass", "gdl_bilinear_fwd_add_bn_ok",
+               "gdl_head_1x1_bn_ok", "gdl_bn_head_bwd_ok"}
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "gdlhip.h").read_text(), flags=re.S)
+    for name, (res, _) in _lib.SIGNATURES.items():
+        decl = re.search(r"\b" + name + r"\s*\(([^)]*)\)", text).group(1)
+        assert (name in _lib.STATUS_FUNCTIONS) == (res is C.c_int and "gdl_stream_t" in decl), name
+        assert res is C.c_int or name not in _lib.STATUS_FUNCTIONS
+    assert {n for n, (res, _) in _lib.SIGNATURES.items() if res is C.c_int} - _lib.STATUS_FUNCTIONS == queries
+    assert len(_lib.STATUS_FUNCTIONS) == 151
+
+    class Fn:
+        __name__ = "gdl_some_kernel"
+
+    class FakeLib:
+        def gdl_last_error(self):
+            return b"C must be a multiple of 8"
+
+    monkeypatch.setattr(_lib, "load", lambda: FakeLib())
+    assert _lib.status_errcheck(0, Fn(), ()) == 0
+    with pytest.raises(ValueError) as e:
+        _lib.status_errcheck(-1, Fn(), ())
+    assert str(e.value) == "gdl_some_kernel: C must be a multiple of 8" and not isinstance(e.value, _lib.GdlHipError)
+    with pytest.raises(_lib.GdlHipError) as e:
+        _lib.status_errcheck(-2, Fn(), ())
+    assert str(e.value) == "gdl_some_kernel: status -2: C must be a multiple of 8"
+
+
+def test_checked_view_binds_the_errcheck_to_the_status_functions(lib):
+    from gdlhip import _lib
+    chk = _lib.checked()
+    assert chk is not lib and chk is _lib.checked() and lib is _lib.load()
+    for name, (res, args) in _lib.SIGNATURES.items():
+        raw, fn = getattr(lib, name), getattr(chk, name)
+        assert fn.restype is res and fn.argtypes == args and raw.argtypes == args and fn.__name__ == name
+        assert (getattr(fn, "errcheck", None) is _lib.status_errcheck) == (name in _lib.STATUS_FUNCTIONS), name
+        assert getattr(raw, "errcheck", None) is not _lib.status_errcheck, f"{name}: load() must return the status"
+    assert chk.gdl_version() == lib.gdl_version()
+
+
+def test_environment_hooks_are_applied_once_by_load(monkeypatch):
+    """The GDL_* tuning variables: load() calls the hook of every variable that is set, with its integer value (GDL_FLASH_FWD
+    with GDL_FLASH_DEFER, default 6, as its second argument), and of no other."""
+    from gdlhip import _lib
+    seen = []
+
+    class FakeLib:
+        def __getattr__(self, name):
+            return lambda *a: seen.append((name, a))
+
+    monkeypatch.setattr(_lib, "_open", lambda errcheck=None: FakeLib())
+    monkeypatch.setattr(_lib, "_lib", None)
+    for var in _lib.ENV_HOOKS:
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setenv("GDL_CONV_W4P", "1024")
+    monkeypatch.setenv("GDL_FLASH_FWD", "2")
+    monkeypatch.setenv("GDL_WGRAD_MODE", "9")
+    monkeypatch.delenv("GDL_FLASH_DEFER", raising=False)
+    _lib.load(), _lib.load()
+    assert seen == [("gdl_debug_set_conv_w4p", (1024,)), ("gdl_debug_set_flash_fwd", (2, 6.0)), ("gdl_debug_force_wgrad_small", (9,))]
+    seen.clear()
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setenv("GDL_FLASH_DEFER", "0")
+    _lib.load()
+    assert ("gdl_debug_set_flash_fwd", (2, 0.0)) in seen
 
 
 def test_ops_refuse_cpu_tensors(lib):
@@ -193,7 +339,6 @@ def test_conv_tile_selection(lib):
     assert plan(32, 144, 144, 768, 256, 1)[0] == 9           # lateral 1x1: persistent 256^2 ping-pong (dense 1x1, more tiles than CUs)
     assert plan(1, 1, 32 * 1297, 768, 2304, 1)[0] == 9       # ViT qkv
     # the parked tile (variant 10, round 6) is opt-in: faster per layer, +-0 end to end (see gdl_conv_gemm_plan)
-    lib.gdl_debug_set_conv_w4p.argtypes = [C.c_int]
     lib.gdl_debug_set_conv_w4p(1)
     try:
         assert plan(1, 1, 32 * 1297, 768, 2304, 1)[0] == 10     # N >= 768, 12 K-steps, 1467 tiles

@@ -303,6 +303,22 @@ def test_c_entry_points_return_error_codes():
         ops.lovasz_bwd(x, y, buf[:7], buf[:3], None)
 
 
+def test_checked_view_raises_where_the_raw_view_returns_the_status():
+    """The null-logits call of the test above through both views of the binding: ``_lib.load()`` returns GDL_ERR_INVALID,
+    ``_lib.checked()`` (what gdlhip.ops launches through) raises ValueError, the symbol first, then gdl_last_error()'s message.  The
+    argument check returns before any launch."""
+    raw, chk = gdlhip._lib.load(), gdlhip._lib.checked()
+    y, buf = torch.zeros(1, 4, 4, dtype=torch.int64, device=DEV), torch.zeros(4096, device=DEV)
+    args = (None, y.data_ptr(), 1, 3, 16, 0, 0, 0, *[buf.data_ptr()] * 4, 16384, None)
+    assert raw.gdl_lovasz_fwd(*args) == -1
+    message = raw.gdl_last_error().decode()
+    assert "null pointer" in message
+    with pytest.raises(ValueError) as e:
+        chk.gdl_lovasz_fwd(*args)
+    assert str(e.value) == "gdl_lovasz_fwd: " + message and not isinstance(e.value, gdlhip.GdlHipError)
+    assert chk.gdl_lovasz_workspace(3, 16, 3) == raw.gdl_lovasz_workspace(3, 16, 3) > 0      # a query: its value, unchecked
+
+
 # ------------------------------------------------------------------------------------------------ 7. captured step
 def test_graphed_train_step_reproduces_the_eager_losses_bit_for_bit():
     """GraphedTrainStep (hipGraph capture of forward + LovaszLoss + backward + Adam) on the toy task: one capture and three replays

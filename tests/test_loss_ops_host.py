@@ -145,20 +145,26 @@ def _kind_ok(value, ctype) -> bool:
 
 @pytest.mark.parametrize("call,symbol,want,sized", [c[1:] for c in CASES], ids=[c[0] for c in CASES])
 def test_wrapper_hands_the_entry_point_its_arguments_in_order(monkeypatch, call, symbol, want, sized):
-    calls, sizes, checked = [], [], []
+    calls, sizes = [], []
 
     class Recorder:
+        """Either view of the library: a size query may go through both, a launch only through the one that checks its status."""
+
+        def __init__(self, checks_status):
+            self.checks_status = checks_status
+
         def __getattr__(self, name):
             if name.endswith("_workspace") or name.endswith("_state"):
                 return lambda *a: sizes.append((name, a)) or WS
+            assert self.checks_status and name in _lib.STATUS_FUNCTIONS, f"{name}: launched through the view that drops its status"
             return lambda *a: calls.append((name, a)) or 0
 
-    monkeypatch.setattr(_lib, "load", lambda: Recorder())
+    monkeypatch.setattr(_lib, "load", lambda: Recorder(False))
+    monkeypatch.setattr(_lib, "checked", lambda: Recorder(True))
     monkeypatch.setattr(ops, "_need_cuda", lambda *ts: None)
     monkeypatch.setattr(ops, "_stream", lambda: STREAM)
-    monkeypatch.setattr(ops, "check", lambda status, what: checked.append((status, what)))
     call()
-    assert [c[0] for c in calls] == [symbol] and checked == [(0, symbol)]
+    assert [c[0] for c in calls] == [symbol]
     assert sizes == sized
     args, types = calls[0][1], _lib.SIGNATURES[symbol][1]
     assert len(args) == len(types)
@@ -183,9 +189,9 @@ def test_a_fused_soft_ce_forward_the_shape_does_not_take_runs_the_plain_one(monk
             return lambda *a: calls.append(name) or 0
 
     monkeypatch.setattr(_lib, "load", lambda: Recorder())
+    monkeypatch.setattr(_lib, "checked", lambda: Recorder())
     monkeypatch.setattr(ops, "_need_cuda", lambda *ts: None)
     monkeypatch.setattr(ops, "_stream", lambda: STREAM)
-    monkeypatch.setattr(ops, "check", lambda status, what: None)
     loss, state = ops.soft_ce_lowres_fwd(LOWK, Y, (HO, WO), SCE, fused=True)
     assert calls == ["gdl_soft_ce_lowres_fwd"] and state is None and loss.shape == ()
 
