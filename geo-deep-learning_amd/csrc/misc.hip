@@ -7,6 +7,7 @@
 
 #include "gdl_common.h"
 #include "bilinear_index.h"
+#include "infer_expr.h"
 
 namespace {
 
@@ -198,9 +199,8 @@ __global__ __launch_bounds__(256) void normalize_raw_kernel(const TI* __restrict
 }
 
 // The caller's sensor range instead of 0..255 -> 0..1 (tools/script_model.py:45-52 with any image_min / image_max / norm_min /
-// norm_max): ((d * (x - image_min)) / span + norm_min - mean[c]) / std[c] with d = norm_max - norm_min and span = image_max -
-// image_min, every step rounded to f32 in the order utils/tensors.py:19-21,34 takes them on an f32 tensor (not folded into one scale
-// and offset: that form differs from the reference by up to a few ulp).  V elements of the flat NCHW tile per thread (V == 4: one
+// norm_max): normalize_range_value of infer_expr.h per element (gdl_scene_cut evaluates the same function).
+// V elements of the flat NCHW tile per thread (V == 4: one
 // vector load and one 16-byte store; a group may straddle a channel when H*W % 4 != 0, so the channel advances per element); the
 // total % V elements behind the last whole group are done one per thread by the first threads of the grid.
 template <typename TI, int V>
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void normalize_range_kernel(const TI* __restri
     VecF o;
 #pragma unroll
     for (int e = 0; e < V; ++e) {
-      o.v[e] = ((d * ((float)x.v[e] - imin)) / span + nmin - mean[c]) / stdv[c];
+      o.v[e] = normalize_range_value((float)x.v[e], imin, span, d, nmin, mean[c], stdv[c]);
       if (++r == HW) { r = 0; if (++c == C) c = 0; }
     }
     *(VecF*)(out + i0) = o;
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256) void normalize_range_kernel(const TI* __restri
   const int64_t i = groups * V + tid;
   if (i < total) {
     const int c = (int)((i / HW) % C);
-    out[i] = ((d * ((float)in[i] - imin)) / span + nmin - mean[c]) / stdv[c];
+    out[i] = normalize_range_value((float)in[i], imin, span, d, nmin, mean[c], stdv[c]);
   }
 }
 
@@ -1149,17 +1149,7 @@ __global__ __launch_bounds__(256) void upsample_probs_kernel(const float* __rest
       int x0, x1; float lx;
       src_index2(rx, ox0 + e, Wi, x0, x1, lx);
       bilinear_logits<K>(low, b, Hi, Wi, y0, y1, x0, x1, ly, lx, x[e]);
-      if constexpr (K == 1) {
-        x[e][0] = 1.0f / (1.0f + expf(-x[e][0]));
-      } else {
-        float mx = -INFINITY, s = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) mx = fmaxf(mx, x[e][k]);
-#pragma unroll
-        for (int k = 0; k < K; ++k) { x[e][k] = expf(x[e][k] - mx); s += x[e][k]; }
-#pragma unroll
-        for (int k = 0; k < K; ++k) x[e][k] = x[e][k] / s;
-      }
+      logits_to_probs<K>(x[e]);
     }
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -1424,8 +1414,8 @@ extern "C" int gdl_normalize_range(const void* in, int kind, float* out, int B, 
   GDL_CHECK_ARG(image_max != image_min, "gdl_normalize_range: image_max == image_min (%d): the range is empty", image_min);
   const int64_t total = (int64_t)B * C * HW;
   // the scalars as Python forms them before they meet the f32 tensor: differences in int / double, one rounding to f32 each
-  const float imin = (float)image_min, span = (float)((int64_t)image_max - (int64_t)image_min);
-  const float d = (float)(norm_max - norm_min), nmin = (float)norm_min;
+  const RangeScalars r = range_scalars(image_min, image_max, norm_min, norm_max);
+  const float imin = r.imin, span = r.span, d = r.d, nmin = r.nmin;
   const bool vec = (uintptr_t)in % 16 == 0 && (uintptr_t)out % 16 == 0;
   hipStream_t s = (hipStream_t)stream;
 #define NR(T)                                                                                                                      \

@@ -1,0 +1,320 @@
+// Whole-scene inference (include/gdlhip_scene.h): cut normalised tiles out of a raster, stitch the tiles' class probabilities into a
+// weighted canvas, label the canvas.  All four kernels are bound by memory traffic; none uses atomics, so every result is
+// reproducible bit for bit.
+#include <cmath>
+
+#include "gdl_common.h"
+#include "bilinear_index.h"
+#include "infer_expr.h"
+#include "../../include/gdlhip_scene.h"
+
+namespace {
+
+// ------------------------------------------------------------------ cut
+// A thread writes V consecutive values of one tile row (V == 4: one 16-byte store, tw % 4 == 0); the raster is read element by
+// element because a tile origin has no alignment.  The value is normalize_range_value of infer_expr.h, the function
+// normalize_range_kernel evaluates, on the raw sample or, outside the raster, on `fill`.
+template <typename TI, int V>
+__global__ __launch_bounds__(256) void scene_cut_kernel(const TI* __restrict__ raster, int C, int H, int W,
+                                                        const int32_t* __restrict__ origins, int th, int tw, float fill,
+                                                        float* __restrict__ tiles, int64_t groups, float imin, float span, float d,
+                                                        float nmin, const float* __restrict__ mean, const float* __restrict__ stdv) {
+  struct alignas(sizeof(float) * V) VecF { float v[V]; };
+  const int twv = tw / V;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const int dx0 = (int)(g % twv) * V;
+    int64_t t = g / twv;
+    const int dy = (int)(t % th);
+    t /= th;
+    const int c = (int)(t % C), b = (int)(t / C);
+    const int64_t y = (int64_t)origins[2 * b] + dy, x0 = (int64_t)origins[2 * b + 1] + dx0;
+    const bool row_in = y >= 0 && y < H;
+    const TI* row = raster + ((int64_t)c * H + (row_in ? y : 0)) * W;
+    const float m = mean[c], s = stdv[c];
+    VecF o;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const int64_t x = x0 + e;
+      const float raw = row_in && x >= 0 && x < W ? (float)row[x] : fill;
+      o.v[e] = normalize_range_value(raw, imin, span, d, nmin, m, s);
+    }
+    *(VecF*)(tiles + g * V) = o;
+  }
+}
+
+// ------------------------------------------------------------------ blend
+// Where the class probabilities of tile pixel (dy, dx0 + e), e < V, come from.  `cov[e]` says which of the V pixels the tile covers;
+// only those are read and only their p[e] is defined.
+
+// the tiles' full-resolution probabilities [B, K, th, tw]
+template <int K>
+struct ProbsSource {
+  const float* probs;
+  int th, tw;
+  bool vec;   // tw % 4 == 0 and a 16-byte aligned base: four covered pixels at dx0 % 4 == 0 are one 16-byte load per class
+  __device__ __forceinline__ void prepare() {}
+  template <int V>
+  __device__ __forceinline__ void load(int t, int dy, int dx0, const bool (&cov)[V], float (&p)[V][K]) const {
+    const float* base = probs + (((int64_t)t * K) * th + dy) * tw + dx0;
+    const int64_t plane = (int64_t)th * tw;
+    if constexpr (V == 4) {
+      if (vec && (dx0 & 3) == 0 && cov[0] && cov[1] && cov[2] && cov[3]) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const float4 q = *(const float4*)(base + k * plane);
+          p[0][k] = q.x; p[1][k] = q.y; p[2][k] = q.z; p[3][k] = q.w;
+        }
+        return;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e)
+      if (cov[e]) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) p[e][k] = base[k * plane + e];
+      }
+  }
+};
+
+// a head's own map [B, hi, wi, K] (NHWC): the pixel's probabilities as upsample_probs_kernel evaluates them -- src_index2 and
+// bilinear_logits of bilinear_index.h, logits_to_probs of infer_expr.h, the ratios formed on the device as that kernel forms them
+template <int K>
+struct LowresSource {
+  const float* low;
+  int hi, wi, th, tw;
+  float ry, rx;
+  __device__ __forceinline__ void prepare() { ry = (float)hi / (float)th; rx = (float)wi / (float)tw; }
+  template <int V>
+  __device__ __forceinline__ void load(int t, int dy, int dx0, const bool (&cov)[V], float (&p)[V][K]) const {
+    int y0, y1; float ly;
+    src_index2(ry, dy, hi, y0, y1, ly);
+#pragma unroll
+    for (int e = 0; e < V; ++e)
+      if (cov[e]) {
+        int x0, x1; float lx;
+        src_index2(rx, dx0 + e, wi, x0, x1, lx);
+        bilinear_logits<K>(low, t, hi, wi, y0, y1, x0, x1, ly, lx, p[e]);
+        logits_to_probs<K>(p[e]);
+      }
+  }
+};
+
+constexpr int PATCH_W = 64;   // canvas columns of one workgroup's patch; its rows: 256 threads / (PATCH_W / V) = 16 (V == 4) or 4 (V == 1)
+
+// One workgroup per patch of the batch's bounding box, one thread per V consecutive canvas pixels of a row (V == 4: W % 4 == 0 and
+// a 16-byte aligned canvas, so every plane is read and written with 16-byte accesses along W; V == 1 otherwise).  The tiles of the
+// batch are taken 256 at a time: thread i tests tile base + i against the patch, a ballot compaction writes the hits to LDS in
+// ascending tile order, and all threads walk that list (the list reads are LDS broadcasts, the loop bounds workgroup-uniform).
+// A thread holds its K + 1 canvas values in registers from the first tile to the last and stores them only if a tile covered
+// one of its pixels: canvas = fma(w, p, canvas) per class and canvas[K] += w, in ascending tile order whatever the batching.
+template <int K, int V, typename Src>
+__global__ __launch_bounds__(256) void scene_blend_kernel(Src src, int B, int th, int tw, const int32_t* __restrict__ origins,
+                                                          const float* __restrict__ wy, const float* __restrict__ wx,
+                                                          float* __restrict__ canvas, int H, int W, int y0, int y1, int x0, int x1,
+                                                          int xa, int patches_x) {
+  struct alignas(sizeof(float) * V) VecF { float v[V]; };
+  constexpr int LPR = PATCH_W / V, PH = 256 / LPR;
+  __shared__ int s_tile[256], s_oy[256], s_ox[256], s_count[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int py0 = y0 + (int)(blockIdx.x / patches_x) * PH, px0 = xa + (int)(blockIdx.x % patches_x) * PATCH_W;
+  const int py1 = py0 + PH < y1 ? py0 + PH : y1, px1 = px0 + PATCH_W < x1 ? px0 + PATCH_W : x1;
+  const int y = py0 + tid / LPR, xb = px0 + (tid % LPR) * V;
+  src.prepare();
+
+  bool in[V], any_in = false;
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    in[e] = y < y1 && xb + e >= x0 && xb + e < x1;
+    any_in |= in[e];
+  }
+  // V == 4: xb % 4 == 0 and W % 4 == 0, so the four pixels are inside the canvas row as soon as one of them is inside the box
+  float acc[K + 1][V];
+  float* const mine = canvas + (int64_t)y * W + xb;
+  const int64_t plane = (int64_t)H * W;
+  if (any_in) {
+#pragma unroll
+    for (int k = 0; k <= K; ++k) {
+      const VecF c = *(const VecF*)(mine + k * plane);
+#pragma unroll
+      for (int e = 0; e < V; ++e) acc[k][e] = c.v[e];
+    }
+  }
+  bool touched = false;
+
+  for (int base = 0; base < B; base += 256) {
+    const int t = base + tid;
+    int oy = 0, ox = 0;
+    bool hit = false;
+    if (t < B) {
+      oy = origins[2 * t];
+      ox = origins[2 * t + 1];
+      hit = oy < py1 && (int64_t)oy + th > py0 && ox < px1 && (int64_t)ox + tw > px0;
+    }
+    const unsigned long long m = __ballot(hit);
+    if (lane == 0) s_count[wave] = __popcll(m);
+    __syncthreads();
+    int before = 0, n = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const int c = s_count[w];
+      before += w < wave ? c : 0;
+      n += c;
+    }
+    if (hit) {
+      const int pos = before + __popcll(m & ((1ull << lane) - 1ull));
+      s_tile[pos] = t; s_oy[pos] = oy; s_ox[pos] = ox;
+    }
+    __syncthreads();
+    for (int j = 0; j < n; ++j) {
+      const int dy = y - s_oy[j], dx0 = xb - s_ox[j];
+      if (!any_in || dy < 0 || dy >= th) continue;
+      bool cov[V], any = false;
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        cov[e] = in[e] && dx0 + e >= 0 && dx0 + e < tw;
+        any |= cov[e];
+      }
+      if (!any) continue;
+      float p[V][K];
+      src.template load<V>(s_tile[j], dy, dx0, cov, p);
+      const float wrow = wy[dy];
+#pragma unroll
+      for (int e = 0; e < V; ++e)
+        if (cov[e]) {
+          const float w = wrow * wx[dx0 + e];
+#pragma unroll
+          for (int k = 0; k < K; ++k) acc[k][e] = fmaf(w, p[e][k], acc[k][e]);
+          acc[K][e] += w;
+        }
+      touched = true;
+    }
+    __syncthreads();   // the next 256 tiles overwrite the list
+  }
+
+  if (touched) {
+#pragma unroll
+    for (int k = 0; k <= K; ++k) {
+      VecF c;
+#pragma unroll
+      for (int e = 0; e < V; ++e) c.v[e] = acc[k][e];
+      *(VecF*)(mine + k * plane) = c;
+    }
+  }
+}
+
+// ------------------------------------------------------------------ finish
+// A thread labels V consecutive pixels (V == 4: HW % 4 == 0 and aligned pointers, 16-byte loads of every plane and one 4-byte
+// store of the mask).  The class count is a loop bound only: nothing is kept per class.
+template <int V>
+__global__ __launch_bounds__(256) void scene_finish_kernel(const float* __restrict__ canvas, int K, int64_t HW, float threshold,
+                                                           uint8_t* __restrict__ mask, float* __restrict__ probs) {
+  struct alignas(sizeof(float) * V) VecF { float v[V]; };
+  struct alignas(V) VecB { uint8_t v[V]; };
+  const int64_t groups = HW / V;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const int64_t i0 = g * V;
+    const VecF den = *(const VecF*)(canvas + (int64_t)K * HW + i0);
+    float best_v[V], first[V];
+    int best[V];
+    for (int k = 0; k < K; ++k) {
+      const VecF c = *(const VecF*)(canvas + (int64_t)k * HW + i0);
+      VecF q;
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        q.v[e] = den.v[e] != 0.f ? c.v[e] / den.v[e] : 0.f;
+        if (k == 0) { best_v[e] = c.v[e]; best[e] = 0; first[e] = q.v[e]; }
+        else if (c.v[e] > best_v[e]) { best_v[e] = c.v[e]; best[e] = k; }
+      }
+      if (probs) *(VecF*)(probs + (int64_t)k * HW + i0) = q;
+    }
+    VecB o;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      const int label = K == 1 ? (first[e] > threshold ? 1 : 0) : best[e];
+      o.v[e] = den.v[e] != 0.f ? (uint8_t)label : (uint8_t)0;
+    }
+    *(VecB*)(mask + i0) = o;
+  }
+}
+
+template <int K, typename Src>
+void launch_blend(Src src, int B, int th, int tw, const int32_t* origins, const float* wy, const float* wx, float* canvas, int H, int W,
+                  int y0, int y1, int x0, int x1, hipStream_t s) {
+  const bool vec = W % 4 == 0 && (uintptr_t)canvas % 16 == 0;
+  const int V = vec ? 4 : 1, ph = 256 / (PATCH_W / V);
+  const int xa = vec ? x0 & ~3 : x0;
+  const int patches_x = (x1 - xa + PATCH_W - 1) / PATCH_W, patches_y = (y1 - y0 + ph - 1) / ph;
+  const dim3 grid((unsigned)((int64_t)patches_x * patches_y));
+  if (vec) hipLaunchKernelGGL((scene_blend_kernel<K, 4, Src>), grid, dim3(256), 0, s, src, B, th, tw, origins, wy, wx, canvas, H, W, y0, y1, x0, x1, xa, patches_x);
+  else hipLaunchKernelGGL((scene_blend_kernel<K, 1, Src>), grid, dim3(256), 0, s, src, B, th, tw, origins, wy, wx, canvas, H, W, y0, y1, x0, x1, xa, patches_x);
+}
+
+// the bounding box clipped to the canvas; false = nothing of it is left
+bool clip_box(int H, int W, int& y0, int& y1, int& x0, int& x1) {
+  y0 = y0 < 0 ? 0 : y0; x0 = x0 < 0 ? 0 : x0;
+  y1 = y1 > H ? H : y1; x1 = x1 > W ? W : x1;
+  return y0 < y1 && x0 < x1;
+}
+
+}  // namespace
+
+extern "C" int gdl_scene_cut(const void* raster, int kind, int C, int H, int W, const int32_t* origins, int B, int th, int tw, int fill,
+                             float* tiles, int image_min, int image_max, double norm_min, double norm_max, const float* mean,
+                             const float* stdv, gdl_stream_t stream) {
+  GDL_CHECK_ARG(raster && origins && tiles && mean && stdv, "gdl_scene_cut: null pointer");
+  GDL_CHECK_ARG(kind >= GDL_RAW_U8 && kind <= GDL_RAW_F32, "gdl_scene_cut: bad sample kind %d", kind);
+  GDL_CHECK_ARG(C > 0 && H > 0 && W > 0 && B > 0 && th > 0 && tw > 0, "gdl_scene_cut: bad sizes");
+  GDL_CHECK_ARG(image_max != image_min, "gdl_scene_cut: image_max == image_min (%d): the range is empty", image_min);
+  const RangeScalars r = range_scalars(image_min, image_max, norm_min, norm_max);
+  const bool vec = tw % 4 == 0 && (uintptr_t)tiles % 16 == 0;
+  const int64_t groups = (int64_t)B * C * th * (tw / (vec ? 4 : 1));
+  hipStream_t s = (hipStream_t)stream;
+#define CUT(T)                                                                                                                        \
+  if (vec) hipLaunchKernelGGL((scene_cut_kernel<T, 4>), dim3(grid_for(groups)), dim3(256), 0, s, (const T*)raster, C, H, W, origins,  \
+                              th, tw, (float)fill, tiles, groups, r.imin, r.span, r.d, r.nmin, mean, stdv);                           \
+  else hipLaunchKernelGGL((scene_cut_kernel<T, 1>), dim3(grid_for(groups)), dim3(256), 0, s, (const T*)raster, C, H, W, origins, th,  \
+                          tw, (float)fill, tiles, groups, r.imin, r.span, r.d, r.nmin, mean, stdv)
+  if (kind == GDL_RAW_U8) { CUT(uint8_t); }
+  else if (kind == GDL_RAW_U16) { CUT(uint16_t); }
+  else if (kind == GDL_RAW_I16) { CUT(int16_t); }
+  else { CUT(float); }
+#undef CUT
+  GDL_CHECK_LAUNCH("gdl_scene_cut");
+  return GDL_OK;
+}
+
+extern "C" int gdl_scene_blend(const float* probs, int B, int K, int th, int tw, const int32_t* origins, const float* wy,
+                               const float* wx, float* canvas, int H, int W, int y0, int y1, int x0, int x1, gdl_stream_t stream) {
+  GDL_CHECK_ARG(probs && origins && wy && wx && canvas, "gdl_scene_blend: null pointer");
+  GDL_CHECK_ARG(B > 0 && th > 0 && tw > 0 && H > 0 && W > 0, "gdl_scene_blend: bad sizes");
+  GDL_CHECK_ARG(K >= 1 && K <= 16, "gdl_scene_blend: 1..16 classes, got %d", K);
+  if (!clip_box(H, W, y0, y1, x0, x1)) return GDL_OK;
+  const bool vec = tw % 4 == 0 && (uintptr_t)probs % 16 == 0;
+  K_SWITCH(K, launch_blend<KK>(ProbsSource<KK>{probs, th, tw, vec}, B, th, tw, origins, wy, wx, canvas, H, W, y0, y1, x0, x1, (hipStream_t)stream));
+  GDL_CHECK_LAUNCH("gdl_scene_blend");
+  return GDL_OK;
+}
+
+extern "C" int gdl_scene_blend_lowres(const float* low, int B, int hi, int wi, int K, int th, int tw, const int32_t* origins,
+                                      const float* wy, const float* wx, float* canvas, int H, int W, int y0, int y1, int x0, int x1,
+                                      gdl_stream_t stream) {
+  GDL_CHECK_ARG(low && origins && wy && wx && canvas, "gdl_scene_blend_lowres: null pointer");
+  GDL_CHECK_ARG(B > 0 && hi > 0 && wi > 0 && th > 0 && tw > 0 && H > 0 && W > 0, "gdl_scene_blend_lowres: bad sizes");
+  GDL_CHECK_ARG(K >= 1 && K <= 16, "gdl_scene_blend_lowres: 1..16 classes, got %d (more: gdl_class_probs + gdl_scene_blend)", K);
+  if (!clip_box(H, W, y0, y1, x0, x1)) return GDL_OK;
+  K_SWITCH(K, launch_blend<KK>(LowresSource<KK>{low, hi, wi, th, tw, 0.f, 0.f}, B, th, tw, origins, wy, wx, canvas, H, W, y0, y1, x0, x1, (hipStream_t)stream));
+  GDL_CHECK_LAUNCH("gdl_scene_blend_lowres");
+  return GDL_OK;
+}
+
+extern "C" int gdl_scene_finish(const float* canvas, int K, int64_t HW, float threshold, uint8_t* mask, float* probs,
+                                gdl_stream_t stream) {
+  GDL_CHECK_ARG(canvas && mask, "gdl_scene_finish: null pointer");
+  GDL_CHECK_ARG(K >= 1 && K <= 255 && HW > 0, "gdl_scene_finish: bad sizes (1..255 classes, got %d)", K);
+  const bool vec = HW % 4 == 0 && (uintptr_t)canvas % 16 == 0 && (uintptr_t)probs % 16 == 0 && (uintptr_t)mask % 4 == 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (vec) hipLaunchKernelGGL(scene_finish_kernel<4>, dim3(grid_for(HW / 4)), dim3(256), 0, s, canvas, K, HW, threshold, mask, probs);
+  else hipLaunchKernelGGL(scene_finish_kernel<1>, dim3(grid_for(HW)), dim3(256), 0, s, canvas, K, HW, threshold, mask, probs);
+  GDL_CHECK_LAUNCH("gdl_scene_finish");
+  return GDL_OK;
+}

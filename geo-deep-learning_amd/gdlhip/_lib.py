@@ -33,7 +33,7 @@ _STRUCTS = {"gdl_conv_args": ("ConvArgs", True), "gdl_wgrad_args": ("WgradArgs",
 _TYPED = {("gdl_dice_options", "classes"): C.POINTER(c_i), ("gdl_overlap_options", "classes"): C.POINTER(c_i),
           ("gdl_conv_gemm_plan", "flops"): C.POINTER(c_l)}
 _RENAMED = {"in": "inp"}                                 # C field names that are Python keywords
-_PREPROCESSOR = re.compile(r'#\s*(ifndef \w+|define \w+|include <stdint\.h>|ifdef __cplusplus|endif)$|extern "C" \{$|\}$')
+_PREPROCESSOR = re.compile(r'#\s*(ifndef \w+|define \w+|include <stdint\.h>|include "gdlhip\.h"|ifdef __cplusplus|endif)$|extern "C" \{$|\}$')
 _DECLARATOR = re.compile(r"(?:const\s+)?(\w+)(\s*(?:\*\s*(?:const\s*)?)+|\s+)(\w+)\s*(\[\])?$")
 _NEXT = re.compile(r"\S")
 _STATEMENTS = [(kind, re.compile(rx)) for kind, rx in (
@@ -136,10 +136,13 @@ class Header:
 
 _ABI = Header((INCLUDE / "gdlhip.h").read_text())
 _DEBUG = Header((INCLUDE / "gdlhip_debug.h").read_text())
+_SCENE = Header((INCLUDE / "gdlhip_scene.h").read_text())
 
-# name -> (restype, argtypes); every symbol declared in include/gdlhip.h, and the gdl_debug_* hooks of include/gdlhip_debug.h
-SIGNATURES, DEBUG_SIGNATURES = _ABI.functions, _DEBUG.functions
+# name -> (restype, argtypes); every symbol declared in include/gdlhip.h, the gdl_debug_* hooks of include/gdlhip_debug.h and the
+# whole-scene inference calls of include/gdlhip_scene.h
+SIGNATURES, DEBUG_SIGNATURES, SCENE_SIGNATURES = _ABI.functions, _DEBUG.functions, _SCENE.functions
 STATUS_FUNCTIONS = frozenset(_ABI.status)      # they return a gdl_status; every other function returns a value
+_CHECKED = STATUS_FUNCTIONS | _SCENE.status    # what checked() gives the errcheck: the scene calls return a gdl_status too
 ConvArgs, WgradArgs, DiceOptions, OverlapOptions = (_ABI.structs[c] for c in _STRUCTS)
 # the header's enumerators and integer #defines without their GDL_ prefix: F32, BF16, ACT_*, FOCAL_* (the `form` argument of the
 # *_lowres_bwd calls), BCE_TARGET_* (the `target_type` of gdl_soft_bce_*), OVERLAP_* (gdl_overlap_options.kind), ...
@@ -181,11 +184,11 @@ def _open(errcheck=None) -> C.CDLL:
                "There is no PyTorch/CPU fallback for the gdlhip ops.")
         raise GdlHipError(msg)
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in (*SIGNATURES.items(), *DEBUG_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *DEBUG_SIGNATURES.items(), *SCENE_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args
-        if errcheck is not None and name in STATUS_FUNCTIONS:
+        if errcheck is not None and name in _CHECKED:
             fn.errcheck = errcheck
     return lib
 

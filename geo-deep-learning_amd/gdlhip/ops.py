@@ -1920,6 +1920,103 @@ def upsample_probs(low: Tensor, size: tuple[int, int]) -> Tensor:
     return out
 
 
+# ------------------------------------------------------------------ whole-scene inference (include/gdlhip_scene.h)
+_RAW_LIMITS = {torch.uint8: (0, 255), torch.uint16: (0, 65535), torch.int16: (-32768, 32767)}
+
+
+def _scene_origins(op: str, origins: Tensor) -> int:
+    if origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or origins.shape[0] < 1 or not origins.is_contiguous():
+        raise ValueError(f"{op}: origins must be a contiguous int32 [B, 2] tensor of (y0, x0), got {origins.dtype} {tuple(origins.shape)}")
+    return int(origins.shape[0])
+
+
+def scene_cut(raster: Tensor, origins: Tensor, tile: tuple[int, int], mean: Tensor, std: Tensor, image_min: int = 0,
+              image_max: int = 255, norm_min: float = 0.0, norm_max: float = 1.0, fill: int = 0) -> Tensor:
+    """Normalised NCHW f32 tiles [B, C, th, tw] cut out of a raw raster [C, H, W] (uint8 / uint16 / int16 / f32) at the origins
+    int32 [B, 2] = (y0, x0), which may be negative or reach past the raster: a position outside it takes the raw value ``fill``.
+    The values are those of ``normalize_range`` on the sliced (and padded) tile, bit for bit (gdl_scene_cut)."""
+    if raster.dtype not in _RAW_KIND or not raster.is_contiguous() or raster.dim() != 3:
+        raise ValueError(f"scene_cut: contiguous [C, H, W] uint8/uint16/int16/float32 raster expected, got {raster.dtype} {tuple(raster.shape)}")
+    if int(image_max) == int(image_min):
+        raise ValueError(f"scene_cut: image_max == image_min ({int(image_min)}): the range is empty")
+    _need_cuda(raster, origins, mean, std)
+    B = _scene_origins("scene_cut", origins)
+    th, tw = int(tile[0]), int(tile[1])
+    if th < 1 or tw < 1:
+        raise ValueError(f"scene_cut: bad tile {th} x {tw}")
+    lo, hi = _RAW_LIMITS.get(raster.dtype, (-2 ** 31, 2 ** 31 - 1))
+    if not lo <= int(fill) <= hi:
+        raise ValueError(f"scene_cut: fill {fill} is not a value of {raster.dtype}")
+    Cc, H, W = raster.shape
+    out = torch.empty((B, Cc, th, tw), device=raster.device, dtype=torch.float32)
+    _lib.checked().gdl_scene_cut(_p(raster), _RAW_KIND[raster.dtype], Cc, H, W, _p(origins), B, th, tw, int(fill), _p(out),
+                                 int(image_min), int(image_max), float(norm_min), float(norm_max), _p(_f32vec(mean, Cc, "mean")),
+                                 _p(_f32vec(std, Cc, "std")), _stream())
+    return out
+
+
+def _scene_blend_check(op: str, src: Tensor, K: int, tile: tuple[int, int], origins: Tensor, wy: Tensor, wx: Tensor, canvas: Tensor,
+                       box: tuple[int, int, int, int] | None) -> tuple[int, int, int, int, int, int]:
+    _need_cuda(src, origins, wy, wx, canvas)
+    if not 1 <= K <= 16:
+        raise ValueError(f"{op}: 1..16 classes, got {K}")
+    if _scene_origins(op, origins) != src.shape[0]:
+        raise ValueError(f"{op}: {origins.shape[0]} origins for {src.shape[0]} tiles")
+    th, tw = tile
+    _f32vec(wy, th, f"{op}: the row window wy")
+    _f32vec(wx, tw, f"{op}: the column window wx")
+    if canvas.dtype != torch.float32 or canvas.dim() != 3 or canvas.shape[0] != K + 1 or not canvas.is_contiguous():
+        raise ValueError(f"{op}: canvas must be a contiguous f32 [K+1, H, W] = [{K + 1}, H, W] tensor, got {canvas.dtype} {tuple(canvas.shape)}")
+    H, W = int(canvas.shape[1]), int(canvas.shape[2])
+    y0, y1, x0, x1 = (0, H, 0, W) if box is None else (int(v) for v in box)
+    return H, W, y0, y1, x0, x1
+
+
+def scene_blend(probs: Tensor, origins: Tensor, wy: Tensor, wx: Tensor, canvas: Tensor,
+                box: tuple[int, int, int, int] | None = None) -> Tensor:
+    """Adds the window-weighted probabilities [B, K, th, tw] f32 of the tiles at ``origins`` into ``canvas`` [K+1, H, W] f32 in
+    place (plane K: the weights), over the canvas pixels of ``box`` = (y0, y1, x0, x1), the batch's bounding box (default: the
+    whole canvas).  A gather in ascending tile order without atomics: the result does not depend on the batching (gdl_scene_blend)."""
+    if probs.dtype != torch.float32 or probs.dim() != 4 or not probs.is_contiguous():
+        raise ValueError("scene_blend: contiguous f32 probabilities [B, K, th, tw] expected")
+    B, K, th, tw = probs.shape
+    H, W, y0, y1, x0, x1 = _scene_blend_check("scene_blend", probs, K, (th, tw), origins, wy, wx, canvas, box)
+    _lib.checked().gdl_scene_blend(_p(probs), B, K, th, tw, _p(origins), _p(wy), _p(wx), _p(canvas), H, W, y0, y1, x0, x1, _stream())
+    return canvas
+
+
+def scene_blend_lowres(low: Tensor, size: tuple[int, int], origins: Tensor, wy: Tensor, wx: Tensor, canvas: Tensor,
+                       box: tuple[int, int, int, int] | None = None) -> Tensor:
+    """``scene_blend`` of ``upsample_probs(low, size)`` without those probabilities: each tile pixel's softmax (2..16 classes) or
+    sigmoid (one class) is evaluated from the head's NHWC f32 map [B, h, w, K] where it is added (gdl_scene_blend_lowres)."""
+    if low.dtype != torch.float32 or low.dim() != 4 or not low.is_contiguous():
+        raise ValueError("scene_blend_lowres: contiguous f32 NHWC logits [B, h, w, K] expected")
+    B, hi, wi, K = low.shape
+    th, tw = int(size[0]), int(size[1])
+    if min(hi, wi, th, tw) < 1:
+        raise ValueError(f"scene_blend_lowres: bad sizes {tuple(low.shape)} -> {th} x {tw}")
+    H, W, y0, y1, x0, x1 = _scene_blend_check("scene_blend_lowres", low, K, (th, tw), origins, wy, wx, canvas, box)
+    _lib.checked().gdl_scene_blend_lowres(_p(low), B, hi, wi, K, th, tw, _p(origins), _p(wy), _p(wx), _p(canvas), H, W, y0, y1, x0, x1,
+                                          _stream())
+    return canvas
+
+
+def scene_finish(canvas: Tensor, threshold: float = 0.5, return_probs: bool = False) -> tuple[Tensor, Tensor | None]:
+    """Canvas [K+1, H, W] f32 -> (mask uint8 [H, W], probabilities f32 [K, H, W] or None): arg-max over the K weighted sums (the
+    lowest index wins a tie) or, for one class, ``canvas[0] / canvas[1] > threshold``; a pixel that no tile covered (weight 0)
+    gets mask 0 and probabilities 0 (gdl_scene_finish)."""
+    _need_cuda(canvas)
+    if canvas.dtype != torch.float32 or canvas.dim() != 3 or not canvas.is_contiguous() or not 2 <= canvas.shape[0] <= 17:
+        raise ValueError(f"scene_finish: contiguous f32 canvas [K+1, H, W] with 1..16 classes expected, got {canvas.dtype} {tuple(canvas.shape)}")
+    K, H, W = canvas.shape[0] - 1, int(canvas.shape[1]), int(canvas.shape[2])
+    if H * W < 1:
+        raise ValueError(f"scene_finish: empty canvas {tuple(canvas.shape)}")
+    mask = torch.empty((H, W), device=canvas.device, dtype=torch.uint8)
+    probs = torch.empty((K, H, W), device=canvas.device, dtype=torch.float32) if return_probs else None
+    _lib.checked().gdl_scene_finish(_p(canvas), K, H * W, float(threshold), _p(mask), _p(probs), _stream())
+    return mask, probs
+
+
 def iou_counts(pred: Tensor, target: Tensor, num_classes: int) -> Tensor:
     """int64 [B, 3, K]: per sample and class (intersection, |pred==k|, |target==k|); exact integer counts."""
     _need_cuda(pred, target)

@@ -1,0 +1,92 @@
+"""Whole-scene inference: an ortho-image or satellite scene of any H x W in, one label mask (and, on request, the blended class
+probabilities) out.  The scene is covered by overlapping tiles (``gdlhip.scene.plan_tiles``); per batch of tiles one kernel cuts
+and normalises them (``ops.scene_cut``), the exported model (a ``ScriptModel``) runs, and one kernel adds the window-weighted
+class probabilities into a canvas [K+1, H, W] -- straight from the heads' low-resolution maps where the model hands them over
+(``ops.scene_blend_lowres``: the [B, K, th, tw] probabilities are never written), otherwise from ``class_probs``
+(``ops.scene_blend``).  ``ops.scene_finish`` labels the canvas once at the end.
+
+Determinism: the canvas is accumulated by a gather in tile order without atomics, so the mask and the probabilities do not
+depend on ``batch_size`` and are the same bits from run to run.  The reference has no counterpart (its inference stops at the
+tile, tools/script_model.py)."""
+
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import torch
+
+from gdlhip import nn as gnn
+from gdlhip import ops
+from gdlhip import scene as gscene
+
+from .script_model import ScriptModel
+
+_RASTER_DTYPES = (torch.uint8, torch.uint16, torch.int16, torch.float32)
+
+
+class SceneResult(NamedTuple):
+    mask: torch.Tensor                  # uint8 [H, W]
+    probs: torch.Tensor | None          # f32 [K, H, W], None unless asked for
+
+
+class SceneInference:
+    """``SceneInference(script_model, tile=(512, 512), overlap=0.5).predict(raster)``.
+
+    ``script_model``: a ``ScriptModel`` / ``SegmentationScriptModel``; its input range, mean, std, bf16 flag and wavelengths apply.
+    ``tile``: the model's input size.  ``overlap`` (a fraction of the tile, 0 <= overlap < 1) or ``stride`` = (sy, sx) sets the
+    grid: origins 0, s, 2s, ... along an axis and a last one clamped to ``L - tile``; a scene smaller than the tile is one tile
+    at the origin, padded with the raw value ``fill``.  ``window``: ``"hann"`` (strictly positive, the default) or ``"flat"``.
+    ``lowres=False`` takes the ``class_probs`` + ``scene_blend`` route even where the model returns its heads' maps."""
+
+    def __init__(self, script_model: ScriptModel, tile: tuple[int, int] = (512, 512), overlap: float = 0.5,
+                 stride: tuple[int, int] | None = None, window: str = "hann", batch_size: int = 64, threshold: float = 0.5,
+                 fill: int = 0, *, lowres: bool = True) -> None:
+        if not isinstance(script_model, ScriptModel):
+            raise TypeError(f"SceneInference: a ScriptModel is expected, got {type(script_model).__name__}")
+        self.model = script_model
+        self.tile = (int(tile[0]), int(tile[1]))
+        if stride is None:
+            if not 0.0 <= overlap < 1.0:
+                raise ValueError(f"SceneInference: overlap {overlap} must be in [0, 1)")
+            stride = tuple(max(1, round(t * (1.0 - overlap))) for t in self.tile)
+        self.stride = (int(stride[0]), int(stride[1]))
+        gscene.axis_origins(self.tile[0], self.tile[0], self.stride[0])      # 1 <= stride <= tile, or ValueError
+        gscene.axis_origins(self.tile[1], self.tile[1], self.stride[1])
+        if batch_size < 1:
+            raise ValueError(f"SceneInference: batch_size {batch_size}")
+        self.batch_size, self.threshold, self.fill, self.lowres = int(batch_size), float(threshold), int(fill), bool(lowres)
+        dev = script_model.device
+        self.wy, self.wx = gscene.window(self.tile[0], window).to(dev), gscene.window(self.tile[1], window).to(dev)
+
+    def _blend(self, out, origins: torch.Tensor, canvas: torch.Tensor, box: tuple[int, int, int, int]) -> None:
+        if isinstance(out, gnn.LowresLogits) and self.lowres:
+            low = out.low
+            if low.dtype == torch.float32 and low.dim() == 4 and 1 <= low.shape[3] <= 16:
+                ops.scene_blend_lowres(low.contiguous(), self.tile, origins, self.wy, self.wx, canvas, box)
+                return
+        ops.scene_blend(gnn.predict_probs(out), origins, self.wy, self.wx, canvas, box)
+
+    def canvas(self, raster: torch.Tensor) -> torch.Tensor:
+        """The finished canvas [K+1, H, W] f32 of ``raster``: planes 0..K-1 the weighted probability sums, plane K the weights."""
+        m = self.model
+        if raster.dim() != 3 or raster.dtype not in _RASTER_DTYPES:
+            raise ValueError(f"SceneInference: a [C, H, W] uint8/uint16/int16/float32 raster is expected, got {raster.dtype} {tuple(raster.shape)}")
+        if raster.shape[0] != m.mean.numel():
+            raise ValueError(f"SceneInference: the raster has {raster.shape[0]} channels, the model's mean / std have {m.mean.numel()}")
+        raster = raster.to(m.device).contiguous()      # a host raster is uploaded once
+        _, H, W = raster.shape
+        plan = gscene.plan_tiles(H, W, self.tile, self.stride)
+        plan_dev = plan.to(m.device)
+        K = int(m.num_classes)
+        canvas = torch.zeros((K + 1, H, W), device=m.device, dtype=torch.float32)
+        for i in range(0, plan.shape[0], self.batch_size):
+            origins = plan_dev[i:i + self.batch_size]
+            tiles = ops.scene_cut(raster, origins, self.tile, m.mean, m.std, m.image_min, m.image_max, m.norm_min, m.norm_max, self.fill)
+            out = m.raw_output(tiles)
+            with torch.no_grad():
+                self._blend(out, origins, canvas, gscene.bounding_box(plan[i:i + self.batch_size], self.tile))
+        return canvas
+
+    def predict(self, raster: torch.Tensor, return_probs: bool = False) -> SceneResult:
+        mask, probs = ops.scene_finish(self.canvas(raster), self.threshold, return_probs)
+        return SceneResult(mask, probs)

@@ -60,14 +60,19 @@ class ScriptModel(nn.Module):
     def _logits(self, x: torch.Tensor):
         return self._call(x)
 
+    def raw_output(self, x: torch.Tensor):
+        """The model's own output for tiles that are normalised already (``gdlhip.nn.LowresLogits`` where the model hands its
+        heads' maps over, otherwise the resized logits): what ``forward`` turns into probabilities, and what whole-scene
+        inference (tools/scene_inference.py) stitches without them."""
+        with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.bf16):
+            return self._logits(x)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         x = x.to(self.device)
         if x.dtype not in (torch.uint8, torch.uint16, torch.int16):
             x = x.float()
-        x = self._normalize(x.contiguous())
+        out = self.raw_output(self._normalize(x.contiguous()))
         with torch.no_grad():
-            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.bf16):
-                out = self._logits(x)
             if self.from_logits:
                 return gnn.predict_probs(out)
             # the reference returns the resized logits here

@@ -1,0 +1,160 @@
+#!/usr/bin/env python
+"""Whole-scene inference (tools/scene_inference.py, include/gdlhip_scene.h), two measurements in one process.
+
+1. The tail of one batch of 64 tiles of 512^2 at stride 256 (an 8 x 8 grid over a 2304^2 uint8 scene), K = 5, the model excluded:
+   its head map [64, 128, 128, 5] is drawn once.  ms per batch from HIP events around ``--inner`` repetitions, the variants
+   alternating round by round:
+     (a) fused, low-resolution  -- scene_cut, scene_blend_lowres, scene_finish (what SceneInference runs),
+     (b) fused, full-resolution -- scene_cut, upsample_probs, scene_blend, scene_finish (its route for a model without head maps),
+     (c) composed               -- what the code allowed before: a host loop of 64 slice copies, normalize_range, upsample_probs,
+                                   a torch multiply by the window, 64 indexed adds into the canvas, a divide and an argmax.
+   Every variant zeroes its canvas first; (a) and (b) are compared with (c) before anything is timed.
+2. SceneInference on a synthetic 4096^2 scene (15 x 15 = 225 tiles) with the DOFA-base model in bf16, as tiles per second of the
+   whole call, next to ScriptModel's tiles per second on the same tiles (batches of host-sliced tiles, probabilities written)."""
+import argparse
+import sys
+import time
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT / "geo-deep-learning_amd"))
+from gdlhip import ops  # noqa: E402
+from gdlhip import scene as gscene  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--classes", type=int, default=5)
+ap.add_argument("--tile", type=int, default=512)
+ap.add_argument("--stride", type=int, default=256)
+ap.add_argument("--grid", type=int, default=8, help="tiles per side of the batch (8 x 8 = 64)")
+ap.add_argument("--rounds", type=int, default=7)
+ap.add_argument("--inner", type=int, default=5)
+ap.add_argument("--scene", type=int, default=4096, help="side of the whole scene of part 2 (0 = skip part 2)")
+ap.add_argument("--batch", type=int, default=64)
+ap.add_argument("--scene-repeats", type=int, default=3)
+args = ap.parse_args()
+
+K, T, S = args.classes, args.tile, args.stride
+side = T + S * (args.grid - 1)
+print(f"tools/bench_scene.py --classes {K} --tile {T} --stride {S} --grid {args.grid} --rounds {args.rounds} --inner {args.inner} "
+      f"--scene {args.scene} --batch {args.batch}   ({torch.cuda.get_device_name(0)}, torch {torch.__version__})")
+g = torch.Generator(device="cuda").manual_seed(0)
+mean, std = torch.tensor([0.485, 0.456, 0.406], device="cuda"), torch.tensor([0.229, 0.224, 0.225], device="cuda")
+RANGE = (0, 255, 0.0, 1.0)
+
+# ------------------------------------------------------------------ 1. the tail of one batch
+raster = torch.randint(0, 256, (3, side, side), device="cuda", dtype=torch.uint8, generator=g)
+plan = gscene.plan_tiles(side, side, (T, T), (S, S))
+B = plan.shape[0]
+assert B == args.grid ** 2
+origins, box, where = plan.cuda(), gscene.bounding_box(plan, (T, T)), plan.tolist()
+low = torch.randn(B, T // 4, T // 4, K, device="cuda", generator=g) * 4
+wy = wx = gscene.window(T, "hann").cuda()
+w2 = wy[:, None] * wx[None, :]
+canvas = torch.zeros(K + 1, side, side, device="cuda")
+
+
+def fused_lowres():
+    canvas.zero_()
+    ops.scene_cut(raster, origins, (T, T), mean, std, *RANGE)
+    ops.scene_blend_lowres(low, (T, T), origins, wy, wx, canvas, box)
+    return ops.scene_finish(canvas)[0]
+
+
+def fused_full():
+    canvas.zero_()
+    ops.scene_cut(raster, origins, (T, T), mean, std, *RANGE)
+    ops.scene_blend(ops.upsample_probs(low, (T, T)), origins, wy, wx, canvas, box)
+    return ops.scene_finish(canvas)[0]
+
+
+def composed():
+    canvas.zero_()
+    ops.normalize_range(torch.stack([raster[:, y:y + T, x:x + T] for y, x in where]), mean, std, *RANGE)
+    weighted = ops.upsample_probs(low, (T, T)) * w2
+    for t, (y, x) in enumerate(where):
+        canvas[:K, y:y + T, x:x + T] += weighted[t]
+        canvas[K, y:y + T, x:x + T] += w2
+    return (canvas[:K] / canvas[K]).argmax(0)
+
+
+def timed(variants, rounds, inner):
+    for fn in variants.values():      # warm-up: every variant
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in variants}
+    for _ in range(rounds):           # the variants alternate round by round
+        for name, fn in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / inner)
+    return {k: sorted(v) for k, v in times.items()}
+
+
+want_mask = composed()
+want_canvas = canvas.clone()
+for name, fn in (("(a)", fused_lowres), ("(b)", fused_full)):
+    mask = fn()
+    d = (canvas - want_canvas).abs().max().item()
+    differ = (mask.long() != want_mask).float().mean().item()
+    print(f"{name} vs (c): canvas max |diff| {d:.3e} (sums of up to four weighted probabilities), labels that differ {differ:.2e} of the pixels")
+    assert d <= 1e-5 and differ <= 1e-4, (name, d, differ)
+
+MIB = 2 ** 20
+px, tile_px = side * side, B * T * T
+# bytes each route moves through HBM-visible tensors, from the shapes (the maps and windows, a few MiB, left out)
+cut = tile_px * 3 * (1 + 4)      # one raw byte read and one f32 written per tile value
+bytes_fused = cut + 2 * (K + 1) * px * 4 + (K + 1) * px * 4 + px + (K + 1) * px * 4      # cut, blend read + write, finish read + mask, zero fill
+bytes_full = bytes_fused + 2 * tile_px * K * 4      # + the probabilities written and read
+bytes_composed = (2 * tile_px * 3 + tile_px * 3 + tile_px * 3 * 4 + 3 * tile_px * K * 4      # slices, normalise, probabilities, x window
+                  + 3 * tile_px * (K + 1) * 4 + 3 * K * px * 4 + K * px * 4 + 8 * px + (K + 1) * px * 4)      # adds, divide, argmax, zero fill
+times = timed({"(a) fused, low-resolution": fused_lowres, "(b) fused, full-resolution": fused_full, "(c) composed": composed}, args.rounds, args.inner)
+ref = times["(c) composed"][args.rounds // 2]
+print(f"tail of one batch: {B} tiles of {T}^2 at stride {S} over {side}^2, K = {K}; ms per batch, {args.rounds} rounds of {args.inner}")
+for (name, ts), nbytes in zip(times.items(), (bytes_fused, bytes_full, bytes_composed)):
+    med = ts[len(ts) // 2]
+    print(f"  {name:28s} median {med:8.3f}  min {ts[0]:8.3f}  max {ts[-1]:8.3f}   ({med / ref:5.3f} x (c))   {nbytes / MIB:7.0f} MiB of tensor traffic, "
+          f"{nbytes / (med * 1e-3) / 1e9:6.0f} GB/s")
+del raster, low, canvas, want_canvas, want_mask
+
+# ------------------------------------------------------------------ 2. a whole scene through the model
+if args.scene:
+    from geo_deep_learning.models.segmentation.dofa import DOFASegmentationModel
+    from geo_deep_learning.tools.scene_inference import SceneInference
+    from geo_deep_learning.tools.script_model import SegmentationScriptModel
+
+    torch.manual_seed(0)
+    model = DOFASegmentationModel(encoder="dofa_base", image_size=(T, T), freeze_layers=["encoder"], num_classes=K, pretrained=False)
+    sm = SegmentationScriptModel(model, wavelengths=torch.tensor([0.665, 0.560, 0.490]), device=torch.device("cuda"), num_classes=K,
+                                 input_shape=(1, 3, T, T), mean=mean.tolist(), std=std.tolist(), bf16=True)
+    scene = torch.randint(0, 256, (3, args.scene, args.scene), dtype=torch.uint8)
+    si = SceneInference(sm, tile=(T, T), stride=(S, S), batch_size=args.batch)
+    tiles = gscene.plan_tiles(args.scene, args.scene, (T, T), (S, S)).tolist()
+
+    def whole_scene():
+        return si.predict(scene).mask
+
+    def tile_by_tile():
+        dev = scene.cuda()
+        for i in range(0, len(tiles), args.batch):
+            sm(torch.stack([dev[:, y:y + T, x:x + T] for y, x in tiles[i:i + args.batch]]))
+
+    for name, fn in (("SceneInference.predict (upload, cut, model, blend, finish)", whole_scene),
+                     ("ScriptModel on the same tiles (upload, slices, model, probabilities)", tile_by_tile)):
+        fn()      # warm-up: every shape of the timed call, the short last batch included
+        torch.cuda.synchronize()
+        rates = []
+        for _ in range(args.scene_repeats):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            rates.append(len(tiles) / (time.perf_counter() - t0))
+        rates.sort()
+        print(f"scene {args.scene}^2, {len(tiles)} tiles, batch {args.batch}, bf16 DOFA-base: {name}: median {rates[len(rates) // 2]:7.1f} tiles/s  "
+              f"(min {rates[0]:7.1f}, max {rates[-1]:7.1f}; {args.scene_repeats} runs)")
