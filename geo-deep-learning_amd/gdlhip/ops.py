@@ -1373,7 +1373,7 @@ def _bwgrad(x: Tensor, x_sW: int, x_sZ: tuple[int, int], dy: Tensor, dy_sW: int,
     a.dy_sZ0, a.dy_sZ1 = dy_sZ
     a.dw_sZ0, a.dw_sZ1 = nz_inner * N * Cc, N * Cc
     lib = _lib.load()
-    nbytes = lib.gdl_conv_wgrad_workspace(C.byref(a))      # non-zero only for nz == 1 (split-K)
+    nbytes = lib.gdl_conv_wgrad_workspace(C.byref(a))      # nz * splits partials: batched problems are split too (up to 64 ways)
     ws = torch.empty(max(nbytes, 4) // 4, device=x.device, dtype=torch.float32)
     a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
     check(lib.gdl_conv_wgrad(C.byref(a), _stream()), "gdl_conv_wgrad(batched)")
