@@ -879,6 +879,10 @@ extern "C" int gdl_flash_attn_bwd(const void* q, int64_t q_sB, int64_t q_sN, con
   GDL_CHECK_ARG(((int64_t)Nkv - 1) * k_sN * 2 + 128 < lim && ((int64_t)Nkv - 1) * v_sN * 2 + 128 < lim &&
                     ((int64_t)Nq - 1) * q_sN * 2 + 128 < lim && ((int64_t)Nq - 1) * do_sN * 2 + 128 < lim,
                 "gdl_flash_attn_bwd: one (batch, head) slab spans more than 2 GiB");
+  // (checked before the first launch: a refused call writes nothing, not even dvec and dq)
+  const int qsplit = dkv_qsplit(B, H, Nq, Nkv);
+  GDL_CHECK_ARG(qsplit == 1 || (ws && ((uintptr_t)ws % 16 == 0) && ws_bytes >= gdl_flash_attn_bwd_workspace(B, H, Nq, Nkv)),
+                "gdl_flash_attn_bwd: workspace of gdl_flash_attn_bwd_workspace() bytes needed (16-byte aligned)");
   Attn2Args f = {};
   f.q = (const uint16_t*)q; f.k = (const uint16_t*)k; f.v = (const uint16_t*)v; f.o = (const uint16_t*)o;
   f.dout = (const uint16_t*)dout; f.lse = const_cast<float*>(lse); f.dvec = dvec;
@@ -890,10 +894,8 @@ extern "C" int gdl_flash_attn_bwd(const void* q, int64_t q_sB, int64_t q_sN, con
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(flash_bwd_dot_kernel, dim3((unsigned)(((int64_t)B * Nq + 3) / 4)), dim3(256), 0, s, f);
   hipLaunchKernelGGL(flash_bwd_dq_kernel, dim3((unsigned)((Nq + 127) / 128 * B * H)), dim3(256), 0, s, f);
-  f.qsplit = dkv_qsplit(B, H, Nq, Nkv);
+  f.qsplit = qsplit;
   f.dkv_part = ws;
-  GDL_CHECK_ARG(f.qsplit == 1 || (ws && ((uintptr_t)ws % 16 == 0) && ws_bytes >= gdl_flash_attn_bwd_workspace(B, H, Nq, Nkv)),
-                "gdl_flash_attn_bwd: workspace of gdl_flash_attn_bwd_workspace() bytes needed (16-byte aligned)");
   hipLaunchKernelGGL(flash_bwd_dkv_kernel, dim3((unsigned)((Nkv + 127) / 128 * B * H), (unsigned)f.qsplit), dim3(256), 0, s, f);
   if (f.qsplit > 1)
     hipLaunchKernelGGL(flash_bwd_dkv_reduce_kernel, dim3((unsigned)(((int64_t)B * H * Nkv * 32 + 255) / 256)), dim3(256), 0, s, f);
