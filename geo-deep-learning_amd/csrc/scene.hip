@@ -1,24 +1,44 @@
 // Whole-scene inference (include/gdlhip_scene.h): cut normalised tiles out of a raster, stitch the tiles' class probabilities into a
 // weighted canvas, label the canvas.  All four kernels are bound by memory traffic; none uses atomics, so every result is
-// reproducible bit for bit.
+// reproducible bit for bit.  Test-time augmentation (include/gdlhip_scene_tta.h) is the same cut and blend kernels with a D4 code
+// per tile in the index arithmetic of their gathers: a flag of the cut kernel, two further sources of the blend kernel.
 #include <cmath>
 
 #include "gdl_common.h"
 #include "bilinear_index.h"
 #include "infer_expr.h"
 #include "../../include/gdlhip_scene.h"
+#include "../../include/gdlhip_scene_tta.h"
 
 namespace {
+
+// ------------------------------------------------------------------ D4 transform codes (include/gdlhip_scene_tta.h)
+// T_g(x)[i][j] = x[r][c] for a result of rows x cols (square where g & 4): flip, then swap.  With g in 0..7 (0..3 for a tile that
+// is not square) r stays inside 0..rows-1 and c inside 0..cols-1 of x.
+__device__ __forceinline__ void d4_src(int g, int rows, int cols, int i, int j, int& r, int& c) {
+  const int a = g & 2 ? rows - 1 - i : i, b = g & 1 ? cols - 1 - j : j;
+  r = g & 4 ? b : a;
+  c = g & 4 ? a : b;
+}
+
+// the code of tile t as the kernels take it: whatever the array holds, no code transposes a tile that is not square
+__device__ __forceinline__ int d4_code(const int32_t* __restrict__ xforms, int t, int th, int tw) { return xforms[t] & (th == tw ? 7 : 3); }
+
+__device__ __forceinline__ int d4_inverse(int g) { return g & 4 ? 4 | (g & 1) << 1 | (g >> 1 & 1) : g; }
 
 // ------------------------------------------------------------------ cut
 // A thread writes V consecutive values of one tile row (V == 4: one 16-byte store, tw % 4 == 0); the raster is read element by
 // element because a tile origin has no alignment.  The value is normalize_range_value of infer_expr.h, the function
 // normalize_range_kernel evaluates, on the raw sample or, outside the raster, on `fill`.
-template <typename TI, int V>
+//
+// D4 (include/gdlhip_scene_tta.h): the tile written is T_g of the tile cut, g = xforms[b].  The stores stay what they are; the V
+// raster elements of a thread lie along a row (backwards where g flips x) or, under a transpose, down a column.
+template <typename TI, int V, bool D4>
 __global__ __launch_bounds__(256) void scene_cut_kernel(const TI* __restrict__ raster, int C, int H, int W,
-                                                        const int32_t* __restrict__ origins, int th, int tw, float fill,
-                                                        float* __restrict__ tiles, int64_t groups, float imin, float span, float d,
-                                                        float nmin, const float* __restrict__ mean, const float* __restrict__ stdv) {
+                                                        const int32_t* __restrict__ origins, const int32_t* __restrict__ xforms, int th,
+                                                        int tw, float fill, float* __restrict__ tiles, int64_t groups, float imin,
+                                                        float span, float d, float nmin, const float* __restrict__ mean,
+                                                        const float* __restrict__ stdv) {
   struct alignas(sizeof(float) * V) VecF { float v[V]; };
   const int twv = tw / V;
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
@@ -27,16 +47,30 @@ __global__ __launch_bounds__(256) void scene_cut_kernel(const TI* __restrict__ r
     const int dy = (int)(t % th);
     t /= th;
     const int c = (int)(t % C), b = (int)(t / C);
-    const int64_t y = (int64_t)origins[2 * b] + dy, x0 = (int64_t)origins[2 * b + 1] + dx0;
-    const bool row_in = y >= 0 && y < H;
-    const TI* row = raster + ((int64_t)c * H + (row_in ? y : 0)) * W;
     const float m = mean[c], s = stdv[c];
     VecF o;
+    if constexpr (D4) {
+      const int code = d4_code(xforms, b, th, tw);
+      const int64_t oy = origins[2 * b], ox = origins[2 * b + 1];
+      const TI* plane = raster + (int64_t)c * H * W;
 #pragma unroll
-    for (int e = 0; e < V; ++e) {
-      const int64_t x = x0 + e;
-      const float raw = row_in && x >= 0 && x < W ? (float)row[x] : fill;
-      o.v[e] = normalize_range_value(raw, imin, span, d, nmin, m, s);
+      for (int e = 0; e < V; ++e) {
+        int r, q;
+        d4_src(code, th, tw, dy, dx0 + e, r, q);
+        const int64_t y = oy + r, x = ox + q;
+        const float raw = y >= 0 && y < H && x >= 0 && x < W ? (float)plane[y * W + x] : fill;
+        o.v[e] = normalize_range_value(raw, imin, span, d, nmin, m, s);
+      }
+    } else {
+      const int64_t y = (int64_t)origins[2 * b] + dy, x0 = (int64_t)origins[2 * b + 1] + dx0;
+      const bool row_in = y >= 0 && y < H;
+      const TI* row = raster + ((int64_t)c * H + (row_in ? y : 0)) * W;
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        const int64_t x = x0 + e;
+        const float raw = row_in && x >= 0 && x < W ? (float)row[x] : fill;
+        o.v[e] = normalize_range_value(raw, imin, span, d, nmin, m, s);
+      }
     }
     *(VecF*)(tiles + g * V) = o;
   }
@@ -93,6 +127,71 @@ struct LowresSource {
       if (cov[e]) {
         int x0, x1; float lx;
         src_index2(rx, dx0 + e, wi, x0, x1, lx);
+        bilinear_logits<K>(low, t, hi, wi, y0, y1, x0, x1, ly, lx, p[e]);
+        logits_to_probs<K>(p[e]);
+      }
+  }
+};
+
+// The two sources with a D4 code per tile: the tile's values are in the transformed frame, so tile-frame pixel (dy, dx) of the
+// canvas reads T_g^-1(.)[dy][dx] = d4_src with the inverse code.  The kernel, its canvas accesses and the weight wy[dy] * wx[dx]
+// are untouched.  The tile index is the same in every lane of a workgroup, so the branches on the code do not diverge.
+template <int K>
+struct ProbsSourceD4 {
+  const float* probs;
+  const int32_t* xforms;
+  int th, tw;
+  bool vec;   // as in ProbsSource
+  __device__ __forceinline__ void prepare() {}
+  template <int V>
+  __device__ __forceinline__ void load(int t, int dy, int dx0, const bool (&cov)[V], float (&p)[V][K]) const {
+    const int g = d4_inverse(d4_code(xforms, t, th, tw));
+    const int64_t plane = (int64_t)th * tw;
+    const float* tile = probs + (int64_t)t * K * plane;
+    if constexpr (V == 4) {
+      // without a transpose the four pixels are four neighbours of one tile row, ascending or (flip x) descending: tw % 4 == 0
+      // and dx0 % 4 == 0 make tw - 4 - dx0 a multiple of four as well, so either way it is one 16-byte load per class
+      if (!(g & 4) && vec && (dx0 & 3) == 0 && cov[0] && cov[1] && cov[2] && cov[3]) {
+        const bool rev = g & 1;
+        const float* base = tile + (int64_t)(g & 2 ? th - 1 - dy : dy) * tw + (rev ? tw - 4 - dx0 : dx0);
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          const float4 q = *(const float4*)(base + k * plane);
+          p[0][k] = rev ? q.w : q.x; p[1][k] = rev ? q.z : q.y; p[2][k] = rev ? q.y : q.z; p[3][k] = rev ? q.x : q.w;
+        }
+        return;
+      }
+    }
+    // under a transpose the four pixels read a column of the tile: one load per element
+#pragma unroll
+    for (int e = 0; e < V; ++e)
+      if (cov[e]) {
+        int r, c;
+        d4_src(g, th, tw, dy, dx0 + e, r, c);
+        const float* base = tile + (int64_t)r * tw + c;
+#pragma unroll
+        for (int k = 0; k < K; ++k) p[e][k] = base[k * plane];
+      }
+  }
+};
+
+template <int K>
+struct LowresSourceD4 {
+  const float* low;
+  const int32_t* xforms;
+  int hi, wi, th, tw;
+  float ry, rx;
+  __device__ __forceinline__ void prepare() { ry = (float)hi / (float)th; rx = (float)wi / (float)tw; }
+  template <int V>
+  __device__ __forceinline__ void load(int t, int dy, int dx0, const bool (&cov)[V], float (&p)[V][K]) const {
+    const int g = d4_inverse(d4_code(xforms, t, th, tw));
+#pragma unroll
+    for (int e = 0; e < V; ++e)
+      if (cov[e]) {
+        int r, c, y0, y1, x0, x1; float ly, lx;
+        d4_src(g, th, tw, dy, dx0 + e, r, c);      // where the pixel lies in the transformed tile, whose map `low` is
+        src_index2(ry, r, hi, y0, y1, ly);
+        src_index2(rx, c, wi, x0, x1, lx);
         bilinear_logits<K>(low, t, hi, wi, y0, y1, x0, x1, ly, lx, p[e]);
         logits_to_probs<K>(p[e]);
       }
@@ -256,31 +355,48 @@ bool clip_box(int H, int W, int& y0, int& y1, int& x0, int& x1) {
   return y0 < y1 && x0 < x1;
 }
 
+// gdl_scene_cut and gdl_scene_cut_d4 (xforms != nullptr): one body, `fn` is the entry point's name in the messages
+int scene_cut(const char* fn, const void* raster, int kind, int C, int H, int W, const int32_t* origins, const int32_t* xforms, bool d4,
+              int B, int th, int tw, int fill, float* tiles, int image_min, int image_max, double norm_min, double norm_max,
+              const float* mean, const float* stdv, gdl_stream_t stream) {
+  GDL_CHECK_ARG(raster && origins && tiles && mean && stdv && (xforms || !d4), "%s: null pointer", fn);
+  GDL_CHECK_ARG(kind >= GDL_RAW_U8 && kind <= GDL_RAW_F32, "%s: bad sample kind %d", fn, kind);
+  GDL_CHECK_ARG(C > 0 && H > 0 && W > 0 && B > 0 && th > 0 && tw > 0, "%s: bad sizes", fn);
+  GDL_CHECK_ARG(image_max != image_min, "%s: image_max == image_min (%d): the range is empty", fn, image_min);
+  const RangeScalars r = range_scalars(image_min, image_max, norm_min, norm_max);
+  const bool vec = tw % 4 == 0 && (uintptr_t)tiles % 16 == 0;
+  const int64_t groups = (int64_t)B * C * th * (tw / (vec ? 4 : 1));
+  hipStream_t s = (hipStream_t)stream;
+#define CUT_V(T, V, D4)                                                                                                               \
+  hipLaunchKernelGGL((scene_cut_kernel<T, V, D4>), dim3(grid_for(groups)), dim3(256), 0, s, (const T*)raster, C, H, W, origins, xforms, \
+                     th, tw, (float)fill, tiles, groups, r.imin, r.span, r.d, r.nmin, mean, stdv)
+#define CUT(T)                                                                  \
+  if (d4) { if (vec) CUT_V(T, 4, true); else CUT_V(T, 1, true); }               \
+  else { if (vec) CUT_V(T, 4, false); else CUT_V(T, 1, false); }
+  if (kind == GDL_RAW_U8) { CUT(uint8_t) }
+  else if (kind == GDL_RAW_U16) { CUT(uint16_t) }
+  else if (kind == GDL_RAW_I16) { CUT(int16_t) }
+  else { CUT(float) }
+#undef CUT
+#undef CUT_V
+  GDL_CHECK_LAUNCH(fn);
+  return GDL_OK;
+}
+
 }  // namespace
 
 extern "C" int gdl_scene_cut(const void* raster, int kind, int C, int H, int W, const int32_t* origins, int B, int th, int tw, int fill,
                              float* tiles, int image_min, int image_max, double norm_min, double norm_max, const float* mean,
                              const float* stdv, gdl_stream_t stream) {
-  GDL_CHECK_ARG(raster && origins && tiles && mean && stdv, "gdl_scene_cut: null pointer");
-  GDL_CHECK_ARG(kind >= GDL_RAW_U8 && kind <= GDL_RAW_F32, "gdl_scene_cut: bad sample kind %d", kind);
-  GDL_CHECK_ARG(C > 0 && H > 0 && W > 0 && B > 0 && th > 0 && tw > 0, "gdl_scene_cut: bad sizes");
-  GDL_CHECK_ARG(image_max != image_min, "gdl_scene_cut: image_max == image_min (%d): the range is empty", image_min);
-  const RangeScalars r = range_scalars(image_min, image_max, norm_min, norm_max);
-  const bool vec = tw % 4 == 0 && (uintptr_t)tiles % 16 == 0;
-  const int64_t groups = (int64_t)B * C * th * (tw / (vec ? 4 : 1));
-  hipStream_t s = (hipStream_t)stream;
-#define CUT(T)                                                                                                                        \
-  if (vec) hipLaunchKernelGGL((scene_cut_kernel<T, 4>), dim3(grid_for(groups)), dim3(256), 0, s, (const T*)raster, C, H, W, origins,  \
-                              th, tw, (float)fill, tiles, groups, r.imin, r.span, r.d, r.nmin, mean, stdv);                           \
-  else hipLaunchKernelGGL((scene_cut_kernel<T, 1>), dim3(grid_for(groups)), dim3(256), 0, s, (const T*)raster, C, H, W, origins, th,  \
-                          tw, (float)fill, tiles, groups, r.imin, r.span, r.d, r.nmin, mean, stdv)
-  if (kind == GDL_RAW_U8) { CUT(uint8_t); }
-  else if (kind == GDL_RAW_U16) { CUT(uint16_t); }
-  else if (kind == GDL_RAW_I16) { CUT(int16_t); }
-  else { CUT(float); }
-#undef CUT
-  GDL_CHECK_LAUNCH("gdl_scene_cut");
-  return GDL_OK;
+  return scene_cut("gdl_scene_cut", raster, kind, C, H, W, origins, nullptr, false, B, th, tw, fill, tiles, image_min, image_max, norm_min,
+                   norm_max, mean, stdv, stream);
+}
+
+extern "C" int gdl_scene_cut_d4(const void* raster, int kind, int C, int H, int W, const int32_t* origins, const int32_t* xforms, int B,
+                                int th, int tw, int fill, float* tiles, int image_min, int image_max, double norm_min, double norm_max,
+                                const float* mean, const float* stdv, gdl_stream_t stream) {
+  return scene_cut("gdl_scene_cut_d4", raster, kind, C, H, W, origins, xforms, true, B, th, tw, fill, tiles, image_min, image_max,
+                   norm_min, norm_max, mean, stdv, stream);
 }
 
 extern "C" int gdl_scene_blend(const float* probs, int B, int K, int th, int tw, const int32_t* origins, const float* wy,
@@ -295,6 +411,19 @@ extern "C" int gdl_scene_blend(const float* probs, int B, int K, int th, int tw,
   return GDL_OK;
 }
 
+extern "C" int gdl_scene_blend_d4(const float* probs, int B, int K, int th, int tw, const int32_t* origins, const int32_t* xforms,
+                                  const float* wy, const float* wx, float* canvas, int H, int W, int y0, int y1, int x0, int x1,
+                                  gdl_stream_t stream) {
+  GDL_CHECK_ARG(probs && origins && xforms && wy && wx && canvas, "gdl_scene_blend_d4: null pointer");
+  GDL_CHECK_ARG(B > 0 && th > 0 && tw > 0 && H > 0 && W > 0, "gdl_scene_blend_d4: bad sizes");
+  GDL_CHECK_ARG(K >= 1 && K <= 16, "gdl_scene_blend_d4: 1..16 classes, got %d", K);
+  if (!clip_box(H, W, y0, y1, x0, x1)) return GDL_OK;
+  const bool vec = tw % 4 == 0 && (uintptr_t)probs % 16 == 0;
+  K_SWITCH(K, launch_blend<KK>(ProbsSourceD4<KK>{probs, xforms, th, tw, vec}, B, th, tw, origins, wy, wx, canvas, H, W, y0, y1, x0, x1, (hipStream_t)stream));
+  GDL_CHECK_LAUNCH("gdl_scene_blend_d4");
+  return GDL_OK;
+}
+
 extern "C" int gdl_scene_blend_lowres(const float* low, int B, int hi, int wi, int K, int th, int tw, const int32_t* origins,
                                       const float* wy, const float* wx, float* canvas, int H, int W, int y0, int y1, int x0, int x1,
                                       gdl_stream_t stream) {
@@ -304,6 +433,18 @@ extern "C" int gdl_scene_blend_lowres(const float* low, int B, int hi, int wi, i
   if (!clip_box(H, W, y0, y1, x0, x1)) return GDL_OK;
   K_SWITCH(K, launch_blend<KK>(LowresSource<KK>{low, hi, wi, th, tw, 0.f, 0.f}, B, th, tw, origins, wy, wx, canvas, H, W, y0, y1, x0, x1, (hipStream_t)stream));
   GDL_CHECK_LAUNCH("gdl_scene_blend_lowres");
+  return GDL_OK;
+}
+
+extern "C" int gdl_scene_blend_lowres_d4(const float* low, int B, int hi, int wi, int K, int th, int tw, const int32_t* origins,
+                                         const int32_t* xforms, const float* wy, const float* wx, float* canvas, int H, int W, int y0,
+                                         int y1, int x0, int x1, gdl_stream_t stream) {
+  GDL_CHECK_ARG(low && origins && xforms && wy && wx && canvas, "gdl_scene_blend_lowres_d4: null pointer");
+  GDL_CHECK_ARG(B > 0 && hi > 0 && wi > 0 && th > 0 && tw > 0 && H > 0 && W > 0, "gdl_scene_blend_lowres_d4: bad sizes");
+  GDL_CHECK_ARG(K >= 1 && K <= 16, "gdl_scene_blend_lowres_d4: 1..16 classes, got %d (more: gdl_class_probs + gdl_scene_blend_d4)", K);
+  if (!clip_box(H, W, y0, y1, x0, x1)) return GDL_OK;
+  K_SWITCH(K, launch_blend<KK>(LowresSourceD4<KK>{low, xforms, hi, wi, th, tw, 0.f, 0.f}, B, th, tw, origins, wy, wx, canvas, H, W, y0, y1, x0, x1, (hipStream_t)stream));
+  GDL_CHECK_LAUNCH("gdl_scene_blend_lowres_d4");
   return GDL_OK;
 }
 

@@ -137,12 +137,15 @@ class Header:
 _ABI = Header((INCLUDE / "gdlhip.h").read_text())
 _DEBUG = Header((INCLUDE / "gdlhip_debug.h").read_text())
 _SCENE = Header((INCLUDE / "gdlhip_scene.h").read_text())
+_SCENE_TTA = Header((INCLUDE / "gdlhip_scene_tta.h").read_text())
 
-# name -> (restype, argtypes); every symbol declared in include/gdlhip.h, the gdl_debug_* hooks of include/gdlhip_debug.h and the
-# whole-scene inference calls of include/gdlhip_scene.h
+# name -> (restype, argtypes); every symbol declared in include/gdlhip.h, the gdl_debug_* hooks of include/gdlhip_debug.h, the
+# whole-scene inference calls of include/gdlhip_scene.h and their test-time augmentation forms of include/gdlhip_scene_tta.h
 SIGNATURES, DEBUG_SIGNATURES, SCENE_SIGNATURES = _ABI.functions, _DEBUG.functions, _SCENE.functions
+SCENE_TTA_SIGNATURES = _SCENE_TTA.functions
 STATUS_FUNCTIONS = frozenset(_ABI.status)      # they return a gdl_status; every other function returns a value
-_CHECKED = STATUS_FUNCTIONS | _SCENE.status    # what checked() gives the errcheck: the scene calls return a gdl_status too
+# what checked() gives the errcheck: the scene calls return a gdl_status too
+_CHECKED = STATUS_FUNCTIONS | _SCENE.status | _SCENE_TTA.status
 ConvArgs, WgradArgs, DiceOptions, OverlapOptions = (_ABI.structs[c] for c in _STRUCTS)
 # the header's enumerators and integer #defines without their GDL_ prefix: F32, BF16, ACT_*, FOCAL_* (the `form` argument of the
 # *_lowres_bwd calls), BCE_TARGET_* (the `target_type` of gdl_soft_bce_*), OVERLAP_* (gdl_overlap_options.kind), ...
@@ -184,7 +187,8 @@ def _open(errcheck=None) -> C.CDLL:
                "There is no PyTorch/CPU fallback for the gdlhip ops.")
         raise GdlHipError(msg)
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in (*SIGNATURES.items(), *DEBUG_SIGNATURES.items(), *SCENE_SIGNATURES.items()):
+    for name, (res, args) in (*SIGNATURES.items(), *DEBUG_SIGNATURES.items(), *SCENE_SIGNATURES.items(),
+                              *SCENE_TTA_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

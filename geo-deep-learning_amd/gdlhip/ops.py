@@ -2001,6 +2001,82 @@ def scene_blend_lowres(low: Tensor, size: tuple[int, int], origins: Tensor, wy: 
     return canvas
 
 
+# test-time augmentation (include/gdlhip_scene_tta.h): the cut and the two blends with a transform code per tile
+def _scene_xforms(op: str, xforms: Tensor, B: int, tile: tuple[int, int], check_codes: bool) -> None:
+    """``xforms``: int32 [B] on the device, codes in 0..7 (gdlhip.scene: 1 = flip x, 2 = flip y, 4 = transpose; a code that
+    transposes needs a square tile).  The values are read back and checked here, before anything is launched, unless
+    ``check_codes`` is False (a caller whose codes come from ``gdlhip.scene.tta_codes``, which checks the same; the kernels mask
+    the codes, so a bad one never addresses outside a tile)."""
+    _need_cuda(xforms)
+    if xforms.dtype != torch.int32 or xforms.dim() != 1 or not xforms.is_contiguous():
+        raise ValueError(f"{op}: xforms must be a contiguous int32 [B] tensor of transform codes, got {xforms.dtype} {tuple(xforms.shape)}")
+    if xforms.shape[0] != B:
+        raise ValueError(f"{op}: {xforms.shape[0]} transform codes for {B} tiles")
+    if check_codes:
+        codes = xforms.cpu()
+        if int(codes.min()) < 0 or int(codes.max()) > 7:
+            raise ValueError(f"{op}: a transform code is in 0..7, got {int(codes.min())}..{int(codes.max())}")
+        if tile[0] != tile[1] and bool((codes & 4).any()):
+            raise ValueError(f"{op}: a transform code with bit 4 (transpose) needs a square tile, not {tile[0]} x {tile[1]}")
+
+
+def scene_cut_d4(raster: Tensor, origins: Tensor, xforms: Tensor, tile: tuple[int, int], mean: Tensor, std: Tensor, image_min: int = 0,
+                 image_max: int = 255, norm_min: float = 0.0, norm_max: float = 1.0, fill: int = 0, *, check_codes: bool = True) -> Tensor:
+    """``scene_cut`` with a transform per tile: tile ``b`` is ``gdlhip.scene.d4_apply`` of the tile ``scene_cut`` cuts at
+    ``origins[b]``, with the code ``xforms[b]`` (int32 [B] on the device), bit for bit (gdl_scene_cut_d4)."""
+    if raster.dtype not in _RAW_KIND or not raster.is_contiguous() or raster.dim() != 3:
+        raise ValueError(f"scene_cut_d4: contiguous [C, H, W] uint8/uint16/int16/float32 raster expected, got {raster.dtype} {tuple(raster.shape)}")
+    if int(image_max) == int(image_min):
+        raise ValueError(f"scene_cut_d4: image_max == image_min ({int(image_min)}): the range is empty")
+    _need_cuda(raster, origins, mean, std)
+    B = _scene_origins("scene_cut_d4", origins)
+    th, tw = int(tile[0]), int(tile[1])
+    if th < 1 or tw < 1:
+        raise ValueError(f"scene_cut_d4: bad tile {th} x {tw}")
+    _scene_xforms("scene_cut_d4", xforms, B, (th, tw), check_codes)
+    lo, hi = _RAW_LIMITS.get(raster.dtype, (-2 ** 31, 2 ** 31 - 1))
+    if not lo <= int(fill) <= hi:
+        raise ValueError(f"scene_cut_d4: fill {fill} is not a value of {raster.dtype}")
+    Cc, H, W = raster.shape
+    out = torch.empty((B, Cc, th, tw), device=raster.device, dtype=torch.float32)
+    _lib.checked().gdl_scene_cut_d4(_p(raster), _RAW_KIND[raster.dtype], Cc, H, W, _p(origins), _p(xforms), B, th, tw, int(fill), _p(out),
+                                    int(image_min), int(image_max), float(norm_min), float(norm_max), _p(_f32vec(mean, Cc, "mean")),
+                                    _p(_f32vec(std, Cc, "std")), _stream())
+    return out
+
+
+def scene_blend_d4(probs: Tensor, origins: Tensor, xforms: Tensor, wy: Tensor, wx: Tensor, canvas: Tensor,
+                   box: tuple[int, int, int, int] | None = None, *, check_codes: bool = True) -> Tensor:
+    """``scene_blend`` of probabilities [B, K, th, tw] f32 that are in the transformed frame of their tiles (the model's answer
+    to ``scene_cut_d4``): the canvas takes the inverse transform of tile ``b``, code ``xforms[b]``, the window stays in the canvas
+    frame.  The canvas is ``scene_blend`` of the inverse-permuted probabilities, bit for bit (gdl_scene_blend_d4)."""
+    if probs.dtype != torch.float32 or probs.dim() != 4 or not probs.is_contiguous():
+        raise ValueError("scene_blend_d4: contiguous f32 probabilities [B, K, th, tw] expected")
+    B, K, th, tw = probs.shape
+    H, W, y0, y1, x0, x1 = _scene_blend_check("scene_blend_d4", probs, K, (th, tw), origins, wy, wx, canvas, box)
+    _scene_xforms("scene_blend_d4", xforms, B, (th, tw), check_codes)
+    _lib.checked().gdl_scene_blend_d4(_p(probs), B, K, th, tw, _p(origins), _p(xforms), _p(wy), _p(wx), _p(canvas), H, W, y0, y1, x0, x1,
+                                      _stream())
+    return canvas
+
+
+def scene_blend_lowres_d4(low: Tensor, size: tuple[int, int], origins: Tensor, xforms: Tensor, wy: Tensor, wx: Tensor, canvas: Tensor,
+                          box: tuple[int, int, int, int] | None = None, *, check_codes: bool = True) -> Tensor:
+    """``scene_blend_d4`` of ``upsample_probs(low, size)`` without those probabilities: ``low`` [B, h, w, K] is the head's NHWC
+    f32 map of the transformed tile, evaluated where each canvas pixel lies in that tile (gdl_scene_blend_lowres_d4)."""
+    if low.dtype != torch.float32 or low.dim() != 4 or not low.is_contiguous():
+        raise ValueError("scene_blend_lowres_d4: contiguous f32 NHWC logits [B, h, w, K] expected")
+    B, hi, wi, K = low.shape
+    th, tw = int(size[0]), int(size[1])
+    if min(hi, wi, th, tw) < 1:
+        raise ValueError(f"scene_blend_lowres_d4: bad sizes {tuple(low.shape)} -> {th} x {tw}")
+    H, W, y0, y1, x0, x1 = _scene_blend_check("scene_blend_lowres_d4", low, K, (th, tw), origins, wy, wx, canvas, box)
+    _scene_xforms("scene_blend_lowres_d4", xforms, B, (th, tw), check_codes)
+    _lib.checked().gdl_scene_blend_lowres_d4(_p(low), B, hi, wi, K, th, tw, _p(origins), _p(xforms), _p(wy), _p(wx), _p(canvas), H, W,
+                                             y0, y1, x0, x1, _stream())
+    return canvas
+
+
 def scene_finish(canvas: Tensor, threshold: float = 0.5, return_probs: bool = False) -> tuple[Tensor, Tensor | None]:
     """Canvas [K+1, H, W] f32 -> (mask uint8 [H, W], probabilities f32 [K, H, W] or None): arg-max over the K weighted sums (the
     lowest index wins a tie) or, for one class, ``canvas[0] / canvas[1] > threshold``; a pixel that no tile covered (weight 0)

@@ -1,4 +1,5 @@
-"""Host side of whole-scene inference: where the tiles of a scene lie and what window weights them.  The device side is
+"""Host side of whole-scene inference: where the tiles of a scene lie and what window weights them, and the transform codes of test-time augmentation (``tta_codes``, ``plan_tta``; the device side of
+those: ``ops.scene_cut_d4`` / ``scene_blend_d4`` / ``scene_blend_lowres_d4``, include/gdlhip_scene_tta.h).  The device side is
 ``gdlhip.ops.scene_cut`` / ``scene_blend`` / ``scene_blend_lowres`` / ``scene_finish`` (include/gdlhip_scene.h); the user-facing
 class is ``geo_deep_learning.tools.scene_inference.SceneInference``."""
 
@@ -48,3 +49,58 @@ def bounding_box(origins: Tensor, tile: tuple[int, int]) -> tuple[int, int, int,
     """(y0, y1, x0, x1) around the tiles at ``origins`` (a host tensor)."""
     lo, hi = origins.min(dim=0).values, origins.max(dim=0).values
     return int(lo[0]), int(hi[0]) + int(tile[0]), int(lo[1]), int(hi[1]) + int(tile[1])
+
+
+# ------------------------------------------------------------------ test-time augmentation (include/gdlhip_scene_tta.h)
+# A transform code is 3 bits: 1 = flip x, 2 = flip y, 4 = transpose (applied first).  The eight codes are the symmetries of the
+# square (the dihedral group D4); torch.rot90(x, 1) is code 6, rot90(x, 2) code 3 and rot90(x, 3) code 5.
+D4 = tuple(range(8))
+FLIPS = (0, 1, 2, 3)
+
+
+def d4_apply(x: Tensor, g: int) -> Tensor:
+    """T_g(x) on the last two dimensions, the host reference of the definition the kernels index by."""
+    if not 0 <= int(g) <= 7:
+        raise ValueError(f"d4_apply: a transform code is in 0..7, got {g}")
+    y = x.transpose(-2, -1) if g & 4 else x
+    y = y.flip(-2) if g & 2 else y
+    return y.flip(-1) if g & 1 else y
+
+
+def d4_inverse(g: int) -> int:
+    """The code of T_g's inverse: g itself without a transpose, otherwise g with the two flip bits swapped."""
+    if not 0 <= int(g) <= 7:
+        raise ValueError(f"d4_inverse: a transform code is in 0..7, got {g}")
+    return 4 | (g & 1) << 1 | (g >> 1 & 1) if g & 4 else int(g)
+
+
+def tta_codes(tta, tile: tuple[int, int]) -> tuple[int, ...]:
+    """The transform codes of one tile: ``None`` / ``"none"`` -> (0,), ``"flips"`` -> FLIPS, ``"d4"`` -> D4, or a sequence of
+    distinct codes in 0..7, kept in its order.  A code that transposes needs a square tile."""
+    if tta is None or isinstance(tta, str):
+        named = {None: (0,), "none": (0,), "flips": FLIPS, "d4": D4}
+        if tta not in named:
+            raise ValueError(f"tta_codes: unknown tta {tta!r} (None, 'none', 'flips', 'd4' or a sequence of codes in 0..7)")
+        codes = named[tta]
+    else:
+        try:
+            codes = tuple(tta)
+        except TypeError:
+            raise ValueError(f"tta_codes: unknown tta {tta!r} (None, 'none', 'flips', 'd4' or a sequence of codes in 0..7)") from None
+        if not codes or any(isinstance(g, bool) or not isinstance(g, int) or not 0 <= g <= 7 for g in codes):
+            raise ValueError(f"tta_codes: a non-empty sequence of int codes in 0..7 is expected, got {tta!r}")
+        if len(set(codes)) != len(codes):
+            raise ValueError(f"tta_codes: a code is repeated in {codes}")
+    if int(tile[0]) != int(tile[1]) and any(g & 4 for g in codes):
+        raise ValueError(f"tta_codes: the codes {tuple(g for g in codes if g & 4)} transpose, which needs a square tile, not "
+                         f"{int(tile[0])} x {int(tile[1])}")
+    return codes
+
+
+def plan_tta(plan: Tensor, codes) -> tuple[Tensor, Tensor]:
+    """(origins int32 [T*G, 2], xforms int32 [T*G]) of the (tile, transform) pairs: tile-major, the G codes in the given order
+    inside a tile.  That order is the order in which the blend accumulates."""
+    codes = torch.tensor(tuple(codes), dtype=torch.int32)
+    if plan.dim() != 2 or plan.shape[1] != 2 or codes.numel() < 1:
+        raise ValueError(f"plan_tta: a plan [T, 2] and at least one code are expected, got {tuple(plan.shape)} and {codes.numel()} codes")
+    return plan.to(torch.int32).repeat_interleave(codes.numel(), dim=0).contiguous(), codes.repeat(plan.shape[0])

@@ -5,6 +5,12 @@ class probabilities into a canvas [K+1, H, W] -- straight from the heads' low-re
 (``ops.scene_blend_lowres``: the [B, K, th, tw] probabilities are never written), otherwise from ``class_probs``
 (``ops.scene_blend``).  ``ops.scene_finish`` labels the canvas once at the end.
 
+Test-time augmentation (``tta=``): every tile is fed once per transform of ``gdlhip.scene.tta_codes`` (flips, or all eight
+symmetries of the square), the tile list becoming (origin, transform) pairs (``gdlhip.scene.plan_tta``).  The cut writes the
+transformed tile and the blend reads the model's answer back through the inverse transform (``ops.scene_cut_d4`` /
+``scene_blend_d4`` / ``scene_blend_lowres_d4``): the transform lives in the index arithmetic of the two gathers, nothing is
+permuted in memory, and the canvas simply collects G times the weight.
+
 Determinism: the canvas is accumulated by a gather in tile order without atomics, so the mask and the probabilities do not
 depend on ``batch_size`` and are the same bits from run to run.  The reference has no counterpart (its inference stops at the
 tile, tools/script_model.py)."""
@@ -36,11 +42,15 @@ class SceneInference:
     ``tile``: the model's input size.  ``overlap`` (a fraction of the tile, 0 <= overlap < 1) or ``stride`` = (sy, sx) sets the
     grid: origins 0, s, 2s, ... along an axis and a last one clamped to ``L - tile``; a scene smaller than the tile is one tile
     at the origin, padded with the raw value ``fill``.  ``window``: ``"hann"`` (strictly positive, the default) or ``"flat"``.
-    ``lowres=False`` takes the ``class_probs`` + ``scene_blend`` route even where the model returns its heads' maps."""
+    ``lowres=False`` takes the ``class_probs`` + ``scene_blend`` route even where the model returns its heads' maps.
+    ``tta``: ``None`` (no augmentation: the calls and the bits of before), ``"flips"`` (identity and the three flips), ``"d4"`` (all
+    eight symmetries; a square tile) or a sequence of distinct codes in 0..7 (``gdlhip.scene``: 1 = flip x, 2 = flip y, 4 =
+    transpose); the probabilities of a tile's transforms are averaged with the window.  ``batch_size`` then counts
+    (tile, transform) pairs."""
 
     def __init__(self, script_model: ScriptModel, tile: tuple[int, int] = (512, 512), overlap: float = 0.5,
                  stride: tuple[int, int] | None = None, window: str = "hann", batch_size: int = 64, threshold: float = 0.5,
-                 fill: int = 0, *, lowres: bool = True) -> None:
+                 fill: int = 0, *, lowres: bool = True, tta=None) -> None:
         if not isinstance(script_model, ScriptModel):
             raise TypeError(f"SceneInference: a ScriptModel is expected, got {type(script_model).__name__}")
         self.model = script_model
@@ -55,16 +65,25 @@ class SceneInference:
         if batch_size < 1:
             raise ValueError(f"SceneInference: batch_size {batch_size}")
         self.batch_size, self.threshold, self.fill, self.lowres = int(batch_size), float(threshold), int(fill), bool(lowres)
+        self.tta = None if tta is None else gscene.tta_codes(tta, self.tile)      # ValueError for what is no set of codes
         dev = script_model.device
         self.wy, self.wx = gscene.window(self.tile[0], window).to(dev), gscene.window(self.tile[1], window).to(dev)
 
-    def _blend(self, out, origins: torch.Tensor, canvas: torch.Tensor, box: tuple[int, int, int, int]) -> None:
+    def _blend(self, out, origins: torch.Tensor, canvas: torch.Tensor, box: tuple[int, int, int, int],
+               xforms: torch.Tensor | None = None) -> None:
+        """``xforms``: the batch's transform codes (already checked by ``tta_codes``), None without augmentation."""
         if isinstance(out, gnn.LowresLogits) and self.lowres:
             low = out.low
             if low.dtype == torch.float32 and low.dim() == 4 and 1 <= low.shape[3] <= 16:
-                ops.scene_blend_lowres(low.contiguous(), self.tile, origins, self.wy, self.wx, canvas, box)
+                if xforms is None:
+                    ops.scene_blend_lowres(low.contiguous(), self.tile, origins, self.wy, self.wx, canvas, box)
+                else:
+                    ops.scene_blend_lowres_d4(low.contiguous(), self.tile, origins, xforms, self.wy, self.wx, canvas, box, check_codes=False)
                 return
-        ops.scene_blend(gnn.predict_probs(out), origins, self.wy, self.wx, canvas, box)
+        if xforms is None:
+            ops.scene_blend(gnn.predict_probs(out), origins, self.wy, self.wx, canvas, box)
+        else:
+            ops.scene_blend_d4(gnn.predict_probs(out), origins, xforms, self.wy, self.wx, canvas, box, check_codes=False)
 
     def canvas(self, raster: torch.Tensor) -> torch.Tensor:
         """The finished canvas [K+1, H, W] f32 of ``raster``: planes 0..K-1 the weighted probability sums, plane K the weights."""
@@ -76,15 +95,24 @@ class SceneInference:
         raster = raster.to(m.device).contiguous()      # a host raster is uploaded once
         _, H, W = raster.shape
         plan = gscene.plan_tiles(H, W, self.tile, self.stride)
+        codes_dev = None
+        if self.tta is not None:
+            plan, codes = gscene.plan_tta(plan, self.tta)      # (tile, transform) pairs, tile-major: the accumulation order
+            codes_dev = codes.to(m.device)
         plan_dev = plan.to(m.device)
         K = int(m.num_classes)
         canvas = torch.zeros((K + 1, H, W), device=m.device, dtype=torch.float32)
+        norm = (m.mean, m.std, m.image_min, m.image_max, m.norm_min, m.norm_max, self.fill)
         for i in range(0, plan.shape[0], self.batch_size):
             origins = plan_dev[i:i + self.batch_size]
-            tiles = ops.scene_cut(raster, origins, self.tile, m.mean, m.std, m.image_min, m.image_max, m.norm_min, m.norm_max, self.fill)
+            xforms = None if codes_dev is None else codes_dev[i:i + self.batch_size]
+            if xforms is None:
+                tiles = ops.scene_cut(raster, origins, self.tile, *norm)
+            else:
+                tiles = ops.scene_cut_d4(raster, origins, xforms, self.tile, *norm, check_codes=False)
             out = m.raw_output(tiles)
             with torch.no_grad():
-                self._blend(out, origins, canvas, gscene.bounding_box(plan[i:i + self.batch_size], self.tile))
+                self._blend(out, origins, canvas, gscene.bounding_box(plan[i:i + self.batch_size], self.tile), xforms)
         return canvas
 
     def predict(self, raster: torch.Tensor, return_probs: bool = False) -> SceneResult:

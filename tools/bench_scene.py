@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Whole-scene inference (tools/scene_inference.py, include/gdlhip_scene.h), two measurements in one process.
+"""Whole-scene inference (tools/scene_inference.py, include/gdlhip_scene.h, include/gdlhip_scene_tta.h), three measurements in one
+process.
 
 1. The tail of one batch of 64 tiles of 512^2 at stride 256 (an 8 x 8 grid over a 2304^2 uint8 scene), K = 5, the model excluded:
    its head map [64, 128, 128, 5] is drawn once.  ms per batch from HIP events around ``--inner`` repetitions, the variants
@@ -9,6 +10,15 @@
      (c) composed               -- what the code allowed before: a host loop of 64 slice copies, normalize_range, upsample_probs,
                                    a torch multiply by the window, 64 indexed adds into the canvas, a divide and an argmax.
    Every variant zeroes its canvas first; (a) and (b) are compared with (c) before anything is timed.
+1b. The same tail with test-time augmentation: one batch of 64 (tile, transform) pairs, for three sets of codes -- "flips"
+   (16 tiles x codes 0..3), "transposing" (16 tiles x codes 4..7) and "d4" (8 tiles x all eight) -- the model excluded as above
+   (its head map of the transformed tiles is drawn once):
+     (a) fused, low-resolution  -- scene_cut_d4, scene_blend_lowres_d4, scene_finish (what SceneInference(tta=...) runs),
+     (b) fused, full-resolution -- scene_cut_d4, upsample_probs, scene_blend_d4, scene_finish,
+     (c) composed               -- from the pieces without a transform: scene_cut, one torch flip / transpose copy per code into
+                                   the model's batch, upsample_probs, one torch inverse permutation copy per code, scene_blend,
+                                   scene_finish.
+   (b) must equal (c) to the bit and (a) agree with it before anything is timed.
 2. SceneInference on a synthetic 4096^2 scene (15 x 15 = 225 tiles) with the DOFA-base model in bf16, as tiles per second of the
    whole call, next to ScriptModel's tiles per second on the same tiles (batches of host-sliced tiles, probabilities written)."""
 import argparse
@@ -33,6 +43,7 @@ ap.add_argument("--inner", type=int, default=5)
 ap.add_argument("--scene", type=int, default=4096, help="side of the whole scene of part 2 (0 = skip part 2)")
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--scene-repeats", type=int, default=3)
+ap.add_argument("--no-tta", action="store_true", help="skip part 1b")
 args = ap.parse_args()
 
 K, T, S = args.classes, args.tile, args.stride
@@ -122,6 +133,83 @@ for (name, ts), nbytes in zip(times.items(), (bytes_fused, bytes_full, bytes_com
     print(f"  {name:28s} median {med:8.3f}  min {ts[0]:8.3f}  max {ts[-1]:8.3f}   ({med / ref:5.3f} x (c))   {nbytes / MIB:7.0f} MiB of tensor traffic, "
           f"{nbytes / (med * 1e-3) / 1e9:6.0f} GB/s")
 del raster, low, canvas, want_canvas, want_mask
+
+# ------------------------------------------------------------------ 1b. the tail of one batch of (tile, transform) pairs
+def tta_tail(label, grid, codes):
+    """Times the three variants for ``grid`` = (rows, columns) of tiles, each with the transforms ``codes``."""
+    G = len(codes)
+    h, w = T + S * (grid[0] - 1), T + S * (grid[1] - 1)
+    raster = torch.randint(0, 256, (3, h, w), device="cuda", dtype=torch.uint8, generator=g)
+    tiles_plan = gscene.plan_tiles(h, w, (T, T), (S, S))
+    plan, xf = gscene.plan_tta(tiles_plan, codes)
+    B = plan.shape[0]
+    assert B == grid[0] * grid[1] * G
+    origins, xforms, box = plan.cuda(), xf.cuda(), gscene.bounding_box(plan, (T, T))
+    low = torch.randn(B, T // 4, T // 4, K, device="cuda", generator=g) * 4      # the head's maps of the transformed tiles
+    canvas = torch.zeros(K + 1, h, w, device="cuda")
+
+    def fused_lowres():
+        canvas.zero_()
+        ops.scene_cut_d4(raster, origins, xforms, (T, T), mean, std, *RANGE, check_codes=False)
+        ops.scene_blend_lowres_d4(low, (T, T), origins, xforms, wy, wx, canvas, box, check_codes=False)
+        return ops.scene_finish(canvas)[0]
+
+    def fused_full():
+        canvas.zero_()
+        ops.scene_cut_d4(raster, origins, xforms, (T, T), mean, std, *RANGE, check_codes=False)
+        ops.scene_blend_d4(ops.upsample_probs(low, (T, T)), origins, xforms, wy, wx, canvas, box, check_codes=False)
+        return ops.scene_finish(canvas)[0]
+
+    def composed():
+        canvas.zero_()
+        cut = ops.scene_cut(raster, origins, (T, T), mean, std, *RANGE)
+        fed = torch.empty_like(cut)                      # the model's batch: pair j of every tile is its j-th transform
+        for j, code in enumerate(codes):
+            fed[j::G] = gscene.d4_apply(cut[j::G], code)
+        probs = ops.upsample_probs(low, (T, T))
+        back = torch.empty_like(probs)
+        for j, code in enumerate(codes):
+            back[j::G] = gscene.d4_apply(probs[j::G], gscene.d4_inverse(code))
+        ops.scene_blend(back, origins, wy, wx, canvas, box)
+        return ops.scene_finish(canvas)[0]
+
+    want_mask = composed()
+    want_canvas = canvas.clone()
+    cut_want = torch.empty(B, 3, T, T, device="cuda")
+    plain = ops.scene_cut(raster, origins, (T, T), mean, std, *RANGE)
+    for j, code in enumerate(codes):
+        cut_want[j::G] = gscene.d4_apply(plain[j::G], code)
+    assert torch.equal(ops.scene_cut_d4(raster, origins, xforms, (T, T), mean, std, *RANGE), cut_want), label
+    del cut_want, plain
+    mask = fused_full()
+    assert torch.equal(canvas, want_canvas) and torch.equal(mask, want_mask), f"{label}: (b) differs from (c)"
+    mask = fused_lowres()
+    d = (canvas - want_canvas).abs().max().item()
+    differ = (mask != want_mask).float().mean().item()
+    print(f"TTA {label}: (b) equals (c) to the bit; (a) vs (c): canvas max |diff| {d:.3e} (sums of up to {4 * G} weighted probabilities), "
+          f"labels that differ {differ:.2e} of the pixels")
+    assert d <= 1e-5 * G and differ <= 1e-4, (label, d, differ)
+
+    px, tile_px = h * w, B * T * T
+    cut_b = tile_px * 3 * (1 + 4)
+    b_fused = cut_b + 2 * (K + 1) * px * 4 + (K + 1) * px * 4 + px + (K + 1) * px * 4      # as in part 1: nothing is added by the transform
+    b_full = b_fused + 2 * tile_px * K * 4
+    b_composed = b_full + 2 * tile_px * 3 * 4 + 2 * tile_px * K * 4      # + the tiles and the probabilities read and written once more
+    times = timed({"(a) fused, low-resolution": fused_lowres, "(b) fused, full-resolution": fused_full, "(c) composed": composed},
+                  args.rounds, args.inner)
+    ref = times["(c) composed"][args.rounds // 2]
+    print(f"TTA tail of one batch, {label}: {B} pairs = {B // G} tiles of {T}^2 at stride {S} over {h} x {w}, codes {tuple(codes)}, K = {K}; "
+          f"ms per batch, {args.rounds} rounds of {args.inner}")
+    for (name, ts), nbytes in zip(times.items(), (b_fused, b_full, b_composed)):
+        med = ts[len(ts) // 2]
+        print(f"  {name:28s} median {med:8.3f}  min {ts[0]:8.3f}  max {ts[-1]:8.3f}   ({med / ref:5.3f} x (c))   {nbytes / MIB:7.0f} MiB of tensor traffic, "
+              f"{nbytes / (med * 1e-3) / 1e9:6.0f} GB/s")
+
+
+if not args.no_tta:
+    tta_tail("flips", (4, 4), gscene.FLIPS)
+    tta_tail("transposing", (4, 4), (4, 5, 6, 7))
+    tta_tail("d4", (2, 4), gscene.D4)
 
 # ------------------------------------------------------------------ 2. a whole scene through the model
 if args.scene:
