@@ -1234,6 +1234,30 @@ __global__ __launch_bounds__(256, PXB == 8 ? 3 : 4) void resize_conv3x3_fwd_sum_
   }
 }
 
+// ---- what versions 2 and 3 share: the output tile, and the counted waits of their steady state.
+// A step's outputs leave through an LDS tile of 4 rows x `cols` pixels x 64 bf16 channels (128 bytes), 16 bytes per thread and store.
+constexpr int tap_tile_bytes(int cols) { return 4 * cols * 128; }
+constexpr int kTapTileBytes = tap_tile_bytes(16);          // version 3 (and version 2 at PXB = 4): 4 x 16 pixels
+constexpr int tap_stores_per_flush(int tile_bytes, int threads) { return tile_bytes / (threads * 16); }
+constexpr int kTapM2Threads = 256, kRollThreads = 256, kRoll3Threads = 512;   // workgroup sizes: launch bounds, store loops, launcher
+// The vmcnt immediate that leaves everything younger than a step's fetch in flight (the vm counter retires in order, LDS-DMA
+// fetches and stores alike): with the fetches running `depth` steps ahead, the fetch that is waited for was followed by the
+// stores of one flush and then depth - 1 times by a fetch and a flush.  The arguments are the constants the fetch and store
+// loops run over: an edit to either side moves the immediate with it.
+constexpr int steady_vmcnt(int depth, int dma_per_step, int stores_per_step) {
+  return stores_per_step + (depth - 1) * (dma_per_step + stores_per_step);
+}
+template <int N>
+__device__ __forceinline__ void wait_vmcnt() {
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wait_vmcnt_lgkm0() {       // (why lgkmcnt(0) rides along: see resize_conv3x3_fwd_sum_roll_kernel)
+  static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit field");
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
+
 // ---- version 2: one block owns its 4 x 4 PXB output pixels for ALL channels and walks the 64-channel chunks (and, per chunk,
 // the sources) through LDS window slots: the window of step i + 1 is in flight while step i runs on the matrix cores.
 // Everything that does not depend on the channel is computed ONCE per block and kept in registers: the weight fragments
@@ -1248,18 +1272,24 @@ __global__ __launch_bounds__(256, PXB == 8 ? 3 : 4) void resize_conv3x3_fwd_sum_
 // LF0 (single source only): the factor as a template parameter -- the fragment count per channel tile, the DMA piece count and
 // the window slot then need no run-time branches (0 = read a.LF[k] at run time)
 template <int PXB, int NSRC, int LF0 = 0>
-__global__ __launch_bounds__(256, NSRC == 1 ? 3 : 1) void resize_conv3x3_fwd_sum_mfma2_kernel(const TapMArgs a, float* stats) {
+__global__ __launch_bounds__(kTapM2Threads, NSRC == 1 ? 3 : 1) void resize_conv3x3_fwd_sum_mfma2_kernel(const TapMArgs a, float* stats) {
   static_assert(LF0 == 0 || NSRC == 1, "compile-time factor: one source");
   auto lf_of = [&](int k) { return LF0 ? LF0 : a.LF[k]; };
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int COLS = 4 * PXB, TBL = 256 + COLS * 64, NPW = PXB / 4;
   constexpr int MAXP = PXB == 8 ? 9 : 12;                 // DMA pieces per wave and window (factor 2 needs 4 x 16 blocks)
+  constexpr int TILE = tap_tile_bytes(COLS);
+  constexpr int STORES = tap_stores_per_flush(TILE, kTapM2Threads);   // output stores per thread and chunk (PXB / 2)
+  static_assert(STORES * kTapM2Threads * 16 == TILE, "version 2: the tile is exactly threads * stores * 16 bytes");
+  constexpr int AHEAD = 1;                                 // steps the window fetches run ahead: issue(it + AHEAD) while step it computes
+  static_assert(AHEAD == 1, "version 2: one step ahead, so only stores are younger than the fetch that is waited for; the fetches "
+                            "are not padded (their count differs between the waves) and must not enter the wait");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int nchunks = a.N >> 6, nprow = (a.Ho + 3) >> 2;
   const int nblk = a.nblk;
   unsigned char* tile = smem + NSRC * TBL;
-  unsigned char* ring = tile + 4 * COLS * 128;
+  unsigned char* ring = tile + TILE;
   const unsigned lds_ring = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)ring);
   const int L = lane & 15, g = lane >> 4;
   bf16x8_t wf[NSRC][NPW][6];                              // weight fragments (B operand: column = pixel L of the patch)
@@ -1387,21 +1417,16 @@ __global__ __launch_bounds__(256, NSRC == 1 ? 3 : 1) void resize_conv3x3_fwd_sum
   for (int it = 0; it < nit; ++it) {
     const int c = it / NSRC, k = it - c * NSRC;
     // this wave's pieces of step `it` have landed.  They were issued BEFORE the previous step's output stores, and vmcnt
-    // retires in order: inside the image (every thread stores exactly PXB / 2 pieces per chunk) the wait leaves those stores
-    // in flight instead of exposing their acknowledgement
+    // retires in order: inside the image (every thread stores exactly STORES pieces per chunk) the wait leaves those stores
+    // in flight instead of exposing their acknowledgement.  The fetches run one step ahead, so nothing else is younger.
     if (full && it > 0 && (it - 1) % NSRC == NSRC - 1) {
-      if (stats && wave < 2) {                             // (waves 0 and 1 also wrote one statistics row each)
-        if constexpr (PXB == 8) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-      } else {
-        if constexpr (PXB == 8) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      }
+      if (stats && wave < 2) wait_vmcnt<steady_vmcnt(AHEAD, 0, STORES + 1)>();   // (waves 0 and 1 also wrote one statistics row each)
+      else wait_vmcnt<steady_vmcnt(AHEAD, 0, STORES)>();
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __syncthreads();                                      // ... everyone's; nobody reads the other slot or the tile any more
-    if (it + 1 < nit) issue(it + 1);
+    if (it + AHEAD < nit) issue(it + AHEAD);
     const unsigned char* stage = ring + (NSRC == 1 ? (it & 1) * a.slot_off[1] : a.slot_off[it % a.nslots]);
 #pragma unroll
     for (int kk = 0; kk < NSRC; ++kk) {
@@ -1437,8 +1462,8 @@ __global__ __launch_bounds__(256, NSRC == 1 ? 3 : 1) void resize_conv3x3_fwd_sum
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s1[e] = 0.f; s2[e] = 0.f; }
 #pragma unroll
-    for (int u = 0; u < (4 * COLS * 8) / 256; ++u) {
-      const int i = tid + 256 * u;
+    for (int u = 0; u < STORES; ++u) {
+      const int i = tid + kTapM2Threads * u;
       const int pp = i >> 3, chunk = i & 7;                // chunk = tid & 7 for every u: a thread always owns the same 8 channels
       const int py = pp / COLS, oy = oy0 + py, ox = oxb0 + pp - py * COLS;
       if (full || (oy < a.Ho && ox < a.Wo)) {               // `full` is uniform: then every thread stores, and the wait above counts on it
@@ -1470,7 +1495,7 @@ __global__ __launch_bounds__(256, NSRC == 1 ? 3 : 1) void resize_conv3x3_fwd_sum
         for (int e = 0; e < 8; ++e) { red[(wave * 2) * 64 + lane * 8 + e] = s1[e]; red[(wave * 2 + 1) * 64 + lane * 8 + e] = s2[e]; }
       }
       __syncthreads();
-      if (tid < 128) {
+      if (tid < 128) {                                     // waves 0 and 1: the `+ 1` of their wait
         const int which = tid >> 6, ch = tid & 63;
         const float t = ((red[(0 * 2 + which) * 64 + ch] + red[(1 * 2 + which) * 64 + ch]) + red[(2 * 2 + which) * 64 + ch]) +
                         red[(3 * 2 + which) * 64 + ch];
@@ -1521,8 +1546,10 @@ struct RollSrc {
   static constexpr int WC = (12 >> LF) + WIN, ROWS = WC * 9, PIECES = (ROWS + 7) / 8, SLOT = PIECES * 1024;
   static constexpr int RPS = LF == 1 ? 2 : 1;              // new window rows of a step that fetches
   static constexpr int NSLOT = WIN + (LF == 3 ? (D + 1) / 2 : D * RPS);
-  static constexpr int MAXP = (PIECES + NW - 1) / NW, NDMA = RPS * MAXP, BYTES = NSLOT * SLOT;
+  static constexpr int MAXP = (PIECES + NW - 1) / NW, NDMA = RPS * MAXP, BYTES = NSLOT * SLOT;   // NDMA: DMA instructions of a padded fetching step
+  static constexpr int NWAVES = NW;
   static constexpr int NMW = (NKS + 3) / 4;
+  static_assert(LF != 3 || RPS == 1, "factor 8: a step fetches one row or (every other step) none; the idle step pads one row's worth");
   bf16x8_t wf[NPH][NKS];                                   // weight fragments (B operand: column = pixel of the patch)
   unsigned mtop[NMW], mbot[NMW];                           // bit 8 (ks % 4) + e of word ks / 4: element e of K-step ks is zero in the first / last step
   unsigned araddr[NKS][2];                                 // ring-relative byte offset of the lane's two fragment pieces, window row 0 of the step in slot 0
@@ -1618,6 +1645,8 @@ struct RollSrc {
   __device__ __forceinline__ void set_image(const uint16_t* z, int b) {
     srd = make_srd(z + (int64_t)b * Hi * (row_bytes / 2), (unsigned)((int64_t)Hi * row_bytes));
   }
+  // one window row: (PIECES - wave + NW - 1) / NW instructions in wave `wave`; pad: MAXP in every wave (the pieces a wave does not
+  // have are all-out-of-range fetches)
   __device__ __forceinline__ void issue_row(int cc, int y, int wave, unsigned lds_dummy, bool pad) const {
     const int yc = y < 0 ? 0 : (y > Hi - 1 ? Hi - 1 : y);
     const int slot = (y + 1) % NSLOT;
@@ -1628,21 +1657,25 @@ struct RollSrc {
       else if (pad) dma16_buf(kTmOob, srd, 0u, lds_dummy);
     }
   }
-  // the window rows step s adds (step 0: the whole window); pad: always NDMA instructions per wave
+  // the window rows step s adds (step 0: the whole window, never padded).  A step s > 0 issues, with pad, NDMA = RPS rows x MAXP
+  // instructions in every wave and step -- what a counted wait may rely on; without, the count differs between the waves (RPS x
+  // the wave's pieces of a row) and, for factor 8, between the steps
   __device__ __forceinline__ void issue_step(int cc, int s, int wave, unsigned lds_dummy, bool pad) const {
     if (s == 0) {
 #pragma unroll
       for (int y = 0; y < WIN; ++y) issue_row(cc, y - 1, wave, lds_dummy, false);
     } else if (LF == 1) {
+      static_assert(LF != 1 || RPS == 2, "factor 2: two new rows per step");
       issue_row(cc, 2 * s + 1, wave, lds_dummy, pad);
       issue_row(cc, 2 * s + 2, wave, lds_dummy, pad);
     } else if (LF == 2) {
+      static_assert(LF != 2 || RPS == 1, "factor 4: one new row per step");
       issue_row(cc, s + 1, wave, lds_dummy, pad);
-    } else {
+    } else {                                               // factor 8: a new row every other step, one row's worth of padding in between
       if ((s & 1) == 0) issue_row(cc, (s >> 1) + 1, wave, lds_dummy, pad);
       else if (pad) {
 #pragma unroll
-        for (int i = 0; i < MAXP; ++i) dma16_buf(kTmOob, srd, 0u, lds_dummy);
+        for (int i = 0; i < RPS * MAXP; ++i) dma16_buf(kTmOob, srd, 0u, lds_dummy);
       }
     }
   }
@@ -1738,9 +1771,12 @@ __device__ __forceinline__ void roll_to_tile(unsigned char* tile, const f32x4_t 
 }
 
 template <int LF, bool STATS, int D>
-__global__ __launch_bounds__(256, LF == 2 ? 3 : 2) void resize_conv3x3_fwd_sum_roll_kernel(const TapRArgs a) {
+__global__ __launch_bounds__(kRollThreads, LF == 2 ? 3 : 2) void resize_conv3x3_fwd_sum_roll_kernel(const TapRArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  using S = RollSrc<LF, D>;
+  using S = RollSrc<LF, D>;                                // dynamic LDS = kTapTileBytes + S::BYTES (the launcher reads it off the same type)
+  constexpr int STORES = tap_stores_per_flush(kTapTileBytes, kRollThreads);   // output stores per thread and flush
+  static_assert(kRollThreads == 64 * S::NWAVES, "one-source kernel: the ring's pieces are dealt to the workgroup's waves");
+  static_assert(STORES * kRollThreads * 16 == kTapTileBytes, "one-source kernel: the tile is exactly threads * stores * 16 bytes");
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int L = lane & 15, g = lane >> 4;
@@ -1748,13 +1784,13 @@ __global__ __launch_bounds__(256, LF == 2 ? 3 : 2) void resize_conv3x3_fwd_sum_r
   const int grp = idx / a.nstrips, strip = idx - grp * a.nstrips;
   const int oxb0 = strip * 16;
   unsigned char* tile = smem;                              // [4 rows][16 pixels] x 128 B; the two weight tables during the set-up
-  const unsigned char* ring = smem + 4 * 16 * 128;
+  const unsigned char* ring = smem + kTapTileBytes;
   S s;
-  s.setup((float*)tile, (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)(smem + 4 * 16 * 128)),
+  s.setup((float*)tile, (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)(smem + kTapTileBytes)),
           a.Hi, a.Wi, a.Wo, a.N, oxb0, tid, wave);
   const int nsteps = a.Ho >> 2;
-  const bool fullstrip = oxb0 + 16 <= a.Wo;                // every thread stores its two pieces of every tile
-  const int npw = (S::PIECES - wave + 3) / 4;              // DMA instructions of this wave per window row
+  const bool fullstrip = oxb0 + 16 <= a.Wo;                // every thread stores its STORES pieces of every tile
+  const int npw = (S::PIECES - wave + S::NWAVES - 1) / S::NWAVES;   // DMA instructions of this wave per window row (issue_row, not padded)
   const int gg = xcd * a.G + grp, gstride = 8 * a.G;
   bool primed = false;
   for (int col = gg; col < a.ncols; col += gstride) {
@@ -1780,8 +1816,8 @@ __global__ __launch_bounds__(256, LF == 2 ? 3 : 2) void resize_conv3x3_fwd_sum_r
       asm volatile("" : "+v"(t));                          // (addresses from an opaque thread id: not kept in registers across the steps)
       uint16_t* orow = obase + (int64_t)step * 4 * a.Wo * a.N;
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int i = t + 256 * u, pp = i >> 3, chunk = i & 7;
+      for (int u = 0; u < STORES; ++u) {
+        const int i = t + kRollThreads * u, pp = i >> 3, chunk = i & 7;
         const uint4 v = *(const uint4*)(tile + pp * 128 + ((chunk ^ (pp & 7)) << 4));
         if (oxb0 + (pp & 15) < a.Wo) *(uint4*)(orow + ((int64_t)(pp >> 4) * a.Wo + oxb0 + (pp & 15)) * a.N + chunk * 8) = v;
       }
@@ -1806,11 +1842,12 @@ __global__ __launch_bounds__(256, LF == 2 ? 3 : 2) void resize_conv3x3_fwd_sum_r
       // (lgkmcnt(0) in every wait: hipcc drops its own LDS wait in front of the barrier below -- behind these asm statements the
       // last ds_write of the previous step's tile was still in flight when other waves read the tile: one patch row of the last
       // channel tile wrong in 1 of 4 launches)
-      // this wave's pieces of step i's rows have landed.  Steady state (the fetch of step i was followed by two stores, then
-      // D - 1 times by a fetch and two stores): those may stay in flight
+      // this wave's pieces of step i's rows have landed.  Steady state (the fetch of step i was followed by STORES stores, then
+      // D - 1 times by a fetch of S::RPS rows and STORES stores): those may stay in flight.  A wave has S::MAXP pieces of a row or
+      // one fewer (S::PIECES dealt to S::NWAVES waves); the immediate is a constant, hence one arm per count
       if (D > 1 && fullstrip && i > D && i + D <= nsteps) {
-        if (npw == 2) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 + (D - 1) * (2 * S::RPS + 2)) : "memory");
-        else if (npw == 1) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 + (D - 1) * (1 * S::RPS + 2)) : "memory");
+        if (npw == S::MAXP) wait_vmcnt_lgkm0<steady_vmcnt(D, S::RPS * S::MAXP, STORES)>();
+        else if (npw == S::MAXP - 1) wait_vmcnt_lgkm0<steady_vmcnt(D, S::RPS * (S::MAXP - 1), STORES)>();
         else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       } else {
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
@@ -1861,15 +1898,32 @@ struct TapR3Args {
 // 512 threads: wave w works on patch w & 3 and the channel tiles 2 (w >> 2), 2 (w >> 2) + 1 -- two waves per SIMD, so that one's LDS
 // round trips and address arithmetic run under the other's matrix-core work (with 256 threads the waves were issuing 60 % of
 // their cycles and parked the rest: 720 us of compute against 608 us for all memory traffic)
+// the three rings and the LDS layout of the kernel below (the launcher's dynamic LDS size is BYTES of the same type)
 template <int D>
-__global__ __launch_bounds__(512, 1) void resize_conv3x3_fwd_sum_roll3_kernel(const TapR3Args a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int NW = 8, NTN = 2;
+struct Roll3Lds {
+  static constexpr int NW = kRoll3Threads / 64;
   using SA = RollSrc<1, D, NW>;
   using SB = RollSrc<2, D, NW>;
   using SC = RollSrc<3, D, NW>;
+  static constexpr int OA = kTapTileBytes, OB = OA + SA::BYTES, OC = OB + SB::BYTES, OD = OC + SC::BYTES;   // rings and the spare KiB behind the tile
+  static constexpr int BYTES = OD + 1024;
+  static_assert(BYTES <= 160 * 1024, "LDS budget");
+};
+
+template <int D>
+__global__ __launch_bounds__(kRoll3Threads, 1) void resize_conv3x3_fwd_sum_roll3_kernel(const TapR3Args a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  using Lds = Roll3Lds<D>;
+  using SA = typename Lds::SA;
+  using SB = typename Lds::SB;
+  using SC = typename Lds::SC;
+  constexpr int NTN = 2;
+  constexpr bool PAD = true;                               // what the three steady-state issue_step calls pass: the same count in every wave and step
   constexpr int NDMA = SA::NDMA + SB::NDMA + SC::NDMA;     // per wave and steady-state step
-  constexpr int OA = 4 * 16 * 128, OB = OA + SA::BYTES, OC = OB + SB::BYTES, OD = OC + SC::BYTES;   // rings and the spare KiB behind the tile
+  static_assert(PAD, "roll3: every wave issues NDMA fetches per step (pad=true): the counted wait relies on it");
+  constexpr int STORES = tap_stores_per_flush(kTapTileBytes, kRoll3Threads);   // output stores per thread and flush
+  static_assert(STORES * kRoll3Threads * 16 == kTapTileBytes, "roll3: the tile is exactly threads * stores * 16 bytes");
+  constexpr int OA = Lds::OA, OB = Lds::OB, OC = Lds::OC, OD = Lds::OD;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int pw = wave & 3, nt0 = 2 * (wave >> 2);
@@ -1907,6 +1961,7 @@ __global__ __launch_bounds__(512, 1) void resize_conv3x3_fwd_sum_roll3_kernel(co
     }
     uint16_t* obase = a.out + (int64_t)b * a.Ho * a.Wo * a.N + c * 64;
     auto flush = [&](int step) {                           // 512 threads x 16 bytes = the tile
+      static_assert(STORES == 1, "roll3: flush() issues one store per thread; more stores need a loop over STORES here");
       int t = tid;
       asm volatile("" : "+v"(t));
       uint16_t* orow = obase + (int64_t)step * 4 * a.Wo * a.N;
@@ -1916,13 +1971,13 @@ __global__ __launch_bounds__(512, 1) void resize_conv3x3_fwd_sum_roll3_kernel(co
     };
 #pragma unroll 1
     for (int i = 0; i < nsteps; ++i) {
-      // (lgkmcnt(0) with every wait: see the one-source kernel.)  Steady state: the fetch of step i was followed by one store, then
-      // D - 1 times by a fetch (NDMA instructions in every wave) and a store
-      if (D > 1 && fullstrip && i > D && i + D <= nsteps) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(1 + (D - 1) * (NDMA + 1)) : "memory");
+      // (lgkmcnt(0) with every wait: see the one-source kernel.)  Steady state: the fetch of step i was followed by STORES stores,
+      // then D - 1 times by a fetch (NDMA instructions in every wave) and STORES stores
+      if (D > 1 && fullstrip && i > D && i + D <= nsteps) wait_vmcnt_lgkm0<steady_vmcnt(D, NDMA, STORES)>();
       else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
       __syncthreads();
       if (i + D < nsteps && !(a.dbg & 32)) {
-        sa.issue_step(c, i + D, wave, lds_dummy, true); sb.issue_step(c, i + D, wave, lds_dummy, true); sc.issue_step(c, i + D, wave, lds_dummy, true);
+        sa.issue_step(c, i + D, wave, lds_dummy, PAD); sb.issue_step(c, i + D, wave, lds_dummy, PAD); sc.issue_step(c, i + D, wave, lds_dummy, PAD);
       }
       if (i > 0 && !(a.dbg & 64)) flush(i - 1);
       f32x4_t acc[NTN];
@@ -2416,7 +2471,7 @@ static int tapsum_num_cus() {
   return n;
 }
 static int g_tapsum_roll = 1;
-constexpr int kRollDepth4 = 3;    // factor 4: steps the row fetches of version 3 run ahead (ring of 3 + depth slots of 7 KiB, three workgroups per CU)
+constexpr int kRollDepth4 = 3;    // factor 4: steps the row fetches of version 3 run ahead (ring of RollSrc<2, depth>::NSLOT = 3 + depth slots, three workgroups per CU)
 extern "C" void gdl_debug_set_tapsum_roll(int on) { g_tapsum_roll = on; }  // A/B hook: 0 = versions 1 / 2 where version 3 (rolling row window) applies
 // stat_rows (with stats): the number of partial rows the launch wrote (<= gdl_resize_conv3x3_fwd_sum_bn_rows)
 static int tapsum_launch(const void* const* zs, const int* hs, const int* ws, int nsrc, int dtype, int B, int N, void* out, int Ho, int Wo,
@@ -2465,10 +2520,8 @@ static int tapsum_launch(const void* const* zs, const int* hs, const int* ws, in
       if (streams < 1) streams = 1;
       r.nstreams = streams; r.nblocks = streams * r.nstrips;
       r.dbg = g_tapsum_roll >= 16 ? g_tapsum_roll : 0;
-      const size_t lds = 4 * 16 * 128 + RollSrc<1, D3, 8>::BYTES + RollSrc<2, D3, 8>::BYTES + RollSrc<3, D3, 8>::BYTES + 1024;
-      static_assert(4 * 16 * 128 + RollSrc<1, D3, 8>::BYTES + RollSrc<2, D3, 8>::BYTES + RollSrc<3, D3, 8>::BYTES + 1024 <= 160 * 1024, "LDS budget");
       GDL_SET_MAX_LDS_ONCE((resize_conv3x3_fwd_sum_roll3_kernel<D3>), 160 * 1024);
-      hipLaunchKernelGGL((resize_conv3x3_fwd_sum_roll3_kernel<D3>), dim3((unsigned)r.nblocks), dim3(512), lds, st, r);
+      hipLaunchKernelGGL((resize_conv3x3_fwd_sum_roll3_kernel<D3>), dim3((unsigned)r.nblocks), dim3(kRoll3Threads), (size_t)Roll3Lds<D3>::BYTES, st, r);
       GDL_CHECK_LAUNCH("gdl_resize_conv3x3_fwd_sum");
       return GDL_OK;
     }
@@ -2484,9 +2537,11 @@ static int tapsum_launch(const void* const* zs, const int* hs, const int* ws, in
       if (G < 1) G = 1;
       r.G = G;
       const dim3 grid((unsigned)(8 * G * r.nstrips));
-      const size_t lds = 4 * 16 * 128 + (size_t)(m.LF[0] == 2 ? (3 + (g_tapsum_roll == 2 ? 1 : kRollDepth4)) * 7 : 6 * 12) * 1024;
-#define TAPR(LF_, ST_, D_) do { GDL_SET_MAX_LDS_ONCE((resize_conv3x3_fwd_sum_roll_kernel<LF_, ST_, D_>), 160 * 1024);                    \
-    hipLaunchKernelGGL((resize_conv3x3_fwd_sum_roll_kernel<LF_, ST_, D_>), grid, dim3(256), lds, st, r); } while (0)
+      // (the dynamic LDS -- the tile and the ring -- is read off the RollSrc the instantiation indexes by)
+#define TAPR(LF_, ST_, D_) do { constexpr size_t lds = kTapTileBytes + RollSrc<LF_, D_>::BYTES;                                          \
+    static_assert(lds <= 160 * 1024, "LDS budget");                                                                                      \
+    GDL_SET_MAX_LDS_ONCE((resize_conv3x3_fwd_sum_roll_kernel<LF_, ST_, D_>), 160 * 1024);                                                \
+    hipLaunchKernelGGL((resize_conv3x3_fwd_sum_roll_kernel<LF_, ST_, D_>), grid, dim3(kRollThreads), lds, st, r); } while (0)
       if (m.LF[0] == 2 && g_tapsum_roll == 2) { if (stats) TAPR(2, true, 1); else TAPR(2, false, 1); }      // (A/B: one step ahead)
       else if (m.LF[0] == 2) { if (stats) TAPR(2, true, kRollDepth4); else TAPR(2, false, kRollDepth4); }
       else { if (stats) TAPR(1, true, 1); else TAPR(1, false, 1); }
@@ -2507,7 +2562,7 @@ static int tapsum_launch(const void* const* zs, const int* hs, const int* ws, in
       int ring = 0;
       m.nslots = nsrc == 1 ? 2 : nsrc;
       for (int j = 0; j < m.nslots; ++j) { m.slot_off[j] = ring; ring += window_bytes_lf(cols, m.LF[nsrc == 1 ? 0 : j]); }
-      const size_t lds = (size_t)nsrc * (256 + cols * 64) + 4 * cols * 128 + ring;
+      const size_t lds = (size_t)nsrc * (256 + cols * 64) + tap_tile_bytes(cols) + ring;
       GDL_CHECK_ARG(lds <= 160 * 1024 || !stats, "gdl_resize_conv3x3_fwd_sum_bn: LDS budget exceeded");
       m.gx = (Wo + cols - 1) / cols;
       m.nblk = m.gx * B * ((Ho + 3) / 4);
@@ -2517,7 +2572,7 @@ static int tapsum_launch(const void* const* zs, const int* hs, const int* ws, in
         // (does not happen for 1..3 sources of factors 2 / 4 / 8; version 1 below would take over)
       } else
 #define TAPM2(PXB_, NSRC_, LF_) do { GDL_SET_MAX_LDS_ONCE((resize_conv3x3_fwd_sum_mfma2_kernel<PXB_, NSRC_, LF_>), 160 * 1024);                 \
-    hipLaunchKernelGGL((resize_conv3x3_fwd_sum_mfma2_kernel<PXB_, NSRC_, LF_>), grid, dim3(256), lds, st, m, stats); } while (0)
+    hipLaunchKernelGGL((resize_conv3x3_fwd_sum_mfma2_kernel<PXB_, NSRC_, LF_>), grid, dim3(kTapM2Threads), lds, st, m, stats); } while (0)
       if (nsrc == 1 && m.LF[0] == 2) TAPM2(4, 1, 2); else if (nsrc == 1 && m.LF[0] == 3) TAPM2(4, 1, 3); else if (nsrc == 1) TAPM2(4, 1, 1);
       else if (nsrc == 2) TAPM2(4, 2, 0); else TAPM2(4, 3, 0);
 #undef TAPM2
@@ -2530,7 +2585,7 @@ static int tapsum_launch(const void* const* zs, const int* hs, const int* ws, in
     auto window_bytes = [&](int cols) { return window_bytes_lf(cols, lfmin); };
     const int pxb = (window_bytes(32) <= 48 * 1024 && g_tapsum_mfma != 4) ? 8 : 4;
     const int cols = 4 * pxb;
-    const int tile_bytes = 4 * cols * 128;
+    const int tile_bytes = tap_tile_bytes(cols);
     const size_t lds = 256 + cols * 64 + (size_t)(window_bytes(cols) > tile_bytes ? window_bytes(cols) : tile_bytes);
     const dim3 grid((unsigned)(((Wo + cols - 1) / cols) * (N / 64)), (unsigned)(B * ((Ho + 3) / 4)));
     if (pxb == 8) {

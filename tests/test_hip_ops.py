@@ -2053,6 +2053,56 @@ def test_resize_conv3x3_fwd_sum_rolling_window(B, H, W, N, f):
     close(rv, bn.running_var, torch.float32, "running_var")
 
 
+@pytest.mark.parametrize("B,H,W,N,factors,roll", [
+    (3, 32, 40, 256, (4,), 1),          # D = 3: 8 steps (partial waits in steps 4, 5), two full strips + a partial one (vmcnt(0) arm);
+                                        # waves 0-2 fetch two pieces of a row, wave 3 one.  12 columns: every workgroup walks ONE
+    (65, 32, 40, 256, (4,), 1),         # the same with 260 columns: the launcher (256 CUs) keeps 256 / 8 * 3 = 96 workgroups per XCD,
+                                        # 96 / 3 strips = 32 column groups, x 8 XCDs = 256 columns per pass -- four groups walk a second
+                                        # column, whose first rows were fetched under the first one's tail (`primed`)
+    (1, 16, 24, 64, (2,), 1),           # D = 1: never a partial wait
+    (1, 24, 40, 64, (2, 4, 8), 1),      # three rings, D = 2: 6 steps (partial waits in steps 3, 4)
+    (43, 24, 40, 128, (2, 4, 8), 1),    # 86 columns over 3 strips: more than 256 CUs / 3 = 85 streams, a workgroup walks a second column
+                                        # (this case and the 260-column one count on the launcher seeing 256 CUs, the MI355X's)
+    (1, 8, 32, 128, (4,), 0),           # version 2, interior patches, two chunks: with statistics waves 0-1 wait for one store more
+])
+def test_resize_conv3x3_fwd_sum_repeated_launches(B, H, W, N, factors, roll):
+    """The gather-sum kernels wait with counted `s_waitcnt vmcnt(N)` in steady state; a count that is too high reads window
+    rows that have not landed, and not in every launch.  The kernels use no atomics, so every launch on the same input must
+    give the same bits: each form (plain, addend + ReLU, with BatchNorm statistics for one source) is launched 8 times and
+    compared bit for bit with its first result, which in turn agrees with the other version's (the same products in another
+    summation order: one bf16 step apart at most, and rarely)."""
+    import ctypes
+    from gdlhip import _lib
+    lib = _lib.load()
+    lib.gdl_debug_set_tapsum_roll.argtypes = [ctypes.c_int]
+    dtype = torch.bfloat16
+    zs = [q(rnd(B, H // f, W // f, 9 * N, seed=31 + f), dtype).to(DEV, dtype) for f in factors]
+    add = rnd(N, seed=5).to(DEV)
+    forms = [("plain", lambda: (ops.resize_conv3x3_fwd_sum(zs, (H, W)),)),
+             ("addvec + relu", lambda: (ops.resize_conv3x3_fwd_sum(zs, (H, W), addvec=add, relu=True),))]
+    if len(factors) == 1:
+        forms.append(("bn", lambda: ops.resize_conv3x3_fwd_sum_bn(zs, (H, W), addvec=add)))
+    try:
+        lib.gdl_debug_set_tapsum_roll(1 - roll)
+        others = [fn() for _, fn in forms]
+        lib.gdl_debug_set_tapsum_roll(roll)
+        for (name, fn), other in zip(forms, others):
+            first = fn()
+            for rep in range(1, 8):
+                for got, want in zip(fn(), first):
+                    assert torch.equal(got, want), f"{name}: launch {rep} differs from the first in {int((got != want).sum())} elements"
+            d = (first[0].float() - other[0].float()).abs()
+            print(f"{name}: max dev {d.max().item():.3e}, share of differing elements {(d > 0).float().mean().item():.4f}")
+            assert d.max().item() <= 2.0 ** -7 * other[0].float().abs().max().item(), (name, d.max().item())
+            assert (d > 0).float().mean().item() < 0.02, (name, (d > 0).float().mean().item())
+            if name == "bn":                                # (out, mean, var): the statistics against the other version's as well
+                scale = first[0].float().abs().max().item()
+                close(first[1], other[1], torch.float32, "mean vs the other version", scale=scale)
+                close(first[2], other[2], torch.float32, "var vs the other version")
+    finally:
+        lib.gdl_debug_set_tapsum_roll(1)
+
+
 def _rel_l2(got, ref):
     got, ref = got.detach().float().cpu(), ref.detach().float().cpu()
     return float((got - ref).norm() / ref.norm().clamp_min(1e-12))
