@@ -1,7 +1,9 @@
 // Whole-scene inference (include/gdlhip_scene.h): cut normalised tiles out of a raster, stitch the tiles' class probabilities into a
 // weighted canvas, label the canvas.  All four kernels are bound by memory traffic; none uses atomics, so every result is
 // reproducible bit for bit.  Test-time augmentation (include/gdlhip_scene_tta.h) is the same cut and blend kernels with a D4 code
-// per tile in the index arithmetic of their gathers: a flag of the cut kernel, two further sources of the blend kernel.
+// per tile in the index arithmetic of their gathers: a flag of the cut kernel, two further sources of the blend kernel.  Nodata
+// (include/gdlhip_scene_nodata.h) is a validity plane of the raster: one kernel builds it, one counts it per tile, and the cut and
+// the finish kernels read it under one more flag each.
 #include <cmath>
 
 #include "gdl_common.h"
@@ -9,6 +11,7 @@
 #include "infer_expr.h"
 #include "../../include/gdlhip_scene.h"
 #include "../../include/gdlhip_scene_tta.h"
+#include "../../include/gdlhip_scene_nodata.h"
 
 namespace {
 
@@ -33,12 +36,15 @@ __device__ __forceinline__ int d4_inverse(int g) { return g & 4 ? 4 | (g & 1) <<
 //
 // D4 (include/gdlhip_scene_tta.h): the tile written is T_g of the tile cut, g = xforms[b].  The stores stay what they are; the V
 // raster elements of a thread lie along a row (backwards where g flips x) or, under a transpose, down a column.
-template <typename TI, int V, bool D4>
+//
+// MASKED (include/gdlhip_scene_nodata.h): a pixel inside the raster whose valid[y, x] is 0 takes `fill` as well; one more byte read
+// per element, the same for every band.  Without the flag `valid` is not looked at.
+template <typename TI, int V, bool D4, bool MASKED>
 __global__ __launch_bounds__(256) void scene_cut_kernel(const TI* __restrict__ raster, int C, int H, int W,
                                                         const int32_t* __restrict__ origins, const int32_t* __restrict__ xforms, int th,
                                                         int tw, float fill, float* __restrict__ tiles, int64_t groups, float imin,
                                                         float span, float d, float nmin, const float* __restrict__ mean,
-                                                        const float* __restrict__ stdv) {
+                                                        const float* __restrict__ stdv, const uint8_t* __restrict__ valid) {
   struct alignas(sizeof(float) * V) VecF { float v[V]; };
   const int twv = tw / V;
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
@@ -58,17 +64,22 @@ __global__ __launch_bounds__(256) void scene_cut_kernel(const TI* __restrict__ r
         int r, q;
         d4_src(code, th, tw, dy, dx0 + e, r, q);
         const int64_t y = oy + r, x = ox + q;
-        const float raw = y >= 0 && y < H && x >= 0 && x < W ? (float)plane[y * W + x] : fill;
+        bool in = y >= 0 && y < H && x >= 0 && x < W;
+        if constexpr (MASKED) in = in && valid[y * W + x] != 0;
+        const float raw = in ? (float)plane[y * W + x] : fill;
         o.v[e] = normalize_range_value(raw, imin, span, d, nmin, m, s);
       }
     } else {
       const int64_t y = (int64_t)origins[2 * b] + dy, x0 = (int64_t)origins[2 * b + 1] + dx0;
       const bool row_in = y >= 0 && y < H;
       const TI* row = raster + ((int64_t)c * H + (row_in ? y : 0)) * W;
+      const uint8_t* vrow = MASKED ? valid + (row_in ? y : 0) * W : nullptr;
 #pragma unroll
       for (int e = 0; e < V; ++e) {
         const int64_t x = x0 + e;
-        const float raw = row_in && x >= 0 && x < W ? (float)row[x] : fill;
+        bool in = row_in && x >= 0 && x < W;
+        if constexpr (MASKED) in = in && vrow[x] != 0;
+        const float raw = in ? (float)row[x] : fill;
         o.v[e] = normalize_range_value(raw, imin, span, d, nmin, m, s);
       }
     }
@@ -304,15 +315,32 @@ __global__ __launch_bounds__(256) void scene_blend_kernel(Src src, int B, int th
 // ------------------------------------------------------------------ finish
 // A thread labels V consecutive pixels (V == 4: HW % 4 == 0 and aligned pointers, 16-byte loads of every plane and one 4-byte
 // store of the mask).  The class count is a loop bound only: nothing is kept per class.
-template <int V>
+//
+// ND (include/gdlhip_scene_nodata.h): a pixel counts as labelled only where its weight is not 0 and `valid` (if there is one) is
+// not 0; every other pixel gets `nodata_label` and probabilities 0.  The quotient and the arg-max are the same expressions.
+template <int V, bool ND>
 __global__ __launch_bounds__(256) void scene_finish_kernel(const float* __restrict__ canvas, int K, int64_t HW, float threshold,
-                                                           uint8_t* __restrict__ mask, float* __restrict__ probs) {
+                                                           uint8_t* __restrict__ mask, float* __restrict__ probs,
+                                                           const uint8_t* __restrict__ valid, int nodata_label) {
   struct alignas(sizeof(float) * V) VecF { float v[V]; };
   struct alignas(V) VecB { uint8_t v[V]; };
   const int64_t groups = HW / V;
   for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
     const int64_t i0 = g * V;
     const VecF den = *(const VecF*)(canvas + (int64_t)K * HW + i0);
+    [[maybe_unused]] VecB data;      // ND: the plane's bytes, all ones where there is no plane
+    if constexpr (ND) {
+      if (valid) data = *(const VecB*)(valid + i0);
+      else {
+#pragma unroll
+        for (int e = 0; e < V; ++e) data.v[e] = 1;
+      }
+    }
+    // whether pixel e gets a label and probabilities of its own
+    const auto live = [&](int e) {
+      if constexpr (ND) return den.v[e] != 0.f && data.v[e] != 0;
+      else return den.v[e] != 0.f;
+    };
     float best_v[V], first[V];
     int best[V];
     for (int k = 0; k < K; ++k) {
@@ -320,7 +348,7 @@ __global__ __launch_bounds__(256) void scene_finish_kernel(const float* __restri
       VecF q;
 #pragma unroll
       for (int e = 0; e < V; ++e) {
-        q.v[e] = den.v[e] != 0.f ? c.v[e] / den.v[e] : 0.f;
+        q.v[e] = live(e) ? c.v[e] / den.v[e] : 0.f;
         if (k == 0) { best_v[e] = c.v[e]; best[e] = 0; first[e] = q.v[e]; }
         else if (c.v[e] > best_v[e]) { best_v[e] = c.v[e]; best[e] = k; }
       }
@@ -330,10 +358,64 @@ __global__ __launch_bounds__(256) void scene_finish_kernel(const float* __restri
 #pragma unroll
     for (int e = 0; e < V; ++e) {
       const int label = K == 1 ? (first[e] > threshold ? 1 : 0) : best[e];
-      o.v[e] = den.v[e] != 0.f ? (uint8_t)label : (uint8_t)0;
+      o.v[e] = live(e) ? (uint8_t)label : (uint8_t)(ND ? nodata_label : 0);
     }
     *(VecB*)(mask + i0) = o;
   }
+}
+
+// ------------------------------------------------------------------ nodata (include/gdlhip_scene_nodata.h)
+// A thread decides V consecutive pixels (V == 4: W % 4 == 0 and aligned pointers, so every band is one load of 4 samples and the
+// plane one 4-byte store).  A sample is nodata when it equals the band's value as a float or, for a NaN value, when it is NaN.
+template <typename TI, int V>
+__global__ __launch_bounds__(256) void scene_valid_kernel(const TI* __restrict__ raster, int C, int64_t HW, const float* __restrict__ nodata,
+                                                          int rule, uint8_t* __restrict__ valid) {
+  struct alignas(sizeof(TI) * V) VecT { TI v[V]; };
+  struct alignas(V) VecB { uint8_t v[V]; };
+  const int64_t groups = HW / V;
+  for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (int64_t)gridDim.x * 256) {
+    const int64_t i0 = g * V;
+    bool all[V], any[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) { all[e] = true; any[e] = false; }
+    for (int c = 0; c < C; ++c) {
+      const float nd = nodata[c];
+      const VecT s = *(const VecT*)(raster + (int64_t)c * HW + i0);
+#pragma unroll
+      for (int e = 0; e < V; ++e) {
+        const float v = (float)s.v[e];
+        const bool is = nd != nd ? v != v : v == nd;
+        all[e] = all[e] && is;
+        any[e] = any[e] || is;
+      }
+    }
+    VecB o;
+#pragma unroll
+    for (int e = 0; e < V; ++e) o.v[e] = (rule ? any[e] : all[e]) ? 0 : 1;
+    *(VecB*)(valid + i0) = o;
+  }
+}
+
+// One workgroup per tile: its 256 threads stride over the part of the tile inside the raster (rows y0..y1, columns x0..x1, the
+// same in every thread), a wave adds its 64 partial counts by shuffles, the four waves meet in LDS and thread 0 stores the count.
+__global__ __launch_bounds__(256) void scene_tile_valid_kernel(const uint8_t* __restrict__ valid, int H, int W,
+                                                               const int32_t* __restrict__ origins, int th, int tw,
+                                                               int32_t* __restrict__ counts) {
+  __shared__ int s_part[4];
+  const int t = blockIdx.x, tid = threadIdx.x;
+  const int64_t oy = origins[2 * t], ox = origins[2 * t + 1];
+  const int64_t y0 = oy < 0 ? 0 : oy, x0 = ox < 0 ? 0 : ox;
+  const int64_t y1 = oy + th < H ? oy + th : H, x1 = ox + tw < W ? ox + tw : W;
+  int n = 0;
+  if (y0 < y1 && x0 < x1) {
+    const int cols = (int)(x1 - x0), total = (int)(y1 - y0) * cols;      // at most th * tw, which the entry point holds below 2^31
+    for (int i = tid; i < total; i += 256) n += valid[(y0 + i / cols) * W + x0 + i % cols] != 0;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  if ((tid & 63) == 0) s_part[tid >> 6] = n;
+  __syncthreads();
+  if (tid == 0) counts[t] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
 }
 
 template <int K, typename Src>
@@ -355,11 +437,12 @@ bool clip_box(int H, int W, int& y0, int& y1, int& x0, int& x1) {
   return y0 < y1 && x0 < x1;
 }
 
-// gdl_scene_cut and gdl_scene_cut_d4 (xforms != nullptr): one body, `fn` is the entry point's name in the messages
-int scene_cut(const char* fn, const void* raster, int kind, int C, int H, int W, const int32_t* origins, const int32_t* xforms, bool d4,
-              int B, int th, int tw, int fill, float* tiles, int image_min, int image_max, double norm_min, double norm_max,
-              const float* mean, const float* stdv, gdl_stream_t stream) {
-  GDL_CHECK_ARG(raster && origins && tiles && mean && stdv && (xforms || !d4), "%s: null pointer", fn);
+// gdl_scene_cut, gdl_scene_cut_d4 (d4: xforms != nullptr) and gdl_scene_cut_valid (masked: valid != nullptr): one body, `fn` is
+// the entry point's name in the messages
+int scene_cut(const char* fn, const void* raster, int kind, int C, int H, int W, const uint8_t* valid, bool masked, const int32_t* origins,
+              const int32_t* xforms, bool d4, int B, int th, int tw, int fill, float* tiles, int image_min, int image_max,
+              double norm_min, double norm_max, const float* mean, const float* stdv, gdl_stream_t stream) {
+  GDL_CHECK_ARG(raster && origins && tiles && mean && stdv && (xforms || !d4) && (valid || !masked), "%s: null pointer", fn);
   GDL_CHECK_ARG(kind >= GDL_RAW_U8 && kind <= GDL_RAW_F32, "%s: bad sample kind %d", fn, kind);
   GDL_CHECK_ARG(C > 0 && H > 0 && W > 0 && B > 0 && th > 0 && tw > 0, "%s: bad sizes", fn);
   GDL_CHECK_ARG(image_max != image_min, "%s: image_max == image_min (%d): the range is empty", fn, image_min);
@@ -367,17 +450,20 @@ int scene_cut(const char* fn, const void* raster, int kind, int C, int H, int W,
   const bool vec = tw % 4 == 0 && (uintptr_t)tiles % 16 == 0;
   const int64_t groups = (int64_t)B * C * th * (tw / (vec ? 4 : 1));
   hipStream_t s = (hipStream_t)stream;
-#define CUT_V(T, V, D4)                                                                                                               \
-  hipLaunchKernelGGL((scene_cut_kernel<T, V, D4>), dim3(grid_for(groups)), dim3(256), 0, s, (const T*)raster, C, H, W, origins, xforms, \
-                     th, tw, (float)fill, tiles, groups, r.imin, r.span, r.d, r.nmin, mean, stdv)
-#define CUT(T)                                                                  \
-  if (d4) { if (vec) CUT_V(T, 4, true); else CUT_V(T, 1, true); }               \
-  else { if (vec) CUT_V(T, 4, false); else CUT_V(T, 1, false); }
+#define CUT_V(T, V, D4, M)                                                                                                               \
+  hipLaunchKernelGGL((scene_cut_kernel<T, V, D4, M>), dim3(grid_for(groups)), dim3(256), 0, s, (const T*)raster, C, H, W, origins, xforms, \
+                     th, tw, (float)fill, tiles, groups, r.imin, r.span, r.d, r.nmin, mean, stdv, valid)
+#define CUT_D(T, D4)                                                                     \
+  if (masked) { if (vec) CUT_V(T, 4, D4, true); else CUT_V(T, 1, D4, true); }            \
+  else { if (vec) CUT_V(T, 4, D4, false); else CUT_V(T, 1, D4, false); }
+#define CUT(T) \
+  if (d4) { CUT_D(T, true) } else { CUT_D(T, false) }
   if (kind == GDL_RAW_U8) { CUT(uint8_t) }
   else if (kind == GDL_RAW_U16) { CUT(uint16_t) }
   else if (kind == GDL_RAW_I16) { CUT(int16_t) }
   else { CUT(float) }
 #undef CUT
+#undef CUT_D
 #undef CUT_V
   GDL_CHECK_LAUNCH(fn);
   return GDL_OK;
@@ -388,14 +474,14 @@ int scene_cut(const char* fn, const void* raster, int kind, int C, int H, int W,
 extern "C" int gdl_scene_cut(const void* raster, int kind, int C, int H, int W, const int32_t* origins, int B, int th, int tw, int fill,
                              float* tiles, int image_min, int image_max, double norm_min, double norm_max, const float* mean,
                              const float* stdv, gdl_stream_t stream) {
-  return scene_cut("gdl_scene_cut", raster, kind, C, H, W, origins, nullptr, false, B, th, tw, fill, tiles, image_min, image_max, norm_min,
+  return scene_cut("gdl_scene_cut", raster, kind, C, H, W, nullptr, false, origins, nullptr, false, B, th, tw, fill, tiles, image_min, image_max, norm_min,
                    norm_max, mean, stdv, stream);
 }
 
 extern "C" int gdl_scene_cut_d4(const void* raster, int kind, int C, int H, int W, const int32_t* origins, const int32_t* xforms, int B,
                                 int th, int tw, int fill, float* tiles, int image_min, int image_max, double norm_min, double norm_max,
                                 const float* mean, const float* stdv, gdl_stream_t stream) {
-  return scene_cut("gdl_scene_cut_d4", raster, kind, C, H, W, origins, xforms, true, B, th, tw, fill, tiles, image_min, image_max,
+  return scene_cut("gdl_scene_cut_d4", raster, kind, C, H, W, nullptr, false, origins, xforms, true, B, th, tw, fill, tiles, image_min, image_max,
                    norm_min, norm_max, mean, stdv, stream);
 }
 
@@ -454,8 +540,61 @@ extern "C" int gdl_scene_finish(const float* canvas, int K, int64_t HW, float th
   GDL_CHECK_ARG(K >= 1 && K <= 255 && HW > 0, "gdl_scene_finish: bad sizes (1..255 classes, got %d)", K);
   const bool vec = HW % 4 == 0 && (uintptr_t)canvas % 16 == 0 && (uintptr_t)probs % 16 == 0 && (uintptr_t)mask % 4 == 0;
   hipStream_t s = (hipStream_t)stream;
-  if (vec) hipLaunchKernelGGL(scene_finish_kernel<4>, dim3(grid_for(HW / 4)), dim3(256), 0, s, canvas, K, HW, threshold, mask, probs);
-  else hipLaunchKernelGGL(scene_finish_kernel<1>, dim3(grid_for(HW)), dim3(256), 0, s, canvas, K, HW, threshold, mask, probs);
+  if (vec) hipLaunchKernelGGL((scene_finish_kernel<4, false>), dim3(grid_for(HW / 4)), dim3(256), 0, s, canvas, K, HW, threshold, mask, probs, nullptr, 0);
+  else hipLaunchKernelGGL((scene_finish_kernel<1, false>), dim3(grid_for(HW)), dim3(256), 0, s, canvas, K, HW, threshold, mask, probs, nullptr, 0);
   GDL_CHECK_LAUNCH("gdl_scene_finish");
+  return GDL_OK;
+}
+
+// ------------------------------------------------------------------ nodata (include/gdlhip_scene_nodata.h)
+extern "C" int gdl_scene_valid(const void* raster, int kind, int C, int H, int W, const float* nodata, int rule, uint8_t* valid,
+                               gdl_stream_t stream) {
+  GDL_CHECK_ARG(raster && nodata && valid, "gdl_scene_valid: null pointer");
+  GDL_CHECK_ARG(kind >= GDL_RAW_U8 && kind <= GDL_RAW_F32, "gdl_scene_valid: bad sample kind %d", kind);
+  GDL_CHECK_ARG(C > 0 && H > 0 && W > 0, "gdl_scene_valid: bad sizes");
+  GDL_CHECK_ARG(rule == 0 || rule == 1, "gdl_scene_valid: rule %d is neither 0 (all bands) nor 1 (any band)", rule);
+  const int64_t HW = (int64_t)H * W;
+  const size_t esz = kind == GDL_RAW_U8 ? 1 : kind == GDL_RAW_F32 ? 4 : 2;
+  const bool vec = W % 4 == 0 && (uintptr_t)raster % (4 * esz) == 0 && (uintptr_t)valid % 4 == 0;
+  hipStream_t s = (hipStream_t)stream;
+#define VALID(T)                                                                                                                          \
+  if (vec) hipLaunchKernelGGL((scene_valid_kernel<T, 4>), dim3(grid_for(HW / 4)), dim3(256), 0, s, (const T*)raster, C, HW, nodata, rule, valid); \
+  else hipLaunchKernelGGL((scene_valid_kernel<T, 1>), dim3(grid_for(HW)), dim3(256), 0, s, (const T*)raster, C, HW, nodata, rule, valid);
+  if (kind == GDL_RAW_U8) { VALID(uint8_t) }
+  else if (kind == GDL_RAW_U16) { VALID(uint16_t) }
+  else if (kind == GDL_RAW_I16) { VALID(int16_t) }
+  else { VALID(float) }
+#undef VALID
+  GDL_CHECK_LAUNCH("gdl_scene_valid");
+  return GDL_OK;
+}
+
+extern "C" int gdl_scene_tile_valid(const uint8_t* valid, int H, int W, const int32_t* origins, int T, int th, int tw, int32_t* counts,
+                                    gdl_stream_t stream) {
+  GDL_CHECK_ARG(valid && origins && counts, "gdl_scene_tile_valid: null pointer");
+  GDL_CHECK_ARG(H > 0 && W > 0 && T > 0 && th > 0 && tw > 0, "gdl_scene_tile_valid: bad sizes");
+  GDL_CHECK_ARG((int64_t)th * tw <= INT32_MAX, "gdl_scene_tile_valid: a tile of %d x %d pixels does not count in an int32", th, tw);
+  hipLaunchKernelGGL(scene_tile_valid_kernel, dim3((unsigned)T), dim3(256), 0, (hipStream_t)stream, valid, H, W, origins, th, tw, counts);
+  GDL_CHECK_LAUNCH("gdl_scene_tile_valid");
+  return GDL_OK;
+}
+
+extern "C" int gdl_scene_cut_valid(const void* raster, int kind, int C, int H, int W, const uint8_t* valid, const int32_t* origins,
+                                   const int32_t* xforms, int B, int th, int tw, int fill, float* tiles, int image_min, int image_max,
+                                   double norm_min, double norm_max, const float* mean, const float* stdv, gdl_stream_t stream) {
+  return scene_cut("gdl_scene_cut_valid", raster, kind, C, H, W, valid, true, origins, xforms, xforms != nullptr, B, th, tw, fill, tiles,
+                   image_min, image_max, norm_min, norm_max, mean, stdv, stream);
+}
+
+extern "C" int gdl_scene_finish_valid(const float* canvas, int K, int64_t HW, float threshold, const uint8_t* valid, int nodata_label,
+                                      uint8_t* mask, float* probs, gdl_stream_t stream) {
+  GDL_CHECK_ARG(canvas && mask, "gdl_scene_finish_valid: null pointer");
+  GDL_CHECK_ARG(K >= 1 && K <= 255 && HW > 0, "gdl_scene_finish_valid: bad sizes (1..255 classes, got %d)", K);
+  GDL_CHECK_ARG(nodata_label >= 0 && nodata_label <= 255, "gdl_scene_finish_valid: nodata_label %d is not in 0..255", nodata_label);
+  const bool vec = HW % 4 == 0 && (uintptr_t)canvas % 16 == 0 && (uintptr_t)probs % 16 == 0 && (uintptr_t)mask % 4 == 0 && (uintptr_t)valid % 4 == 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (vec) hipLaunchKernelGGL((scene_finish_kernel<4, true>), dim3(grid_for(HW / 4)), dim3(256), 0, s, canvas, K, HW, threshold, mask, probs, valid, nodata_label);
+  else hipLaunchKernelGGL((scene_finish_kernel<1, true>), dim3(grid_for(HW)), dim3(256), 0, s, canvas, K, HW, threshold, mask, probs, valid, nodata_label);
+  GDL_CHECK_LAUNCH("gdl_scene_finish_valid");
   return GDL_OK;
 }

@@ -1930,23 +1930,32 @@ def _scene_origins(op: str, origins: Tensor) -> int:
     return int(origins.shape[0])
 
 
+def _scene_cut_check(op: str, raster: Tensor, origins: Tensor, xforms: Tensor | None, tile: tuple[int, int], mean: Tensor, std: Tensor,
+                     image_min: int, image_max: int, fill: int, check_codes: bool = True) -> tuple[int, int, int]:
+    """The argument checks of the three cuts, in one order; (B, th, tw)."""
+    if raster.dtype not in _RAW_KIND or not raster.is_contiguous() or raster.dim() != 3:
+        raise ValueError(f"{op}: contiguous [C, H, W] uint8/uint16/int16/float32 raster expected, got {raster.dtype} {tuple(raster.shape)}")
+    if int(image_max) == int(image_min):
+        raise ValueError(f"{op}: image_max == image_min ({int(image_min)}): the range is empty")
+    _need_cuda(raster, origins, mean, std)
+    B = _scene_origins(op, origins)
+    th, tw = int(tile[0]), int(tile[1])
+    if th < 1 or tw < 1:
+        raise ValueError(f"{op}: bad tile {th} x {tw}")
+    if xforms is not None:
+        _scene_xforms(op, xforms, B, (th, tw), check_codes)
+    lo, hi = _RAW_LIMITS.get(raster.dtype, (-2 ** 31, 2 ** 31 - 1))
+    if not lo <= int(fill) <= hi:
+        raise ValueError(f"{op}: fill {fill} is not a value of {raster.dtype}")
+    return B, th, tw
+
+
 def scene_cut(raster: Tensor, origins: Tensor, tile: tuple[int, int], mean: Tensor, std: Tensor, image_min: int = 0,
               image_max: int = 255, norm_min: float = 0.0, norm_max: float = 1.0, fill: int = 0) -> Tensor:
     """Normalised NCHW f32 tiles [B, C, th, tw] cut out of a raw raster [C, H, W] (uint8 / uint16 / int16 / f32) at the origins
     int32 [B, 2] = (y0, x0), which may be negative or reach past the raster: a position outside it takes the raw value ``fill``.
     The values are those of ``normalize_range`` on the sliced (and padded) tile, bit for bit (gdl_scene_cut)."""
-    if raster.dtype not in _RAW_KIND or not raster.is_contiguous() or raster.dim() != 3:
-        raise ValueError(f"scene_cut: contiguous [C, H, W] uint8/uint16/int16/float32 raster expected, got {raster.dtype} {tuple(raster.shape)}")
-    if int(image_max) == int(image_min):
-        raise ValueError(f"scene_cut: image_max == image_min ({int(image_min)}): the range is empty")
-    _need_cuda(raster, origins, mean, std)
-    B = _scene_origins("scene_cut", origins)
-    th, tw = int(tile[0]), int(tile[1])
-    if th < 1 or tw < 1:
-        raise ValueError(f"scene_cut: bad tile {th} x {tw}")
-    lo, hi = _RAW_LIMITS.get(raster.dtype, (-2 ** 31, 2 ** 31 - 1))
-    if not lo <= int(fill) <= hi:
-        raise ValueError(f"scene_cut: fill {fill} is not a value of {raster.dtype}")
+    B, th, tw = _scene_cut_check("scene_cut", raster, origins, None, tile, mean, std, image_min, image_max, fill)
     Cc, H, W = raster.shape
     out = torch.empty((B, Cc, th, tw), device=raster.device, dtype=torch.float32)
     _lib.checked().gdl_scene_cut(_p(raster), _RAW_KIND[raster.dtype], Cc, H, W, _p(origins), B, th, tw, int(fill), _p(out),
@@ -2024,19 +2033,9 @@ def scene_cut_d4(raster: Tensor, origins: Tensor, xforms: Tensor, tile: tuple[in
                  image_max: int = 255, norm_min: float = 0.0, norm_max: float = 1.0, fill: int = 0, *, check_codes: bool = True) -> Tensor:
     """``scene_cut`` with a transform per tile: tile ``b`` is ``gdlhip.scene.d4_apply`` of the tile ``scene_cut`` cuts at
     ``origins[b]``, with the code ``xforms[b]`` (int32 [B] on the device), bit for bit (gdl_scene_cut_d4)."""
-    if raster.dtype not in _RAW_KIND or not raster.is_contiguous() or raster.dim() != 3:
-        raise ValueError(f"scene_cut_d4: contiguous [C, H, W] uint8/uint16/int16/float32 raster expected, got {raster.dtype} {tuple(raster.shape)}")
-    if int(image_max) == int(image_min):
-        raise ValueError(f"scene_cut_d4: image_max == image_min ({int(image_min)}): the range is empty")
-    _need_cuda(raster, origins, mean, std)
-    B = _scene_origins("scene_cut_d4", origins)
-    th, tw = int(tile[0]), int(tile[1])
-    if th < 1 or tw < 1:
-        raise ValueError(f"scene_cut_d4: bad tile {th} x {tw}")
-    _scene_xforms("scene_cut_d4", xforms, B, (th, tw), check_codes)
-    lo, hi = _RAW_LIMITS.get(raster.dtype, (-2 ** 31, 2 ** 31 - 1))
-    if not lo <= int(fill) <= hi:
-        raise ValueError(f"scene_cut_d4: fill {fill} is not a value of {raster.dtype}")
+    if xforms is None:
+        raise ValueError("scene_cut_d4: xforms must be a contiguous int32 [B] tensor of transform codes, got None")
+    B, th, tw = _scene_cut_check("scene_cut_d4", raster, origins, xforms, tile, mean, std, image_min, image_max, fill, check_codes)
     Cc, H, W = raster.shape
     out = torch.empty((B, Cc, th, tw), device=raster.device, dtype=torch.float32)
     _lib.checked().gdl_scene_cut_d4(_p(raster), _RAW_KIND[raster.dtype], Cc, H, W, _p(origins), _p(xforms), B, th, tw, int(fill), _p(out),
@@ -2090,6 +2089,116 @@ def scene_finish(canvas: Tensor, threshold: float = 0.5, return_probs: bool = Fa
     mask = torch.empty((H, W), device=canvas.device, dtype=torch.uint8)
     probs = torch.empty((K, H, W), device=canvas.device, dtype=torch.float32) if return_probs else None
     _lib.checked().gdl_scene_finish(_p(canvas), K, H * W, float(threshold), _p(mask), _p(probs), _stream())
+    return mask, probs
+
+
+# nodata (include/gdlhip_scene_nodata.h): a validity plane of the raster, its count per tile, and the cut and the labelling with it
+NODATA_RULES = {"all": 0, "any": 1}
+
+
+def scene_nodata_values(nodata, dtype: torch.dtype, channels: int, who: str = "scene_valid") -> Tensor:
+    """The nodata value of every band as a host f32 [channels] vector, from one number or one per band.  A value that no sample of
+    ``dtype`` can hold (a fraction, a NaN or a value outside the range of an integer raster) is a ValueError: it would never match,
+    which is a mistake of the caller's and not a scene without nodata.  For an f32 raster every value goes, NaN included (a NaN
+    sample is then nodata); it is compared after rounding to f32, as the samples were."""
+    if isinstance(nodata, Tensor):
+        nodata = nodata.detach().cpu().tolist()
+    values = list(nodata) if isinstance(nodata, (list, tuple)) else [nodata]
+    if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in values) or not values:
+        raise ValueError(f"{who}: nodata must be one number or one per band, got {nodata!r}")
+    if len(values) == 1:
+        values = values * int(channels)
+    if len(values) != int(channels):
+        raise ValueError(f"{who}: {len(values)} nodata values for {int(channels)} bands")
+    if dtype in _RAW_LIMITS:
+        lo, hi = _RAW_LIMITS[dtype]
+        for v in values:
+            if v != v:
+                raise ValueError(f"{who}: a NaN nodata needs a float32 raster, not {dtype}")
+            if abs(v) == float("inf") or v != int(v):
+                raise ValueError(f"{who}: nodata {v!r} is not an integer, so no sample of {dtype} equals it")
+            if not lo <= int(v) <= hi:
+                raise ValueError(f"{who}: nodata {v!r} is outside {lo}..{hi}, so no sample of {dtype} equals it")
+    elif dtype != torch.float32:
+        raise ValueError(f"{who}: uint8/uint16/int16/float32 raster expected, got {dtype}")
+    return torch.tensor([float(v) for v in values], dtype=torch.float64).float()
+
+
+def _scene_plane(op: str, valid: Tensor, H: int, W: int) -> Tensor:
+    """The plane as the kernels read it: uint8 (a bool plane is the same bytes) [H, W], contiguous, on the device."""
+    _need_cuda(valid)
+    if valid.dtype not in (torch.uint8, torch.bool) or tuple(valid.shape) != (H, W) or not valid.is_contiguous():
+        raise ValueError(f"{op}: valid must be a contiguous uint8 / bool [H, W] = [{H}, {W}] plane, got {valid.dtype} {tuple(valid.shape)}")
+    return valid.view(torch.uint8)
+
+
+def scene_valid(raster: Tensor, nodata, rule: str = "all") -> Tensor:
+    """uint8 [H, W], 1 where the raw raster [C, H, W] holds data: a sample is nodata when it equals its band's ``nodata`` (one
+    number or one per band; NaN for an f32 raster: when it is NaN), and a pixel is invalid when every band (``rule="all"``, the
+    dataset-mask convention) or at least one band (``"any"``) is nodata (gdl_scene_valid)."""
+    if raster.dtype not in _RAW_KIND or not raster.is_contiguous() or raster.dim() != 3:
+        raise ValueError(f"scene_valid: contiguous [C, H, W] uint8/uint16/int16/float32 raster expected, got {raster.dtype} {tuple(raster.shape)}")
+    if rule not in NODATA_RULES:
+        raise ValueError(f"scene_valid: unknown rule {rule!r} ('all' or 'any')")
+    Cc, H, W = raster.shape
+    values = scene_nodata_values(nodata, raster.dtype, Cc)
+    _need_cuda(raster)
+    if H * W < 1:
+        raise ValueError(f"scene_valid: empty raster {tuple(raster.shape)}")
+    valid = torch.empty((H, W), device=raster.device, dtype=torch.uint8)
+    _lib.checked().gdl_scene_valid(_p(raster), _RAW_KIND[raster.dtype], Cc, H, W, _p(values.to(raster.device)), NODATA_RULES[rule],
+                                   _p(valid), _stream())
+    return valid
+
+
+def scene_tile_valid(valid: Tensor, origins: Tensor, tile: tuple[int, int]) -> Tensor:
+    """int32 [T] on the device: the number of valid pixels of each tile at ``origins`` (int32 [T, 2]) that lie inside the plane
+    ``valid`` uint8 / bool [H, W]; origins may be negative or reach past it (gdl_scene_tile_valid)."""
+    if valid.dim() != 2:
+        raise ValueError(f"scene_tile_valid: valid must be a [H, W] plane, got {tuple(valid.shape)}")
+    H, W = int(valid.shape[0]), int(valid.shape[1])
+    plane = _scene_plane("scene_tile_valid", valid, H, W)
+    _need_cuda(origins)
+    T = _scene_origins("scene_tile_valid", origins)
+    th, tw = int(tile[0]), int(tile[1])
+    if th < 1 or tw < 1 or H * W < 1:
+        raise ValueError(f"scene_tile_valid: bad sizes: tile {th} x {tw}, plane {H} x {W}")
+    counts = torch.empty((T,), device=valid.device, dtype=torch.int32)
+    _lib.checked().gdl_scene_tile_valid(_p(plane), H, W, _p(origins), T, th, tw, _p(counts), _stream())
+    return counts
+
+
+def scene_cut_valid(raster: Tensor, valid: Tensor, origins: Tensor, xforms: Tensor | None, tile: tuple[int, int], mean: Tensor,
+                    std: Tensor, image_min: int = 0, image_max: int = 255, norm_min: float = 0.0, norm_max: float = 1.0, fill: int = 0,
+                    *, check_codes: bool = True) -> Tensor:
+    """``scene_cut`` (``xforms`` None) or ``scene_cut_d4`` in which a pixel whose ``valid`` (uint8 / bool [H, W]) is 0 takes the raw
+    value ``fill``, like a position outside the raster.  With a plane of ones: their tiles, bit for bit (gdl_scene_cut_valid)."""
+    B, th, tw = _scene_cut_check("scene_cut_valid", raster, origins, xforms, tile, mean, std, image_min, image_max, fill, check_codes)
+    Cc, H, W = raster.shape
+    plane = _scene_plane("scene_cut_valid", valid, H, W)
+    out = torch.empty((B, Cc, th, tw), device=raster.device, dtype=torch.float32)
+    _lib.checked().gdl_scene_cut_valid(_p(raster), _RAW_KIND[raster.dtype], Cc, H, W, _p(plane), _p(origins), _p(xforms), B, th, tw,
+                                       int(fill), _p(out), int(image_min), int(image_max), float(norm_min), float(norm_max),
+                                       _p(_f32vec(mean, Cc, "mean")), _p(_f32vec(std, Cc, "std")), _stream())
+    return out
+
+
+def scene_finish_valid(canvas: Tensor, valid: Tensor | None, nodata_label: int = 255, threshold: float = 0.5,
+                       return_probs: bool = False) -> tuple[Tensor, Tensor | None]:
+    """``scene_finish`` in which a pixel whose ``valid`` (uint8 / bool [H, W], or None) is 0 or that no tile covered gets the mask
+    ``nodata_label`` (0..255) and probabilities 0; every other pixel gets the bits of ``scene_finish`` (gdl_scene_finish_valid)."""
+    _need_cuda(canvas)
+    if canvas.dtype != torch.float32 or canvas.dim() != 3 or not canvas.is_contiguous() or not 2 <= canvas.shape[0] <= 17:
+        raise ValueError(f"scene_finish_valid: contiguous f32 canvas [K+1, H, W] with 1..16 classes expected, got {canvas.dtype} {tuple(canvas.shape)}")
+    if isinstance(nodata_label, bool) or not isinstance(nodata_label, int) or not 0 <= nodata_label <= 255:
+        raise ValueError(f"scene_finish_valid: nodata_label must be an int in 0..255, got {nodata_label!r}")
+    K, H, W = canvas.shape[0] - 1, int(canvas.shape[1]), int(canvas.shape[2])
+    if H * W < 1:
+        raise ValueError(f"scene_finish_valid: empty canvas {tuple(canvas.shape)}")
+    plane = None if valid is None else _scene_plane("scene_finish_valid", valid, H, W)
+    mask = torch.empty((H, W), device=canvas.device, dtype=torch.uint8)
+    probs = torch.empty((K, H, W), device=canvas.device, dtype=torch.float32) if return_probs else None
+    _lib.checked().gdl_scene_finish_valid(_p(canvas), K, H * W, float(threshold), _p(plane), nodata_label, _p(mask), _p(probs), _stream())
     return mask, probs
 
 

@@ -11,6 +11,13 @@ transformed tile and the blend reads the model's answer back through the inverse
 ``scene_blend_d4`` / ``scene_blend_lowres_d4``): the transform lives in the index arithmetic of the two gathers, nothing is
 permuted in memory, and the canvas simply collects G times the weight.
 
+Nodata (``nodata=`` and / or ``valid=``): a validity plane of the raster (``ops.scene_valid`` from one nodata value per band, or
+the caller's own mask, or both ANDed) decides three things.  The tiles that hold fewer than ``min_valid`` valid pixels are dropped
+from the plan before the model sees them (``ops.scene_tile_valid``: one launch and one small copy for the whole plan); an invalid
+pixel inside a kept tile reaches the model as the raw value ``fill``, like a position outside the raster (``ops.scene_cut_valid``);
+and the mask says ``nodata_label`` where the plane is 0 or no kept tile covers the pixel (``ops.scene_finish_valid``).  The blends
+are untouched, and without ``nodata=`` and ``valid=`` so is everything else.
+
 Determinism: the canvas is accumulated by a gather in tile order without atomics, so the mask and the probabilities do not
 depend on ``batch_size`` and are the same bits from run to run.  The reference has no counterpart (its inference stops at the
 tile, tools/script_model.py)."""
@@ -46,11 +53,17 @@ class SceneInference:
     ``tta``: ``None`` (no augmentation: the calls and the bits of before), ``"flips"`` (identity and the three flips), ``"d4"`` (all
     eight symmetries; a square tile) or a sequence of distinct codes in 0..7 (``gdlhip.scene``: 1 = flip x, 2 = flip y, 4 =
     transpose); the probabilities of a tile's transforms are averaged with the window.  ``batch_size`` then counts
-    (tile, transform) pairs."""
+    (tile, transform) pairs.
+    ``nodata``: ``None`` (every sample is data), one number or one per band; a NaN means "a NaN sample" (float32 rasters).
+    ``nodata_rule``: ``"all"`` (a pixel is invalid when every band is nodata) or ``"any"``.  ``nodata_label``: the mask value, 0..255,
+    of an invalid or uncovered pixel.  ``min_valid``: a tile with fewer valid pixels than this is not fed to the model.  They act
+    only where ``nodata`` is set or ``predict`` / ``canvas`` / ``tile_plan`` get a ``valid=`` plane (uint8 / bool [H, W], nonzero =
+    valid: an alpha band, a mask from elsewhere), which is ANDed with the plane of ``nodata``."""
 
     def __init__(self, script_model: ScriptModel, tile: tuple[int, int] = (512, 512), overlap: float = 0.5,
                  stride: tuple[int, int] | None = None, window: str = "hann", batch_size: int = 64, threshold: float = 0.5,
-                 fill: int = 0, *, lowres: bool = True, tta=None) -> None:
+                 fill: int = 0, *, lowres: bool = True, tta=None, nodata=None, nodata_rule: str = "all", nodata_label: int = 255,
+                 min_valid: int = 1) -> None:
         if not isinstance(script_model, ScriptModel):
             raise TypeError(f"SceneInference: a ScriptModel is expected, got {type(script_model).__name__}")
         self.model = script_model
@@ -66,6 +79,15 @@ class SceneInference:
             raise ValueError(f"SceneInference: batch_size {batch_size}")
         self.batch_size, self.threshold, self.fill, self.lowres = int(batch_size), float(threshold), int(fill), bool(lowres)
         self.tta = None if tta is None else gscene.tta_codes(tta, self.tile)      # ValueError for what is no set of codes
+        if nodata_rule not in ops.NODATA_RULES:
+            raise ValueError(f"SceneInference: unknown nodata_rule {nodata_rule!r} ('all' or 'any')")
+        if isinstance(nodata_label, bool) or not isinstance(nodata_label, int) or not 0 <= nodata_label <= 255:
+            raise ValueError(f"SceneInference: nodata_label must be an int in 0..255, got {nodata_label!r}")
+        if isinstance(min_valid, bool) or not isinstance(min_valid, int) or min_valid < 1:
+            raise ValueError(f"SceneInference: min_valid must be a pixel count of at least 1, got {min_valid!r}")
+        if nodata is not None:      # numbers, one or one per band; whether the raster's type can hold them is checked with the raster
+            ops.scene_nodata_values(nodata, torch.float32, script_model.mean.numel(), "SceneInference")
+        self.nodata, self.nodata_rule, self.nodata_label, self.min_valid = nodata, nodata_rule, nodata_label, min_valid
         dev = script_model.device
         self.wy, self.wx = gscene.window(self.tile[0], window).to(dev), gscene.window(self.tile[1], window).to(dev)
 
@@ -85,28 +107,62 @@ class SceneInference:
         else:
             ops.scene_blend_d4(gnn.predict_probs(out), origins, xforms, self.wy, self.wx, canvas, box, check_codes=False)
 
-    def canvas(self, raster: torch.Tensor) -> torch.Tensor:
-        """The finished canvas [K+1, H, W] f32 of ``raster``: planes 0..K-1 the weighted probability sums, plane K the weights."""
+    def _upload(self, raster: torch.Tensor, valid: torch.Tensor | None) -> tuple[torch.Tensor, torch.Tensor | None]:
+        """The raster on the device and its validity plane (uint8 [H, W] on the device), None where neither ``nodata`` nor
+        ``valid`` is given.  Every argument is checked before anything is uploaded."""
         m = self.model
         if raster.dim() != 3 or raster.dtype not in _RASTER_DTYPES:
             raise ValueError(f"SceneInference: a [C, H, W] uint8/uint16/int16/float32 raster is expected, got {raster.dtype} {tuple(raster.shape)}")
         if raster.shape[0] != m.mean.numel():
             raise ValueError(f"SceneInference: the raster has {raster.shape[0]} channels, the model's mean / std have {m.mean.numel()}")
-        raster = raster.to(m.device).contiguous()      # a host raster is uploaded once
         _, H, W = raster.shape
+        if self.nodata is not None:
+            ops.scene_nodata_values(self.nodata, raster.dtype, raster.shape[0], "SceneInference")
+        if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or tuple(valid.shape) != (H, W)):
+            raise ValueError(f"SceneInference: valid must be a uint8 / bool [H, W] = [{H}, {W}] plane, got {valid.dtype} {tuple(valid.shape)}")
+        raster = raster.to(m.device).contiguous()      # a host raster is uploaded once
+        plane = None if valid is None else valid.to(m.device).contiguous()
+        if self.nodata is not None:
+            own = ops.scene_valid(raster, self.nodata, self.nodata_rule)
+            plane = own if plane is None else ((own != 0) & (plane != 0)).view(torch.uint8)
+        return raster, plane
+
+    def _plan(self, H: int, W: int, plane: torch.Tensor | None) -> tuple[torch.Tensor, torch.Tensor]:
+        """(the origins kept, the valid pixels of every tile of the full plan), both int32 on the host."""
         plan = gscene.plan_tiles(H, W, self.tile, self.stride)
+        if plane is None:      # every pixel is data: the part of a tile inside the raster, and nothing is dropped
+            area = min(self.tile[0], H) * min(self.tile[1], W)
+            return plan, torch.full((plan.shape[0],), area, dtype=torch.int32)
+        counts = ops.scene_tile_valid(plane, plan.to(plane.device), self.tile).cpu()
+        return plan[counts >= self.min_valid].contiguous(), counts
+
+    def tile_plan(self, raster: torch.Tensor, valid: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+        """What ``predict`` feeds of ``raster``: (kept_origins int32 [T', 2], counts int32 [T]), both on the host -- the origins
+        of ``gdlhip.scene.plan_tiles`` whose tile holds at least ``min_valid`` valid pixels, in plan order, and the number of
+        valid pixels of every tile of the full plan.  The model is not run."""
+        raster, plane = self._upload(raster, valid)
+        return self._plan(int(raster.shape[1]), int(raster.shape[2]), plane)
+
+    def _canvas(self, raster: torch.Tensor, plane: torch.Tensor | None) -> torch.Tensor:
+        m = self.model
+        _, H, W = raster.shape
+        plan, _ = self._plan(H, W, plane)
+        K = int(m.num_classes)
+        canvas = torch.zeros((K + 1, H, W), device=m.device, dtype=torch.float32)
+        if plan.shape[0] == 0:      # no tile holds data: the model is not called
+            return canvas
         codes_dev = None
         if self.tta is not None:
             plan, codes = gscene.plan_tta(plan, self.tta)      # (tile, transform) pairs, tile-major: the accumulation order
             codes_dev = codes.to(m.device)
         plan_dev = plan.to(m.device)
-        K = int(m.num_classes)
-        canvas = torch.zeros((K + 1, H, W), device=m.device, dtype=torch.float32)
         norm = (m.mean, m.std, m.image_min, m.image_max, m.norm_min, m.norm_max, self.fill)
         for i in range(0, plan.shape[0], self.batch_size):
             origins = plan_dev[i:i + self.batch_size]
             xforms = None if codes_dev is None else codes_dev[i:i + self.batch_size]
-            if xforms is None:
+            if plane is not None:
+                tiles = ops.scene_cut_valid(raster, plane, origins, xforms, self.tile, *norm, check_codes=False)
+            elif xforms is None:
                 tiles = ops.scene_cut(raster, origins, self.tile, *norm)
             else:
                 tiles = ops.scene_cut_d4(raster, origins, xforms, self.tile, *norm, check_codes=False)
@@ -115,6 +171,16 @@ class SceneInference:
                 self._blend(out, origins, canvas, gscene.bounding_box(plan[i:i + self.batch_size], self.tile), xforms)
         return canvas
 
-    def predict(self, raster: torch.Tensor, return_probs: bool = False) -> SceneResult:
-        mask, probs = ops.scene_finish(self.canvas(raster), self.threshold, return_probs)
+    def canvas(self, raster: torch.Tensor, valid: torch.Tensor | None = None) -> torch.Tensor:
+        """The finished canvas [K+1, H, W] f32 of ``raster``: planes 0..K-1 the weighted probability sums, plane K the weights
+        (0 where no tile that was fed covers the pixel)."""
+        return self._canvas(*self._upload(raster, valid))
+
+    def predict(self, raster: torch.Tensor, return_probs: bool = False, valid: torch.Tensor | None = None) -> SceneResult:
+        raster, plane = self._upload(raster, valid)
+        canvas = self._canvas(raster, plane)
+        if plane is None:
+            mask, probs = ops.scene_finish(canvas, self.threshold, return_probs)
+        else:
+            mask, probs = ops.scene_finish_valid(canvas, plane, self.nodata_label, self.threshold, return_probs)
         return SceneResult(mask, probs)

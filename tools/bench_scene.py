@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""Whole-scene inference (tools/scene_inference.py, include/gdlhip_scene.h, include/gdlhip_scene_tta.h), three measurements in one
-process.
+"""Whole-scene inference (tools/scene_inference.py, include/gdlhip_scene.h, include/gdlhip_scene_tta.h,
+include/gdlhip_scene_nodata.h), four measurements in one process.
 
 1. The tail of one batch of 64 tiles of 512^2 at stride 256 (an 8 x 8 grid over a 2304^2 uint8 scene), K = 5, the model excluded:
    its head map [64, 128, 128, 5] is drawn once.  ms per batch from HIP events around ``--inner`` repetitions, the variants
@@ -20,7 +20,11 @@ process.
                                    scene_finish.
    (b) must equal (c) to the bit and (a) agree with it before anything is timed.
 2. SceneInference on a synthetic 4096^2 scene (15 x 15 = 225 tiles) with the DOFA-base model in bf16, as tiles per second of the
-   whole call, next to ScriptModel's tiles per second on the same tiles (batches of host-sliced tiles, probabilities written)."""
+   whole call, next to ScriptModel's tiles per second on the same tiles (batches of host-sliced tiles, probabilities written).
+3. The same scene and model with a nodata border: the samples outside a centred square are 0 in every band, the border taking
+   ``--nodata-share`` of the pixels.  Seconds per scene of ``SceneInference.predict`` without ``nodata=`` (every tile is fed) and
+   with ``nodata=0`` (scene_valid, scene_tile_valid, the tiles without data dropped, scene_cut_valid, scene_finish_valid), the two
+   alternating, with the tiles kept of the total; the masks are compared on the valid pixels first."""
 import argparse
 import sys
 import time
@@ -44,6 +48,7 @@ ap.add_argument("--scene", type=int, default=4096, help="side of the whole scene
 ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--scene-repeats", type=int, default=3)
 ap.add_argument("--no-tta", action="store_true", help="skip part 1b")
+ap.add_argument("--nodata-share", type=float, default=0.4, help="share of the scene of part 3 that is a nodata border (0 = skip part 3)")
 args = ap.parse_args()
 
 K, T, S = args.classes, args.tile, args.stride
@@ -246,3 +251,33 @@ if args.scene:
         rates.sort()
         print(f"scene {args.scene}^2, {len(tiles)} tiles, batch {args.batch}, bf16 DOFA-base: {name}: median {rates[len(rates) // 2]:7.1f} tiles/s  "
               f"(min {rates[0]:7.1f}, max {rates[-1]:7.1f}; {args.scene_repeats} runs)")
+
+    # -------------------------------------------------------------- 3. the same scene inside a nodata border
+    if args.nodata_share > 0:
+        n = args.scene
+        inner = round(n * (1.0 - args.nodata_share) ** 0.5)      # the side of the centred square that holds data
+        lo = (n - inner) // 2
+        bordered = torch.zeros_like(scene)
+        bordered[:, lo:lo + inner, lo:lo + inner] = scene[:, lo:lo + inner, lo:lo + inner].clamp(min=1)
+        share = 1.0 - inner * inner / (n * n)
+        si_nd = SceneInference(sm, tile=(T, T), stride=(S, S), batch_size=args.batch, nodata=0)
+        kept, counts = si_nd.tile_plan(bordered)
+        data = (bordered != 0).any(0).cuda()
+        every, skipping = si.predict(bordered).mask, si_nd.predict(bordered).mask
+        assert torch.equal(every[data], skipping[data]) and (skipping[~data] == 255).all(), "nodata= changes a valid pixel"
+        variants = {"without nodata= (every tile fed)": lambda: si.predict(bordered).mask, "with nodata=0 (empty tiles dropped)": lambda: si_nd.predict(bordered).mask}
+        secs = {k: [] for k in variants}
+        for _ in range(args.scene_repeats):      # both are warm: the comparison above ran them
+            for name, fn in variants.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                secs[name].append(time.perf_counter() - t0)
+        print(f"scene {n}^2 with a nodata border of {share:.1%} of the pixels (data in the centred {inner}^2), batch {args.batch}, bf16 DOFA-base: "
+              f"{kept.shape[0]} of {counts.shape[0]} tiles hold data")
+        base = sorted(secs["without nodata= (every tile fed)"])[args.scene_repeats // 2]
+        for name, ts in secs.items():
+            ts.sort()
+            print(f"  SceneInference.predict {name:36s} median {ts[len(ts) // 2]:7.3f} s  (min {ts[0]:7.3f}, max {ts[-1]:7.3f}; {args.scene_repeats} runs)   "
+                  f"{ts[len(ts) // 2] / base:5.3f} x")
