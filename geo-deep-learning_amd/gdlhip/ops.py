@@ -2202,6 +2202,65 @@ def scene_finish_valid(canvas: Tensor, valid: Tensor | None, nodata_label: int =
     return mask, probs
 
 
+# the sieve (include/gdlhip_scene_sieve.h): connected components of a label mask, the small ones dissolved into their neighbours
+def _sieve_check(op: str, mask: Tensor, connectivity: int, ignore_label: int | None) -> tuple[Tensor, int, int, int]:
+    """The argument checks the two calls share, but for the device (which is asked for last); (the mask as uint8, H, W,
+    ignore_label or -1)."""
+    if not isinstance(mask, Tensor) or mask.dtype not in (torch.uint8, torch.bool) or mask.dim() != 2 or not mask.is_contiguous():
+        got = f"{mask.dtype} {tuple(mask.shape)}" if isinstance(mask, Tensor) else type(mask).__name__
+        raise ValueError(f"{op}: contiguous uint8 / bool [H, W] mask expected, got {got}")
+    if isinstance(connectivity, bool) or connectivity not in (4, 8):
+        raise ValueError(f"{op}: connectivity must be 4 or 8, got {connectivity!r}")
+    if ignore_label is not None and (isinstance(ignore_label, bool) or not isinstance(ignore_label, int) or not 0 <= ignore_label <= 255):
+        raise ValueError(f"{op}: ignore_label must be None or an int in 0..255, got {ignore_label!r}")
+    H, W = int(mask.shape[0]), int(mask.shape[1])
+    if H * W < 1:
+        raise ValueError(f"{op}: empty mask {tuple(mask.shape)}")
+    if H * W >= 2 ** 31:
+        raise ValueError(f"{op}: {H} x {W} pixels: a linear index must fit an int32 (H * W < 2^31)")
+    return mask.view(torch.uint8), H, W, -1 if ignore_label is None else ignore_label
+
+
+def scene_components(mask: Tensor, connectivity: int = 4, ignore_label: int | None = None) -> tuple[Tensor, Tensor]:
+    """(labels int32 [H, W], sizes int32 [H*W]) of a uint8 / bool mask [H, W] on the device.  A component is a maximal set of equal
+    pixels connected under ``connectivity`` (4 or 8); ``labels`` holds the smallest linear index ``y * W + x`` of the pixel's
+    component and ``sizes`` the pixel count of a component at that index, 0 elsewhere.  Pixels equal to ``ignore_label`` belong to
+    no component: label -1.  Exact and the same bits from run to run (gdl_scene_components)."""
+    m, H, W, ignore = _sieve_check("scene_components", mask, connectivity, ignore_label)
+    _need_cuda(mask)
+    labels = torch.empty((H, W), device=mask.device, dtype=torch.int32)
+    sizes = torch.empty((H * W,), device=mask.device, dtype=torch.int32)
+    _lib.checked().gdl_scene_components(_p(m), H, W, connectivity, ignore, _p(labels), _p(sizes), _stream())
+    return labels, sizes
+
+
+def scene_sieve(mask: Tensor, min_size: int, connectivity: int = 4, ignore_label: int | None = None, iterations: int = 1) -> Tensor:
+    """A new uint8 [H, W] mask in which every component of fewer than ``min_size`` pixels has taken the value of the largest
+    component of at least ``min_size`` pixels that touches it (of two equally large ones: the lower value); one that touches none
+    keeps its value, and so does every pixel equal to ``ignore_label``.  ``iterations`` repeats labelling and sieving on the
+    result, which lets a small component surrounded by small ones go once those have gone.  ``min_size <= 1`` copies the mask
+    (gdl_scene_components + gdl_scene_sieve)."""
+    m, H, W, ignore = _sieve_check("scene_sieve", mask, connectivity, ignore_label)
+    if isinstance(min_size, bool) or not isinstance(min_size, int):
+        raise ValueError(f"scene_sieve: min_size must be an int (a pixel count), got {min_size!r}")
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or iterations < 1:
+        raise ValueError(f"scene_sieve: iterations must be an int of at least 1, got {iterations!r}")
+    _need_cuda(mask)
+    if min_size <= 1:
+        return m.clone()
+    min_size = min(min_size, 2 ** 31 - 1)      # no component has more pixels than that
+    labels = torch.empty((H, W), device=mask.device, dtype=torch.int32)
+    sizes = torch.empty((H * W,), device=mask.device, dtype=torch.int32)
+    best = torch.empty((H * W,), device=mask.device, dtype=torch.int64)
+    lib, src = _lib.checked(), m
+    for _ in range(iterations):
+        out = torch.empty_like(m)
+        lib.gdl_scene_components(_p(src), H, W, connectivity, ignore, _p(labels), _p(sizes), _stream())
+        lib.gdl_scene_sieve(_p(src), _p(labels), _p(sizes), H, W, connectivity, min_size, ignore, _p(best), _p(out), _stream())
+        src = out
+    return src
+
+
 def iou_counts(pred: Tensor, target: Tensor, num_classes: int) -> Tensor:
     """int64 [B, 3, K]: per sample and class (intersection, |pred==k|, |target==k|); exact integer counts."""
     _need_cuda(pred, target)

@@ -1,7 +1,8 @@
 """Host side of whole-scene inference: where the tiles of a scene lie and what window weights them, and the transform codes of test-time augmentation (``tta_codes``, ``plan_tta``; the device side of
 those: ``ops.scene_cut_d4`` / ``scene_blend_d4`` / ``scene_blend_lowres_d4``, include/gdlhip_scene_tta.h).  The device side is
 ``gdlhip.ops.scene_cut`` / ``scene_blend`` / ``scene_blend_lowres`` / ``scene_finish`` (include/gdlhip_scene.h) and, for nodata,
-``scene_valid`` / ``scene_tile_valid`` / ``scene_cut_valid`` / ``scene_finish_valid`` (include/gdlhip_scene_nodata.h); the user-facing
+``scene_valid`` / ``scene_tile_valid`` / ``scene_cut_valid`` / ``scene_finish_valid`` (include/gdlhip_scene_nodata.h) and, for the sieve
+of the finished mask, ``scene_components`` / ``scene_sieve`` (include/gdlhip_scene_sieve.h); the user-facing
 class is ``geo_deep_learning.tools.scene_inference.SceneInference``."""
 
 from __future__ import annotations

@@ -18,6 +18,11 @@ pixel inside a kept tile reaches the model as the raw value ``fill``, like a pos
 and the mask says ``nodata_label`` where the plane is 0 or no kept tile covers the pixel (``ops.scene_finish_valid``).  The blends
 are untouched, and without ``nodata=`` and ``valid=`` so is everything else.
 
+Sieve (``sieve=``): the finished mask is cleaned of speckle on the device before it is returned.  ``ops.scene_sieve`` labels its
+connected components and gives every component of fewer than ``sieve`` pixels (the minimum mapping unit) the class of the largest
+neighbour that is at least that large; ``nodata_label`` pixels are left alone where a validity plane is in play.  The sieve edits
+the map, not the probabilities: ``probs`` are returned as blended.
+
 Determinism: the canvas is accumulated by a gather in tile order without atomics, so the mask and the probabilities do not
 depend on ``batch_size`` and are the same bits from run to run.  The reference has no counterpart (its inference stops at the
 tile, tools/script_model.py)."""
@@ -58,12 +63,18 @@ class SceneInference:
     ``nodata_rule``: ``"all"`` (a pixel is invalid when every band is nodata) or ``"any"``.  ``nodata_label``: the mask value, 0..255,
     of an invalid or uncovered pixel.  ``min_valid``: a tile with fewer valid pixels than this is not fed to the model.  They act
     only where ``nodata`` is set or ``predict`` / ``canvas`` / ``tile_plan`` get a ``valid=`` plane (uint8 / bool [H, W], nonzero =
-    valid: an alpha band, a mask from elsewhere), which is ANDed with the plane of ``nodata``."""
+    valid: an alpha band, a mask from elsewhere), which is ANDed with the plane of ``nodata``.
+    ``sieve``: ``None`` (the mask as labelled: the calls and the bits of before) or the minimum mapping unit in pixels: a connected
+    region of one class with fewer pixels takes the class of its largest neighbouring region of at least that many (equally large:
+    the lower class), a region with no such neighbour stays (``ops.scene_sieve``).  ``sieve_connectivity``: 4 or 8, for the regions
+    and for what counts as a neighbour.  ``sieve_iterations``: how often the labelling and the sieve are repeated.  With a validity
+    plane the ``nodata_label`` pixels are no region: they are never changed and no pixel takes their label.  ``probs`` are the
+    blended probabilities either way, so where the sieve changed a pixel their arg-max is no longer the mask."""
 
     def __init__(self, script_model: ScriptModel, tile: tuple[int, int] = (512, 512), overlap: float = 0.5,
                  stride: tuple[int, int] | None = None, window: str = "hann", batch_size: int = 64, threshold: float = 0.5,
                  fill: int = 0, *, lowres: bool = True, tta=None, nodata=None, nodata_rule: str = "all", nodata_label: int = 255,
-                 min_valid: int = 1) -> None:
+                 min_valid: int = 1, sieve: int | None = None, sieve_connectivity: int = 4, sieve_iterations: int = 1) -> None:
         if not isinstance(script_model, ScriptModel):
             raise TypeError(f"SceneInference: a ScriptModel is expected, got {type(script_model).__name__}")
         self.model = script_model
@@ -88,6 +99,13 @@ class SceneInference:
         if nodata is not None:      # numbers, one or one per band; whether the raster's type can hold them is checked with the raster
             ops.scene_nodata_values(nodata, torch.float32, script_model.mean.numel(), "SceneInference")
         self.nodata, self.nodata_rule, self.nodata_label, self.min_valid = nodata, nodata_rule, nodata_label, min_valid
+        if sieve is not None and (isinstance(sieve, bool) or not isinstance(sieve, int) or sieve < 1):
+            raise ValueError(f"SceneInference: sieve must be None or a pixel count of at least 1, got {sieve!r}")
+        if isinstance(sieve_connectivity, bool) or sieve_connectivity not in (4, 8):
+            raise ValueError(f"SceneInference: sieve_connectivity must be 4 or 8, got {sieve_connectivity!r}")
+        if isinstance(sieve_iterations, bool) or not isinstance(sieve_iterations, int) or sieve_iterations < 1:
+            raise ValueError(f"SceneInference: sieve_iterations must be an int of at least 1, got {sieve_iterations!r}")
+        self.sieve, self.sieve_connectivity, self.sieve_iterations = sieve, sieve_connectivity, sieve_iterations
         dev = script_model.device
         self.wy, self.wx = gscene.window(self.tile[0], window).to(dev), gscene.window(self.tile[1], window).to(dev)
 
@@ -183,4 +201,7 @@ class SceneInference:
             mask, probs = ops.scene_finish(canvas, self.threshold, return_probs)
         else:
             mask, probs = ops.scene_finish_valid(canvas, plane, self.nodata_label, self.threshold, return_probs)
+        if self.sieve is not None:      # the map alone: probs stay as blended
+            mask = ops.scene_sieve(mask, self.sieve, self.sieve_connectivity, None if plane is None else self.nodata_label,
+                                   self.sieve_iterations)
         return SceneResult(mask, probs)

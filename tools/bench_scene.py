@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Whole-scene inference (tools/scene_inference.py, include/gdlhip_scene.h, include/gdlhip_scene_tta.h,
-include/gdlhip_scene_nodata.h), four measurements in one process.
+include/gdlhip_scene_nodata.h, include/gdlhip_scene_sieve.h), five measurements in one process.
 
 1. The tail of one batch of 64 tiles of 512^2 at stride 256 (an 8 x 8 grid over a 2304^2 uint8 scene), K = 5, the model excluded:
    its head map [64, 128, 128, 5] is drawn once.  ms per batch from HIP events around ``--inner`` repetitions, the variants
@@ -24,7 +24,11 @@ include/gdlhip_scene_nodata.h), four measurements in one process.
 3. The same scene and model with a nodata border: the samples outside a centred square are 0 in every band, the border taking
    ``--nodata-share`` of the pixels.  Seconds per scene of ``SceneInference.predict`` without ``nodata=`` (every tile is fed) and
    with ``nodata=0`` (scene_valid, scene_tile_valid, the tiles without data dropped, scene_cut_valid, scene_finish_valid), the two
-   alternating, with the tiles kept of the total; the masks are compared on the valid pixels first."""
+   alternating, with the tiles kept of the total; the masks are compared on the valid pixels first.
+4. ``ops.scene_sieve`` alone on a label mask of the scene's size (``--scene``, 4096 where that is 0): K classes in blocks of 64^2
+   with 2 % of the pixels redrawn at random, sieved at ``--sieve`` pixels, connectivity 4 and 8.  ms per call from HIP events, the
+   bytes its kernels move per pixel (from the shapes) as GB/s and as a share of the HBM rate, and beside it the seconds
+   ``scipy.ndimage.label`` needs on the host for the labelling alone of the same mask (where scipy is there)."""
 import argparse
 import sys
 import time
@@ -49,6 +53,8 @@ ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--scene-repeats", type=int, default=3)
 ap.add_argument("--no-tta", action="store_true", help="skip part 1b")
 ap.add_argument("--nodata-share", type=float, default=0.4, help="share of the scene of part 3 that is a nodata border (0 = skip part 3)")
+ap.add_argument("--sieve", type=int, default=64, help="minimum mapping unit of part 4 in pixels (0 = skip part 4)")
+ap.add_argument("--hbm-gbs", type=float, default=8000.0, help="the HBM rate part 4 compares with, GB/s")
 args = ap.parse_args()
 
 K, T, S = args.classes, args.tile, args.stride
@@ -281,3 +287,41 @@ if args.scene:
             ts.sort()
             print(f"  SceneInference.predict {name:36s} median {ts[len(ts) // 2]:7.3f} s  (min {ts[0]:7.3f}, max {ts[-1]:7.3f}; {args.scene_repeats} runs)   "
                   f"{ts[len(ts) // 2] / base:5.3f} x")
+
+# ------------------------------------------------------------------ 4. the sieve alone
+if args.sieve > 0:
+    n = args.scene or 4096
+    gs = torch.Generator().manual_seed(4)
+    blocks = torch.randint(0, K, ((n + 63) // 64, (n + 63) // 64), generator=gs, dtype=torch.uint8)
+    label_mask = blocks.repeat_interleave(64, 0).repeat_interleave(64, 1)[:n, :n].contiguous()
+    noise = torch.rand((n, n), generator=gs) < 0.02
+    label_mask[noise] = torch.randint(0, K, (int(noise.sum()),), generator=gs, dtype=torch.uint8)
+    dev_mask = label_mask.cuda()
+    # per pixel: the tile kernel reads the mask and writes parents and zeroed sizes (1 + 4 + 4), the flattening reads and writes the
+    # labels (4 + 4), the clearing reads the sizes (4), the vote reads mask, labels and sizes (1 + 4 + 4) and the rewrite the same
+    # and writes the mask (1 + 4 + 4 + 1); the unions across tile edges and the atomics touch a few per cent of that
+    sieve_bytes = 9 + 8 + 4 + 9 + 10
+    for connectivity in (4, 8):
+        variants = {f"scene_sieve, connectivity {connectivity}": lambda c=connectivity: ops.scene_sieve(dev_mask, args.sieve, c),
+                    f"scene_components alone, connectivity {connectivity}": lambda c=connectivity: ops.scene_components(dev_mask, c)}
+        out = ops.scene_sieve(dev_mask, args.sieve, connectivity)
+        changed = int((out != dev_mask).sum())
+        times = timed(variants, args.rounds, args.inner)
+        print(f"sieve of a {n}^2 mask, K = {K}, min_size {args.sieve}, connectivity {connectivity}: {changed} pixels changed; ms per call, "
+              f"{args.rounds} rounds of {args.inner}")
+        for (name, ts), nbytes in zip(times.items(), (sieve_bytes, 17)):
+            med = ts[len(ts) // 2]
+            rate = nbytes * n * n / (med * 1e-3) / 1e9
+            print(f"  {name:40s} median {med:8.3f}  min {ts[0]:8.3f}  max {ts[-1]:8.3f}   {nbytes} B per pixel, {rate:6.0f} GB/s, "
+                  f"{rate / args.hbm_gbs:6.1%} of {args.hbm_gbs:.0f} GB/s")
+    try:
+        from scipy import ndimage
+    except ImportError:
+        print("  scipy is not installed: no host time beside it")
+    else:
+        host = label_mask.numpy()
+        t0 = time.perf_counter()
+        for value in range(K):
+            ndimage.label(host == value)
+        print(f"  scipy.ndimage.label on the host, the {K} classes one after the other (labelling alone, connectivity 4): "
+              f"{time.perf_counter() - t0:.2f} s")
