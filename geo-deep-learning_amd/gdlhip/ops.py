@@ -2261,6 +2261,71 @@ def scene_sieve(mask: Tensor, min_size: int, connectivity: int = 4, ignore_label
     return src
 
 
+# the polygon rings (include/gdlhip_scene_rings.h): the boundaries of a mask's regions as closed rings of lattice points
+class SceneRings(NamedTuple):
+    vertices: Tensor          # int32 [V, 2]: (x, y) lattice points, ring after ring, every ring open
+    ring_offsets: Tensor      # int32 [R + 1]: ring r is vertices[ring_offsets[r]:ring_offsets[r + 1]]
+    value: Tensor             # uint8 [R]: the class of the ring's pixels
+    label: Tensor             # int32 [R]: their component (scene_components)
+    start: Tensor             # int32 [R]: the ring's smallest slot 4 * (y * W + x) + side, ascending
+    area2: Tensor             # int64 [R]: twice the enclosed pixel count for an exterior ring, negative for a hole
+
+
+def _keep_table(values) -> list[int]:
+    """256 flags of the keep set ``values`` (None: every value)."""
+    if values is None:
+        return [1] * 256
+    items = None if isinstance(values, (str, bytes, Tensor)) or not hasattr(values, "__iter__") else list(values)
+    if items is None or any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255 for v in items):
+        raise ValueError(f"scene_rings: values must be None or an iterable of ints in 0..255, got {values!r}")
+    return [int(v in items) for v in range(256)]
+
+
+def scene_rings(mask: Tensor, connectivity: int = 4, ignore_label: int | None = None, values=None,
+                labels: Tensor | None = None) -> SceneRings:
+    """The boundaries of the regions of a uint8 / bool mask [H, W] on the device as closed rings of lattice points (pixel (y, x)
+    is the square (x, y) .. (x + 1, y + 1)), the region on the right hand of the direction of travel: an exterior ring has
+    ``area2 > 0``, a hole ``area2 < 0``.  A region is a component of ``scene_components`` under ``connectivity`` and
+    ``ignore_label``; ``values`` (an iterable of ints in 0..255) keeps the regions of those classes alone.  ``labels``: the int32
+    [H, W] labels ``scene_components`` gave for the same mask, connectivity and ignore_label, computed here when None.  Rings
+    start at their smallest slot and come in the order of their starts; every component has one exterior ring, whose start is
+    ``4 * label``.  Exact and the same bits from run to run; the mask is not modified.  Two small device-to-host copies (the
+    number of boundary sides, then of rings and vertices) size the buffers (gdl_scene_rings_count / _trace / _write)."""
+    m, H, W, ignore = _sieve_check("scene_rings", mask, connectivity, ignore_label)
+    if H * W >= 2 ** 29:
+        raise ValueError(f"scene_rings: {H} x {W} pixels: a slot 4 * (y * W + x) + side must fit an int32 (H * W < 2^29)")
+    table = _keep_table(values)
+    if labels is not None and (not isinstance(labels, Tensor) or labels.dtype != torch.int32 or tuple(labels.shape) != (H, W)
+                               or not labels.is_contiguous()):
+        got = f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, Tensor) else type(labels).__name__
+        raise ValueError(f"scene_rings: labels must be a contiguous int32 [H, W] = [{H}, {W}] tensor, got {got}")
+    _need_cuda(mask, labels)
+    dev, lib = mask.device, _lib.checked()
+    if labels is None:
+        labels = scene_components(m, connectivity, ignore_label)[0]
+
+    def i32(n: int) -> Tensor:
+        return torch.empty((n,), device=dev, dtype=torch.int32)
+
+    def blocks(n: int) -> int:      # the block sums a scan over n entries needs
+        return -(-n // _lib.SCENE_RINGS_SCAN_TILE)
+
+    keep = torch.tensor(table, dtype=torch.uint8).to(dev)
+    offsets, n_sides = i32(H * W), i32(1)
+    lib.gdl_scene_rings_count(_p(m), H, W, ignore, _p(keep), _p(offsets), _p(i32(blocks(H * W))), _p(n_sides), _stream())
+    E = int(n_sides.item())
+    side_slot, side_next, side_ring, side_rank = i32(E), i32(E), i32(E), i32(E)
+    work, counts = i32(3 * E + 2 * blocks(E) + _lib.SCENE_RINGS_FLAGS), i32(2)
+    lib.gdl_scene_rings_trace(_p(m), H, W, connectivity, ignore, _p(keep), _p(offsets), E, _p(side_slot), _p(side_next), _p(side_ring),
+                              _p(side_rank), _p(work), _p(counts), _stream())
+    R, V = (int(c) for c in counts.tolist())
+    out = SceneRings(torch.empty((V, 2), device=dev, dtype=torch.int32), i32(R + 1), torch.empty((R,), device=dev, dtype=torch.uint8),
+                     i32(R), i32(R), torch.empty((R,), device=dev, dtype=torch.int64))
+    lib.gdl_scene_rings_write(_p(m), _p(labels), W, E, R, V, _p(side_slot), _p(side_next), _p(side_ring), _p(side_rank), _p(work),
+                              *(_p(t) for t in out), _stream())
+    return out
+
+
 def iou_counts(pred: Tensor, target: Tensor, num_classes: int) -> Tensor:
     """int64 [B, 3, K]: per sample and class (intersection, |pred==k|, |target==k|); exact integer counts."""
     _need_cuda(pred, target)

@@ -2,7 +2,8 @@
 those: ``ops.scene_cut_d4`` / ``scene_blend_d4`` / ``scene_blend_lowres_d4``, include/gdlhip_scene_tta.h).  The device side is
 ``gdlhip.ops.scene_cut`` / ``scene_blend`` / ``scene_blend_lowres`` / ``scene_finish`` (include/gdlhip_scene.h) and, for nodata,
 ``scene_valid`` / ``scene_tile_valid`` / ``scene_cut_valid`` / ``scene_finish_valid`` (include/gdlhip_scene_nodata.h) and, for the sieve
-of the finished mask, ``scene_components`` / ``scene_sieve`` (include/gdlhip_scene_sieve.h); the user-facing
+of the finished mask, ``scene_components`` / ``scene_sieve`` (include/gdlhip_scene_sieve.h) and, for its polygon rings,
+``scene_rings`` (include/gdlhip_scene_rings.h), which ``polygons`` here groups into features; the user-facing
 class is ``geo_deep_learning.tools.scene_inference.SceneInference``."""
 
 from __future__ import annotations
@@ -106,3 +107,42 @@ def plan_tta(plan: Tensor, codes) -> tuple[Tensor, Tensor]:
     if plan.dim() != 2 or plan.shape[1] != 2 or codes.numel() < 1:
         raise ValueError(f"plan_tta: a plan [T, 2] and at least one code are expected, got {tuple(plan.shape)} and {codes.numel()} codes")
     return plan.to(torch.int32).repeat_interleave(codes.numel(), dim=0).contiguous(), codes.repeat(plan.shape[0])
+
+
+# ------------------------------------------------------------------ polygons of the rings (include/gdlhip_scene_rings.h)
+def polygons(rings, transform=None) -> list[dict]:
+    """The rings of ``ops.scene_rings`` (anything with its six fields, tensors or arrays) as GeoJSON-style features, one per
+    component, ordered by label::
+
+        {"type": "Feature", "properties": {"value": v, "label": l, "pixels": n},
+         "geometry": {"type": "Polygon", "coordinates": [exterior, hole, ...]}}
+
+    Every ring is closed (its first vertex stands at the end again); the exterior is the label's one ring with ``area2 > 0``, the
+    holes follow by ascending ``start``; ``pixels`` is half the sum of the label's ``area2``.  ``transform``: None (coordinates
+    stay Python ints) or six numbers (a, b, c, d, e, f) that map (x, y) to (a x + b y + c, d x + e y + f), the affine order of
+    rasterio.  The rings are copied to the host once.  A label without exactly one exterior ring is a ValueError."""
+    vertices, offsets, value, label, start, area2 = (f.tolist() for f in (rings.vertices, rings.ring_offsets, rings.value,
+                                                                           rings.label, rings.start, rings.area2))
+    if len(offsets) != len(value) + 1 or not len(value) == len(label) == len(start) == len(area2) or offsets[-1] != len(vertices):
+        raise ValueError(f"polygons: {len(offsets)} ring offsets, {len(value)} values and {len(vertices)} vertices do not belong together")
+    if transform is not None:
+        try:
+            a, b, c, d, e, f = (float(t) for t in transform)
+        except (TypeError, ValueError):
+            raise ValueError(f"polygons: transform must be None or six numbers (a, b, c, d, e, f), got {transform!r}") from None
+        vertices = [[a * x + b * y + c, d * x + e * y + f] for x, y in vertices]
+    by_label: dict[int, list[int]] = {}
+    for r in sorted(range(len(value)), key=start.__getitem__):
+        by_label.setdefault(label[r], []).append(r)
+    features = []
+    for lab in sorted(by_label):
+        members = by_label[lab]
+        exterior = [r for r in members if area2[r] > 0]
+        if len(exterior) != 1:
+            raise ValueError(f"polygons: label {lab} has {len(exterior)} exterior rings (area2 > 0), exactly one is expected")
+        order = exterior + [r for r in members if area2[r] <= 0]
+        coordinates = [vertices[offsets[r]:offsets[r + 1]] + vertices[offsets[r]:offsets[r] + 1] for r in order]
+        features.append({"type": "Feature",
+                         "properties": {"value": value[exterior[0]], "label": lab, "pixels": sum(area2[r] for r in members) // 2},
+                         "geometry": {"type": "Polygon", "coordinates": coordinates}})
+    return features

@@ -23,6 +23,9 @@ connected components and gives every component of fewer than ``sieve`` pixels (t
 neighbour that is at least that large; ``nodata_label`` pixels are left alone where a validity plane is in play.  The sieve edits
 the map, not the probabilities: ``probs`` are returned as blended.
 
+Polygons (``predict_rings``): the boundaries of the mask's regions as closed rings of lattice points, traced on the device
+(``ops.scene_rings``), the step GDAL polygonize takes on the host; ``gdlhip.scene.polygons`` groups them into features with holes.
+
 Determinism: the canvas is accumulated by a gather in tile order without atomics, so the mask and the probabilities do not
 depend on ``batch_size`` and are the same bits from run to run.  The reference has no counterpart (its inference stops at the
 tile, tools/script_model.py)."""
@@ -45,6 +48,11 @@ _RASTER_DTYPES = (torch.uint8, torch.uint16, torch.int16, torch.float32)
 class SceneResult(NamedTuple):
     mask: torch.Tensor                  # uint8 [H, W]
     probs: torch.Tensor | None          # f32 [K, H, W], None unless asked for
+
+
+class SceneVectors(NamedTuple):
+    mask: torch.Tensor                  # uint8 [H, W], what ``predict`` returns
+    rings: ops.SceneRings               # the rings of its regions, on the device
 
 
 class SceneInference:
@@ -205,3 +213,13 @@ class SceneInference:
             mask = ops.scene_sieve(mask, self.sieve, self.sieve_connectivity, None if plane is None else self.nodata_label,
                                    self.sieve_iterations)
         return SceneResult(mask, probs)
+
+    def predict_rings(self, raster: torch.Tensor, valid: torch.Tensor | None = None, *, connectivity: int = 4,
+                      values=None) -> SceneVectors:
+        """``predict`` as configured (sieve included), then the polygon rings of the mask's regions under ``connectivity``
+        (``ops.scene_rings``; ``values``: the classes to keep, None for all).  Where a validity plane is in play -- ``nodata=``
+        or ``valid=``, as for the sieve -- the ``nodata_label`` pixels are no region and get no ring.
+        ``gdlhip.scene.polygons(result.rings)`` turns the rings into features."""
+        mask = self.predict(raster, valid=valid).mask
+        plane_in_play = self.nodata is not None or valid is not None
+        return SceneVectors(mask, ops.scene_rings(mask, connectivity, self.nodata_label if plane_in_play else None, values))

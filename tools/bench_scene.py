@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Whole-scene inference (tools/scene_inference.py, include/gdlhip_scene.h, include/gdlhip_scene_tta.h,
-include/gdlhip_scene_nodata.h, include/gdlhip_scene_sieve.h), five measurements in one process.
+include/gdlhip_scene_nodata.h, include/gdlhip_scene_sieve.h, include/gdlhip_scene_rings.h), six measurements in one process.
 
 1. The tail of one batch of 64 tiles of 512^2 at stride 256 (an 8 x 8 grid over a 2304^2 uint8 scene), K = 5, the model excluded:
    its head map [64, 128, 128, 5] is drawn once.  ms per batch from HIP events around ``--inner`` repetitions, the variants
@@ -28,7 +28,11 @@ include/gdlhip_scene_nodata.h, include/gdlhip_scene_sieve.h), five measurements 
 4. ``ops.scene_sieve`` alone on a label mask of the scene's size (``--scene``, 4096 where that is 0): K classes in blocks of 64^2
    with 2 % of the pixels redrawn at random, sieved at ``--sieve`` pixels, connectivity 4 and 8.  ms per call from HIP events, the
    bytes its kernels move per pixel (from the shapes) as GB/s and as a share of the HBM rate, and beside it the seconds
-   ``scipy.ndimage.label`` needs on the host for the labelling alone of the same mask (where scipy is there)."""
+   ``scipy.ndimage.label`` needs on the host for the labelling alone of the same mask (where scipy is there).
+5. ``ops.scene_rings`` on a ``--rings`` x ``--rings`` mask, for two inputs: site percolation at the threshold (p = 0.5927) sieved at
+   ``--sieve`` pixels (64 where that is 0), and a constant mask.  The counts E (boundary sides), R (rings) and V (vertices), ms of
+   the whole call on the host clock (it holds two device-to-host copies and the allocations), and ms of each stage from HIP
+   events around its entry point alone: gdl_scene_components, gdl_scene_rings_count, _trace and _write."""
 import argparse
 import sys
 import time
@@ -54,6 +58,7 @@ ap.add_argument("--scene-repeats", type=int, default=3)
 ap.add_argument("--no-tta", action="store_true", help="skip part 1b")
 ap.add_argument("--nodata-share", type=float, default=0.4, help="share of the scene of part 3 that is a nodata border (0 = skip part 3)")
 ap.add_argument("--sieve", type=int, default=64, help="minimum mapping unit of part 4 in pixels (0 = skip part 4)")
+ap.add_argument("--rings", type=int, default=8192, help="side of the mask of part 5 (0 = skip part 5)")
 ap.add_argument("--hbm-gbs", type=float, default=8000.0, help="the HBM rate part 4 compares with, GB/s")
 args = ap.parse_args()
 
@@ -325,3 +330,71 @@ if args.sieve > 0:
             ndimage.label(host == value)
         print(f"  scipy.ndimage.label on the host, the {K} classes one after the other (labelling alone, connectivity 4): "
               f"{time.perf_counter() - t0:.2f} s")
+
+# ------------------------------------------------------------------ 5. the polygon rings
+if args.rings > 0:
+    from gdlhip import _lib
+    n = args.rings
+    lib, stream = _lib.checked(), torch.cuda.current_stream().cuda_stream
+    percolation = (torch.rand((n, n), generator=torch.Generator().manual_seed(5)) < 0.5927).to(torch.uint8).cuda()
+    inputs = {f"percolation (p = 0.5927) sieved at {args.sieve or 64} pixels": ops.scene_sieve(percolation, args.sieve or 64, 4),
+              "constant": torch.full((n, n), 3, dtype=torch.uint8, device="cuda")}
+    del percolation
+
+    def i32(count):
+        return torch.empty((count,), device="cuda", dtype=torch.int32)
+
+    def blocks(count):
+        return -(-count // _lib.SCENE_RINGS_SCAN_TILE)
+
+    def stages(mask, connectivity):
+        """ops.scene_rings call by call, every entry point between two HIP events of its own: ({stage: ms}, (E, R, V))."""
+        ms, keep = {}, torch.ones(256, dtype=torch.uint8, device="cuda")
+
+        def p(x):
+            return x.data_ptr()
+
+        def run(name, fn, *a):
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            fn(*a, stream)
+            end.record()
+            end.synchronize()
+            ms[name] = start.elapsed_time(end)
+
+        labels, sizes, offsets, n_sides, counts = torch.empty((n, n), device="cuda", dtype=torch.int32), i32(n * n), i32(n * n), i32(1), i32(2)
+        run("gdl_scene_components", lib.gdl_scene_components, p(mask), n, n, connectivity, -1, p(labels), p(sizes))
+        del sizes
+        run("gdl_scene_rings_count", lib.gdl_scene_rings_count, p(mask), n, n, -1, p(keep), p(offsets), p(i32(blocks(n * n))), p(n_sides))
+        E = int(n_sides.item())
+        side = [i32(E) for _ in range(4)]
+        work = i32(3 * E + 2 * blocks(E) + _lib.SCENE_RINGS_FLAGS)
+        run("gdl_scene_rings_trace", lib.gdl_scene_rings_trace, p(mask), n, n, connectivity, -1, p(keep), p(offsets), E, *map(p, side), p(work),
+            p(counts))
+        R, V = counts.tolist()
+        out = (torch.empty((V, 2), device="cuda", dtype=torch.int32), i32(R + 1), torch.empty((R,), device="cuda", dtype=torch.uint8),
+               i32(R), i32(R), torch.empty((R,), device="cuda", dtype=torch.int64))
+        run("gdl_scene_rings_write", lib.gdl_scene_rings_write, p(mask), p(labels), n, E, R, V, *map(p, side), p(work), *map(p, out))
+        return ms, (E, R, V)
+
+    for name, mask in inputs.items():
+        for connectivity in (4, 8):
+            whole = ops.scene_rings(mask, connectivity)      # warm-up, and what the stages must add up to
+            runs, clock = [], []
+            for _ in range(args.rounds):
+                runs.append(stages(mask, connectivity))
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ops.scene_rings(mask, connectivity)
+                torch.cuda.synchronize()
+                clock.append((time.perf_counter() - t0) * 1e3)
+            E, R, V = runs[0][1]
+            assert (R, V) == (whole.value.numel(), whole.vertices.shape[0]) and all(r[1] == (E, R, V) for r in runs)
+            clock.sort()
+            print(f"rings of a {n}^2 mask, {name}, connectivity {connectivity}: E = {E} sides, R = {R} rings, V = {V} vertices, "
+                  f"{max(E - 1, 0).bit_length()} doubling rounds at the most; ms, {args.rounds} runs")
+            print(f"  {'ops.scene_rings, whole call (host clock)':44s} median {clock[len(clock) // 2]:9.3f}  min {clock[0]:9.3f}  max {clock[-1]:9.3f}")
+            for stage in runs[0][0]:
+                ts = sorted(r[0][stage] for r in runs)
+                print(f"  {stage:44s} median {ts[len(ts) // 2]:9.3f}  min {ts[0]:9.3f}  max {ts[-1]:9.3f}")
+            del whole
