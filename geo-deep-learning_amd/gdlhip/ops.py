@@ -10,6 +10,7 @@ argument checks (dofa_v2.py:439-441, multilevel_neck.py:141-146).
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import NamedTuple
 
@@ -2324,6 +2325,96 @@ def scene_rings(mask: Tensor, connectivity: int = 4, ignore_label: int | None = 
     lib.gdl_scene_rings_write(_p(m), _p(labels), W, E, R, V, _p(side_slot), _p(side_next), _p(side_ring), _p(side_rank), _p(work),
                               *(_p(t) for t in out), _stream())
     return out
+
+
+# their simplification (include/gdlhip_scene_simplify.h): Douglas-Peucker per arc between the junctions of the boundaries
+SIMPLIFY_TOLERANCE_MAX = 2 ** 20      # pixels; tol_q8 = round(tolerance * 256) then fits 2^28
+
+
+def _rings_check(op: str, rings) -> tuple[int, int]:
+    """(R, V) of a SceneRings whose six fields belong together by type, shape and device, or ValueError."""
+    fields = {"vertices": torch.int32, "ring_offsets": torch.int32, "value": torch.uint8, "label": torch.int32, "start": torch.int32,
+              "area2": torch.int64}
+    got = [getattr(rings, name, None) for name in fields]
+    if not all(isinstance(t, Tensor) for t in got):
+        raise ValueError(f"{op}: rings must have the six tensor fields of SceneRings ({', '.join(fields)}), got {type(rings).__name__}")
+    vertices, offsets = got[0], got[1]
+    R = int(offsets.numel()) - 1
+    shapes = {"vertices": (int(vertices.shape[0]), 2) if vertices.dim() else None, "ring_offsets": (R + 1,)}
+    for (name, dtype), t in zip(fields.items(), got):
+        if t.dtype != dtype or tuple(t.shape) != shapes.get(name, (R,)) or not t.is_contiguous() or t.device != vertices.device:
+            raise ValueError(f"{op}: rings.{name} must be a contiguous {dtype} {shapes.get(name, (R,))} tensor on {vertices.device}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    V = int(vertices.shape[0])
+    if R < 0 or 4 * R > V or (R == 0) != (V == 0):
+        raise ValueError(f"{op}: {R} rings and {V} vertices do not belong together (a ring has at least 4 vertices)")
+    return R, V
+
+
+def scene_rings_simplify(rings: SceneRings, mask: Tensor, tolerance: float, ignore_label: int | None = None, values=None) -> SceneRings:
+    """The rings of ``scene_rings`` simplified by Douglas-Peucker with ``tolerance`` (pixels, 0 .. 2^20, quantised to 1 / 256),
+    arc by arc between the nodes of the boundaries -- the lattice points where three or four boundary edges meet -- so that two
+    regions that share a boundary get the same simplified boundary, vertex for vertex, and no gap or overlap opens between them.
+    ``mask``, ``ignore_label`` and ``values`` must be those ``rings`` was made with: they define the nodes.  The result has the
+    same rings in the same order; ``value``, ``label``, ``start`` and ``area2`` are the input's tensors, so ``area2`` stays the
+    area of the *pixel* ring (``gdlhip.scene.polygons`` still tells exterior from hole by it, and its ``pixels`` stays the true
+    pixel count).  Nodes are always kept, also where a ring runs straight through one; a ring without nodes (an island, a hole
+    between two regions) keeps its smallest (y, x) vertex.  A ring may come out with fewer than 3 vertices: it collapsed.
+    ``tolerance=0`` drops the vertices at distance 0 from their chords alone.  Integer arithmetic: exact, and the same bits from
+    run to run; neither the rings nor the mask are modified.  Small device-to-host copies size the buffers and end the rounds:
+    the dense vertex count, one flag per group of ``GDL_SCENE_SIMPLIFY_ROUNDS`` rounds (the depth of Douglas-Peucker depends
+    on the data), and the output vertex count (gdl_scene_nodes / gdl_scene_simplify_count / _dense / _rounds / _write)."""
+    op = "scene_rings_simplify"
+    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float)) or not math.isfinite(tolerance) \
+            or not 0 <= tolerance <= SIMPLIFY_TOLERANCE_MAX:
+        raise ValueError(f"{op}: tolerance must be a finite number of pixels in 0..2^20, got {tolerance!r}")
+    R, V = _rings_check(op, rings)
+    m, H, W, ignore = _sieve_check(op, mask, 4, ignore_label)
+    if H * W >= 2 ** 29:
+        raise ValueError(f"{op}: {H} x {W} pixels: the rings are those of a raster of H * W < 2^29")
+    if V > 4 * H * W:
+        raise ValueError(f"{op}: {V} vertices are more than a {H} x {W} mask has pixel sides")
+    table = _keep_table(values)
+    if rings.vertices.device != mask.device:
+        raise ValueError(f"{op}: the rings are on {rings.vertices.device}, the mask on {mask.device}")
+    _need_cuda(mask, rings.vertices)
+    dev, lib, tol_q8 = mask.device, _lib.checked(), int(round(tolerance * 256))
+
+    def i32(n: int) -> Tensor:
+        return torch.empty((n,), device=dev, dtype=torch.int32)
+
+    def blocks(n: int) -> int:      # the block sums a scan over n entries needs
+        return -(-n // _lib.SCENE_SIMPLIFY_SCAN_TILE)
+
+    if R == 0:
+        return SceneRings(torch.empty((0, 2), device=dev, dtype=torch.int32), torch.zeros((1,), device=dev, dtype=torch.int32), rings.value, rings.label, rings.start, rings.area2)
+    keep = torch.tensor(table, dtype=torch.uint8).to(dev)
+    nodes = torch.empty((H + 1, W + 1), device=dev, dtype=torch.uint8)
+    lib.gdl_scene_nodes(_p(m), H, W, ignore, _p(keep), _p(nodes), _stream())
+    pos, n_dense = i32(V + 1), i32(1)
+    lib.gdl_scene_simplify_count(_p(nodes), H, W, _p(rings.vertices), _p(rings.ring_offsets), R, V, _p(pos), _p(i32(blocks(V + 1))),
+                                 _p(n_dense), _stream())
+    D = int(n_dense.item())
+    dense, dense_offsets = torch.empty((D, 2), device=dev, dtype=torch.int32), i32(R + 1)
+    kept, seg = torch.empty((D,), device=dev, dtype=torch.uint8), i32(4 * D + _lib.SCENE_SIMPLIFY_ROUNDS)
+    key = torch.empty((D,), device=dev, dtype=torch.int64)
+    work = torch.empty((R + D + 1 + blocks(D + 1),), device=dev, dtype=torch.int64)      # int64: 8-byte aligned, at least as large
+    lib.gdl_scene_simplify_dense(_p(nodes), H, W, _p(rings.vertices), _p(rings.ring_offsets), R, V, _p(pos), D, _p(dense),
+                                 _p(dense_offsets), _p(kept), _p(seg), _p(key), _p(work), _stream())
+    del work, pos, nodes
+    changed, first = i32(1), 1
+    while True:
+        lib.gdl_scene_simplify_rounds(_p(dense), W, D, tol_q8, first, _lib.SCENE_SIMPLIFY_ROUNDS, _p(kept), _p(seg), _p(key), _p(changed),
+                                      _stream())
+        first = 0
+        if not int(changed.item()):
+            break
+    del seg, key
+    out, offsets, n_out = torch.empty((D, 2), device=dev, dtype=torch.int32), i32(R + 1), i32(1)
+    lib.gdl_scene_simplify_write(_p(dense), _p(dense_offsets), R, D, _p(kept), _p(i32(D + 1 + blocks(D + 1))), _p(out), _p(offsets),
+                                 _p(n_out), _stream())
+    n = int(n_out.item())
+    return SceneRings(out if n == D else out[:n].clone(), offsets, rings.value, rings.label, rings.start, rings.area2)
 
 
 def iou_counts(pred: Tensor, target: Tensor, num_classes: int) -> Tensor:

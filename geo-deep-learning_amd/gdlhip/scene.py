@@ -3,7 +3,8 @@ those: ``ops.scene_cut_d4`` / ``scene_blend_d4`` / ``scene_blend_lowres_d4``, in
 ``gdlhip.ops.scene_cut`` / ``scene_blend`` / ``scene_blend_lowres`` / ``scene_finish`` (include/gdlhip_scene.h) and, for nodata,
 ``scene_valid`` / ``scene_tile_valid`` / ``scene_cut_valid`` / ``scene_finish_valid`` (include/gdlhip_scene_nodata.h) and, for the sieve
 of the finished mask, ``scene_components`` / ``scene_sieve`` (include/gdlhip_scene_sieve.h) and, for its polygon rings,
-``scene_rings`` (include/gdlhip_scene_rings.h), which ``polygons`` here groups into features; the user-facing
+``scene_rings`` (include/gdlhip_scene_rings.h) and their simplification ``scene_rings_simplify``
+(include/gdlhip_scene_simplify.h), which ``polygons`` here groups into features; the user-facing
 class is ``geo_deep_learning.tools.scene_inference.SceneInference``."""
 
 from __future__ import annotations
@@ -120,7 +121,14 @@ def polygons(rings, transform=None) -> list[dict]:
     Every ring is closed (its first vertex stands at the end again); the exterior is the label's one ring with ``area2 > 0``, the
     holes follow by ascending ``start``; ``pixels`` is half the sum of the label's ``area2``.  ``transform``: None (coordinates
     stay Python ints) or six numbers (a, b, c, d, e, f) that map (x, y) to (a x + b y + c, d x + e y + f), the affine order of
-    rasterio.  The rings are copied to the host once.  A label without exactly one exterior ring is a ValueError."""
+    rasterio.  The rings are copied to the host once.  A label without exactly one exterior ring is a ValueError.
+
+    Simplified rings (``ops.scene_rings_simplify``) can have collapsed to fewer than 3 vertices, which traced rings never have: a
+    hole with fewer than 3 vertices is left out, and a label whose exterior has fewer than 3 vertices yields no feature (its
+    holes go with it).  That is consistent: a collapsed island and the collapsed hole it sat in are the same arc, simplified to
+    the same points, so the island's feature and the hole in its surroundings vanish together and the surrounding polygon covers
+    the place.  ``area2`` is the pixel ring's, so exterior and hole are told apart, and ``pixels`` counted, as before the
+    simplification."""
     vertices, offsets, value, label, start, area2 = (f.tolist() for f in (rings.vertices, rings.ring_offsets, rings.value,
                                                                            rings.label, rings.start, rings.area2))
     if len(offsets) != len(value) + 1 or not len(value) == len(label) == len(start) == len(area2) or offsets[-1] != len(vertices):
@@ -140,7 +148,9 @@ def polygons(rings, transform=None) -> list[dict]:
         exterior = [r for r in members if area2[r] > 0]
         if len(exterior) != 1:
             raise ValueError(f"polygons: label {lab} has {len(exterior)} exterior rings (area2 > 0), exactly one is expected")
-        order = exterior + [r for r in members if area2[r] <= 0]
+        if offsets[exterior[0] + 1] - offsets[exterior[0]] < 3:      # collapsed by the simplification
+            continue
+        order = exterior + [r for r in members if area2[r] <= 0 and offsets[r + 1] - offsets[r] >= 3]
         coordinates = [vertices[offsets[r]:offsets[r + 1]] + vertices[offsets[r]:offsets[r] + 1] for r in order]
         features.append({"type": "Feature",
                          "properties": {"value": value[exterior[0]], "label": lab, "pixels": sum(area2[r] for r in members) // 2},

@@ -25,6 +25,8 @@ the map, not the probabilities: ``probs`` are returned as blended.
 
 Polygons (``predict_rings``): the boundaries of the mask's regions as closed rings of lattice points, traced on the device
 (``ops.scene_rings``), the step GDAL polygonize takes on the host; ``gdlhip.scene.polygons`` groups them into features with holes.
+``predict_rings(simplify=tolerance)`` simplifies them on the device before they leave it (``ops.scene_rings_simplify``):
+Douglas-Peucker per arc between the junctions of the boundaries, so that a boundary two regions share stays shared.
 
 Determinism: the canvas is accumulated by a gather in tile order without atomics, so the mask and the probabilities do not
 depend on ``batch_size`` and are the same bits from run to run.  The reference has no counterpart (its inference stops at the
@@ -32,6 +34,7 @@ tile, tools/script_model.py)."""
 
 from __future__ import annotations
 
+import math
 from typing import NamedTuple
 
 import torch
@@ -77,7 +80,9 @@ class SceneInference:
     the lower class), a region with no such neighbour stays (``ops.scene_sieve``).  ``sieve_connectivity``: 4 or 8, for the regions
     and for what counts as a neighbour.  ``sieve_iterations``: how often the labelling and the sieve are repeated.  With a validity
     plane the ``nodata_label`` pixels are no region: they are never changed and no pixel takes their label.  ``probs`` are the
-    blended probabilities either way, so where the sieve changed a pixel their arg-max is no longer the mask."""
+    blended probabilities either way, so where the sieve changed a pixel their arg-max is no longer the mask.
+    ``predict_rings`` goes on from the mask to the polygon rings of its regions, and with ``simplify=`` to their Douglas-Peucker
+    simplification per shared arc (``ops.scene_rings`` / ``ops.scene_rings_simplify``)."""
 
     def __init__(self, script_model: ScriptModel, tile: tuple[int, int] = (512, 512), overlap: float = 0.5,
                  stride: tuple[int, int] | None = None, window: str = "hann", batch_size: int = 64, threshold: float = 0.5,
@@ -215,11 +220,21 @@ class SceneInference:
         return SceneResult(mask, probs)
 
     def predict_rings(self, raster: torch.Tensor, valid: torch.Tensor | None = None, *, connectivity: int = 4,
-                      values=None) -> SceneVectors:
+                      values=None, simplify: float | None = None) -> SceneVectors:
         """``predict`` as configured (sieve included), then the polygon rings of the mask's regions under ``connectivity``
         (``ops.scene_rings``; ``values``: the classes to keep, None for all).  Where a validity plane is in play -- ``nodata=``
         or ``valid=``, as for the sieve -- the ``nodata_label`` pixels are no region and get no ring.
+        ``simplify``: ``None`` (the rings follow every pixel edge: the calls and the bits of before) or a Douglas-Peucker
+        tolerance in pixels, 0 .. 2^20: the rings are simplified on the device arc by arc between the junctions of the boundaries
+        (``ops.scene_rings_simplify`` with the same mask, ``nodata_label`` rule and ``values``), so neighbouring regions keep one
+        common boundary.  ``area2`` stays the area of the pixel ring, and a ring may collapse to fewer than 3 vertices.
         ``gdlhip.scene.polygons(result.rings)`` turns the rings into features."""
+        if simplify is not None and (isinstance(simplify, bool) or not isinstance(simplify, (int, float)) or not math.isfinite(simplify)
+                                     or not 0 <= simplify <= ops.SIMPLIFY_TOLERANCE_MAX):
+            raise ValueError(f"SceneInference.predict_rings: simplify must be None or a finite tolerance in 0..2^20 pixels, got {simplify!r}")
         mask = self.predict(raster, valid=valid).mask
-        plane_in_play = self.nodata is not None or valid is not None
-        return SceneVectors(mask, ops.scene_rings(mask, connectivity, self.nodata_label if plane_in_play else None, values))
+        ignore = self.nodata_label if self.nodata is not None or valid is not None else None
+        rings = ops.scene_rings(mask, connectivity, ignore, values)
+        if simplify is not None:
+            rings = ops.scene_rings_simplify(rings, mask, simplify, ignore, values)
+        return SceneVectors(mask, rings)
