@@ -2,6 +2,7 @@
 // HBM-bound: one thread per (pixel, 4-channel vector); f32 arithmetic; gather formulation in
 // both directions (no atomics -> deterministic backward).
 #include "gdl_common.h"
+#include <atomic>
 #include <type_traits>
 
 namespace {
@@ -1237,6 +1238,8 @@ __global__ __launch_bounds__(256, PXB == 8 ? 3 : 4) void resize_conv3x3_fwd_sum_
 // ---- what versions 2 and 3 share: the output tile, and the counted waits of their steady state.
 // A step's outputs leave through an LDS tile of 4 rows x `cols` pixels x 64 bf16 channels (128 bytes), 16 bytes per thread and store.
 constexpr int tap_tile_bytes(int cols) { return 4 * cols * 128; }
+// the low-resolution window of a 4 x cols block of a factor-2^lf source; the staging loops write whole 1 KiB pieces (8 rows): rounded up to that
+constexpr int tap_window_bytes(int cols, int lf) { return ((lf == 1 ? 4 : 3) * (((cols - 4) >> lf) + (lf == 1 ? 4 : 3)) * 9 * 128 + 1023) / 1024 * 1024; }
 constexpr int kTapTileBytes = tap_tile_bytes(16);          // version 3 (and version 2 at PXB = 4): 4 x 16 pixels
 constexpr int tap_stores_per_flush(int tile_bytes, int threads) { return tile_bytes / (threads * 16); }
 constexpr int kTapM2Threads = 256, kRollThreads = 256, kRoll3Threads = 512;   // workgroup sizes: launch bounds, store loops, launcher
@@ -2458,137 +2461,202 @@ extern "C" int gdl_resize_conv3x3_bwd_gather_bn(const void* dz, const void* x, i
   return GDL_OK;
 }
 
-// shared launcher; stats != nullptr: per-block partial sums of the outputs ([rows][2][N] f32, rows = gdl_resize_conv3x3_fwd_sum_bn_rows)
 static int g_tapsum_persist = 1;
 extern "C" void gdl_debug_set_tapsum_persist(int on) { g_tapsum_persist = on; }  // A/B hook: 0 = one workgroup per patch (round 3)
+static std::atomic<int> g_tapsum_cus{0};       // the device's CU count once a launch has asked for it
 static int tapsum_num_cus() {
   static int n = [] {
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
       cus = 256;
+    g_tapsum_cus.store(cus);
     return cus;
   }();
   return n;
 }
 static int g_tapsum_roll = 1;
 constexpr int kRollDepth4 = 3;    // factor 4: steps the row fetches of version 3 run ahead (ring of RollSrc<2, depth>::NSLOT = 3 + depth slots, three workgroups per CU)
+constexpr int kRoll3Depth = 2;    // the same for the three rings of roll3
 extern "C" void gdl_debug_set_tapsum_roll(int on) { g_tapsum_roll = on; }  // A/B hook: 0 = versions 1 / 2 where version 3 (rolling row window) applies
-// stat_rows (with stats): the number of partial rows the launch wrote (<= gdl_resize_conv3x3_fwd_sum_bn_rows)
-static int tapsum_launch(const void* const* zs, const int* hs, const int* ws, int nsrc, int dtype, int B, int N, void* out, int Ho, int Wo,
-                         const float* addvec, int relu, float* stats, hipStream_t st, int64_t* stat_rows = nullptr) {
-  GDL_CHECK_ARG(zs && hs && ws && out && nsrc >= 1 && nsrc <= 3, "gdl_resize_conv3x3_fwd_sum: 1..3 sources");
+
+// The form of the forward gather-sum for one call: what tapsum_launch runs and what gdl_resize_conv3x3_fwd_sum_plan reports.
+// Every choice between kernels, template instantiations and grid shapes is made HERE (from the shape, the hooks and the CU
+// count); the launcher only fills argument structs from it.
+enum { TAP_VALU = 0, TAP_V1 = 1, TAP_V2 = 2, TAP_ROLL = 3, TAP_ROLL3 = 4 };
+struct TapPlan {
+  int kind;            // TAP_*
+  int p, q;            // VALU: elements per vector (4 / 8), pixels per run (2 / 4 / 8); version 1: 16-column units per block (1 / 2), 0;
+                       // version 2: NSRC, LF of the instantiation (0 for several sources); rolling window: LF, depth; roll3: 3, depth
+  int walks;           // a workgroup takes more than one patch (version 2: the persistent grid) / column (rolling forms)
+  int F[3], LF[3], run, lfmin;
+  int nblk, grid;      // version 2: patches, workgroups launched; rolling window: columns, 8 * G * nstrips; roll3: columns, streams * nstrips
+  int G;               // rolling window: column groups per XCD; roll3: streams
+  int code() const { return 1000 * kind + 100 * p + 10 * q + walks; }
+};
+// out16 / add16: out / addvec are 16-byte aligned (every kernel stores vectors; the matrix-core kernels load the addend as vectors)
+static int tapsum_plan(const int* hs, const int* ws, int nsrc, int dtype, int B, int N, int Ho, int Wo, bool stats, bool out16, bool add16,
+                       int cus, TapPlan& t) {
+  GDL_CHECK_ARG(hs && ws && nsrc >= 1 && nsrc <= 3, "gdl_resize_conv3x3_fwd_sum: 1..3 sources");
   GDL_CHECK_ARG(dtype == GDL_F32 || dtype == GDL_BF16, "gdl_resize_conv3x3_fwd_sum: bad dtype");
   GDL_CHECK_ARG(B > 0 && Ho > 0 && Wo > 0 && N > 0, "gdl_resize_conv3x3_fwd_sum: bad sizes");
-  TapSrc s;
-  int run = 2;
-  for (int k = 0; k < 3; ++k) {
-    s.p[k] = nullptr; s.H[k] = 1; s.W[k] = 1; s.F[k] = 0;
-    if (k >= nsrc) continue;
-    GDL_CHECK_ARG(zs[k] && hs[k] > 0 && ws[k] > 0 && (uintptr_t)zs[k] % 16 == 0, "gdl_resize_conv3x3_fwd_sum: bad source %d", k);
+  t = TapPlan{};
+  t.run = 2; t.lfmin = 3;
+  bool img_ok = out16;
+  for (int k = 0; k < nsrc; ++k) {
+    GDL_CHECK_ARG(hs[k] > 0 && ws[k] > 0, "gdl_resize_conv3x3_fwd_sum: bad source %d", k);
     const int f = Ho / hs[k];
     GDL_CHECK_ARG((f == 2 || f == 4 || f == 8) && hs[k] * f == Ho && ws[k] * f == Wo,
                   "gdl_resize_conv3x3_fwd_sum: source %d: the resize factor must be 2, 4 or 8 in both directions", k);
-    s.p[k] = zs[k]; s.H[k] = hs[k]; s.W[k] = ws[k]; s.F[k] = f;
-    run = f > run ? f : run;
+    t.F[k] = f; t.LF[k] = f == 8 ? 3 : (f == 4 ? 2 : 1);
+    t.run = f > t.run ? f : t.run;
+    t.lfmin = t.LF[k] < t.lfmin ? t.LF[k] : t.lfmin;
+    img_ok = img_ok && (int64_t)hs[k] * ws[k] * 9 * N * 2 < 0x7ffffff0ll;   // 32-bit buffer offsets per image
   }
-  GDL_CHECK_ARG(Wo % run == 0, "gdl_resize_conv3x3_fwd_sum: Wo must be a multiple of the largest factor");
-  bool img_ok = (uintptr_t)out % 16 == 0;
-  for (int k = 0; k < nsrc; ++k) img_ok = img_ok && (int64_t)s.H[k] * s.W[k] * 9 * N * 2 < 0x7ffffff0ll;   // 32-bit buffer offsets per image
-  const bool mfma_ok = dtype == GDL_BF16 && N % 64 == 0 && img_ok && (int64_t)B * ((Ho + 3) / 4) <= 65535 && (uintptr_t)addvec % 16 == 0;
+  for (int k = nsrc; k < 3; ++k) t.LF[k] = 1;      // (unused sources: as factor 0 always was)
+  GDL_CHECK_ARG(Wo % t.run == 0, "gdl_resize_conv3x3_fwd_sum: Wo must be a multiple of the largest factor");
+  const bool mfma_ok = dtype == GDL_BF16 && N % 64 == 0 && img_ok && (int64_t)B * ((Ho + 3) / 4) <= 65535 && add16;
   GDL_CHECK_ARG(!stats || mfma_ok, "gdl_resize_conv3x3_fwd_sum_bn: needs bf16, N %% 64 == 0, 16-byte aligned output and per-channel "
                 "addend (bias), sources below 2 GiB per image, B * ceil(Ho / 4) <= 65535");
   if (mfma_ok && (g_tapsum_mfma || stats)) {
+    const int nstrips = (Wo + 15) / 16, ncols = B * (N / 64);
+    // version 3 for the three upsampled levels of fpn_bottleneck: factors 2, 4, 8 in that order, whole cells of the coarsest one
+    if (g_tapsum_roll && !stats && nsrc == 3 && t.LF[0] == 1 && t.LF[1] == 2 && t.LF[2] == 3 && Ho % 8 == 0 && g_tapsum_mfma == 1) {
+      int streams = cus / nstrips;            // one workgroup per CU
+      if (streams > ncols) streams = ncols;
+      if (streams < 1) streams = 1;
+      t.kind = TAP_ROLL3; t.p = 3; t.q = kRoll3Depth;
+      t.nblk = ncols; t.G = streams; t.grid = streams * nstrips; t.walks = ncols > streams;
+      return GDL_OK;
+    }
+    // version 3 (rolling row window): one source of factor 2 or 4 whose output rows come in whole patches
+    if (g_tapsum_roll && nsrc == 1 && (t.LF[0] == 1 || t.LF[0] == 2) && Ho % 4 == 0 && Ho >= 8 && (g_tapsum_mfma == 1 || stats)) {
+      const int occ = t.LF[0] == 2 ? 3 : 2, slots = cus / 8 * occ;         // resident workgroups per XCD (launch bounds)
+      int G = slots / nstrips;
+      if (G > (ncols + 7) / 8) G = (ncols + 7) / 8;
+      if (G < 1) G = 1;
+      t.kind = TAP_ROLL; t.p = t.LF[0]; t.q = t.LF[0] == 2 ? (g_tapsum_roll == 2 ? 1 : kRollDepth4) : 1;      // (roll hook 2, A/B: one step ahead)
+      t.nblk = ncols; t.G = G; t.grid = 8 * G * nstrips; t.walks = ncols > 8 * G;
+      return GDL_OK;
+    }
+    // version 2 (all channels of a 4 x 16 pixel block per workgroup, windows double-buffered) where three blocks fit a CU: ONE
+    // source of factor 4 or 8 (measured on the neck's x4 level: 442 us against 768; with the 46 KiB windows of a factor-2
+    // source, or three sources, one block per CU remains and version 1 is the faster one: 284 vs 315 us, 693 vs 1148 us);
+    // always for the statistics variant
+    const bool v2_pays = nsrc == 1 && t.lfmin >= 2;
+    if ((g_tapsum_mfma == 1 && v2_pays) || g_tapsum_mfma == 5 || stats) {
+      const int cols = 16;   // (4 x 32 blocks: the cached fragments of two patches per wave do not fit the register budget)
+      size_t ring = 0;
+      for (int j = 0; j < (nsrc == 1 ? 2 : nsrc); ++j) ring += tap_window_bytes(cols, t.LF[nsrc == 1 ? 0 : j]);
+      const size_t lds = (size_t)nsrc * (256 + cols * 64) + tap_tile_bytes(cols) + ring;
+      GDL_CHECK_ARG(lds <= 160 * 1024 || !stats, "gdl_resize_conv3x3_fwd_sum_bn: LDS budget exceeded");
+      if (lds <= 160 * 1024) {        // (always, for 1..3 sources of factors 2 / 4 / 8; version 1 below would take over)
+        const int resident = cus * (nsrc == 1 ? 3 : 1);       // workgroups a launch keeps resident (launch bounds)
+        t.kind = TAP_V2; t.p = nsrc; t.q = nsrc == 1 ? t.LF[0] : 0;
+        t.nblk = ((Wo + cols - 1) / cols) * B * ((Ho + 3) / 4);
+        t.walks = g_tapsum_persist && t.nblk > resident;
+        t.grid = t.walks ? resident : t.nblk;
+        return GDL_OK;
+      }
+    }
+    // version 1: one block = 4 rows x 16 or 32 columns x 64 channels; 32 columns when every window stays under 48 KiB
+    t.kind = TAP_V1; t.p = (tap_window_bytes(32, t.lfmin) <= 48 * 1024 && g_tapsum_mfma != 4) ? 2 : 1;
+    return GDL_OK;
+  }
+  t.kind = TAP_VALU; t.p = dtype == GDL_BF16 ? 8 : 4; t.q = t.run;
+  // 16-byte vectors with 8-pixel runs need more than 256 registers: 8-byte vectors there (and wherever N % 8 != 0)
+  if (dtype == GDL_BF16 && (g_tapsum_vec == 4 || N % 8 != 0 || (t.run == 8 && g_tapsum_vec != 8))) t.p = 4;
+  GDL_CHECK_ARG(N % t.p == 0 && out16, "gdl_resize_conv3x3_fwd_sum: N must be a multiple of 4, out 16-byte aligned");
+  GDL_CHECK_ARG((int64_t)B * Ho <= 65535, "gdl_resize_conv3x3_fwd_sum: B * Ho must fit one grid dimension");
+  return GDL_OK;
+}
+
+// The form gdl_resize_conv3x3_fwd_sum (with_stats: gdl_resize_conv3x3_fwd_sum_bn) takes for this call, for 16-byte aligned
+// pointers, under the current gdl_debug_set_tapsum_* hooks: see include/gdlhip.h for the code.  A pure host query: no launch, no
+// call into the HIP runtime -- the CU count is the one the launcher has seen, 256 (the MI355X's) before its first launch.
+extern "C" int gdl_resize_conv3x3_fwd_sum_plan(const int* hs, const int* ws, int nsrc, int dtype, int B, int N, int Ho, int Wo,
+                                               int with_stats) {
+  TapPlan t;
+  const int cus = g_tapsum_cus.load();
+  if (tapsum_plan(hs, ws, nsrc, dtype, B, N, Ho, Wo, with_stats != 0, true, true, cus > 0 ? cus : 256, t) != GDL_OK) return -1;
+  return t.code();
+}
+
+// shared launcher; stats != nullptr: per-block partial sums of the outputs ([rows][2][N] f32, rows = gdl_resize_conv3x3_fwd_sum_bn_rows)
+// stat_rows (with stats): the number of partial rows the launch wrote (<= gdl_resize_conv3x3_fwd_sum_bn_rows)
+static int tapsum_launch(const void* const* zs, const int* hs, const int* ws, int nsrc, int dtype, int B, int N, void* out, int Ho, int Wo,
+                         const float* addvec, int relu, float* stats, hipStream_t st, int64_t* stat_rows = nullptr) {
+  GDL_CHECK_ARG(zs && out, "gdl_resize_conv3x3_fwd_sum: 1..3 sources");
+  TapPlan t;
+  const int status = tapsum_plan(hs, ws, nsrc, dtype, B, N, Ho, Wo, stats != nullptr, (uintptr_t)out % 16 == 0, (uintptr_t)addvec % 16 == 0,
+                                 tapsum_num_cus(), t);
+  if (status != GDL_OK) return status;
+  for (int k = 0; k < nsrc; ++k)
+    GDL_CHECK_ARG(zs[k] && (uintptr_t)zs[k] % 16 == 0, "gdl_resize_conv3x3_fwd_sum: bad source %d", k);
+  if (t.kind != TAP_VALU) {
     TapMArgs m;
-    int lfmin = 3;
     for (int k = 0; k < 3; ++k) {
-      m.z[k] = (const uint16_t*)s.p[k]; m.H[k] = s.H[k]; m.W[k] = s.W[k];
-      m.LF[k] = s.F[k] == 8 ? 3 : (s.F[k] == 4 ? 2 : 1);
-      if (k < nsrc && m.LF[k] < lfmin) lfmin = m.LF[k];
+      m.z[k] = k < nsrc ? (const uint16_t*)zs[k] : nullptr; m.H[k] = k < nsrc ? hs[k] : 1; m.W[k] = k < nsrc ? ws[k] : 1;
+      m.LF[k] = t.LF[k];
     }
     m.nsrc = nsrc; m.N = N; m.Ho = Ho; m.Wo = Wo; m.B = B; m.out = (uint16_t*)out; m.addvec = addvec; m.relu = relu;
     m.nslots = 0; m.slot_off[0] = m.slot_off[1] = m.slot_off[2] = 0;
     if (stat_rows) *stat_rows = (int64_t)B * ((Ho + 3) / 4) * ((Wo + 15) / 16);
-    // version 3 for the three upsampled levels of fpn_bottleneck: factors 2, 4, 8 in that order, whole cells of the coarsest one
-    if (g_tapsum_roll && !stats && nsrc == 3 && m.LF[0] == 1 && m.LF[1] == 2 && m.LF[2] == 3 && Ho % 8 == 0 && g_tapsum_mfma == 1) {
-      constexpr int D3 = 2;
+    if (t.kind == TAP_ROLL3) {
       TapR3Args r;
       for (int k = 0; k < 3; ++k) { r.z[k] = m.z[k]; r.H[k] = m.H[k]; r.W[k] = m.W[k]; }
       r.out = m.out; r.addvec = addvec; r.N = N; r.Ho = Ho; r.Wo = Wo; r.B = B; r.relu = relu;
-      r.nstrips = (Wo + 15) / 16; r.nchunks = N / 64; r.ncols = B * r.nchunks;
-      int streams = tapsum_num_cus() / r.nstrips;            // one workgroup per CU
-      if (streams > r.ncols) streams = r.ncols;
-      if (streams < 1) streams = 1;
-      r.nstreams = streams; r.nblocks = streams * r.nstrips;
+      r.nstrips = (Wo + 15) / 16; r.nchunks = N / 64; r.ncols = t.nblk;
+      r.nstreams = t.G; r.nblocks = t.grid;
       r.dbg = g_tapsum_roll >= 16 ? g_tapsum_roll : 0;
-      GDL_SET_MAX_LDS_ONCE((resize_conv3x3_fwd_sum_roll3_kernel<D3>), 160 * 1024);
-      hipLaunchKernelGGL((resize_conv3x3_fwd_sum_roll3_kernel<D3>), dim3((unsigned)r.nblocks), dim3(kRoll3Threads), (size_t)Roll3Lds<D3>::BYTES, st, r);
+      GDL_SET_MAX_LDS_ONCE((resize_conv3x3_fwd_sum_roll3_kernel<kRoll3Depth>), 160 * 1024);
+      hipLaunchKernelGGL((resize_conv3x3_fwd_sum_roll3_kernel<kRoll3Depth>), dim3((unsigned)r.nblocks), dim3(kRoll3Threads),
+                         (size_t)Roll3Lds<kRoll3Depth>::BYTES, st, r);
       GDL_CHECK_LAUNCH("gdl_resize_conv3x3_fwd_sum");
       return GDL_OK;
     }
-    // version 3 (rolling row window): one source of factor 2 or 4 whose output rows come in whole patches
-    if (g_tapsum_roll && nsrc == 1 && (m.LF[0] == 1 || m.LF[0] == 2) && Ho % 4 == 0 && Ho >= 8 && (g_tapsum_mfma == 1 || stats)) {
+    if (t.kind == TAP_ROLL) {
       TapRArgs r;
       r.z = m.z[0]; r.out = m.out; r.addvec = addvec; r.stats = stats;
       r.Hi = m.H[0]; r.Wi = m.W[0]; r.N = N; r.Ho = Ho; r.Wo = Wo; r.B = B; r.relu = relu;
-      r.nstrips = (Wo + 15) / 16; r.nchunks = N / 64; r.ncols = B * r.nchunks;
-      const int occ = m.LF[0] == 2 ? 3 : 2, slots = tapsum_num_cus() / 8 * occ;         // resident workgroups per XCD (launch bounds)
-      int G = slots / r.nstrips;
-      if (G > (r.ncols + 7) / 8) G = (r.ncols + 7) / 8;
-      if (G < 1) G = 1;
-      r.G = G;
-      const dim3 grid((unsigned)(8 * G * r.nstrips));
+      r.nstrips = (Wo + 15) / 16; r.nchunks = N / 64; r.ncols = t.nblk;
+      r.G = t.G;
+      const dim3 grid((unsigned)t.grid);
       // (the dynamic LDS -- the tile and the ring -- is read off the RollSrc the instantiation indexes by)
 #define TAPR(LF_, ST_, D_) do { constexpr size_t lds = kTapTileBytes + RollSrc<LF_, D_>::BYTES;                                          \
     static_assert(lds <= 160 * 1024, "LDS budget");                                                                                      \
     GDL_SET_MAX_LDS_ONCE((resize_conv3x3_fwd_sum_roll_kernel<LF_, ST_, D_>), 160 * 1024);                                                \
     hipLaunchKernelGGL((resize_conv3x3_fwd_sum_roll_kernel<LF_, ST_, D_>), grid, dim3(kRollThreads), lds, st, r); } while (0)
-      if (m.LF[0] == 2 && g_tapsum_roll == 2) { if (stats) TAPR(2, true, 1); else TAPR(2, false, 1); }      // (A/B: one step ahead)
-      else if (m.LF[0] == 2) { if (stats) TAPR(2, true, kRollDepth4); else TAPR(2, false, kRollDepth4); }
+      if (t.p == 2 && t.q == 1) { if (stats) TAPR(2, true, 1); else TAPR(2, false, 1); }      // (A/B: one step ahead)
+      else if (t.p == 2) { if (stats) TAPR(2, true, kRollDepth4); else TAPR(2, false, kRollDepth4); }
       else { if (stats) TAPR(1, true, 1); else TAPR(1, false, 1); }
 #undef TAPR
       if (stat_rows) *stat_rows = (int64_t)B * r.nstrips;
       GDL_CHECK_LAUNCH("gdl_resize_conv3x3_fwd_sum");
       return GDL_OK;
     }
-    // the staging loop writes whole 1 KiB pieces (8 rows): round a window up to that
-    auto window_bytes_lf = [&](int cols, int lf) { const int win = lf == 1 ? 4 : 3; return (win * (((cols - 4) >> lf) + win) * 9 * 128 + 1023) / 1024 * 1024; };
-    // version 2 (all channels of a 4 x 16 pixel block per workgroup, windows double-buffered) where three blocks fit a CU: ONE
-    // source of factor 4 or 8 (measured on the neck's x4 level: 442 us against 768; with the 46 KiB windows of a factor-2
-    // source, or three sources, one block per CU remains and version 1 is the faster one: 284 vs 315 us, 693 vs 1148 us);
-    // always for the statistics variant
-    const bool v2_pays = nsrc == 1 && lfmin >= 2;
-    if ((g_tapsum_mfma == 1 && v2_pays) || g_tapsum_mfma == 5 || stats) {
-      const int pxb = 4, cols = 4 * pxb;   // (4 x 32 blocks: the cached fragments of two patches per wave do not fit the register budget)
+    if (t.kind == TAP_V2) {
+      const int cols = 16;
       int ring = 0;
       m.nslots = nsrc == 1 ? 2 : nsrc;
-      for (int j = 0; j < m.nslots; ++j) { m.slot_off[j] = ring; ring += window_bytes_lf(cols, m.LF[nsrc == 1 ? 0 : j]); }
+      for (int j = 0; j < m.nslots; ++j) { m.slot_off[j] = ring; ring += tap_window_bytes(cols, m.LF[nsrc == 1 ? 0 : j]); }
       const size_t lds = (size_t)nsrc * (256 + cols * 64) + tap_tile_bytes(cols) + ring;
-      GDL_CHECK_ARG(lds <= 160 * 1024 || !stats, "gdl_resize_conv3x3_fwd_sum_bn: LDS budget exceeded");
       m.gx = (Wo + cols - 1) / cols;
-      m.nblk = m.gx * B * ((Ho + 3) / 4);
-      const int resident = tapsum_num_cus() * (nsrc == 1 ? 3 : 1);       // workgroups a launch keeps resident (launch bounds)
-      const dim3 grid((unsigned)(g_tapsum_persist && m.nblk > resident ? resident : m.nblk));
-      if (lds > 160 * 1024) {
-        // (does not happen for 1..3 sources of factors 2 / 4 / 8; version 1 below would take over)
-      } else
+      m.nblk = t.nblk;
+      const dim3 grid((unsigned)t.grid);
 #define TAPM2(PXB_, NSRC_, LF_) do { GDL_SET_MAX_LDS_ONCE((resize_conv3x3_fwd_sum_mfma2_kernel<PXB_, NSRC_, LF_>), 160 * 1024);                 \
     hipLaunchKernelGGL((resize_conv3x3_fwd_sum_mfma2_kernel<PXB_, NSRC_, LF_>), grid, dim3(kTapM2Threads), lds, st, m, stats); } while (0)
-      if (nsrc == 1 && m.LF[0] == 2) TAPM2(4, 1, 2); else if (nsrc == 1 && m.LF[0] == 3) TAPM2(4, 1, 3); else if (nsrc == 1) TAPM2(4, 1, 1);
-      else if (nsrc == 2) TAPM2(4, 2, 0); else TAPM2(4, 3, 0);
+      if (t.p == 1 && t.q == 2) TAPM2(4, 1, 2); else if (t.p == 1 && t.q == 3) TAPM2(4, 1, 3); else if (t.p == 1) TAPM2(4, 1, 1);
+      else if (t.p == 2) TAPM2(4, 2, 0); else TAPM2(4, 3, 0);
 #undef TAPM2
-      if (lds <= 160 * 1024) {
-        GDL_CHECK_LAUNCH("gdl_resize_conv3x3_fwd_sum");
-        return GDL_OK;
-      }
+      GDL_CHECK_LAUNCH("gdl_resize_conv3x3_fwd_sum");
+      return GDL_OK;
     }
-    // version 1: one block = 4 rows x 16 or 32 columns x 64 channels; 32 columns when every window stays under 48 KiB
-    auto window_bytes = [&](int cols) { return window_bytes_lf(cols, lfmin); };
-    const int pxb = (window_bytes(32) <= 48 * 1024 && g_tapsum_mfma != 4) ? 8 : 4;
-    const int cols = 4 * pxb;
-    const int tile_bytes = tap_tile_bytes(cols);
-    const size_t lds = 256 + cols * 64 + (size_t)(window_bytes(cols) > tile_bytes ? window_bytes(cols) : tile_bytes);
+    // version 1: one block = 4 rows x 16 or 32 columns x 64 channels
+    const int cols = 16 * t.p;
+    const int tile_bytes = tap_tile_bytes(cols), window = tap_window_bytes(cols, t.lfmin);
+    const size_t lds = 256 + cols * 64 + (size_t)(window > tile_bytes ? window : tile_bytes);
     const dim3 grid((unsigned)(((Wo + cols - 1) / cols) * (N / 64)), (unsigned)(B * ((Ho + 3) / 4)));
-    if (pxb == 8) {
+    if (t.p == 2) {
       GDL_SET_MAX_LDS_ONCE(resize_conv3x3_fwd_sum_mfma_kernel<8>, 160 * 1024);
       hipLaunchKernelGGL(resize_conv3x3_fwd_sum_mfma_kernel<8>, grid, dim3(256), lds, st, m);
     } else {
@@ -2598,11 +2666,11 @@ static int tapsum_launch(const void* const* zs, const int* hs, const int* ws, in
     GDL_CHECK_LAUNCH("gdl_resize_conv3x3_fwd_sum");
     return GDL_OK;
   }
-  int vec = dtype == GDL_BF16 ? 8 : 4;
-  // 16-byte vectors with 8-pixel runs need more than 256 registers: 8-byte vectors there (and wherever N % 8 != 0)
-  if (dtype == GDL_BF16 && (g_tapsum_vec == 4 || N % 8 != 0 || (run == 8 && g_tapsum_vec != 8))) vec = 4;
-  GDL_CHECK_ARG(N % vec == 0 && (uintptr_t)out % 16 == 0, "gdl_resize_conv3x3_fwd_sum: N must be a multiple of 4, out 16-byte aligned");
-  GDL_CHECK_ARG((int64_t)B * Ho <= 65535, "gdl_resize_conv3x3_fwd_sum: B * Ho must fit one grid dimension");
+  TapSrc s;
+  for (int k = 0; k < 3; ++k) {
+    s.p[k] = k < nsrc ? zs[k] : nullptr; s.H[k] = k < nsrc ? hs[k] : 1; s.W[k] = k < nsrc ? ws[k] : 1; s.F[k] = k < nsrc ? t.F[k] : 0;
+  }
+  const int vec = t.p, run = t.run;
   const dim3 grid((unsigned)(((Wo / run) * (N / vec) + 255) / 256), (unsigned)(B * Ho));
 #define TAPSUM(V, VEC, RUN) hipLaunchKernelGGL((resize_conv3x3_fwd_sum_kernel<V, VEC, RUN>), grid, dim3(256), 0, st, s, nsrc, N, out, \
                                                Ho, Wo, addvec, relu)

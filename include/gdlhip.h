@@ -367,6 +367,18 @@ int64_t gdl_resize_conv3x3_fwd_sum_bn_rows(int B, int Ho, int Wo);
 int gdl_resize_conv3x3_fwd_sum_bn(const void* const* zs, const int* hs, const int* ws, int nsrc, int dtype, int B, int N, void* out,
                                   int Ho, int Wo, const float* addvec, float* workspace, int64_t ws_bytes, float* mean, float* var,
                                   float* running_mean, float* running_var, float momentum, gdl_stream_t stream);
+/* Which kernel form gdl_resize_conv3x3_fwd_sum (with_stats != 0: gdl_resize_conv3x3_fwd_sum_bn) runs for this call with
+ * 16-byte aligned pointers, under the current gdl_debug_set_tapsum_* hooks -- the launcher's own decision, not a copy of it.
+ * 1000 * kind + 100 * p + 10 * q + walks:
+ *   kind 0  pixel-by-pixel (VALU) kernel   p = elements per vector (4 / 8), q = output pixels per run (2 / 4 / 8)
+ *   kind 1  matrix cores, version 1        p = 16-column units per block (1 / 2), q = 0
+ *   kind 2  matrix cores, version 2        p = sources of the instantiation, q = its LF (log2 factor; 0 for 2 / 3 sources)
+ *   kind 3  rolling row window             p = LF (1 / 2), q = steps the row fetches run ahead
+ *   kind 4  three rolling rings (roll3)    p = 3, q = steps the row fetches run ahead
+ *   walks = 1: a workgroup takes more than one patch (version 2: the persistent grid) or column (kinds 3, 4).
+ * -1 for arguments the launcher refuses (gdl_last_error says why).  A host-only query: it launches nothing and does not touch
+ * the HIP runtime; `walks` counts on the CU count the launcher has seen, 256 (the MI355X's) before its first launch. */
+int gdl_resize_conv3x3_fwd_sum_plan(const int* hs, const int* ws, int nsrc, int dtype, int B, int N, int Ho, int Wo, int with_stats);
 /* final reduction of [nsplit][2][C] partial sums (sum, sum of squares over P pixels in total) into mean / biased variance
  * (+ running statistics): the second half of gdl_bn_stats, for producers that emit the partials themselves */
 int gdl_bn_stats_finalize(const float* partials, int nsplit, int C, int64_t P, float* mean, float* var, float* running_mean,

@@ -68,7 +68,7 @@ def test_parsed_signatures_spot_checks():
     from gdlhip import _lib
     i, l, f, d, p = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_void_p
     sig = _lib.SIGNATURES
-    assert len(sig) == 187 and not any(n.startswith("gdl_debug_") for n in sig)
+    assert len(sig) == 188 and not any(n.startswith("gdl_debug_") for n in sig)
     tensor = [p, l, l]                  # a pointer with its batch and token strides
     want = [*tensor * 5, p, p, *tensor * 3, i, i, i, i, f, p, l, p]
     assert len(want) == 34 and sig["gdl_flash_attn_bwd"] == (i, want)
@@ -88,6 +88,7 @@ def test_parsed_signatures_spot_checks():
     assert sig["gdl_overlap_loss_fwd"] == sig["gdl_dice_loss_opt_fwd"]
     assert sig["gdl_dice_loss_workspace"] == (l, [i, i, l])
     assert sig["gdl_resize_conv3x3_bwd_gather_one_pass"] == (i, [i] * 7)
+    assert sig["gdl_resize_conv3x3_fwd_sum_plan"] == (i, [p, p, i, i, i, i, i, i, i])              # const int*: a host array
     # struct fields: `in` is spelled inp, a run `int B, H, W, C` is four fields, `classes` is a typed host pointer
     conv = dict(_lib.ConvArgs._fields_)
     assert [n for n, _ in _lib.ConvArgs._fields_][:6] == ["inp", "dtype", "B", "H", "W", "C"]
@@ -141,7 +142,7 @@ def test_checked_view_raises_what_check_raises(monkeypatch):
     import ctypes as C
     from gdlhip import _lib
     queries = {"gdl_version", "gdl_conv_gemm_plan", "gdl_resize_conv3x3_bwd_gather_one_pass", "gdl_bilinear_fwd_add_bn_ok",
-               "gdl_head_1x1_bn_ok", "gdl_bn_head_bwd_ok"}
+               "gdl_head_1x1_bn_ok", "gdl_bn_head_bwd_ok", "gdl_resize_conv3x3_fwd_sum_plan"}
     text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "gdlhip.h").read_text(), flags=re.S)
     for name, (res, _) in _lib.SIGNATURES.items():
         decl = re.search(r"\b" + name + r"\s*\(([^)]*)\)", text).group(1)
