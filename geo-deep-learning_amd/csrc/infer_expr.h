@@ -1,5 +1,6 @@
-// The two per-element expressions of the inference path, each defined once for the kernels that must agree on them bit for bit:
-// misc.hip (gdl_normalize_range, gdl_upsample_probs) and scene.hip (gdl_scene_cut, gdl_scene_blend_lowres).
+// The per-element expressions of the inference path, each defined once for the kernels that must agree on them bit for bit:
+// misc.hip (gdl_normalize_range, gdl_upsample_probs), scene.hip (gdl_scene_cut, gdl_scene_blend_lowres, gdl_scene_finish) and
+// scene_regions.hip (gdl_scene_regions_stats).
 #pragma once
 #include "gdl_common.h"
 
@@ -18,6 +19,11 @@ struct RangeScalars { float imin, span, d, nmin; };
 inline RangeScalars range_scalars(int image_min, int image_max, double norm_min, double norm_max) {
   return {(float)image_min, (float)((int64_t)image_max - (int64_t)image_min), (float)(norm_max - norm_min), (float)norm_min};
 }
+
+// the probability a canvas holds for one class at one pixel: the class's weighted sum over the weight sum, 0 where the pixel is
+// not live (weight 0, or invalid by the plane of gdl_scene_finish_valid).  What gdl_scene_finish writes to `probs`, and what
+// gdl_scene_regions_stats (scene_regions.hip) turns into a pixel's confidence.
+__device__ __forceinline__ float canvas_prob(float c, float den, bool live) { return live ? c / den : 0.f; }
 
 // K logits -> class probabilities in place: 1 / (1 + exp(-x)) for one class, otherwise the softmax with the maximum subtracted
 template <int K>

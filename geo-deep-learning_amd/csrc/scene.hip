@@ -348,7 +348,7 @@ __global__ __launch_bounds__(256) void scene_finish_kernel(const float* __restri
       VecF q;
 #pragma unroll
       for (int e = 0; e < V; ++e) {
-        q.v[e] = live(e) ? c.v[e] / den.v[e] : 0.f;
+        q.v[e] = canvas_prob(c.v[e], den.v[e], live(e));
         if (k == 0) { best_v[e] = c.v[e]; best[e] = 0; first[e] = q.v[e]; }
         else if (c.v[e] > best_v[e]) { best_v[e] = c.v[e]; best[e] = k; }
       }

@@ -142,11 +142,13 @@ _SCENE_NODATA = Header((INCLUDE / "gdlhip_scene_nodata.h").read_text())
 _SCENE_SIEVE = Header((INCLUDE / "gdlhip_scene_sieve.h").read_text())
 _SCENE_RINGS = Header((INCLUDE / "gdlhip_scene_rings.h").read_text())
 _SCENE_SIMPLIFY = Header((INCLUDE / "gdlhip_scene_simplify.h").read_text())
+_SCENE_REGIONS = Header((INCLUDE / "gdlhip_scene_regions.h").read_text())
 
 # name -> (restype, argtypes); every symbol declared in include/gdlhip.h, the gdl_debug_* hooks of include/gdlhip_debug.h, the
 # whole-scene inference calls of include/gdlhip_scene.h, their test-time augmentation forms of include/gdlhip_scene_tta.h, the
 # nodata calls of include/gdlhip_scene_nodata.h, the components and sieve calls of include/gdlhip_scene_sieve.h, the polygon
-# ring calls of include/gdlhip_scene_rings.h and their simplification of include/gdlhip_scene_simplify.h
+# ring calls of include/gdlhip_scene_rings.h, their simplification of include/gdlhip_scene_simplify.h and the per-region
+# attributes of include/gdlhip_scene_regions.h
 SIGNATURES, DEBUG_SIGNATURES, SCENE_SIGNATURES = _ABI.functions, _DEBUG.functions, _SCENE.functions
 SCENE_TTA_SIGNATURES, SCENE_NODATA_SIGNATURES = _SCENE_TTA.functions, _SCENE_NODATA.functions
 SCENE_SIEVE_SIGNATURES, SCENE_RINGS_SIGNATURES = _SCENE_SIEVE.functions, _SCENE_RINGS.functions
@@ -154,10 +156,14 @@ SCENE_RINGS_SCAN_TILE, SCENE_RINGS_FLAGS = (_SCENE_RINGS.constants[k] for k in (
 SCENE_SIMPLIFY_SIGNATURES = _SCENE_SIMPLIFY.functions
 SCENE_SIMPLIFY_SCAN_TILE, SCENE_SIMPLIFY_ROUNDS = (_SCENE_SIMPLIFY.constants[k] for k in ("GDL_SCENE_SIMPLIFY_SCAN_TILE",
                                                                                           "GDL_SCENE_SIMPLIFY_ROUNDS"))
+SCENE_REGIONS_SIGNATURES = _SCENE_REGIONS.functions
+SCENE_REGIONS_SCAN_TILE, SCENE_REGIONS_TILE, SCENE_REGIONS_TABLE, SCENE_REGIONS_PROBES = (
+    _SCENE_REGIONS.constants[k] for k in ("GDL_SCENE_REGIONS_SCAN_TILE", "GDL_SCENE_REGIONS_TILE", "GDL_SCENE_REGIONS_TABLE",
+                                          "GDL_SCENE_REGIONS_PROBES"))
 STATUS_FUNCTIONS = frozenset(_ABI.status)      # they return a gdl_status; every other function returns a value
 # what checked() gives the errcheck: the scene calls return a gdl_status too
 _CHECKED = (STATUS_FUNCTIONS | _SCENE.status | _SCENE_TTA.status | _SCENE_NODATA.status | _SCENE_SIEVE.status | _SCENE_RINGS.status
-            | _SCENE_SIMPLIFY.status)
+            | _SCENE_SIMPLIFY.status | _SCENE_REGIONS.status)
 ConvArgs, WgradArgs, DiceOptions, OverlapOptions = (_ABI.structs[c] for c in _STRUCTS)
 # the header's enumerators and integer #defines without their GDL_ prefix: F32, BF16, ACT_*, FOCAL_* (the `form` argument of the
 # *_lowres_bwd calls), BCE_TARGET_* (the `target_type` of gdl_soft_bce_*), OVERLAP_* (gdl_overlap_options.kind), ...
@@ -201,7 +207,8 @@ def _open(errcheck=None) -> C.CDLL:
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in (*SIGNATURES.items(), *DEBUG_SIGNATURES.items(), *SCENE_SIGNATURES.items(),
                               *SCENE_TTA_SIGNATURES.items(), *SCENE_NODATA_SIGNATURES.items(), *SCENE_SIEVE_SIGNATURES.items(),
-                              *SCENE_RINGS_SIGNATURES.items(), *SCENE_SIMPLIFY_SIGNATURES.items()):
+                              *SCENE_RINGS_SIGNATURES.items(), *SCENE_SIMPLIFY_SIGNATURES.items(),
+                              *SCENE_REGIONS_SIGNATURES.items()):
         fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
         fn.restype = res
         fn.argtypes = args

@@ -2417,6 +2417,66 @@ def scene_rings_simplify(rings: SceneRings, mask: Tensor, tolerance: float, igno
     return SceneRings(out if n == D else out[:n].clone(), offsets, rings.value, rings.label, rings.start, rings.area2)
 
 
+# the per-region attributes (include/gdlhip_scene_regions.h): what a vector layer says about each polygon
+class SceneRegions(NamedTuple):
+    label: Tensor             # int32 [N]: the region's label (scene_components), ascending
+    value: Tensor             # uint8 [N]: the class of its pixels
+    pixels: Tensor            # int32 [N]: their number
+    bbox: Tensor              # int32 [N, 4]: (x0, y0, x1, y1) in pixel indices, x1 and y1 exclusive
+    sum_xy: Tensor            # int64 [N, 2]: the sums of the pixels' x and of their y
+    conf_sum: Tensor | None   # int64 [N]: the sum of the pixels' confidence q (0 .. 65536 each); None without a canvas
+    conf_min: Tensor | None   # int32 [N]: the smallest q of the region; None without a canvas
+
+
+def scene_regions(mask: Tensor, connectivity: int = 4, ignore_label: int | None = None, canvas: Tensor | None = None,
+                  labels: Tensor | None = None) -> SceneRegions:
+    """The attributes of every region of a uint8 / bool mask [H, W] on the device: one entry per component of
+    ``scene_components`` under ``connectivity`` and ``ignore_label``, in the order of the labels.  ``labels``: the int32 [H, W]
+    labels ``scene_components`` gave for the same mask, connectivity and ignore_label, computed here when None.  ``canvas``: the
+    contiguous f32 [K + 1, H, W] canvas the mask was labelled from (``SceneInference.canvas``), on the mask's device; with it a
+    pixel of class v has the confidence ``q = rint(65536 * canvas[v] / canvas[K])`` (one class: ``1 - canvas[0] / canvas[K]``
+    where v is 0), the quotient being the very expression ``scene_finish`` writes to ``probs``; q is 0 where the weight is 0 or
+    the canvas has no plane for v.  ``conf_sum / (65536 * pixels)`` is the region's mean confidence, ``conf_min / 65536`` its
+    lowest.  Integer sums, minima and maxima alone: exact and the same bits from run to run; no input is modified.  One small
+    device-to-host copy (the number of regions) sizes the arrays; a mask of ignored pixels alone gives empty ones
+    (gdl_scene_regions_count / _stats)."""
+    op = "scene_regions"
+    m, H, W, ignore = _sieve_check(op, mask, connectivity, ignore_label)
+    if labels is not None and (not isinstance(labels, Tensor) or labels.dtype != torch.int32 or tuple(labels.shape) != (H, W)
+                               or not labels.is_contiguous()):
+        got = f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, Tensor) else type(labels).__name__
+        raise ValueError(f"{op}: labels must be a contiguous int32 [H, W] = [{H}, {W}] tensor, got {got}")
+    K = 0
+    if canvas is not None:
+        if not isinstance(canvas, Tensor) or canvas.dtype != torch.float32 or canvas.dim() != 3 or tuple(canvas.shape[1:]) != (H, W) \
+                or not 2 <= canvas.shape[0] <= 256 or not canvas.is_contiguous():
+            got = f"{canvas.dtype} {tuple(canvas.shape)}" if isinstance(canvas, Tensor) else type(canvas).__name__
+            raise ValueError(f"{op}: canvas must be a contiguous f32 [K + 1, H, W] = [2..256, {H}, {W}] tensor, got {got}")
+        if canvas.device != mask.device:
+            raise ValueError(f"{op}: the canvas is on {canvas.device}, the mask on {mask.device}")
+        K = int(canvas.shape[0]) - 1
+    if labels is not None and labels.device != mask.device:
+        raise ValueError(f"{op}: the labels are on {labels.device}, the mask on {mask.device}")
+    _need_cuda(mask, labels, canvas)
+    dev, lib = mask.device, _lib.checked()
+    if labels is None:
+        labels = scene_components(m, connectivity, ignore_label)[0]
+
+    def new(shape: tuple, dtype: torch.dtype) -> Tensor:
+        return torch.empty(shape, device=dev, dtype=dtype)
+
+    rank, n_regions = new((H * W,), torch.int32), new((1,), torch.int32)
+    bsum = new((-(-H * W // _lib.SCENE_REGIONS_SCAN_TILE),), torch.int32)
+    lib.gdl_scene_regions_count(_p(labels), H, W, _p(rank), _p(bsum), _p(n_regions), _stream())
+    N = int(n_regions.item())
+    conf = canvas is not None
+    out = SceneRegions(new((N,), torch.int32), new((N,), torch.uint8), new((N,), torch.int32), new((N, 4), torch.int32),
+                       new((N, 2), torch.int64), new((N,), torch.int64) if conf else None, new((N,), torch.int32) if conf else None)
+    if N > 0:
+        lib.gdl_scene_regions_stats(_p(m), _p(labels), _p(rank), _p(canvas), K, H, W, N, *(_p(t) for t in out), _stream())
+    return out
+
+
 def iou_counts(pred: Tensor, target: Tensor, num_classes: int) -> Tensor:
     """int64 [B, 3, K]: per sample and class (intersection, |pred==k|, |target==k|); exact integer counts."""
     _need_cuda(pred, target)

@@ -4,7 +4,8 @@ those: ``ops.scene_cut_d4`` / ``scene_blend_d4`` / ``scene_blend_lowres_d4``, in
 ``scene_valid`` / ``scene_tile_valid`` / ``scene_cut_valid`` / ``scene_finish_valid`` (include/gdlhip_scene_nodata.h) and, for the sieve
 of the finished mask, ``scene_components`` / ``scene_sieve`` (include/gdlhip_scene_sieve.h) and, for its polygon rings,
 ``scene_rings`` (include/gdlhip_scene_rings.h) and their simplification ``scene_rings_simplify``
-(include/gdlhip_scene_simplify.h), which ``polygons`` here groups into features; the user-facing
+(include/gdlhip_scene_simplify.h), which ``polygons`` here groups into features, and the regions' attributes
+``scene_regions`` (include/gdlhip_scene_regions.h), which ``polygons`` adds to their properties; the user-facing
 class is ``geo_deep_learning.tools.scene_inference.SceneInference``."""
 
 from __future__ import annotations
@@ -111,7 +112,7 @@ def plan_tta(plan: Tensor, codes) -> tuple[Tensor, Tensor]:
 
 
 # ------------------------------------------------------------------ polygons of the rings (include/gdlhip_scene_rings.h)
-def polygons(rings, transform=None) -> list[dict]:
+def polygons(rings, transform=None, regions=None) -> list[dict]:
     """The rings of ``ops.scene_rings`` (anything with its six fields, tensors or arrays) as GeoJSON-style features, one per
     component, ordered by label::
 
@@ -128,7 +129,15 @@ def polygons(rings, transform=None) -> list[dict]:
     holes go with it).  That is consistent: a collapsed island and the collapsed hole it sat in are the same arc, simplified to
     the same points, so the island's feature and the hole in its surroundings vanish together and the surrounding polygon covers
     the place.  ``area2`` is the pixel ring's, so exterior and hole are told apart, and ``pixels`` counted, as before the
-    simplification."""
+    simplification.
+
+    ``regions``: None (the features as above) or the ``SceneRegions`` of ``ops.scene_regions`` for the same mask (anything with
+    its seven fields, tensors or arrays, copied to the host once).  Every feature's properties then gain ``bbox`` = [x0, y0, x1,
+    y1] in pixel indices (x1, y1 exclusive), ``centroid`` = [(sum x + n / 2) / n, (sum y + n / 2) / n], the mean of the pixel
+    centres, mapped through ``transform`` where one is given, and, where the regions carry confidences, ``confidence`` =
+    conf_sum / (65536 n) and ``confidence_min`` = conf_min / 65536.  Regions and rings are matched by label: a ring label the
+    regions do not have, or a region whose ``pixels`` is not the rings', is a ValueError; regions without rings (classes that
+    ``values`` left out) are passed over, and a feature dropped for its collapsed exterior stays dropped."""
     vertices, offsets, value, label, start, area2 = (f.tolist() for f in (rings.vertices, rings.ring_offsets, rings.value,
                                                                            rings.label, rings.start, rings.area2))
     if len(offsets) != len(value) + 1 or not len(value) == len(label) == len(start) == len(area2) or offsets[-1] != len(vertices):
@@ -139,6 +148,15 @@ def polygons(rings, transform=None) -> list[dict]:
         except (TypeError, ValueError):
             raise ValueError(f"polygons: transform must be None or six numbers (a, b, c, d, e, f), got {transform!r}") from None
         vertices = [[a * x + b * y + c, d * x + e * y + f] for x, y in vertices]
+    attributes = None
+    if regions is not None:
+        names = ("label", "pixels", "bbox", "sum_xy", "conf_sum", "conf_min")
+        r_label, r_pixels, r_bbox, r_sum, r_csum, r_cmin = (None if getattr(regions, n) is None else getattr(regions, n).tolist()
+                                                            for n in names)
+        if not len(r_label) == len(r_pixels) == len(r_bbox) == len(r_sum) or (r_csum is None) != (r_cmin is None) \
+                or (r_csum is not None and not len(r_csum) == len(r_cmin) == len(r_label)):
+            raise ValueError(f"polygons: the fields of regions do not belong together ({len(r_label)} labels, {len(r_pixels)} pixel counts)")
+        attributes = {lab: k for k, lab in enumerate(r_label)}
     by_label: dict[int, list[int]] = {}
     for r in sorted(range(len(value)), key=start.__getitem__):
         by_label.setdefault(label[r], []).append(r)
@@ -152,7 +170,19 @@ def polygons(rings, transform=None) -> list[dict]:
             continue
         order = exterior + [r for r in members if area2[r] <= 0 and offsets[r + 1] - offsets[r] >= 3]
         coordinates = [vertices[offsets[r]:offsets[r + 1]] + vertices[offsets[r]:offsets[r] + 1] for r in order]
-        features.append({"type": "Feature",
-                         "properties": {"value": value[exterior[0]], "label": lab, "pixels": sum(area2[r] for r in members) // 2},
-                         "geometry": {"type": "Polygon", "coordinates": coordinates}})
+        properties = {"value": value[exterior[0]], "label": lab, "pixels": sum(area2[r] for r in members) // 2}
+        if attributes is not None:
+            k = attributes.get(lab)
+            if k is None:
+                raise ValueError(f"polygons: the rings have label {lab}, the regions do not: they are not those of one mask")
+            n = r_pixels[k]
+            if n != properties["pixels"]:
+                raise ValueError(f"polygons: label {lab} has {properties['pixels']} pixels by its rings and {n} by the regions")
+            cx, cy = (r_sum[k][0] + n / 2) / n, (r_sum[k][1] + n / 2) / n
+            if transform is not None:
+                cx, cy = a * cx + b * cy + c, d * cx + e * cy + f
+            properties["bbox"], properties["centroid"] = list(r_bbox[k]), [cx, cy]
+            if r_csum is not None:
+                properties["confidence"], properties["confidence_min"] = r_csum[k] / (65536 * n), r_cmin[k] / 65536
+        features.append({"type": "Feature", "properties": properties, "geometry": {"type": "Polygon", "coordinates": coordinates}})
     return features

@@ -28,6 +28,10 @@ Polygons (``predict_rings``): the boundaries of the mask's regions as closed rin
 ``predict_rings(simplify=tolerance)`` simplifies them on the device before they leave it (``ops.scene_rings_simplify``):
 Douglas-Peucker per arc between the junctions of the boundaries, so that a boundary two regions share stays shared.
 
+Attributes (``predict_features``): beside the rings, what a vector layer says about each polygon -- pixel count, bounding box,
+centroid sums and the model's mean and lowest confidence in the region -- reduced on the device from the mask, its component
+labels and the canvas (``ops.scene_regions``); neither the probabilities nor the mask have to leave the device for them.
+
 Determinism: the canvas is accumulated by a gather in tile order without atomics, so the mask and the probabilities do not
 depend on ``batch_size`` and are the same bits from run to run.  The reference has no counterpart (its inference stops at the
 tile, tools/script_model.py)."""
@@ -56,6 +60,12 @@ class SceneResult(NamedTuple):
 class SceneVectors(NamedTuple):
     mask: torch.Tensor                  # uint8 [H, W], what ``predict`` returns
     rings: ops.SceneRings               # the rings of its regions, on the device
+
+
+class SceneFeatures(NamedTuple):
+    mask: torch.Tensor                  # uint8 [H, W], what ``predict`` returns
+    rings: ops.SceneRings               # the rings of its regions, on the device
+    regions: ops.SceneRegions           # the attributes of its regions, on the device
 
 
 class SceneInference:
@@ -207,9 +217,8 @@ class SceneInference:
         (0 where no tile that was fed covers the pixel)."""
         return self._canvas(*self._upload(raster, valid))
 
-    def predict(self, raster: torch.Tensor, return_probs: bool = False, valid: torch.Tensor | None = None) -> SceneResult:
-        raster, plane = self._upload(raster, valid)
-        canvas = self._canvas(raster, plane)
+    def _finish(self, canvas: torch.Tensor, plane: torch.Tensor | None, return_probs: bool) -> SceneResult:
+        """The canvas labelled and, where configured, sieved."""
         if plane is None:
             mask, probs = ops.scene_finish(canvas, self.threshold, return_probs)
         else:
@@ -218,6 +227,10 @@ class SceneInference:
             mask = ops.scene_sieve(mask, self.sieve, self.sieve_connectivity, None if plane is None else self.nodata_label,
                                    self.sieve_iterations)
         return SceneResult(mask, probs)
+
+    def predict(self, raster: torch.Tensor, return_probs: bool = False, valid: torch.Tensor | None = None) -> SceneResult:
+        raster, plane = self._upload(raster, valid)
+        return self._finish(self._canvas(raster, plane), plane, return_probs)
 
     def predict_rings(self, raster: torch.Tensor, valid: torch.Tensor | None = None, *, connectivity: int = 4,
                       values=None, simplify: float | None = None) -> SceneVectors:
@@ -238,3 +251,28 @@ class SceneInference:
         if simplify is not None:
             rings = ops.scene_rings_simplify(rings, mask, simplify, ignore, values)
         return SceneVectors(mask, rings)
+
+    def predict_features(self, raster: torch.Tensor, valid: torch.Tensor | None = None, *, connectivity: int = 4,
+                         values=None, simplify: float | None = None) -> SceneFeatures:
+        """``predict_rings`` with the attributes of the regions beside the rings: the mask as ``predict`` gives it (sieve
+        included), its components under ``connectivity`` labelled once, and from those labels both the rings
+        (``ops.scene_rings``; ``values`` and ``simplify`` as in ``predict_rings``, the same ``nodata_label`` rule) and the
+        ``ops.SceneRegions`` of every region (``ops.scene_regions`` with the canvas): pixels, bounding box, coordinate sums and
+        the sum and minimum of the pixels' confidence.  ``values`` selects rings only: the regions are those of all classes.
+        The confidence of a pixel is the blended probability of the class it finally carries.  After a sieve a dissolved pixel
+        counts with the probability of its *new* class, which the model rated low there: a region that absorbed speckle shows a
+        lower confidence, which is the point.  The simplification moves vertices, not pixels: the regions are the same with and
+        without it.  ``gdlhip.scene.polygons(result.rings, regions=result.regions)`` joins the two into features."""
+        if simplify is not None and (isinstance(simplify, bool) or not isinstance(simplify, (int, float)) or not math.isfinite(simplify)
+                                     or not 0 <= simplify <= ops.SIMPLIFY_TOLERANCE_MAX):
+            raise ValueError(f"SceneInference.predict_features: simplify must be None or a finite tolerance in 0..2^20 pixels, got {simplify!r}")
+        raster, plane = self._upload(raster, valid)
+        canvas = self._canvas(raster, plane)
+        mask = self._finish(canvas, plane, False).mask
+        ignore = None if plane is None else self.nodata_label
+        labels = ops.scene_components(mask, connectivity, ignore)[0]
+        rings = ops.scene_rings(mask, connectivity, ignore, values, labels=labels)
+        regions = ops.scene_regions(mask, connectivity, ignore, canvas=canvas, labels=labels)
+        if simplify is not None:
+            rings = ops.scene_rings_simplify(rings, mask, simplify, ignore, values)
+        return SceneFeatures(mask, rings, regions)
