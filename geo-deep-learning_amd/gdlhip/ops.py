@@ -2477,6 +2477,95 @@ def scene_regions(mask: Tensor, connectivity: int = 4, ignore_label: int | None 
     return out
 
 
+# rings burned into a raster (include/gdlhip_scene_burn.h): the inverse of scene_rings
+class SceneBurn(NamedTuple):
+    mask: Tensor              # uint8 [H, W]: the ring's value inside a ring, `background` outside all, `conflict` elsewhere
+    conflicts: int            # the pixels that are neither: overlaps, crossed arcs, reversed rings
+    differ: int | None        # the pixels where mask != reference; None without a reference
+
+
+def _burn_check(op: str, rings, size, bits, background, conflict, reference) -> tuple[int, int, int, int]:
+    """The argument checks of ``scene_burn`` but for the device (which is asked for last); (R, V, H, W)."""
+    fields = {"vertices": torch.int32, "ring_offsets": torch.int32, "value": torch.uint8}
+    got = [getattr(rings, name, None) for name in fields]
+    if not all(isinstance(t, Tensor) for t in got):
+        raise ValueError(f"{op}: rings must have the tensor fields {', '.join(fields)}, got {type(rings).__name__}")
+    vertices, offsets, _ = got
+    R = int(offsets.numel()) - 1
+    shapes = {"vertices": (int(vertices.shape[0]), 2) if vertices.dim() else None, "ring_offsets": (R + 1,), "value": (R,)}
+    for (name, dtype), t in zip(fields.items(), got):
+        if t.dtype != dtype or tuple(t.shape) != shapes[name] or not t.is_contiguous() or t.device != vertices.device:
+            raise ValueError(f"{op}: rings.{name} must be a contiguous {dtype} {shapes[name]} tensor on {vertices.device}, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    if R < 0:
+        raise ValueError(f"{op}: rings.ring_offsets must hold R + 1 >= 1 offsets, got none")
+    try:
+        H, W = size
+        ok = all(isinstance(n, int) and not isinstance(n, bool) for n in (H, W))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok or H < 1 or W < 1:
+        raise ValueError(f"{op}: size must be (H, W), two ints of at least 1, got {size!r}")
+    if H * W >= 2 ** 31:
+        raise ValueError(f"{op}: {H} x {W} pixels: a linear index must fit an int32 (H * W < 2^31)")
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 0 <= bits <= _lib.SCENE_BURN_BITS_MAX:
+        raise ValueError(f"{op}: bits must be an int in 0..{_lib.SCENE_BURN_BITS_MAX}, got {bits!r}")
+    for name, v in (("background", background), ("conflict", conflict)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255:
+            raise ValueError(f"{op}: {name} must be an int in 0..255, got {v!r}")
+    if reference is not None:
+        if not isinstance(reference, Tensor) or reference.dtype not in (torch.uint8, torch.bool) or tuple(reference.shape) != (H, W) \
+                or not reference.is_contiguous():
+            what = f"{reference.dtype} {tuple(reference.shape)}" if isinstance(reference, Tensor) else type(reference).__name__
+            raise ValueError(f"{op}: reference must be a contiguous uint8 / bool [H, W] = [{H}, {W}] tensor, got {what}")
+        if reference.device != vertices.device:
+            raise ValueError(f"{op}: the reference is on {reference.device}, the rings on {vertices.device}")
+    return R, int(vertices.shape[0]), H, W
+
+
+def scene_burn(rings, size: tuple[int, int], *, bits: int = 0, background: int = 0, conflict: int = 255,
+               reference: Tensor | None = None) -> SceneBurn:
+    """Polygon rings burned into a uint8 raster of ``size`` = (H, W): the inverse of ``scene_rings``, what GDAL rasterize does.
+    ``rings``: a ``SceneRings`` or anything with ``vertices`` (int32 [V, 2] of (x, y)), ``ring_offsets`` (int32 [R + 1]) and
+    ``value`` (uint8 [R]) on the device; rings are open, have their region on the right hand (an exterior ring has a positive
+    shoelace sum with y down, a hole a negative one), and one of fewer than 3 vertices contributes nothing.  Coordinates are in
+    units of 1 / 2^``bits`` pixel (``bits`` 0..8; 0 is the lattice of ``scene_rings`` and ``scene_rings_simplify``), at most
+    2^20 pixels in magnitude, and may lie outside the raster.  A pixel belongs to a ring when its centre lies inside, a centre
+    exactly on an edge counting as right of it for every ring alike, so rings that share an edge share no pixel.  The pixel is
+    the ring's ``value`` where exactly one region covers it, ``background`` where none does (a hole whose island is missing
+    included) and ``conflict`` everywhere else; ``conflicts`` counts the last kind.  ``reference``: a uint8 / bool [H, W]
+    plane on the device; ``differ`` is then the number of pixels where the result is not the reference.  Integer sums alone:
+    exact, independent of the order of the rings, and the same bits from run to run; the rings are not modified.  Two small
+    device-to-host copies: the number of crossings and of bad entries, then the two counts (gdl_scene_burn_count / _fill).
+    A coordinate out of range, offsets that do not ascend inside 0..V, and 2^31 or more crossings are a ValueError."""
+    op = "scene_burn"
+    R, V, H, W = _burn_check(op, rings, size, bits, background, conflict, reference)
+    _need_cuda(rings.vertices, reference)
+    dev, lib = rings.vertices.device, _lib.checked()
+    n_cross = 0
+    edge_ring = edge_rows = plane = None
+    if R > 0 and V > 0:
+        edge_ring, edge_rows = torch.empty((V,), device=dev, dtype=torch.int32), torch.empty((V + 1,), device=dev, dtype=torch.int32)
+        bsum = torch.empty((-(-(V + 1) // _lib.SCENE_BURN_SCAN_TILE),), device=dev, dtype=torch.int32)
+        found = torch.empty((2,), device=dev, dtype=torch.int64)
+        lib.gdl_scene_burn_count(_p(rings.vertices), _p(rings.ring_offsets), R, V, bits, H, W, _p(edge_ring), _p(edge_rows), _p(bsum),
+                                 _p(found), _stream())
+        n_cross, bad = (int(c) for c in found.tolist())
+        if bad:
+            raise ValueError(f"{op}: {bad} bad entries in the rings: a coordinate beyond 2^20 pixels, or ring_offsets that do not "
+                             f"ascend inside 0..{V}")
+        if n_cross >= 2 ** 31:
+            raise ValueError(f"{op}: {n_cross} crossings of ring edges with raster rows: fewer than 2^31 are supported")
+        if n_cross > 0:
+            plane = torch.empty((2, H, W), device=dev, dtype=torch.int32)
+    out, counts = torch.empty((H, W), device=dev, dtype=torch.uint8), torch.empty((2,), device=dev, dtype=torch.int64)
+    ref = None if reference is None else reference.view(torch.uint8)
+    lib.gdl_scene_burn_fill(_p(rings.vertices), _p(rings.ring_offsets), _p(rings.value), R, V, bits, H, W, _p(edge_ring), _p(edge_rows),
+                            n_cross, background, conflict, _p(ref), _p(plane), _p(out), _p(counts), _stream())
+    conflicts, differ = (int(c) for c in counts.tolist())
+    return SceneBurn(out, conflicts, None if reference is None else differ)
+
+
 def iou_counts(pred: Tensor, target: Tensor, num_classes: int) -> Tensor:
     """int64 [B, 3, K]: per sample and class (intersection, |pred==k|, |target==k|); exact integer counts."""
     _need_cuda(pred, target)

@@ -5,12 +5,14 @@ those: ``ops.scene_cut_d4`` / ``scene_blend_d4`` / ``scene_blend_lowres_d4``, in
 of the finished mask, ``scene_components`` / ``scene_sieve`` (include/gdlhip_scene_sieve.h) and, for its polygon rings,
 ``scene_rings`` (include/gdlhip_scene_rings.h) and their simplification ``scene_rings_simplify``
 (include/gdlhip_scene_simplify.h), which ``polygons`` here groups into features, and the regions' attributes
-``scene_regions`` (include/gdlhip_scene_regions.h), which ``polygons`` adds to their properties; the user-facing
-class is ``geo_deep_learning.tools.scene_inference.SceneInference``."""
+``scene_regions`` (include/gdlhip_scene_regions.h), which ``polygons`` adds to their properties, and, for the way back from
+rings to a raster, ``scene_burn`` (include/gdlhip_scene_burn.h), for which ``rings_from_features`` here reads features; the
+user-facing class is ``geo_deep_learning.tools.scene_inference.SceneInference``."""
 
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import torch
 from torch import Tensor
@@ -186,3 +188,72 @@ def polygons(rings, transform=None, regions=None) -> list[dict]:
                 properties["confidence"], properties["confidence_min"] = r_csum[k] / (65536 * n), r_cmin[k] / 65536
         features.append({"type": "Feature", "properties": properties, "geometry": {"type": "Polygon", "coordinates": coordinates}})
     return features
+
+
+# ------------------------------------------------------------------ rings of features (include/gdlhip_scene_burn.h)
+class FeatureRings(NamedTuple):
+    """What ``ops.scene_burn`` burns, on the host until ``.to(device)``."""
+
+    vertices: Tensor          # int32 [V, 2]: (x, y) in units of 1 / 2^bits pixel, ring after ring, every ring open
+    ring_offsets: Tensor      # int32 [R + 1]
+    value: Tensor             # uint8 [R]
+
+    def to(self, device) -> "FeatureRings":
+        return FeatureRings(*(t.to(device) for t in self))
+
+
+def rings_from_features(features, transform=None, bits: int = 0, value_key: str = "value") -> FeatureRings:
+    """The inverse of ``polygons``: GeoJSON-style Polygon and MultiPolygon features (a list of them, or a FeatureCollection) as
+    the rings ``ops.scene_burn`` takes after ``.to(device)``, in the order of the features, a polygon's exterior before its
+    holes.  ``transform``: None (the coordinates are pixels) or the six numbers (a, b, c, d, e, f) that map pixel (x, y) to
+    (a x + b y + c, d x + e y + f), as in ``polygons``: the coordinates go through its inverse.  They are then rounded to the
+    nearest 1 / 2^``bits`` pixel (``bits`` 0..8; halves go up), a closing vertex that repeats the first is stripped, and a ring
+    is reversed where needed so that, in pixel coordinates with y down, an exterior has a positive shoelace sum (``area2 > 0``)
+    and a hole a negative one, which is the orientation of ``ops.scene_rings``.  Every ring of a feature burns
+    ``feature["properties"][value_key]``.  A missing value, a value that is no int in 0..255, a geometry that is neither
+    Polygon nor MultiPolygon and a singular transform are a ValueError."""
+    who = "rings_from_features"
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 0 <= bits <= 8:
+        raise ValueError(f"{who}: bits must be an int in 0..8, got {bits!r}")
+    inverse = None
+    if transform is not None:
+        try:
+            a, b, c, d, e, f = (float(t) for t in transform)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: transform must be None or six numbers (a, b, c, d, e, f), got {transform!r}") from None
+        det = a * e - b * d
+        if det == 0 or not math.isfinite(det) or not all(math.isfinite(t) for t in (c, f)):
+            raise ValueError(f"{who}: the transform {tuple(transform)!r} is singular: it has no inverse")
+        inverse = (e / det, -b / det, -d / det, a / det)
+    if isinstance(features, dict) and "features" in features:
+        features = features["features"]
+    scale = 1 << bits
+    vertices, offsets, values = [], [0], []
+    for k, feature in enumerate(features):
+        properties = feature.get("properties") or {}
+        if value_key not in properties:
+            raise ValueError(f"{who}: feature {k} has no property {value_key!r}")
+        v = properties[value_key]
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255:
+            raise ValueError(f"{who}: feature {k}: {value_key} must be an int in 0..255, got {v!r}")
+        geometry = feature.get("geometry") or {}
+        kind = geometry.get("type")
+        if kind not in ("Polygon", "MultiPolygon"):
+            raise ValueError(f"{who}: feature {k}: a Polygon or MultiPolygon geometry is expected, got {kind!r}")
+        for polygon in [geometry["coordinates"]] if kind == "Polygon" else geometry["coordinates"]:
+            for i, ring in enumerate(polygon):
+                points = []
+                for X, Y, *_ in ring:
+                    if inverse is not None:
+                        X, Y = inverse[0] * (X - c) + inverse[1] * (Y - f), inverse[2] * (X - c) + inverse[3] * (Y - f)
+                    points.append((math.floor(X * scale + 0.5), math.floor(Y * scale + 0.5)))
+                if len(points) > 1 and points[0] == points[-1]:
+                    points.pop()
+                area2 = sum(x0 * y1 - x1 * y0 for (x0, y0), (x1, y1) in zip(points, points[1:] + points[:1]))
+                if (area2 < 0) if i == 0 else (area2 > 0):      # an exterior comes first, the holes follow
+                    points.reverse()
+                vertices += points
+                offsets.append(len(vertices))
+                values.append(v)
+    return FeatureRings(torch.tensor(vertices, dtype=torch.int32).reshape(-1, 2), torch.tensor(offsets, dtype=torch.int32),
+                        torch.tensor(values, dtype=torch.uint8))

@@ -32,6 +32,10 @@ Attributes (``predict_features``): beside the rings, what a vector layer says ab
 centroid sums and the model's mean and lowest confidence in the region -- reduced on the device from the mask, its component
 labels and the canvas (``ops.scene_regions``); neither the probabilities nor the mask have to leave the device for them.
 
+Agreement (``agreement=True`` on ``predict_rings`` / ``predict_features``, or ``rings_agreement``): the rings burned back into a
+raster on the device (``ops.scene_burn``, the step GDAL rasterize takes) and compared with the mask: how many pixels the
+simplification moved to another class, how many lie where simplified arcs crossed, and the per-class counts behind an IoU.
+
 Determinism: the canvas is accumulated by a gather in tile order without atomics, so the mask and the probabilities do not
 depend on ``batch_size`` and are the same bits from run to run.  The reference has no counterpart (its inference stops at the
 tile, tools/script_model.py)."""
@@ -66,6 +70,36 @@ class SceneFeatures(NamedTuple):
     mask: torch.Tensor                  # uint8 [H, W], what ``predict`` returns
     rings: ops.SceneRings               # the rings of its regions, on the device
     regions: ops.SceneRegions           # the attributes of its regions, on the device
+
+
+class SceneVectorsAgreement(NamedTuple):
+    mask: torch.Tensor                  # as in SceneVectors
+    rings: ops.SceneRings
+    agreement: dict                     # ``rings_agreement(mask, rings, num_classes)``
+
+
+class SceneFeaturesAgreement(NamedTuple):
+    mask: torch.Tensor                  # as in SceneFeatures
+    rings: ops.SceneRings
+    regions: ops.SceneRegions
+    agreement: dict                     # ``rings_agreement(mask, rings, num_classes)``
+
+
+def rings_agreement(mask: torch.Tensor, rings, num_classes: int) -> dict:
+    """How well ``rings`` (a ``SceneRings`` or what ``ops.scene_burn`` takes, on the mask's device) describe the uint8 [H, W]
+    ``mask``: the rings are burned into a raster of the mask's size (background 0, conflict 255) and compared with it.
+    ``differ``: the pixels where the two are not equal; ``conflicts``: the pixels the rings cover twice or inside out (crossed
+    arcs of a simplification); ``iou_counts``: int64 [3, num_classes] on the device, per class the pixels both have, the burn
+    has and the mask has (``ops.iou_counts`` of the burn against the mask; values of ``num_classes`` and above, the conflict
+    value among them, count for no class).  Rings of every region of a mask, unsimplified, give ``differ == 0`` wherever the
+    mask is not 0 outside the rings (classes that ``values=`` left out, ``nodata_label`` pixels)."""
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or not 1 <= num_classes <= 64:
+        raise ValueError(f"rings_agreement: num_classes must be an int in 1..64 (ops.iou_counts), got {num_classes!r}")
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or mask.dim() != 2 or not mask.is_contiguous():
+        raise ValueError("rings_agreement: a contiguous uint8 [H, W] mask is expected")
+    burn = ops.scene_burn(rings, (int(mask.shape[0]), int(mask.shape[1])), reference=mask)
+    counts = ops.iou_counts(burn.mask.long().reshape(1, -1), mask.long().reshape(1, -1), num_classes)[0]
+    return {"differ": burn.differ, "conflicts": burn.conflicts, "iou_counts": counts}
 
 
 class SceneInference:
@@ -232,8 +266,12 @@ class SceneInference:
         raster, plane = self._upload(raster, valid)
         return self._finish(self._canvas(raster, plane), plane, return_probs)
 
+    def _num_classes(self) -> int:
+        """The classes a mask of this model can hold: two for a one-class (binary) model."""
+        return max(2, int(self.model.num_classes))
+
     def predict_rings(self, raster: torch.Tensor, valid: torch.Tensor | None = None, *, connectivity: int = 4,
-                      values=None, simplify: float | None = None) -> SceneVectors:
+                      values=None, simplify: float | None = None, agreement: bool = False) -> SceneVectors | SceneVectorsAgreement:
         """``predict`` as configured (sieve included), then the polygon rings of the mask's regions under ``connectivity``
         (``ops.scene_rings``; ``values``: the classes to keep, None for all).  Where a validity plane is in play -- ``nodata=``
         or ``valid=``, as for the sieve -- the ``nodata_label`` pixels are no region and get no ring.
@@ -241,7 +279,9 @@ class SceneInference:
         tolerance in pixels, 0 .. 2^20: the rings are simplified on the device arc by arc between the junctions of the boundaries
         (``ops.scene_rings_simplify`` with the same mask, ``nodata_label`` rule and ``values``), so neighbouring regions keep one
         common boundary.  ``area2`` stays the area of the pixel ring, and a ring may collapse to fewer than 3 vertices.
-        ``gdlhip.scene.polygons(result.rings)`` turns the rings into features."""
+        ``gdlhip.scene.polygons(result.rings)`` turns the rings into features.
+        ``agreement``: False (the result, the calls and the bits of before) or True: a ``SceneVectorsAgreement``, the same with
+        ``rings_agreement(mask, rings, num_classes)`` of the rings it returns beside them."""
         if simplify is not None and (isinstance(simplify, bool) or not isinstance(simplify, (int, float)) or not math.isfinite(simplify)
                                      or not 0 <= simplify <= ops.SIMPLIFY_TOLERANCE_MAX):
             raise ValueError(f"SceneInference.predict_rings: simplify must be None or a finite tolerance in 0..2^20 pixels, got {simplify!r}")
@@ -250,10 +290,12 @@ class SceneInference:
         rings = ops.scene_rings(mask, connectivity, ignore, values)
         if simplify is not None:
             rings = ops.scene_rings_simplify(rings, mask, simplify, ignore, values)
+        if agreement:
+            return SceneVectorsAgreement(mask, rings, rings_agreement(mask, rings, self._num_classes()))
         return SceneVectors(mask, rings)
 
     def predict_features(self, raster: torch.Tensor, valid: torch.Tensor | None = None, *, connectivity: int = 4,
-                         values=None, simplify: float | None = None) -> SceneFeatures:
+                         values=None, simplify: float | None = None, agreement: bool = False) -> SceneFeatures | SceneFeaturesAgreement:
         """``predict_rings`` with the attributes of the regions beside the rings: the mask as ``predict`` gives it (sieve
         included), its components under ``connectivity`` labelled once, and from those labels both the rings
         (``ops.scene_rings``; ``values`` and ``simplify`` as in ``predict_rings``, the same ``nodata_label`` rule) and the
@@ -262,7 +304,8 @@ class SceneInference:
         The confidence of a pixel is the blended probability of the class it finally carries.  After a sieve a dissolved pixel
         counts with the probability of its *new* class, which the model rated low there: a region that absorbed speckle shows a
         lower confidence, which is the point.  The simplification moves vertices, not pixels: the regions are the same with and
-        without it.  ``gdlhip.scene.polygons(result.rings, regions=result.regions)`` joins the two into features."""
+        without it.  ``gdlhip.scene.polygons(result.rings, regions=result.regions)`` joins the two into features.
+        ``agreement``: as in ``predict_rings``; True gives a ``SceneFeaturesAgreement``."""
         if simplify is not None and (isinstance(simplify, bool) or not isinstance(simplify, (int, float)) or not math.isfinite(simplify)
                                      or not 0 <= simplify <= ops.SIMPLIFY_TOLERANCE_MAX):
             raise ValueError(f"SceneInference.predict_features: simplify must be None or a finite tolerance in 0..2^20 pixels, got {simplify!r}")
@@ -275,4 +318,6 @@ class SceneInference:
         regions = ops.scene_regions(mask, connectivity, ignore, canvas=canvas, labels=labels)
         if simplify is not None:
             rings = ops.scene_rings_simplify(rings, mask, simplify, ignore, values)
+        if agreement:
+            return SceneFeaturesAgreement(mask, rings, regions, rings_agreement(mask, rings, self._num_classes()))
         return SceneFeatures(mask, rings, regions)
