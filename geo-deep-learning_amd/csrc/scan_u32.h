@@ -1,5 +1,7 @@
 // Exclusive scan of S arrays of L u32, in place, in three launches (256 threads; wave64): shared by loss_lovasz.hip (the radix
-// sort's digit table, the label counts) and scene_rings.hip (the boundary sides per pixel, the ring starts and vertex counts).
+// sort's digit table, the label counts; it issues the launches itself and skips the first two for a single block) and, through
+// scan_exclusive below, by scene_rings.hip (the boundary sides per pixel, the ring starts and vertex counts), scene_simplify.hip
+// (the dense positions, the anchors, the kept vertices), scene_regions.hip (the root flags) and scene_burn.hip (the rows per edge).
 //   scan_reduce  grid (nb, S), nb = ceil(L / SCAN_TILE): the sum of every block of SCAN_TILE entries -> bsum[segment][block]
 //   scan_spine   grid (S): the exclusive prefix of a segment's block sums in place, and their total
 //   scan_apply   grid (nb, S): the exclusive scan of a block's entries plus the block's offset
@@ -80,4 +82,13 @@ __global__ __launch_bounds__(256) void scan_apply_kernel(uint32_t* __restrict__ 
     if (first + j < L) seg[first + j] = run;
     run += v[j];
   }
+}
+
+// the exclusive scan of S arrays of L u32 in place, their totals in total[S] (may be null); bsum: S * ceil(L / SCAN_TILE) words
+void scan_exclusive(uint32_t* data, int S, int64_t L, uint32_t* bsum, uint32_t* total, hipStream_t s) {
+  const int64_t nb = (L + SCAN_TILE - 1) / SCAN_TILE;      // L <= 2^31: at most 2^20 blocks
+  const dim3 grid((unsigned)nb, (unsigned)S);
+  hipLaunchKernelGGL(scan_reduce_kernel, grid, dim3(256), 0, s, (const uint32_t*)data, L, bsum);
+  hipLaunchKernelGGL(scan_spine_kernel, dim3((unsigned)S), dim3(256), 0, s, bsum, nb, total);
+  hipLaunchKernelGGL(scan_apply_kernel, grid, dim3(256), 0, s, data, L, (const uint32_t*)bsum);
 }

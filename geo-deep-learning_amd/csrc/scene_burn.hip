@@ -24,13 +24,12 @@
 namespace {
 
 #include "scan_u32.h"
+#include "scene_common.h"
 static_assert(SCAN_TILE == GDL_SCENE_BURN_SCAN_TILE, "the header states the scan's block size for the callers' scratch");
 
 constexpr int CHUNK = GDL_SCENE_BURN_CHUNK;      // the pixels of a row per turn: one per thread of the workgroup
 constexpr int COORD_BITS = 20;                   // |c| <= 2^COORD_BITS pixels
 static_assert(CHUNK == 256 && GDL_SCENE_BURN_BITS_MAX == 8, "a thread is a pixel; 2^62 bounds the quotient's terms");
-
-#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 __device__ __forceinline__ int64_t ceil_div(int64_t a, int64_t b) {      // b > 0
   const int64_t q = a / b;
@@ -109,15 +108,6 @@ __global__ __launch_bounds__(256) void burn_edges_kernel(const int32_t* __restri
     if (rows) __hip_atomic_fetch_add(counts, rows, RLX_AGENT);
     if (bad) __hip_atomic_fetch_add(counts + 1, bad, RLX_AGENT);
   }
-}
-
-// the exclusive scan of L u32 in place; bsum: ceil(L / SCAN_TILE) words
-void scan_exclusive(uint32_t* data, int64_t L, uint32_t* bsum, hipStream_t s) {
-  const int64_t nb = (L + SCAN_TILE - 1) / SCAN_TILE;      // L <= 2^31: at most 2^20 blocks
-  const dim3 grid((unsigned)nb);
-  hipLaunchKernelGGL(scan_reduce_kernel, grid, dim3(256), 0, s, (const uint32_t*)data, L, bsum);
-  hipLaunchKernelGGL(scan_spine_kernel, dim3(1), dim3(256), 0, s, bsum, nb, (uint32_t*)nullptr);
-  hipLaunchKernelGGL(scan_apply_kernel, grid, dim3(256), 0, s, data, L, (const uint32_t*)bsum);
 }
 
 // ------------------------------------------------------------------ fill
@@ -230,8 +220,7 @@ __global__ __launch_bounds__(256) void burn_background_kernel(int64_t HW, int ba
 }
 
 int check_common(const char* fn, int n_rings, int n_vertices, int bits, int H, int W) {
-  GDL_CHECK_ARG(H > 0 && W > 0, "%s: bad sizes", fn);
-  GDL_CHECK_ARG((int64_t)H * W <= INT32_MAX, "%s: %d x %d pixels: a linear index must fit an int32 (H * W < 2^31)", fn, H, W);
+  if (const int bad = check_raster(fn, H, W, LINEAR_INDEX)) return bad;
   GDL_CHECK_ARG(bits >= 0 && bits <= GDL_SCENE_BURN_BITS_MAX, "%s: bits must be in 0..%d, got %d", fn, GDL_SCENE_BURN_BITS_MAX, bits);
   GDL_CHECK_ARG(n_rings >= 0 && n_vertices >= 0 && n_vertices < INT32_MAX, "%s: %d rings and %d vertices", fn, n_rings, n_vertices);
   return GDL_OK;
@@ -250,7 +239,7 @@ extern "C" int gdl_scene_burn_count(const int32_t* vertices, const int32_t* ring
   hipLaunchKernelGGL(burn_offsets_kernel, dim3(grid_for((int64_t)R + 1)), dim3(256), 0, s, ring_offsets, R, V, counts);
   hipLaunchKernelGGL(burn_edges_kernel, dim3(grid_for((int64_t)V + 1)), dim3(256), 0, s, vertices, ring_offsets, R, V, bits, H, edge_ring,
                      (uint32_t*)edge_rows, counts);
-  scan_exclusive((uint32_t*)edge_rows, (int64_t)V + 1, (uint32_t*)bsum, s);
+  scan_exclusive((uint32_t*)edge_rows, 1, (int64_t)V + 1, (uint32_t*)bsum, nullptr, s);
   GDL_CHECK_LAUNCH("gdl_scene_burn_count");
   return GDL_OK;
 }

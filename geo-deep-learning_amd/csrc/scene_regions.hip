@@ -28,6 +28,7 @@
 namespace {
 
 #include "scan_u32.h"
+#include "scene_common.h"
 static_assert(SCAN_TILE == GDL_SCENE_REGIONS_SCAN_TILE, "the header states the scan's block size for the callers' scratch");
 
 constexpr int TILE = GDL_SCENE_REGIONS_TILE;      // one wave per tile row: a lane is a column
@@ -35,8 +36,6 @@ constexpr int ROWS_PER_WAVE = TILE / 4;           // 256 threads = 4 waves
 constexpr int TABLE = GDL_SCENE_REGIONS_TABLE;    // slots; ten int32 each: 40 KB of LDS, four workgroups per CU
 constexpr int PROBES = GDL_SCENE_REGIONS_PROBES;
 static_assert(TILE == 64 && (TABLE & (TABLE - 1)) == 0 && TABLE % 256 == 0 && PROBES >= 1 && PROBES <= TABLE, "a lane is a column");
-
-#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 // the arrays of gdl_scene_regions_stats; conf_sum / conf_min are looked at only where there is a canvas
 struct RegionArrays {
@@ -68,15 +67,6 @@ __device__ __forceinline__ void add_global(const RegionArrays& out, int r, int N
 // ------------------------------------------------------------------ count
 __global__ __launch_bounds__(256) void regions_roots_kernel(const int32_t* __restrict__ labels, int64_t HW, uint32_t* __restrict__ flag) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < HW; i += (int64_t)gridDim.x * 256) flag[i] = labels[i] == (int32_t)i;
-}
-
-// the exclusive scan of L u32 in place, their total in total[0]; bsum: ceil(L / SCAN_TILE) words
-void scan_exclusive(uint32_t* data, int64_t L, uint32_t* bsum, uint32_t* total, hipStream_t s) {
-  const int64_t nb = (L + SCAN_TILE - 1) / SCAN_TILE;      // L < 2^31: at most 2^20 blocks
-  const dim3 grid((unsigned)nb);
-  hipLaunchKernelGGL(scan_reduce_kernel, grid, dim3(256), 0, s, (const uint32_t*)data, L, bsum);
-  hipLaunchKernelGGL(scan_spine_kernel, dim3(1), dim3(256), 0, s, bsum, nb, total);
-  hipLaunchKernelGGL(scan_apply_kernel, grid, dim3(256), 0, s, data, L, (const uint32_t*)bsum);
 }
 
 // ------------------------------------------------------------------ fill
@@ -207,22 +197,16 @@ __global__ __launch_bounds__(256) void regions_stats_kernel(const uint8_t* __res
   }
 }
 
-int check_raster(const char* fn, int H, int W) {
-  GDL_CHECK_ARG(H > 0 && W > 0, "%s: bad sizes", fn);
-  GDL_CHECK_ARG((int64_t)H * W <= INT32_MAX, "%s: %d x %d pixels: a linear index must fit an int32 (H * W < 2^31)", fn, H, W);
-  return GDL_OK;
-}
-
 }  // namespace
 
 extern "C" int gdl_scene_regions_count(const int32_t* labels, int H, int W, int32_t* rank, int32_t* block_sums, int32_t* n_regions,
                                        gdl_stream_t stream) {
   GDL_CHECK_ARG(labels && rank && block_sums && n_regions, "gdl_scene_regions_count: null pointer");
-  if (const int bad = check_raster("gdl_scene_regions_count", H, W)) return bad;
+  if (const int bad = check_raster("gdl_scene_regions_count", H, W, LINEAR_INDEX)) return bad;
   hipStream_t s = (hipStream_t)stream;
   const int64_t HW = (int64_t)H * W;
   hipLaunchKernelGGL(regions_roots_kernel, dim3(grid_for(HW)), dim3(256), 0, s, labels, HW, (uint32_t*)rank);
-  scan_exclusive((uint32_t*)rank, HW, (uint32_t*)block_sums, (uint32_t*)n_regions, s);
+  scan_exclusive((uint32_t*)rank, 1, HW, (uint32_t*)block_sums, (uint32_t*)n_regions, s);
   GDL_CHECK_LAUNCH("gdl_scene_regions_count");
   return GDL_OK;
 }
@@ -230,7 +214,7 @@ extern "C" int gdl_scene_regions_count(const int32_t* labels, int H, int W, int3
 extern "C" int gdl_scene_regions_stats(const uint8_t* mask, const int32_t* labels, const int32_t* rank, const float* canvas, int K, int H,
                                        int W, int N, int32_t* label, uint8_t* value, int32_t* pixels, int32_t* bbox, int64_t* sum_xy,
                                        int64_t* conf_sum, int32_t* conf_min, gdl_stream_t stream) {
-  if (const int bad = check_raster("gdl_scene_regions_stats", H, W)) return bad;
+  if (const int bad = check_raster("gdl_scene_regions_stats", H, W, LINEAR_INDEX)) return bad;
   GDL_CHECK_ARG(N >= 0 && N <= (int64_t)H * W, "gdl_scene_regions_stats: %d regions in %d x %d pixels", N, H, W);
   if (N == 0) return GDL_OK;
   GDL_CHECK_ARG(mask && labels && rank && label && value && pixels && bbox && sum_xy && (!canvas || (conf_sum && conf_min)),

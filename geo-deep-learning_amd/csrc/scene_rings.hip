@@ -24,30 +24,19 @@
 namespace {
 
 #include "scan_u32.h"
+#include "scene_common.h"
 static_assert(SCAN_TILE == GDL_SCENE_RINGS_SCAN_TILE, "the header states the scan's block size for the callers' scratch");
-
-#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 // d_s, the direction of travel of side s: E, S, W, N.  The outward normal n_s is d_{(s + 3) % 4}.
 __device__ __forceinline__ int dir_x(int s) { return s == 0 ? 1 : s == 2 ? -1 : 0; }
 __device__ __forceinline__ int dir_y(int s) { return s == 1 ? 1 : s == 3 ? -1 : 0; }
 
-struct Raster {
-  const uint8_t* __restrict__ mask;
-  const uint8_t* __restrict__ keep;
-  int H, W, ignore_label;
-  __device__ __forceinline__ bool inside(int y, int x) const { return y >= 0 && y < H && x >= 0 && x < W; }
-  // the pixel's value where it is live, otherwise -1
-  __device__ __forceinline__ int live(int y, int x) const {
-    const int v = mask[(int64_t)y * W + x];
-    return v != ignore_label && keep[v] ? v : -1;
-  }
-  __device__ __forceinline__ bool same(int y, int x, int v) const { return inside(y, x) && mask[(int64_t)y * W + x] == v; }
-  // bit s: side s of the live pixel (y, x) of value v is a boundary side
-  __device__ __forceinline__ int boundary(int y, int x, int v) const {
-    return (int)!same(y - 1, x, v) | (int)!same(y, x + 1, v) << 1 | (int)!same(y + 1, x, v) << 2 | (int)!same(y, x - 1, v) << 3;
-  }
-};
+// v is the value of a live pixel (Raster, scene_common.h): a cell holds it exactly when it is a live pixel of that value
+__device__ __forceinline__ bool same(const Raster& r, int y, int x, int v) { return r.inside(y, x) && r.mask[(int64_t)y * r.W + x] == v; }
+// bit s: side s of the live pixel (y, x) of value v is a boundary side
+__device__ __forceinline__ int boundary(const Raster& r, int y, int x, int v) {
+  return (int)!same(r, y - 1, x, v) | (int)!same(r, y, x + 1, v) << 1 | (int)!same(r, y + 1, x, v) << 2 | (int)!same(r, y, x - 1, v) << 3;
+}
 
 // ------------------------------------------------------------------ 1. count
 __global__ __launch_bounds__(256) void rings_count_kernel(Raster r, uint32_t* __restrict__ offsets) {
@@ -55,17 +44,8 @@ __global__ __launch_bounds__(256) void rings_count_kernel(Raster r, uint32_t* __
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < HW; p += (int64_t)gridDim.x * 256) {
     const int y = (int)(p / r.W), x = (int)(p % r.W);
     const int v = r.live(y, x);
-    offsets[p] = v < 0 ? 0u : (uint32_t)__popc(r.boundary(y, x, v));
+    offsets[p] = v < 0 ? 0u : (uint32_t)__popc(boundary(r, y, x, v));
   }
-}
-
-// the exclusive scan of S arrays of L u32 in place, their totals in total[S]; bsum: S * ceil(L / SCAN_TILE) words
-void scan_exclusive(uint32_t* data, int S, int64_t L, uint32_t* bsum, uint32_t* total, hipStream_t s) {
-  const int64_t nb = (L + SCAN_TILE - 1) / SCAN_TILE;      // L < 2^31: at most 2^20 blocks
-  const dim3 grid((unsigned)nb, (unsigned)S);
-  hipLaunchKernelGGL(scan_reduce_kernel, grid, dim3(256), 0, s, (const uint32_t*)data, L, bsum);
-  hipLaunchKernelGGL(scan_spine_kernel, dim3((unsigned)S), dim3(256), 0, s, bsum, nb, total);
-  hipLaunchKernelGGL(scan_apply_kernel, grid, dim3(256), 0, s, data, L, (const uint32_t*)bsum);
 }
 
 // ------------------------------------------------------------------ 2. trace
@@ -81,17 +61,17 @@ __global__ __launch_bounds__(256) void rings_fill_kernel(Raster r, int conn8, co
     const int y = (int)(p / r.W), x = (int)(p % r.W);
     const int v = r.live(y, x);
     if (v < 0) continue;
-    const int bits = r.boundary(y, x, v);
+    const int bits = boundary(r, y, x, v);
     int e = offsets[p];
     for (int s = 0; s < 4; ++s) {
       if (!(bits >> s & 1)) continue;
       const int n = (s + 3) & 3;
       const int ay = y + dir_y(s), ax = x + dir_x(s), by = ay + dir_y(n), bx = ax + dir_x(n);
-      const bool same_a = r.same(ay, ax, v), same_b = r.same(by, bx, v);
+      const bool same_a = same(r, ay, ax, v), same_b = same(r, by, bx, v);
       int qy = y, qx = x, t = (s + 1) & 3;      // turn on the pixel itself
       if (conn8 ? same_b : same_a && same_b) { qy = by; qx = bx; t = n; }
       else if (same_a) { qy = ay; qx = ax; t = s; }
-      const int q_bits = qy == y && qx == x ? bits : r.boundary(qy, qx, v);
+      const int q_bits = qy == y && qx == x ? bits : boundary(r, qy, qx, v);
       int next = offsets[(int64_t)qy * r.W + qx] + __popc(q_bits & ((1 << t) - 1));
       if (e >= 0 && e < E) {
         if (next < 0 || next >= E) next = e;
@@ -104,10 +84,6 @@ __global__ __launch_bounds__(256) void rings_fill_kernel(Raster r, int conn8, co
     }
   }
 }
-
-// Every index that a kernel below reads from memory and then uses as an address is held against E first: the arrays are the
-// caller's, and a gather must stay inside them even where they were not filled by the calls before.
-__device__ __forceinline__ bool in_range(int i, int E) { return (unsigned)i < (unsigned)E; }
 
 // the round's early exit and its flag: flags[round] goes up when a lane of the wave changed something
 __device__ __forceinline__ bool round_is_idle(const int32_t* flags, int round) { return round > 0 && flags[round - 1] == 0; }
@@ -218,11 +194,9 @@ __global__ __launch_bounds__(256) void rings_write_kernel(const uint8_t* __restr
   }
 }
 
-int check_raster(const char* fn, int H, int W, int ignore_label) {
-  GDL_CHECK_ARG(H > 0 && W > 0, "%s: bad sizes", fn);
-  GDL_CHECK_ARG((int64_t)H * W < ((int64_t)1 << 29), "%s: %d x %d pixels: a slot 4 * (y * W + x) + side must fit an int32 (H * W < 2^29)", fn, H, W);
-  GDL_CHECK_ARG(ignore_label >= -1 && ignore_label <= 255, "%s: ignore_label %d is not in -1..255", fn, ignore_label);
-  return GDL_OK;
+int check_mask(const char* fn, int H, int W, int ignore_label) {
+  if (const int bad = check_raster(fn, H, W, RING_SLOT)) return bad;
+  return check_ignore_label(fn, ignore_label);
 }
 
 inline int doubling_rounds(int E) {
@@ -236,7 +210,7 @@ inline int doubling_rounds(int E) {
 extern "C" int gdl_scene_rings_count(const uint8_t* mask, int H, int W, int ignore_label, const uint8_t* keep, int32_t* offsets,
                                      int32_t* bsum, int32_t* n_sides, gdl_stream_t stream) {
   GDL_CHECK_ARG(mask && keep && offsets && bsum && n_sides, "gdl_scene_rings_count: null pointer");
-  if (const int bad = check_raster("gdl_scene_rings_count", H, W, ignore_label)) return bad;
+  if (const int bad = check_mask("gdl_scene_rings_count", H, W, ignore_label)) return bad;
   hipStream_t s = (hipStream_t)stream;
   const int64_t HW = (int64_t)H * W;
   const Raster r{mask, keep, H, W, ignore_label};
@@ -250,8 +224,8 @@ extern "C" int gdl_scene_rings_trace(const uint8_t* mask, int H, int W, int conn
                                      const int32_t* offsets, int n_sides, int32_t* side_slot, int32_t* side_next, int32_t* side_ring,
                                      int32_t* side_rank, int32_t* work, int32_t* counts, gdl_stream_t stream) {
   GDL_CHECK_ARG(mask && keep && offsets && counts, "gdl_scene_rings_trace: null pointer");
-  if (const int bad = check_raster("gdl_scene_rings_trace", H, W, ignore_label)) return bad;
-  GDL_CHECK_ARG(connectivity == 4 || connectivity == 8, "gdl_scene_rings_trace: connectivity %d is neither 4 nor 8", connectivity);
+  if (const int bad = check_mask("gdl_scene_rings_trace", H, W, ignore_label)) return bad;
+  if (const int bad = check_connectivity("gdl_scene_rings_trace", connectivity)) return bad;
   const int64_t HW = (int64_t)H * W;
   GDL_CHECK_ARG(n_sides >= 0 && n_sides <= 4 * HW, "gdl_scene_rings_trace: n_sides %d is not in 0..4 * H * W", n_sides);
   hipStream_t s = (hipStream_t)stream;
@@ -269,7 +243,7 @@ extern "C" int gdl_scene_rings_trace(const uint8_t* mask, int H, int W, int conn
   int32_t* flags = bsum + 2 * nb;
   const int rounds = doubling_rounds(E);      // at most 31: 2 * rounds flags fit GDL_SCENE_RINGS_FLAGS
   static_assert(GDL_SCENE_RINGS_FLAGS >= 2 * 31, "one flag per round of both doublings");
-  const dim3 sides((unsigned)(((int64_t)E + 255) / 256));      // one side per thread: at most 2^23 workgroups
+  const dim3 sides = one_per_thread(E);
   const Raster r{mask, keep, H, W, ignore_label};
   if (hipMemsetAsync(flags, 0, GDL_SCENE_RINGS_FLAGS * sizeof(int32_t), s) != hipSuccess) GDL_CHECK_LAUNCH("gdl_scene_rings_trace");
 
@@ -316,9 +290,8 @@ extern "C" int gdl_scene_rings_write(const uint8_t* mask, const int32_t* labels,
   GDL_CHECK_ARG(mask && labels && side_slot && side_next && side_ring && side_rank && work && vertices && value && label && start && area2,
                 "gdl_scene_rings_write: null pointer");
   if (hipMemsetAsync(area2, 0, (size_t)n_rings * sizeof(int64_t), s) != hipSuccess) GDL_CHECK_LAUNCH("gdl_scene_rings_write");
-  hipLaunchKernelGGL(rings_write_kernel, dim3((unsigned)(((int64_t)n_sides + 255) / 256)), dim3(256), 0, s, mask, labels, W, n_sides,
-                     n_rings, n_vertices, side_slot, side_next, side_ring, side_rank, work, work + n_sides, vertices, ring_offsets, value,
-                     label, start, area2);
+  hipLaunchKernelGGL(rings_write_kernel, one_per_thread(n_sides), dim3(256), 0, s, mask, labels, W, n_sides, n_rings, n_vertices,
+                     side_slot, side_next, side_ring, side_rank, work, work + n_sides, vertices, ring_offsets, value, label, start, area2);
   GDL_CHECK_LAUNCH("gdl_scene_rings_write");
   return GDL_OK;
 }

@@ -17,11 +17,11 @@
 
 namespace {
 
+#include "scene_common.h"
+
 constexpr int TILE = 64;                 // one wave per tile row: a lane is a column.  64 x 64 int32 parents are 16 KB of LDS
 constexpr int TILE_PIXELS = TILE * TILE;
 constexpr int ROWS_PER_WAVE = TILE / 4;  // 256 threads = 4 waves
-
-#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
 // ------------------------------------------------------------------ union-find
 // find and unite over one parent array, SCOPE telling who else works on it: the workgroup (LDS) or the whole device.
@@ -269,11 +269,9 @@ __global__ __launch_bounds__(256) void sieve_apply_kernel(const uint8_t* __restr
 }
 
 int check_common(const char* fn, int H, int W, int connectivity, int ignore_label) {
-  GDL_CHECK_ARG(H > 0 && W > 0, "%s: bad sizes", fn);
-  GDL_CHECK_ARG((int64_t)H * W <= INT32_MAX, "%s: %d x %d pixels: a linear index must fit an int32 (H * W < 2^31)", fn, H, W);
-  GDL_CHECK_ARG(connectivity == 4 || connectivity == 8, "%s: connectivity %d is neither 4 nor 8", fn, connectivity);
-  GDL_CHECK_ARG(ignore_label >= -1 && ignore_label <= 255, "%s: ignore_label %d is not in -1..255", fn, ignore_label);
-  return GDL_OK;
+  if (const int bad = check_raster(fn, H, W, LINEAR_INDEX)) return bad;
+  if (const int bad = check_connectivity(fn, connectivity)) return bad;
+  return check_ignore_label(fn, ignore_label);
 }
 
 }  // namespace

@@ -29,40 +29,23 @@
 namespace {
 
 #include "scan_u32.h"
+#include "scene_common.h"
 static_assert(SCAN_TILE == GDL_SCENE_SIMPLIFY_SCAN_TILE, "the header states the scan's block size for the callers' scratch");
 
-#define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 typedef unsigned long long u64;
 
-__device__ __forceinline__ bool in_range(int i, int n) { return (unsigned)i < (unsigned)n; }
-
-// the exclusive scan of L u32 in place, their total in total[0]; bsum: ceil(L / SCAN_TILE) words
-void scan_exclusive(uint32_t* data, int64_t L, uint32_t* bsum, uint32_t* total, hipStream_t s) {
-  const int64_t nb = (L + SCAN_TILE - 1) / SCAN_TILE;      // L <= 2^31: at most 2^20 blocks
-  const dim3 grid((unsigned)nb);
-  hipLaunchKernelGGL(scan_reduce_kernel, grid, dim3(256), 0, s, (const uint32_t*)data, L, bsum);
-  hipLaunchKernelGGL(scan_spine_kernel, dim3(1), dim3(256), 0, s, bsum, nb, total);
-  hipLaunchKernelGGL(scan_apply_kernel, grid, dim3(256), 0, s, data, L, (const uint32_t*)bsum);
-}
-
-inline dim3 one_per_thread(int64_t n) { return dim3((unsigned)((n + 255) / 256)); }      // n <= 2^31: at most 2^23 workgroups
-
 // ------------------------------------------------------------------ 1. nodes
-// the class of cell (y, x): the value of a live pixel, 256 for every other cell
-__device__ __forceinline__ int cell_class(const uint8_t* __restrict__ mask, const uint8_t* __restrict__ keep, int H, int W, int ignore_label,
-                                          int y, int x) {
-  if (y < 0 || y >= H || x < 0 || x >= W) return 256;
-  const int v = mask[(int64_t)y * W + x];
-  return v != ignore_label && keep[v] ? v : 256;
+// the class of cell (y, x): the value of a live pixel (Raster, scene_common.h), 256 for every other cell
+__device__ __forceinline__ int cell_class(const Raster& r, int y, int x) {
+  const int v = r.cell(y, x);
+  return v < 0 ? 256 : v;
 }
 
-__global__ __launch_bounds__(256) void simplify_nodes_kernel(const uint8_t* __restrict__ mask, const uint8_t* __restrict__ keep, int H, int W,
-                                                             int ignore_label, uint8_t* __restrict__ nodes) {
-  const int64_t n = (int64_t)(H + 1) * (W + 1);
+__global__ __launch_bounds__(256) void simplify_nodes_kernel(Raster r, uint8_t* __restrict__ nodes) {
+  const int64_t n = (int64_t)(r.H + 1) * (r.W + 1);
   for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < n; q += (int64_t)gridDim.x * 256) {
-    const int y = (int)(q / (W + 1)), x = (int)(q % (W + 1));
-    const int nw = cell_class(mask, keep, H, W, ignore_label, y - 1, x - 1), ne = cell_class(mask, keep, H, W, ignore_label, y - 1, x);
-    const int sw = cell_class(mask, keep, H, W, ignore_label, y, x - 1), se = cell_class(mask, keep, H, W, ignore_label, y, x);
+    const int y = (int)(q / (r.W + 1)), x = (int)(q % (r.W + 1));
+    const int nw = cell_class(r, y - 1, x - 1), ne = cell_class(r, y - 1, x), sw = cell_class(r, y, x - 1), se = cell_class(r, y, x);
     nodes[q] = (nw != ne) + (sw != se) + (nw != sw) + (ne != se) >= 3;
   }
 }
@@ -340,8 +323,7 @@ __global__ __launch_bounds__(256) void simplify_scatter_kernel(const int2* __res
 }
 
 int check_rings(const char* fn, int H, int W, int R, int V) {
-  GDL_CHECK_ARG(H > 0 && W > 0, "%s: bad sizes", fn);
-  GDL_CHECK_ARG((int64_t)H * W < ((int64_t)1 << 29), "%s: %d x %d pixels: the rings are those of a raster of H * W < 2^29", fn, H, W);
+  if (const int bad = check_raster(fn, H, W, RING_RASTER)) return bad;
   GDL_CHECK_ARG(R >= 0 && V >= 0 && V <= 4 * (int64_t)H * W && 4 * (int64_t)R <= V && (R == 0) == (V == 0),
                 "%s: %d rings and %d vertices do not belong together", fn, R, V);
   return GDL_OK;
@@ -352,11 +334,10 @@ int check_rings(const char* fn, int H, int W, int R, int V) {
 extern "C" int gdl_scene_nodes(const uint8_t* mask, int H, int W, int ignore_label, const uint8_t* keep, uint8_t* nodes,
                                gdl_stream_t stream) {
   GDL_CHECK_ARG(mask && keep && nodes, "gdl_scene_nodes: null pointer");
-  GDL_CHECK_ARG(H > 0 && W > 0, "gdl_scene_nodes: bad sizes");
-  GDL_CHECK_ARG((int64_t)H * W < ((int64_t)1 << 29), "gdl_scene_nodes: %d x %d pixels: the rings are those of a raster of H * W < 2^29", H, W);
-  GDL_CHECK_ARG(ignore_label >= -1 && ignore_label <= 255, "gdl_scene_nodes: ignore_label %d is not in -1..255", ignore_label);
-  hipLaunchKernelGGL(simplify_nodes_kernel, dim3(grid_for((int64_t)(H + 1) * (W + 1))), dim3(256), 0, (hipStream_t)stream, mask, keep, H, W,
-                     ignore_label, nodes);
+  if (const int bad = check_raster("gdl_scene_nodes", H, W, RING_RASTER)) return bad;
+  if (const int bad = check_ignore_label("gdl_scene_nodes", ignore_label)) return bad;
+  hipLaunchKernelGGL(simplify_nodes_kernel, dim3(grid_for((int64_t)(H + 1) * (W + 1))), dim3(256), 0, (hipStream_t)stream,
+                     Raster{mask, keep, H, W, ignore_label}, nodes);
   GDL_CHECK_LAUNCH("gdl_scene_nodes");
   return GDL_OK;
 }
@@ -374,7 +355,7 @@ extern "C" int gdl_scene_simplify_count(const uint8_t* nodes, int H, int W, cons
   const int64_t L = (int64_t)n_vertices + 1;
   hipLaunchKernelGGL(simplify_count_kernel, one_per_thread(L), dim3(256), 0, s, nodes, H, W, (const int2*)vertices, ring_offsets, n_rings,
                      n_vertices, (uint32_t*)pos);
-  scan_exclusive((uint32_t*)pos, L, (uint32_t*)bsum, (uint32_t*)n_dense, s);
+  scan_exclusive((uint32_t*)pos, 1, L, (uint32_t*)bsum, (uint32_t*)n_dense, s);
   GDL_CHECK_LAUNCH("gdl_scene_simplify_count");
   return GDL_OK;
 }
@@ -400,7 +381,7 @@ extern "C" int gdl_scene_simplify_dense(const uint8_t* nodes, int H, int W, cons
   hipLaunchKernelGGL(simplify_dense_kernel, one_per_thread(V), dim3(256), 0, s, nodes, H, W, (const int2*)vertices, ring_offsets, R, V, pos, D,
                      (int2*)dense, kept, A);
   hipLaunchKernelGGL(simplify_offsets_kernel, one_per_thread((int64_t)R + 1), dim3(256), 0, s, ring_offsets, R, V, pos, D, dense_offsets);
-  scan_exclusive(A, (int64_t)D + 1, bsum, nullptr, s);
+  scan_exclusive(A, 1, (int64_t)D + 1, bsum, nullptr, s);
   hipLaunchKernelGGL(simplify_anchor_list_kernel, per_dense, dim3(256), 0, s, D, (const uint8_t*)kept, (const uint32_t*)A, alist);
   hipLaunchKernelGGL(simplify_free_min_kernel, per_dense, dim3(256), 0, s, (const int2*)dense, (const int32_t*)dense_offsets, R, D, W,
                      (const uint32_t*)A, ring_min);
@@ -454,7 +435,7 @@ extern "C" int gdl_scene_simplify_write(const int32_t* dense, const int32_t* den
   const int R = n_rings, D = n_dense;
   const int64_t L = (int64_t)D + 1;
   hipLaunchKernelGGL(simplify_flags_kernel, one_per_thread(L), dim3(256), 0, s, D, kept, (uint32_t*)scan);
-  scan_exclusive((uint32_t*)scan, L, (uint32_t*)scan + L, (uint32_t*)n_out, s);
+  scan_exclusive((uint32_t*)scan, 1, L, (uint32_t*)scan + L, (uint32_t*)n_out, s);
   hipLaunchKernelGGL(simplify_scatter_kernel, one_per_thread(D > R + 1 ? D : R + 1), dim3(256), 0, s, (const int2*)dense, dense_offsets, R, D,
                      kept, (const uint32_t*)scan, (int2*)out_vertices, out_offsets);
   GDL_CHECK_LAUNCH("gdl_scene_simplify_write");

@@ -134,44 +134,25 @@ class Header:
             self.status.add(name)
 
 
-_ABI = Header((INCLUDE / "gdlhip.h").read_text())
-_DEBUG = Header((INCLUDE / "gdlhip_debug.h").read_text())
-_SCENE = Header((INCLUDE / "gdlhip_scene.h").read_text())
-_SCENE_TTA = Header((INCLUDE / "gdlhip_scene_tta.h").read_text())
-_SCENE_NODATA = Header((INCLUDE / "gdlhip_scene_nodata.h").read_text())
-_SCENE_SIEVE = Header((INCLUDE / "gdlhip_scene_sieve.h").read_text())
-_SCENE_RINGS = Header((INCLUDE / "gdlhip_scene_rings.h").read_text())
-_SCENE_SIMPLIFY = Header((INCLUDE / "gdlhip_scene_simplify.h").read_text())
-_SCENE_REGIONS = Header((INCLUDE / "gdlhip_scene_regions.h").read_text())
-_SCENE_BURN = Header((INCLUDE / "gdlhip_scene_burn.h").read_text())
-
-# name -> (restype, argtypes); every symbol declared in include/gdlhip.h, the gdl_debug_* hooks of include/gdlhip_debug.h, the
-# whole-scene inference calls of include/gdlhip_scene.h, their test-time augmentation forms of include/gdlhip_scene_tta.h, the
-# nodata calls of include/gdlhip_scene_nodata.h, the components and sieve calls of include/gdlhip_scene_sieve.h, the polygon
-# ring calls of include/gdlhip_scene_rings.h, their simplification of include/gdlhip_scene_simplify.h, the per-region
-# attributes of include/gdlhip_scene_regions.h and the burning of rings into a raster of include/gdlhip_scene_burn.h
-SIGNATURES, DEBUG_SIGNATURES, SCENE_SIGNATURES = _ABI.functions, _DEBUG.functions, _SCENE.functions
-SCENE_TTA_SIGNATURES, SCENE_NODATA_SIGNATURES = _SCENE_TTA.functions, _SCENE_NODATA.functions
-SCENE_SIEVE_SIGNATURES, SCENE_RINGS_SIGNATURES = _SCENE_SIEVE.functions, _SCENE_RINGS.functions
-SCENE_RINGS_SCAN_TILE, SCENE_RINGS_FLAGS = (_SCENE_RINGS.constants[k] for k in ("GDL_SCENE_RINGS_SCAN_TILE", "GDL_SCENE_RINGS_FLAGS"))
-SCENE_SIMPLIFY_SIGNATURES = _SCENE_SIMPLIFY.functions
-SCENE_SIMPLIFY_SCAN_TILE, SCENE_SIMPLIFY_ROUNDS = (_SCENE_SIMPLIFY.constants[k] for k in ("GDL_SCENE_SIMPLIFY_SCAN_TILE",
-                                                                                          "GDL_SCENE_SIMPLIFY_ROUNDS"))
-SCENE_REGIONS_SIGNATURES = _SCENE_REGIONS.functions
-SCENE_REGIONS_SCAN_TILE, SCENE_REGIONS_TILE, SCENE_REGIONS_TABLE, SCENE_REGIONS_PROBES = (
-    _SCENE_REGIONS.constants[k] for k in ("GDL_SCENE_REGIONS_SCAN_TILE", "GDL_SCENE_REGIONS_TILE", "GDL_SCENE_REGIONS_TABLE",
-                                          "GDL_SCENE_REGIONS_PROBES"))
-SCENE_BURN_SIGNATURES = _SCENE_BURN.functions
-SCENE_BURN_SCAN_TILE, SCENE_BURN_BITS_MAX, SCENE_BURN_CHUNK = (
-    _SCENE_BURN.constants[k] for k in ("GDL_SCENE_BURN_SCAN_TILE", "GDL_SCENE_BURN_BITS_MAX", "GDL_SCENE_BURN_CHUNK"))
+# prefix of the module-level names -> the header of include/ that declares them: the C-ABI and its gdl_debug_* hooks first, then
+# the whole-scene inference calls, stage by stage.  A new header is one line here.
+HEADERS = {"": "gdlhip.h", "DEBUG": "gdlhip_debug.h", "SCENE": "gdlhip_scene.h", "SCENE_TTA": "gdlhip_scene_tta.h",
+           "SCENE_NODATA": "gdlhip_scene_nodata.h", "SCENE_SIEVE": "gdlhip_scene_sieve.h", "SCENE_RINGS": "gdlhip_scene_rings.h",
+           "SCENE_SIMPLIFY": "gdlhip_scene_simplify.h", "SCENE_REGIONS": "gdlhip_scene_regions.h",
+           "SCENE_BURN": "gdlhip_scene_burn.h"}
+_PARSED = {prefix: Header((INCLUDE / name).read_text()) for prefix, name in HEADERS.items()}
+_ABI = _PARSED[""]
+for _prefix, _header in _PARSED.items():
+    # SIGNATURES, DEBUG_SIGNATURES, SCENE_SIGNATURES, ...: name -> (restype, argtypes) of every symbol the header declares
+    globals()[f"{_prefix}_SIGNATURES".lstrip("_")] = _header.functions
+    # the header's enumerators and integer #defines without their GDL_ prefix: F32, BF16, ACT_*, FOCAL_* (the `form` argument of
+    # the *_lowres_bwd calls), BCE_TARGET_* (the `target_type` of gdl_soft_bce_*), OVERLAP_* (gdl_overlap_options.kind),
+    # SCENE_RINGS_SCAN_TILE, SCENE_BURN_BITS_MAX, ...
+    globals().update({k.removeprefix("GDL_"): v for k, v in _header.constants.items()})
 STATUS_FUNCTIONS = frozenset(_ABI.status)      # they return a gdl_status; every other function returns a value
-# what checked() gives the errcheck: the scene calls return a gdl_status too
-_CHECKED = (STATUS_FUNCTIONS | _SCENE.status | _SCENE_TTA.status | _SCENE_NODATA.status | _SCENE_SIEVE.status | _SCENE_RINGS.status
-            | _SCENE_SIMPLIFY.status | _SCENE_REGIONS.status | _SCENE_BURN.status)
+# what checked() gives the errcheck: the scene calls return a gdl_status too (the debug hooks are left to their callers)
+_CHECKED = STATUS_FUNCTIONS.union(*(h.status for prefix, h in _PARSED.items() if prefix != "DEBUG"))
 ConvArgs, WgradArgs, DiceOptions, OverlapOptions = (_ABI.structs[c] for c in _STRUCTS)
-# the header's enumerators and integer #defines without their GDL_ prefix: F32, BF16, ACT_*, FOCAL_* (the `form` argument of the
-# *_lowres_bwd calls), BCE_TARGET_* (the `target_type` of gdl_soft_bce_*), OVERLAP_* (gdl_overlap_options.kind), ...
-globals().update({k.removeprefix("GDL_"): v for k, v in _ABI.constants.items()})
 
 # environment variable -> the hook load() calls with its integer value (meanings: include/gdlhip_debug.h)
 ENV_HOOKS = {
@@ -209,15 +190,13 @@ def _open(errcheck=None) -> C.CDLL:
                "There is no PyTorch/CPU fallback for the gdlhip ops.")
         raise GdlHipError(msg)
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in (*SIGNATURES.items(), *DEBUG_SIGNATURES.items(), *SCENE_SIGNATURES.items(),
-                              *SCENE_TTA_SIGNATURES.items(), *SCENE_NODATA_SIGNATURES.items(), *SCENE_SIEVE_SIGNATURES.items(),
-                              *SCENE_RINGS_SIGNATURES.items(), *SCENE_SIMPLIFY_SIGNATURES.items(),
-                              *SCENE_REGIONS_SIGNATURES.items(), *SCENE_BURN_SIGNATURES.items()):
-        fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
-        fn.restype = res
-        fn.argtypes = args
-        if errcheck is not None and name in _CHECKED:
-            fn.errcheck = errcheck
+    for header in _PARSED.values():
+        for name, (res, args) in header.functions.items():
+            fn = getattr(lib, name)  # AttributeError if the .so lacks a declared symbol
+            fn.restype = res
+            fn.argtypes = args
+            if errcheck is not None and name in _CHECKED:
+                fn.errcheck = errcheck
     return lib
 
 

@@ -2191,8 +2191,7 @@ def scene_finish_valid(canvas: Tensor, valid: Tensor | None, nodata_label: int =
     _need_cuda(canvas)
     if canvas.dtype != torch.float32 or canvas.dim() != 3 or not canvas.is_contiguous() or not 2 <= canvas.shape[0] <= 17:
         raise ValueError(f"scene_finish_valid: contiguous f32 canvas [K+1, H, W] with 1..16 classes expected, got {canvas.dtype} {tuple(canvas.shape)}")
-    if isinstance(nodata_label, bool) or not isinstance(nodata_label, int) or not 0 <= nodata_label <= 255:
-        raise ValueError(f"scene_finish_valid: nodata_label must be an int in 0..255, got {nodata_label!r}")
+    byte_check("scene_finish_valid", "nodata_label", nodata_label)
     K, H, W = canvas.shape[0] - 1, int(canvas.shape[1]), int(canvas.shape[2])
     if H * W < 1:
         raise ValueError(f"scene_finish_valid: empty canvas {tuple(canvas.shape)}")
@@ -2201,6 +2200,33 @@ def scene_finish_valid(canvas: Tensor, valid: Tensor | None, nodata_label: int =
     probs = torch.empty((K, H, W), device=canvas.device, dtype=torch.float32) if return_probs else None
     _lib.checked().gdl_scene_finish_valid(_p(canvas), K, H * W, float(threshold), _p(plane), nodata_label, _p(mask), _p(probs), _stream())
     return mask, probs
+
+
+# what the vector stages below share: the range of a mask value, the labels argument and the scratch of a scan
+def is_byte(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, int) and 0 <= v <= 255
+
+
+def byte_check(who: str, name: str, v, none_ok: bool = False) -> None:
+    """ValueError unless ``v`` is an int in 0..255 (a mask value), or None where ``none_ok``."""
+    if not (is_byte(v) or (none_ok and v is None)):
+        raise ValueError(f"{who}: {name} must be {'None or ' if none_ok else ''}an int in 0..255, got {v!r}")
+
+
+def _labels_check(op: str, labels, H: int, W: int) -> None:
+    if labels is not None and (not isinstance(labels, Tensor) or labels.dtype != torch.int32 or tuple(labels.shape) != (H, W)
+                               or not labels.is_contiguous()):
+        got = f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, Tensor) else type(labels).__name__
+        raise ValueError(f"{op}: labels must be a contiguous int32 [H, W] = [{H}, {W}] tensor, got {got}")
+
+
+def _i32(dev, n: int) -> Tensor:
+    return torch.empty((n,), device=dev, dtype=torch.int32)
+
+
+def _scan_blocks(n: int, tile: int) -> int:
+    """The block sums a scan over n entries needs (tile: the stage's GDL_SCENE_*_SCAN_TILE)."""
+    return -(-n // tile)
 
 
 # the sieve (include/gdlhip_scene_sieve.h): connected components of a label mask, the small ones dissolved into their neighbours
@@ -2212,8 +2238,7 @@ def _sieve_check(op: str, mask: Tensor, connectivity: int, ignore_label: int | N
         raise ValueError(f"{op}: contiguous uint8 / bool [H, W] mask expected, got {got}")
     if isinstance(connectivity, bool) or connectivity not in (4, 8):
         raise ValueError(f"{op}: connectivity must be 4 or 8, got {connectivity!r}")
-    if ignore_label is not None and (isinstance(ignore_label, bool) or not isinstance(ignore_label, int) or not 0 <= ignore_label <= 255):
-        raise ValueError(f"{op}: ignore_label must be None or an int in 0..255, got {ignore_label!r}")
+    byte_check(op, "ignore_label", ignore_label, none_ok=True)
     H, W = int(mask.shape[0]), int(mask.shape[1])
     if H * W < 1:
         raise ValueError(f"{op}: empty mask {tuple(mask.shape)}")
@@ -2277,7 +2302,7 @@ def _keep_table(values) -> list[int]:
     if values is None:
         return [1] * 256
     items = None if isinstance(values, (str, bytes, Tensor)) or not hasattr(values, "__iter__") else list(values)
-    if items is None or any(isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255 for v in items):
+    if items is None or not all(is_byte(v) for v in items):
         raise ValueError(f"scene_rings: values must be None or an iterable of ints in 0..255, got {values!r}")
     return [int(v in items) for v in range(256)]
 
@@ -2296,32 +2321,22 @@ def scene_rings(mask: Tensor, connectivity: int = 4, ignore_label: int | None = 
     if H * W >= 2 ** 29:
         raise ValueError(f"scene_rings: {H} x {W} pixels: a slot 4 * (y * W + x) + side must fit an int32 (H * W < 2^29)")
     table = _keep_table(values)
-    if labels is not None and (not isinstance(labels, Tensor) or labels.dtype != torch.int32 or tuple(labels.shape) != (H, W)
-                               or not labels.is_contiguous()):
-        got = f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, Tensor) else type(labels).__name__
-        raise ValueError(f"scene_rings: labels must be a contiguous int32 [H, W] = [{H}, {W}] tensor, got {got}")
+    _labels_check("scene_rings", labels, H, W)
     _need_cuda(mask, labels)
-    dev, lib = mask.device, _lib.checked()
+    dev, lib, tile = mask.device, _lib.checked(), _lib.SCENE_RINGS_SCAN_TILE
     if labels is None:
         labels = scene_components(m, connectivity, ignore_label)[0]
-
-    def i32(n: int) -> Tensor:
-        return torch.empty((n,), device=dev, dtype=torch.int32)
-
-    def blocks(n: int) -> int:      # the block sums a scan over n entries needs
-        return -(-n // _lib.SCENE_RINGS_SCAN_TILE)
-
     keep = torch.tensor(table, dtype=torch.uint8).to(dev)
-    offsets, n_sides = i32(H * W), i32(1)
-    lib.gdl_scene_rings_count(_p(m), H, W, ignore, _p(keep), _p(offsets), _p(i32(blocks(H * W))), _p(n_sides), _stream())
+    offsets, n_sides = _i32(dev, H * W), _i32(dev, 1)
+    lib.gdl_scene_rings_count(_p(m), H, W, ignore, _p(keep), _p(offsets), _p(_i32(dev, _scan_blocks(H * W, tile))), _p(n_sides), _stream())
     E = int(n_sides.item())
-    side_slot, side_next, side_ring, side_rank = i32(E), i32(E), i32(E), i32(E)
-    work, counts = i32(3 * E + 2 * blocks(E) + _lib.SCENE_RINGS_FLAGS), i32(2)
+    side_slot, side_next, side_ring, side_rank = (_i32(dev, E) for _ in range(4))
+    work, counts = _i32(dev, 3 * E + 2 * _scan_blocks(E, tile) + _lib.SCENE_RINGS_FLAGS), _i32(dev, 2)
     lib.gdl_scene_rings_trace(_p(m), H, W, connectivity, ignore, _p(keep), _p(offsets), E, _p(side_slot), _p(side_next), _p(side_ring),
                               _p(side_rank), _p(work), _p(counts), _stream())
     R, V = (int(c) for c in counts.tolist())
-    out = SceneRings(torch.empty((V, 2), device=dev, dtype=torch.int32), i32(R + 1), torch.empty((R,), device=dev, dtype=torch.uint8),
-                     i32(R), i32(R), torch.empty((R,), device=dev, dtype=torch.int64))
+    out = SceneRings(torch.empty((V, 2), device=dev, dtype=torch.int32), _i32(dev, R + 1), torch.empty((R,), device=dev, dtype=torch.uint8),
+                     _i32(dev, R), _i32(dev, R), torch.empty((R,), device=dev, dtype=torch.int64))
     lib.gdl_scene_rings_write(_p(m), _p(labels), W, E, R, V, _p(side_slot), _p(side_next), _p(side_ring), _p(side_rank), _p(work),
                               *(_p(t) for t in out), _stream())
     return out
@@ -2331,21 +2346,36 @@ def scene_rings(mask: Tensor, connectivity: int = 4, ignore_label: int | None = 
 SIMPLIFY_TOLERANCE_MAX = 2 ** 20      # pixels; tol_q8 = round(tolerance * 256) then fits 2^28
 
 
-def _rings_check(op: str, rings) -> tuple[int, int]:
-    """(R, V) of a SceneRings whose six fields belong together by type, shape and device, or ValueError."""
-    fields = {"vertices": torch.int32, "ring_offsets": torch.int32, "value": torch.uint8, "label": torch.int32, "start": torch.int32,
-              "area2": torch.int64}
-    got = [getattr(rings, name, None) for name in fields]
+def simplify_tolerance_ok(x) -> bool:
+    """Whether ``x`` is a tolerance ``scene_rings_simplify`` takes: a finite number of pixels in 0..SIMPLIFY_TOLERANCE_MAX."""
+    return not isinstance(x, bool) and isinstance(x, (int, float)) and math.isfinite(x) and 0 <= x <= SIMPLIFY_TOLERANCE_MAX
+
+
+_RING_FIELDS = {"vertices": torch.int32, "ring_offsets": torch.int32, "value": torch.uint8, "label": torch.int32, "start": torch.int32,
+                "area2": torch.int64}      # of SceneRings, in its order
+
+
+def _ring_fields_check(op: str, rings, names: tuple, must_have: str) -> tuple[int, int]:
+    """(R, V) of rings whose fields ``names`` (vertices and ring_offsets first) belong together by type, shape and device, or
+    ValueError; ``must_have``: how the message calls the fields."""
+    got = [getattr(rings, name, None) for name in names]
     if not all(isinstance(t, Tensor) for t in got):
-        raise ValueError(f"{op}: rings must have the six tensor fields of SceneRings ({', '.join(fields)}), got {type(rings).__name__}")
+        raise ValueError(f"{op}: rings must have {must_have}, got {type(rings).__name__}")
     vertices, offsets = got[0], got[1]
     R = int(offsets.numel()) - 1
     shapes = {"vertices": (int(vertices.shape[0]), 2) if vertices.dim() else None, "ring_offsets": (R + 1,)}
-    for (name, dtype), t in zip(fields.items(), got):
-        if t.dtype != dtype or tuple(t.shape) != shapes.get(name, (R,)) or not t.is_contiguous() or t.device != vertices.device:
-            raise ValueError(f"{op}: rings.{name} must be a contiguous {dtype} {shapes.get(name, (R,))} tensor on {vertices.device}, got "
+    for name, t in zip(names, got):
+        dtype, shape = _RING_FIELDS[name], shapes.get(name, (R,))
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != vertices.device:
+            raise ValueError(f"{op}: rings.{name} must be a contiguous {dtype} {shape} tensor on {vertices.device}, got "
                              f"{t.dtype} {tuple(t.shape)} on {t.device}")
-    V = int(vertices.shape[0])
+    return R, int(vertices.shape[0])
+
+
+def _rings_check(op: str, rings) -> tuple[int, int]:
+    """(R, V) of a SceneRings whose six fields belong together by type, shape and device, or ValueError."""
+    names = tuple(_RING_FIELDS)
+    R, V = _ring_fields_check(op, rings, names, f"the six tensor fields of SceneRings ({', '.join(names)})")
     if R < 0 or 4 * R > V or (R == 0) != (V == 0):
         raise ValueError(f"{op}: {R} rings and {V} vertices do not belong together (a ring has at least 4 vertices)")
     return R, V
@@ -2365,8 +2395,7 @@ def scene_rings_simplify(rings: SceneRings, mask: Tensor, tolerance: float, igno
     the dense vertex count, one flag per group of ``GDL_SCENE_SIMPLIFY_ROUNDS`` rounds (the depth of Douglas-Peucker depends
     on the data), and the output vertex count (gdl_scene_nodes / gdl_scene_simplify_count / _dense / _rounds / _write)."""
     op = "scene_rings_simplify"
-    if isinstance(tolerance, bool) or not isinstance(tolerance, (int, float)) or not math.isfinite(tolerance) \
-            or not 0 <= tolerance <= SIMPLIFY_TOLERANCE_MAX:
+    if not simplify_tolerance_ok(tolerance):
         raise ValueError(f"{op}: tolerance must be a finite number of pixels in 0..2^20, got {tolerance!r}")
     R, V = _rings_check(op, rings)
     m, H, W, ignore = _sieve_check(op, mask, 4, ignore_label)
@@ -2378,31 +2407,24 @@ def scene_rings_simplify(rings: SceneRings, mask: Tensor, tolerance: float, igno
     if rings.vertices.device != mask.device:
         raise ValueError(f"{op}: the rings are on {rings.vertices.device}, the mask on {mask.device}")
     _need_cuda(mask, rings.vertices)
-    dev, lib, tol_q8 = mask.device, _lib.checked(), int(round(tolerance * 256))
-
-    def i32(n: int) -> Tensor:
-        return torch.empty((n,), device=dev, dtype=torch.int32)
-
-    def blocks(n: int) -> int:      # the block sums a scan over n entries needs
-        return -(-n // _lib.SCENE_SIMPLIFY_SCAN_TILE)
-
+    dev, lib, tol_q8, tile = mask.device, _lib.checked(), int(round(tolerance * 256)), _lib.SCENE_SIMPLIFY_SCAN_TILE
     if R == 0:
         return SceneRings(torch.empty((0, 2), device=dev, dtype=torch.int32), torch.zeros((1,), device=dev, dtype=torch.int32), rings.value, rings.label, rings.start, rings.area2)
     keep = torch.tensor(table, dtype=torch.uint8).to(dev)
     nodes = torch.empty((H + 1, W + 1), device=dev, dtype=torch.uint8)
     lib.gdl_scene_nodes(_p(m), H, W, ignore, _p(keep), _p(nodes), _stream())
-    pos, n_dense = i32(V + 1), i32(1)
-    lib.gdl_scene_simplify_count(_p(nodes), H, W, _p(rings.vertices), _p(rings.ring_offsets), R, V, _p(pos), _p(i32(blocks(V + 1))),
-                                 _p(n_dense), _stream())
+    pos, n_dense = _i32(dev, V + 1), _i32(dev, 1)
+    lib.gdl_scene_simplify_count(_p(nodes), H, W, _p(rings.vertices), _p(rings.ring_offsets), R, V, _p(pos),
+                                 _p(_i32(dev, _scan_blocks(V + 1, tile))), _p(n_dense), _stream())
     D = int(n_dense.item())
-    dense, dense_offsets = torch.empty((D, 2), device=dev, dtype=torch.int32), i32(R + 1)
-    kept, seg = torch.empty((D,), device=dev, dtype=torch.uint8), i32(4 * D + _lib.SCENE_SIMPLIFY_ROUNDS)
+    dense, dense_offsets = torch.empty((D, 2), device=dev, dtype=torch.int32), _i32(dev, R + 1)
+    kept, seg = torch.empty((D,), device=dev, dtype=torch.uint8), _i32(dev, 4 * D + _lib.SCENE_SIMPLIFY_ROUNDS)
     key = torch.empty((D,), device=dev, dtype=torch.int64)
-    work = torch.empty((R + D + 1 + blocks(D + 1),), device=dev, dtype=torch.int64)      # int64: 8-byte aligned, at least as large
+    work = torch.empty((R + D + 1 + _scan_blocks(D + 1, tile),), device=dev, dtype=torch.int64)      # int64: 8-byte aligned, at least as large
     lib.gdl_scene_simplify_dense(_p(nodes), H, W, _p(rings.vertices), _p(rings.ring_offsets), R, V, _p(pos), D, _p(dense),
                                  _p(dense_offsets), _p(kept), _p(seg), _p(key), _p(work), _stream())
     del work, pos, nodes
-    changed, first = i32(1), 1
+    changed, first = _i32(dev, 1), 1
     while True:
         lib.gdl_scene_simplify_rounds(_p(dense), W, D, tol_q8, first, _lib.SCENE_SIMPLIFY_ROUNDS, _p(kept), _p(seg), _p(key), _p(changed),
                                       _stream())
@@ -2410,9 +2432,9 @@ def scene_rings_simplify(rings: SceneRings, mask: Tensor, tolerance: float, igno
         if not int(changed.item()):
             break
     del seg, key
-    out, offsets, n_out = torch.empty((D, 2), device=dev, dtype=torch.int32), i32(R + 1), i32(1)
-    lib.gdl_scene_simplify_write(_p(dense), _p(dense_offsets), R, D, _p(kept), _p(i32(D + 1 + blocks(D + 1))), _p(out), _p(offsets),
-                                 _p(n_out), _stream())
+    out, offsets, n_out = torch.empty((D, 2), device=dev, dtype=torch.int32), _i32(dev, R + 1), _i32(dev, 1)
+    lib.gdl_scene_simplify_write(_p(dense), _p(dense_offsets), R, D, _p(kept), _p(_i32(dev, D + 1 + _scan_blocks(D + 1, tile))), _p(out),
+                                 _p(offsets), _p(n_out), _stream())
     n = int(n_out.item())
     return SceneRings(out if n == D else out[:n].clone(), offsets, rings.value, rings.label, rings.start, rings.area2)
 
@@ -2442,10 +2464,7 @@ def scene_regions(mask: Tensor, connectivity: int = 4, ignore_label: int | None 
     (gdl_scene_regions_count / _stats)."""
     op = "scene_regions"
     m, H, W, ignore = _sieve_check(op, mask, connectivity, ignore_label)
-    if labels is not None and (not isinstance(labels, Tensor) or labels.dtype != torch.int32 or tuple(labels.shape) != (H, W)
-                               or not labels.is_contiguous()):
-        got = f"{labels.dtype} {tuple(labels.shape)}" if isinstance(labels, Tensor) else type(labels).__name__
-        raise ValueError(f"{op}: labels must be a contiguous int32 [H, W] = [{H}, {W}] tensor, got {got}")
+    _labels_check(op, labels, H, W)
     K = 0
     if canvas is not None:
         if not isinstance(canvas, Tensor) or canvas.dtype != torch.float32 or canvas.dim() != 3 or tuple(canvas.shape[1:]) != (H, W) \
@@ -2466,7 +2485,7 @@ def scene_regions(mask: Tensor, connectivity: int = 4, ignore_label: int | None 
         return torch.empty(shape, device=dev, dtype=dtype)
 
     rank, n_regions = new((H * W,), torch.int32), new((1,), torch.int32)
-    bsum = new((-(-H * W // _lib.SCENE_REGIONS_SCAN_TILE),), torch.int32)
+    bsum = _i32(dev, _scan_blocks(H * W, _lib.SCENE_REGIONS_SCAN_TILE))
     lib.gdl_scene_regions_count(_p(labels), H, W, _p(rank), _p(bsum), _p(n_regions), _stream())
     N = int(n_regions.item())
     conf = canvas is not None
@@ -2486,17 +2505,9 @@ class SceneBurn(NamedTuple):
 
 def _burn_check(op: str, rings, size, bits, background, conflict, reference) -> tuple[int, int, int, int]:
     """The argument checks of ``scene_burn`` but for the device (which is asked for last); (R, V, H, W)."""
-    fields = {"vertices": torch.int32, "ring_offsets": torch.int32, "value": torch.uint8}
-    got = [getattr(rings, name, None) for name in fields]
-    if not all(isinstance(t, Tensor) for t in got):
-        raise ValueError(f"{op}: rings must have the tensor fields {', '.join(fields)}, got {type(rings).__name__}")
-    vertices, offsets, _ = got
-    R = int(offsets.numel()) - 1
-    shapes = {"vertices": (int(vertices.shape[0]), 2) if vertices.dim() else None, "ring_offsets": (R + 1,), "value": (R,)}
-    for (name, dtype), t in zip(fields.items(), got):
-        if t.dtype != dtype or tuple(t.shape) != shapes[name] or not t.is_contiguous() or t.device != vertices.device:
-            raise ValueError(f"{op}: rings.{name} must be a contiguous {dtype} {shapes[name]} tensor on {vertices.device}, got "
-                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    names = ("vertices", "ring_offsets", "value")
+    R, V = _ring_fields_check(op, rings, names, f"the tensor fields {', '.join(names)}")
+    vertices = rings.vertices
     if R < 0:
         raise ValueError(f"{op}: rings.ring_offsets must hold R + 1 >= 1 offsets, got none")
     try:
@@ -2510,9 +2521,8 @@ def _burn_check(op: str, rings, size, bits, background, conflict, reference) -> 
         raise ValueError(f"{op}: {H} x {W} pixels: a linear index must fit an int32 (H * W < 2^31)")
     if isinstance(bits, bool) or not isinstance(bits, int) or not 0 <= bits <= _lib.SCENE_BURN_BITS_MAX:
         raise ValueError(f"{op}: bits must be an int in 0..{_lib.SCENE_BURN_BITS_MAX}, got {bits!r}")
-    for name, v in (("background", background), ("conflict", conflict)):
-        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255:
-            raise ValueError(f"{op}: {name} must be an int in 0..255, got {v!r}")
+    byte_check(op, "background", background)
+    byte_check(op, "conflict", conflict)
     if reference is not None:
         if not isinstance(reference, Tensor) or reference.dtype not in (torch.uint8, torch.bool) or tuple(reference.shape) != (H, W) \
                 or not reference.is_contiguous():
@@ -2520,7 +2530,7 @@ def _burn_check(op: str, rings, size, bits, background, conflict, reference) -> 
             raise ValueError(f"{op}: reference must be a contiguous uint8 / bool [H, W] = [{H}, {W}] tensor, got {what}")
         if reference.device != vertices.device:
             raise ValueError(f"{op}: the reference is on {reference.device}, the rings on {vertices.device}")
-    return R, int(vertices.shape[0]), H, W
+    return R, V, H, W
 
 
 def scene_burn(rings, size: tuple[int, int], *, bits: int = 0, background: int = 0, conflict: int = 255,
@@ -2545,8 +2555,8 @@ def scene_burn(rings, size: tuple[int, int], *, bits: int = 0, background: int =
     n_cross = 0
     edge_ring = edge_rows = plane = None
     if R > 0 and V > 0:
-        edge_ring, edge_rows = torch.empty((V,), device=dev, dtype=torch.int32), torch.empty((V + 1,), device=dev, dtype=torch.int32)
-        bsum = torch.empty((-(-(V + 1) // _lib.SCENE_BURN_SCAN_TILE),), device=dev, dtype=torch.int32)
+        edge_ring, edge_rows = _i32(dev, V), _i32(dev, V + 1)
+        bsum = _i32(dev, _scan_blocks(V + 1, _lib.SCENE_BURN_SCAN_TILE))
         found = torch.empty((2,), device=dev, dtype=torch.int64)
         lib.gdl_scene_burn_count(_p(rings.vertices), _p(rings.ring_offsets), R, V, bits, H, W, _p(edge_ring), _p(edge_rows), _p(bsum),
                                  _p(found), _stream())

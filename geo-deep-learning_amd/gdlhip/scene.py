@@ -17,6 +17,8 @@ from typing import NamedTuple
 import torch
 from torch import Tensor
 
+from .ops import byte_check
+
 
 def axis_origins(length: int, tile: int, stride: int) -> list[int]:
     """Tile origins along one axis: 0 alone when the axis fits in a tile, otherwise 0, s, 2s, ... while the tile ends before the
@@ -234,8 +236,7 @@ def rings_from_features(features, transform=None, bits: int = 0, value_key: str 
         if value_key not in properties:
             raise ValueError(f"{who}: feature {k} has no property {value_key!r}")
         v = properties[value_key]
-        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255:
-            raise ValueError(f"{who}: feature {k}: {value_key} must be an int in 0..255, got {v!r}")
+        byte_check(f"{who}: feature {k}", value_key, v)
         geometry = feature.get("geometry") or {}
         kind = geometry.get("type")
         if kind not in ("Polygon", "MultiPolygon"):

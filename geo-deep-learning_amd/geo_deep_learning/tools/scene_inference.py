@@ -42,7 +42,6 @@ tile, tools/script_model.py)."""
 
 from __future__ import annotations
 
-import math
 from typing import NamedTuple
 
 import torch
@@ -149,8 +148,7 @@ class SceneInference:
         self.tta = None if tta is None else gscene.tta_codes(tta, self.tile)      # ValueError for what is no set of codes
         if nodata_rule not in ops.NODATA_RULES:
             raise ValueError(f"SceneInference: unknown nodata_rule {nodata_rule!r} ('all' or 'any')")
-        if isinstance(nodata_label, bool) or not isinstance(nodata_label, int) or not 0 <= nodata_label <= 255:
-            raise ValueError(f"SceneInference: nodata_label must be an int in 0..255, got {nodata_label!r}")
+        ops.byte_check("SceneInference", "nodata_label", nodata_label)
         if isinstance(min_valid, bool) or not isinstance(min_valid, int) or min_valid < 1:
             raise ValueError(f"SceneInference: min_valid must be a pixel count of at least 1, got {min_valid!r}")
         if nodata is not None:      # numbers, one or one per band; whether the raster's type can hold them is checked with the raster
@@ -282,17 +280,7 @@ class SceneInference:
         ``gdlhip.scene.polygons(result.rings)`` turns the rings into features.
         ``agreement``: False (the result, the calls and the bits of before) or True: a ``SceneVectorsAgreement``, the same with
         ``rings_agreement(mask, rings, num_classes)`` of the rings it returns beside them."""
-        if simplify is not None and (isinstance(simplify, bool) or not isinstance(simplify, (int, float)) or not math.isfinite(simplify)
-                                     or not 0 <= simplify <= ops.SIMPLIFY_TOLERANCE_MAX):
-            raise ValueError(f"SceneInference.predict_rings: simplify must be None or a finite tolerance in 0..2^20 pixels, got {simplify!r}")
-        mask = self.predict(raster, valid=valid).mask
-        ignore = self.nodata_label if self.nodata is not None or valid is not None else None
-        rings = ops.scene_rings(mask, connectivity, ignore, values)
-        if simplify is not None:
-            rings = ops.scene_rings_simplify(rings, mask, simplify, ignore, values)
-        if agreement:
-            return SceneVectorsAgreement(mask, rings, rings_agreement(mask, rings, self._num_classes()))
-        return SceneVectors(mask, rings)
+        return SceneInference._predict_vectors(self, "predict_rings", False, raster, valid, connectivity, values, simplify, agreement)
 
     def predict_features(self, raster: torch.Tensor, valid: torch.Tensor | None = None, *, connectivity: int = 4,
                          values=None, simplify: float | None = None, agreement: bool = False) -> SceneFeatures | SceneFeaturesAgreement:
@@ -306,18 +294,24 @@ class SceneInference:
         lower confidence, which is the point.  The simplification moves vertices, not pixels: the regions are the same with and
         without it.  ``gdlhip.scene.polygons(result.rings, regions=result.regions)`` joins the two into features.
         ``agreement``: as in ``predict_rings``; True gives a ``SceneFeaturesAgreement``."""
-        if simplify is not None and (isinstance(simplify, bool) or not isinstance(simplify, (int, float)) or not math.isfinite(simplify)
-                                     or not 0 <= simplify <= ops.SIMPLIFY_TOLERANCE_MAX):
-            raise ValueError(f"SceneInference.predict_features: simplify must be None or a finite tolerance in 0..2^20 pixels, got {simplify!r}")
+        return SceneInference._predict_vectors(self, "predict_features", True, raster, valid, connectivity, values, simplify, agreement)
+
+    def _predict_vectors(self, who: str, with_regions: bool, raster, valid, connectivity, values, simplify, agreement):
+        """``predict_rings`` (``with_regions`` False) and ``predict_features`` (True): the mask, its components labelled once, the
+        rings from those labels, the regions where asked for, then the simplification and the agreement."""
+        if simplify is not None and not ops.simplify_tolerance_ok(simplify):
+            raise ValueError(f"SceneInference.{who}: simplify must be None or a finite tolerance in 0..2^20 pixels, got {simplify!r}")
         raster, plane = self._upload(raster, valid)
         canvas = self._canvas(raster, plane)
         mask = self._finish(canvas, plane, False).mask
-        ignore = None if plane is None else self.nodata_label
+        ignore = None if plane is None else self.nodata_label      # no validity plane: every pixel is a region's
         labels = ops.scene_components(mask, connectivity, ignore)[0]
         rings = ops.scene_rings(mask, connectivity, ignore, values, labels=labels)
-        regions = ops.scene_regions(mask, connectivity, ignore, canvas=canvas, labels=labels)
+        regions = ops.scene_regions(mask, connectivity, ignore, canvas=canvas, labels=labels) if with_regions else None
         if simplify is not None:
             rings = ops.scene_rings_simplify(rings, mask, simplify, ignore, values)
+        found = (mask, rings, regions) if with_regions else (mask, rings)
         if agreement:
-            return SceneFeaturesAgreement(mask, rings, regions, rings_agreement(mask, rings, self._num_classes()))
-        return SceneFeatures(mask, rings, regions)
+            kind = SceneFeaturesAgreement if with_regions else SceneVectorsAgreement
+            return kind(*found, rings_agreement(mask, rings, self._num_classes()))
+        return (SceneFeatures if with_regions else SceneVectors)(*found)

@@ -180,6 +180,32 @@ def test_checked_view_binds_the_errcheck_to_the_status_functions(lib):
     assert chk.gdl_version() == lib.gdl_version()
 
 
+def test_the_header_table_names_every_header_and_binds_every_symbol(lib):
+    """A file of include/ that is not in ``_lib.HEADERS`` would be an entry point nobody binds, and one left out of ``_CHECKED``
+    an entry point whose status nobody reads: the table is held against the directory, and what is derived from it against it."""
+    from gdlhip import _lib
+    files = sorted(p.name for p in (ROOT / "include").glob("*.h"))
+    assert sorted(_lib.HEADERS.values()) == files, "include/*.h and gdlhip._lib.HEADERS disagree (none missing, none twice)"
+    assert list(_lib.HEADERS)[:2] == ["", "DEBUG"] and list(_lib.HEADERS.values())[:2] == ["gdlhip.h", "gdlhip_debug.h"]
+    checked, raw, chk, seen = set(_lib.STATUS_FUNCTIONS), lib, _lib.checked(), set()
+    for prefix, name in _lib.HEADERS.items():
+        header = _lib.Header((ROOT / "include" / name).read_text())
+        signatures = getattr(_lib, f"{prefix}_SIGNATURES".lstrip("_"))
+        assert set(signatures) == set(header.functions) and signatures, name      # a second parse makes struct classes of its own
+        assert not seen & set(signatures), f"{name} declares a symbol of another header again"
+        seen |= set(signatures)
+        if prefix != "DEBUG":
+            checked |= header.status
+        for k, v in header.constants.items():
+            assert getattr(_lib, k.removeprefix("GDL_")) == v, k
+        for symbol, (res, args) in signatures.items():
+            for view in (raw, chk):
+                fn = getattr(view, symbol)
+                assert fn.restype is res and fn.argtypes == args, f"{symbol} of {name} is not bound"
+            assert (getattr(getattr(chk, symbol), "errcheck", None) is _lib.status_errcheck) == (symbol in _lib._CHECKED), symbol
+    assert _lib._CHECKED == checked, "STATUS_FUNCTIONS and the status functions of every header but the debug one"
+
+
 def test_environment_hooks_are_applied_once_by_load(monkeypatch):
     """The GDL_* tuning variables: load() calls the hook of every variable that is set, with its integer value (GDL_FLASH_FWD
     with GDL_FLASH_DEFER, default 6, as its second argument), and of no other."""

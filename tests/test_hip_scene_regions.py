@@ -146,6 +146,22 @@ def test_regions_are_the_oracles(name, H, W):
     assert np.array_equal(mask.cpu().numpy(), host), "the mask is not modified"
 
 
+SCAN_TILE = _lib.SCENE_REGIONS_SCAN_TILE
+
+
+@pytest.mark.parametrize("H,W,blocks", [(23, 89, "T - 1"), (32, 64, "T"), (3, 683, "T + 1"), (17, 241, "2 T + 1")])
+def test_the_scan_of_the_roots_at_its_block_boundaries(H, W, blocks):
+    """gdl_scene_regions_count scans H * W root flags in blocks of SCAN_TILE: a last block that is full but for one entry, exactly
+    full, of one entry, and a third block of one entry.  random-5 has a root in most positions, the last pixels included, so a
+    rank that is off by one block sum moves ``label`` and ``pixels``."""
+    assert H * W == {"T - 1": SCAN_TILE - 1, "T": SCAN_TILE, "T + 1": SCAN_TILE + 1, "2 T + 1": 2 * SCAN_TILE + 1}[blocks]
+    host = _mask("random-5", H, W)
+    want = rg.regions(host, _labels("random-5", H, W, 4, None)[0])
+    assert len(want.label) > H * W // 4 and want.label[-1] >= H * W - W, "roots up to the last row"
+    got = _host(ops.scene_regions(torch.from_numpy(host.copy()).to(DEV)))
+    assert np.array_equal(got.label, want.label) and np.array_equal(got.pixels, want.pixels) and rg.same(got, want)
+
+
 @pytest.mark.parametrize("name", ["constant", "ignore-cross"])
 def test_values_without_a_plane(name):
     """The patterns as they are: 7 everywhere, and a cross of 255 -- values a canvas of five classes (or of one) has no plane for."""

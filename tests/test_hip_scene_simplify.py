@@ -129,6 +129,44 @@ def test_no_live_pixel_gives_no_ring():
         assert gscene.polygons(got) == []
 
 
+SCAN_TILE = _lib.SCENE_SIMPLIFY_SCAN_TILE
+
+
+def _islands(pixels: int, trominoes: int, teeth: int) -> np.ndarray:
+    """Islands on a pitch of three pixels in a sea of 0 (ignored by the caller), so that V and D are known by counting: a single
+    pixel is a ring of 4 vertices, an L of three pixels one of 6, and a `tooth` -- a domino of class 1 on a pixel of class 2 under
+    its left half -- two rings of 4 with one node strictly inside the domino's lower run: 8 vertices, 9 dense ones."""
+    n = pixels + trominoes + teeth
+    side = int(np.ceil(np.sqrt(n)))
+    m = np.zeros((3 * side, 3 * side), dtype=np.uint8)
+    for i in range(n):
+        y, x = 3 * (i // side), 3 * (i % side)
+        m[y, x] = 1
+        if i >= pixels:
+            m[y, x + 1] = 1
+            m[y + 1, x] = 1 if i < pixels + trominoes else 2
+    return m
+
+
+# V is even (the rings are rectilinear), so V + 1 is SCAN_TILE - 1 or SCAN_TILE + 1; D + 1 takes all three values around it
+@pytest.mark.parametrize("pixels,trominoes,teeth,V,D", [(510, 1, 0, SCAN_TILE - 2, SCAN_TILE - 2), (508, 1, 1, SCAN_TILE - 2, SCAN_TILE - 1),
+                                                        (506, 1, 2, SCAN_TILE - 2, SCAN_TILE), (512, 0, 0, SCAN_TILE, SCAN_TILE)])
+def test_the_scans_at_their_block_boundaries(pixels, trominoes, teeth, V, D):
+    """gdl_scene_simplify_count scans V + 1 entries, _dense and _write D + 1, in blocks of SCAN_TILE: the last block full but
+    for one entry, exactly full, and a second block of one entry, which holds the total the next call is sized by."""
+    host = _islands(pixels, trominoes, teeth)
+    assert host.size < 5000
+    traced = ro.trace(host, 4, 0)
+    dense = sim.dense_rings(traced, host, 0)
+    assert (len(traced.vertices), sum(len(ring) for ring in dense[0])) == (V, D)
+    mask = torch.from_numpy(host).to(DEV)
+    rings = ops.scene_rings(mask, 4, 0)
+    _equal(rings, traced, "islands")
+    for tolerance in (0, 0.75):      # what lies on its chord alone, and a tolerance that takes corners of the islands
+        where = (pixels, trominoes, teeth, tolerance)
+        _equal(ops.scene_rings_simplify(rings, mask, tolerance, 0), sim.simplify(traced, host, sim.quantise(tolerance), 0, dense=dense)[0], where)
+
+
 # ------------------------------------------------------------------ 2. SceneInference, DOFA, end to end
 def test_predict_rings_simplify(dofa):  # noqa: F811
     nc, img, sm, scene = dofa
