@@ -1,12 +1,13 @@
 // Index arithmetic of the bilinear (align_corners=False) logit resize, shared by the kernels that evaluate it on the fly
 // (misc.hip: gdl_upsample_logits, gdl_upsample_argmax; loss_dice.hip: gdl_dice_loss_lowres_* and the binary forward; lowres_tile.h:
 // the kernel skeletons behind gdl_soft_ce_lowres_*, gdl_focal_lowres_*, gdl_focal_binary_lowres_*, gdl_soft_bce_lowres_* and the
-// binary Dice family's backward).  One definition, so that every kernel evaluates the expression gdl_upsample_logits writes.
+// binary Dice family's backward; resample_vec.h: the resize kernels of resample.hip and resize_conv_*.hip).  One definition, so that every kernel evaluates the expression gdl_upsample_logits writes.
 #pragma once
 #include "gdl_common.h"
 
 namespace {
 
+// torch area_pixel_compute_source_index(align_corners=False) + index/lambda (UpSample.h)
 __device__ __forceinline__ void src_index2(float ratio, int dst, int in_size, int& i0, int& i1, float& l1) {
   float s = ratio * ((float)dst + 0.5f) - 0.5f;
   s = s < 0.f ? 0.f : s;

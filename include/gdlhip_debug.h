@@ -61,7 +61,7 @@ void gdl_debug_set_wgrad_rows_xcd(int on);
  * (default 6; 0 = the exact online softmax) */
 void gdl_debug_set_flash_fwd(int version, float defer);
 
-/* ---- resampling and the low-resolution 3x3 forms (resample.hip) ---- */
+/* ---- resampling (resample.hip) and the low-resolution 3x3 forms (gather_mfma: resize_conv_bwd.hip; tapsum_*: resize_conv_fwd.hip) ---- */
 /* 1 = the flat-index resize / pooling kernels for every shape */
 void gdl_debug_set_flat_resample(int on);
 /* 0 = the VALU gathers of the low-resolution backward instead of the one-pass matrix-core form */

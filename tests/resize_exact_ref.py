@@ -1,4 +1,4 @@
-"""Exact references, exactness proofs and case tables of the resized-conv gather kernels (csrc/resample.hip), shared by
+"""Exact references, exactness proofs and case tables of the resized-conv gather kernels (csrc/resize_conv_fwd.hip, csrc/resize_conv_bwd.hip), shared by
 test_resize_exact_host.py (CPU: proves every case exact) and test_hip_resize_exact.py (GPU: compares bits).  float64 on the CPU.
 
 For resize factors f = 2, 4, 8 the bilinear weights (align_corners=False, edges clamped) are k / (2 f); the weight of a tap is
@@ -154,7 +154,7 @@ def assert_same(got, ref, what):
                          f"got {got[tuple(first)].item()} want {ref[tuple(first)].item()}")
 
 
-# ------------------------------------------------------------------ the forward's planner (csrc/resample.hip: tapsum_plan)
+# ------------------------------------------------------------------ the forward's planner (csrc/resize_conv_fwd.hip: tapsum_plan)
 VALU, V1, V2, ROLL, ROLL3 = range(5)
 CUS = 256                             # the MI355X's; the `walks` digit of every code below counts on it
 

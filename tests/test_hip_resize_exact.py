@@ -1,4 +1,4 @@
-"""Exact tests of the resized-conv gather kernels (csrc/resample.hip): the forward gdl_resize_conv3x3_fwd_sum in every form
+"""Exact tests of the resized-conv gather kernels (csrc/resize_conv_fwd.hip, csrc/resize_conv_bwd.hip; the plain resamplers: csrc/resample.hip): the forward gdl_resize_conv3x3_fwd_sum in every form
 (pixel-by-pixel kernel, matrix-core versions 1 and 2, rolling window, roll3), with BatchNorm statistics, and the backward
 gdl_resize_conv3x3_bwd_gather in every form (one-pass matrix cores, two-pass rows / columns, single pass, BatchNorm backward
 fused), plus the plain integer-factor resamplers and one conv3x3(resize(x)) node end to end.
