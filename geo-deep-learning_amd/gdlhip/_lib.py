@@ -37,7 +37,7 @@ _PREPROCESSOR = re.compile(r'#\s*(ifndef \w+|define \w+|include <stdint\.h>|incl
 _DECLARATOR = re.compile(r"(?:const\s+)?(\w+)(\s*(?:\*\s*(?:const\s*)?)+|\s+)(\w+)\s*(\[\])?$")
 _NEXT = re.compile(r"\S")
 _STATEMENTS = [(kind, re.compile(rx)) for kind, rx in (
-    ("define", r"#\s*define\s+(\w+)\s+(-?\d+)[ \t]*\n"),
+    ("define", r"#\s*define\s+(\w+)\s+(-?\d+(?:\.\d+)?)[ \t]*\n"),
     ("enum", r"enum\s*\{([^{}]*)\}\s*;"),
     ("stream", r"typedef\s+void\s*\*\s*gdl_stream_t\s*;"),
     ("struct", r"typedef\s+struct\s*\{([^{}]*)\}\s*(\w+)\s*;"),
@@ -50,7 +50,7 @@ class HeaderError(ValueError):
 
 class Header:
     """What one header declares: ``functions`` {name: (restype, [argtypes])}, ``structs`` {C name: ctypes.Structure},
-    ``constants`` {name: int} (enumerators and integer #defines) and ``status`` (the functions whose int result is a
+    ``constants`` {name: int or float} (enumerators and the #defines of one integer or decimal literal) and ``status`` (the functions whose int result is a
     gdl_status: exactly the int-returning ones that take a gdl_stream_t)."""
 
     def __init__(self, text: str) -> None:
@@ -71,7 +71,7 @@ class Header:
             pos = m.end()
 
     def _define(self, line: int, name: str, value: str) -> None:
-        self.constants[name] = int(value)
+        self.constants[name] = float(value) if "." in value else int(value)      # 0.25: a decimal literal is a float
 
     def _enum(self, line: int, body: str) -> None:
         for item in filter(None, (s.strip() for s in body.split(","))):
@@ -139,7 +139,7 @@ class Header:
 HEADERS = {"": "gdlhip.h", "DEBUG": "gdlhip_debug.h", "SCENE": "gdlhip_scene.h", "SCENE_TTA": "gdlhip_scene_tta.h",
            "SCENE_NODATA": "gdlhip_scene_nodata.h", "SCENE_SIEVE": "gdlhip_scene_sieve.h", "SCENE_RINGS": "gdlhip_scene_rings.h",
            "SCENE_SIMPLIFY": "gdlhip_scene_simplify.h", "SCENE_REGIONS": "gdlhip_scene_regions.h",
-           "SCENE_BURN": "gdlhip_scene_burn.h"}
+           "SCENE_BURN": "gdlhip_scene_burn.h", "RASTER": "gdlhip_raster.h"}
 _PARSED = {prefix: Header((INCLUDE / name).read_text()) for prefix, name in HEADERS.items()}
 _ABI = _PARSED[""]
 for _prefix, _header in _PARSED.items():
@@ -147,7 +147,7 @@ for _prefix, _header in _PARSED.items():
     globals()[f"{_prefix}_SIGNATURES".lstrip("_")] = _header.functions
     # the header's enumerators and integer #defines without their GDL_ prefix: F32, BF16, ACT_*, FOCAL_* (the `form` argument of
     # the *_lowres_bwd calls), BCE_TARGET_* (the `target_type` of gdl_soft_bce_*), OVERLAP_* (gdl_overlap_options.kind),
-    # SCENE_RINGS_SCAN_TILE, SCENE_BURN_BITS_MAX, ...
+    # SCENE_RINGS_SCAN_TILE, SCENE_BURN_BITS_MAX, RASTER_CUBIC, RASTER_MIN_VALID_WEIGHT (the one float), ...
     globals().update({k.removeprefix("GDL_"): v for k, v in _header.constants.items()})
 STATUS_FUNCTIONS = frozenset(_ABI.status)      # they return a gdl_status; every other function returns a value
 # what checked() gives the errcheck: the scene calls return a gdl_status too (the debug hooks are left to their callers)

@@ -3371,3 +3371,184 @@ def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, lr: float, b1: float, 
     bc1, bc2 = 1.0 - b1**step, 1.0 - b2**step
     _lib.checked().gdl_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, b1, b2, eps, wd, bc1,
                                  bc2, _p(clip), _stream())
+
+
+# raster preparation (include/gdlhip_raster.h): a raster put on another grid, and the sums of the dataset statistics
+RASTER_METHODS = {"nearest": _lib.RASTER_NEAREST, "bilinear": _lib.RASTER_BILINEAR, "cubic": _lib.RASTER_CUBIC}
+RASTER_STATS_DRAIN_PIXELS = 1 << 30      # RasterStats drains its device accumulator before this many pixels per band are in it
+
+
+def _raster_check(op: str, src) -> tuple[int, int, int]:
+    if not isinstance(src, Tensor) or src.dtype not in _RAW_KIND or src.dim() != 3 or not src.is_contiguous() or src.numel() < 1:
+        got = f"{src.dtype} {tuple(src.shape)}" if isinstance(src, Tensor) else type(src).__name__
+        raise ValueError(f"{op}: contiguous non-empty [C, H, W] uint8/uint16/int16/float32 raster expected, got {got}")
+    Cc, H, W = (int(n) for n in src.shape)
+    if H * W >= 1 << 31 or Cc > 65535:
+        raise ValueError(f"{op}: raster {tuple(src.shape)}: H * W must stay below 2^31 and C below 65536")
+    return Cc, H, W
+
+
+def raster_nodata(op: str, nodata, dtype: torch.dtype, channels: int):
+    """(values, present) as the HOST arrays gdl_raster_warp / gdl_raster_stats read, or (None, None) without nodata: ``nodata`` is
+    None, one number, or one entry per band of which any may be None (that band has no nodata).  The numbers are held against
+    ``dtype`` by ``scene_nodata_values`` (a value no sample can hold is a ValueError; a float32 raster compares after rounding
+    to float32, and takes NaN: then a NaN sample is nodata)."""
+    if nodata is None:
+        return None, None
+    if isinstance(nodata, Tensor):
+        nodata = nodata.detach().cpu().tolist()
+    entries = list(nodata) if isinstance(nodata, (list, tuple)) else [nodata] * channels
+    if len(entries) != channels:
+        raise ValueError(f"{op}: {len(entries)} nodata values for {channels} bands")
+    present = [e is not None for e in entries]
+    if not any(present):
+        return None, None
+    given = scene_nodata_values([e for e in entries if e is not None], dtype, sum(present), op).tolist()
+    values = iter(given)
+    return ((C.c_double * channels)(*[next(values) if p else 0.0 for p in present]), (C.c_uint8 * channels)(*[int(p) for p in present]))
+
+
+def _dst_nodata_check(op: str, dst_nodata, dtype: torch.dtype) -> float:
+    if isinstance(dst_nodata, bool) or not isinstance(dst_nodata, (int, float)):
+        raise ValueError(f"{op}: dst_nodata must be a number, got {dst_nodata!r}")
+    if dtype in _RAW_LIMITS:
+        lo, hi = _RAW_LIMITS[dtype]
+        if dst_nodata != dst_nodata or abs(dst_nodata) == float("inf") or dst_nodata != int(dst_nodata) or not lo <= dst_nodata <= hi:
+            raise ValueError(f"{op}: dst_nodata {dst_nodata!r} is not a value of {dtype}")
+    return float(dst_nodata)
+
+
+def raster_warp(src: Tensor, dst_shape: tuple[int, int], sx: float, ox: float, sy: float, oy: float, method: str = "bilinear",
+                nodata=None, dst_nodata: float = 0, out_dtype: torch.dtype | None = None, return_valid: bool = False):
+    """``src`` [C, H, W] (uint8/uint16/int16/float32, on the device) resampled onto a grid of ``dst_shape`` = (Hd, Wd) whose pixel
+    (y, x) lies at the source pixel coordinates u = (x + 0.5) sx + ox, v = (y + 0.5) sy + oy (sx, sy > 0): [C, Hd, Wd] of
+    ``out_dtype`` (the source's, the default, or float32), and with ``return_valid`` also the uint8 [C, Hd, Wd] validity planes
+    (gdl_raster_warp; the rule is stated in include/gdlhip_raster.h).  ``method``: "nearest", "bilinear" or "cubic"; the last
+    two widen with the scale (an antialiased resize) up to a scale of 16.  ``nodata``: None, one number or one per band (None for
+    a band without); a masked sample takes no part, and a pixel whose centre falls on a masked sample or outside the source, or
+    whose unmasked taps carry less than a quarter of the weight, takes ``dst_nodata``.
+
+    A NaN nodata means "a NaN sample", as in ``scene_valid``.  This departs from the reference, whose ``band != nan``
+    (utils/rasters.py:129) excludes nothing.  The resampling is this library's own and is not GDAL's."""
+    op = "raster_warp"
+    Cc, H, W = _raster_check(op, src)
+    if method not in RASTER_METHODS:
+        raise ValueError(f"{op}: unknown method {method!r} ('nearest', 'bilinear' or 'cubic')")
+    out_dtype = src.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (src.dtype, torch.float32):
+        raise ValueError(f"{op}: out_dtype must be the source's ({src.dtype}) or torch.float32, got {out_dtype}")
+    try:
+        Hd, Wd = (int(n) for n in dst_shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"{op}: dst_shape must be (Hd, Wd), got {dst_shape!r}") from None
+    if Hd < 1 or Wd < 1 or Hd * Wd >= 1 << 31:
+        raise ValueError(f"{op}: dst_shape {dst_shape!r}: sizes must be positive and Hd * Wd below 2^31")
+    values, present = raster_nodata(op, nodata, src.dtype, Cc)
+    fill = _dst_nodata_check(op, dst_nodata, out_dtype)
+    geometry = tuple(float(g) for g in (sx, ox, sy, oy))
+    lib, kind = _lib.checked(), RASTER_METHODS[method]
+    nbytes = lib.gdl_raster_warp_workspace(Hd, Wd, geometry[0], geometry[2], kind)
+    if nbytes < 0:
+        check(-1, op)
+    _need_cuda(src)
+    dev = src.device
+    ws = torch.empty(((nbytes + 7) // 8,), device=dev, dtype=torch.float64) if nbytes else None      # the tap tables
+    dst =torch.empty((Cc, Hd, Wd), device=dev, dtype=out_dtype)
+    valid = torch.empty((Cc, Hd, Wd), device=dev, dtype=torch.uint8) if return_valid else None
+    lib.gdl_raster_warp(_p(src), _RAW_KIND[src.dtype], Cc, H, W, Hd, Wd, *geometry, kind, values, present, fill, _p(dst),
+                        _RAW_KIND[out_dtype], _p(valid), _p(ws), _stream())
+    return (dst, valid) if return_valid else dst
+
+
+class RasterStats:
+    """The per-band count, sum and sum of squares of the valid samples of any number of rasters: a device accumulator that
+    ``raster_stats`` adds to (gdl_raster_stats), drained into Python numbers (exact integers for the integer rasters, floats for
+    float32) before ``RASTER_STATS_DRAIN_PIXELS`` pixels per band are in it, so that a uint16 sum of squares never wraps its 64
+    bits.  ``finish()`` gives (means, stds)."""
+
+    def __init__(self) -> None:
+        self.dtype = None            # of the rasters: the first one's
+        self.acc = None              # int64 [C, 3] on the device (words 1 and 2 hold float64 for float32 rasters)
+        self.pending = 0             # pixels per band added since the last drain
+        self.count, self.total, self.total_sq = [], [], []
+
+    @classmethod
+    def from_sums(cls, count, total, total_sq) -> "RasterStats":
+        """A holder of given sums (one entry per band), no device involved."""
+        self = cls()
+        self.count, self.total, self.total_sq = list(count), list(total), list(total_sq)
+        if not len(self.count) == len(self.total) == len(self.total_sq):
+            raise ValueError("RasterStats.from_sums: one count, sum and sum of squares per band")
+        return self
+
+    def admit(self, src: Tensor, pixels: int) -> Tensor:
+        """The accumulator the next ``pixels`` pixels per band of ``src`` go to, drained first where they would reach the limit."""
+        Cc = int(src.shape[0])
+        if self.acc is None:
+            self.dtype = src.dtype
+            self.acc = torch.zeros((Cc, 3), device=src.device, dtype=torch.int64)
+            if not self.count:
+                self.count, self.total, self.total_sq = [0] * Cc, [0] * Cc, [0] * Cc
+        if src.dtype != self.dtype or Cc != len(self.count) or src.device != self.acc.device:
+            raise ValueError(f"raster_stats: the accumulator holds {len(self.count)} bands of {self.dtype} on {self.acc.device}, "
+                             f"got {Cc} of {src.dtype} on {src.device}")
+        if self.pending and self.pending + pixels >= RASTER_STATS_DRAIN_PIXELS:
+            self.drain()
+        self.pending += pixels
+        return self.acc
+
+    def drain(self) -> None:
+        """The device accumulator added to the Python sums and zeroed (one device-to-host copy)."""
+        if self.acc is None or not self.pending:
+            return
+        host = self.acc.cpu()
+        sums = host.tolist() if self.dtype != torch.float32 else [[int(n), s, q] for (n, _, _), (_, s, q) in
+                                                                  zip(host.tolist(), host.view(torch.float64).tolist())]
+        for c, (n, s, q) in enumerate(sums):
+            self.count[c] += n
+            self.total[c] += s
+            self.total_sq[c] += q
+        self.acc.zero_()
+        self.pending = 0
+
+    def finish(self) -> tuple[list[float], list[float]]:
+        """(means, stds) per band: mean = sum / N and std = sqrt(sum of squares / N - mean^2), the reference's population formula
+        (utils/rasters.py:142-143), from the exact integers where the sums are integers (in rationals, rounded once at the end)
+        and in float64 otherwise, a difference below zero (rounding alone) taken as zero.  A band without a valid pixel is a
+        ValueError."""
+        from fractions import Fraction
+        self.drain()
+        means, stds = [], []
+        for c, (n, s, q) in enumerate(zip(self.count, self.total, self.total_sq)):
+            if n <= 0:
+                raise ValueError(f"raster statistics: band {c} has no valid pixel")
+            if isinstance(s, int) and isinstance(q, int):
+                mean = Fraction(s, n)
+                var = Fraction(q, n) - mean * mean
+                means.append(float(mean))
+                stds.append(math.sqrt(var))
+            else:
+                mean = s / n
+                means.append(mean)
+                stds.append(math.sqrt(max(q / n - mean * mean, 0.0)))
+        return means, stds
+
+
+def raster_stats(src: Tensor, nodata=None, acc: RasterStats | None = None) -> RasterStats:
+    """The count, sum and sum of squares of the samples of ``src`` [C, H, W] (uint8/uint16/int16/float32, on the device) that are
+    not their band's ``nodata`` (None, one number or one per band; NaN for float32: the NaN samples), added per band to ``acc``
+    (a ``RasterStats``; a new one where None), which is returned (gdl_raster_stats).  Integer rasters are summed exactly in 64-bit
+    integers; float32 ones in float64 in a fixed order, the same bits from run to run."""
+    op = "raster_stats"
+    Cc, H, W = _raster_check(op, src)
+    if acc is not None and not isinstance(acc, RasterStats):
+        raise ValueError(f"{op}: acc must be a RasterStats, got {type(acc).__name__}")
+    values, present = raster_nodata(op, nodata, src.dtype, Cc)
+    _need_cuda(src)
+    acc = RasterStats() if acc is None else acc
+    words = acc.admit(src, H * W)
+    lib, kind = _lib.checked(), _RAW_KIND[src.dtype]
+    nbytes = lib.gdl_raster_stats_workspace(kind, Cc, H, W)
+    ws = torch.empty((nbytes // 8,), device=src.device, dtype=torch.float64) if nbytes else None
+    lib.gdl_raster_stats(_p(src), kind, Cc, H, W, values, present, _p(words), _p(ws), _stream())
+    return acc
