@@ -12,7 +12,7 @@
 //     float64 (float32), reduces them over the block in a fixed order, and then either adds the three integers to the accumulator
 //     with integer atomics or stores the three float64 as the block's partial, which raster_stats_final_kernel adds up in a
 //     fixed order.
-#include "gdl_common.h"
+#include "raster_common.h"
 #include "../../include/gdlhip_raster.h"
 
 #include <math.h>
@@ -23,12 +23,6 @@ namespace {
 constexpr int TILE_X = 64, TILE_Y = 4;      // destination pixels per workgroup of the warp: a wave is 64 columns of one row
 constexpr int MAX_GRID = 1 << 20;           // workgroups of a launch; every kernel here walks its work with a grid stride
 constexpr int STATS_UNROLL = 8;             // independent loads in flight per thread of the statistics pass
-
-struct NoData {
-  double value;
-  int has, is_nan;
-  __device__ __forceinline__ bool masks(double v) const { return has && (is_nan ? v != v : v == value); }
-};
 
 // ------------------------------------------------------------------ tap tables
 struct AxisTable {      // of one axis of a destination of n entries, tmax taps at most
@@ -223,10 +217,6 @@ __global__ void __launch_bounds__(64) raster_stats_final_kernel(const double* __
 }
 
 // ------------------------------------------------------------------ host
-constexpr int64_t PIXEL_LIMIT = (int64_t)1 << 31;
-
-inline size_t kind_size(int kind) { return kind == GDL_RAW_U8 ? 1 : kind == GDL_RAW_F32 ? 4 : 2; }
-
 // the taps of one axis at most: floor(c + R f + 0.5) - floor(c - R f + 0.5) <= ceil(2 R f)
 inline int raster_tmax(double s, int method) { return (int)ceil(2.0 * method * fmax(1.0, s)) + 1; }
 
@@ -237,17 +227,6 @@ int check_geometry(const char* fn, int Hd, int Wd, double sx, double sy, int met
   GDL_CHECK_ARG(method == GDL_RASTER_NEAREST || (sx <= GDL_RASTER_MAX_SCALE && sy <= GDL_RASTER_MAX_SCALE),
                 "%s: scale %g x %g: bilinear and cubic take a scale of at most %d (their support grows with it)", fn, sx, sy, GDL_RASTER_MAX_SCALE);
   return GDL_OK;
-}
-
-int check_source(const char* fn, int kind, int C, int H, int W) {
-  GDL_CHECK_ARG(kind >= GDL_RAW_U8 && kind <= GDL_RAW_F32, "%s: bad sample kind %d", fn, kind);
-  GDL_CHECK_ARG(C > 0 && C <= 65535 && H > 0 && W > 0 && (int64_t)H * W < PIXEL_LIMIT, "%s: source [%d, %d, %d]: sizes must be positive, C <= 65535 and H * W < 2^31", fn, C, H, W);
-  return GDL_OK;
-}
-
-NoData band_nodata(const double* nodata, const uint8_t* has_nodata, int c) {
-  const bool has = nodata && (!has_nodata || has_nodata[c]);
-  return NoData{has ? nodata[c] : 0.0, has, has && nodata[c] != nodata[c]};
 }
 
 // the doubles of one axis' table, then its ints, carved out of ws; returns the first byte after them

@@ -139,7 +139,8 @@ class Header:
 HEADERS = {"": "gdlhip.h", "DEBUG": "gdlhip_debug.h", "SCENE": "gdlhip_scene.h", "SCENE_TTA": "gdlhip_scene_tta.h",
            "SCENE_NODATA": "gdlhip_scene_nodata.h", "SCENE_SIEVE": "gdlhip_scene_sieve.h", "SCENE_RINGS": "gdlhip_scene_rings.h",
            "SCENE_SIMPLIFY": "gdlhip_scene_simplify.h", "SCENE_REGIONS": "gdlhip_scene_regions.h",
-           "SCENE_BURN": "gdlhip_scene_burn.h", "RASTER": "gdlhip_raster.h"}
+           "SCENE_BURN": "gdlhip_scene_burn.h", "RASTER": "gdlhip_raster.h",
+           "RASTER_TONE": "gdlhip_raster_tone.h"}
 _PARSED = {prefix: Header((INCLUDE / name).read_text()) for prefix, name in HEADERS.items()}
 _ABI = _PARSED[""]
 for _prefix, _header in _PARSED.items():

@@ -3552,3 +3552,165 @@ def raster_stats(src: Tensor, nodata=None, acc: RasterStats | None = None) -> Ra
     ws = torch.empty((nbytes // 8,), device=src.device, dtype=torch.float64) if nbytes else None
     lib.gdl_raster_stats(_p(src), kind, Cc, H, W, values, present, _p(words), _p(ws), _stream())
     return acc
+
+
+# raster radiometry (include/gdlhip_raster_tone.h): per-band histograms, quantiles off them, the stretch to uint8 / float32
+_HIST_LAYOUT = {torch.uint8: (256, 0.0), torch.uint16: (65536, 0.0), torch.int16: (65536, -32768.0)}      # bins, value of bin 0
+
+
+def _number(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, float))
+
+
+def _hist_binning(op: str, dtype: torch.dtype, channels: int, bins, value_range):
+    """(bins, per-band (lo, hi) or None): the fixed layout of an integer dtype, or what the caller gives for float32."""
+    if dtype in _HIST_LAYOUT:
+        if bins is not None or value_range is not None:
+            raise ValueError(f"{op}: bins and value_range are for float32 rasters: the bins of {dtype} are its values")
+        return _HIST_LAYOUT[dtype][0], None
+    if isinstance(bins, bool) or not isinstance(bins, int) or not 1 <= bins <= _lib.RASTER_TONE_MAX_BINS:
+        raise ValueError(f"{op}: a float32 raster needs bins, an int in 1..{_lib.RASTER_TONE_MAX_BINS}, got {bins!r}")
+    pairs = value_range.detach().cpu().tolist() if isinstance(value_range, Tensor) else value_range
+    if isinstance(pairs, (list, tuple)) and len(pairs) == 2 and all(_number(v) for v in pairs):
+        pairs = [pairs] * channels
+    ok = isinstance(pairs, (list, tuple)) and len(pairs) == channels and all(
+        isinstance(p, (list, tuple)) and len(p) == 2 and all(_number(v) for v in p) for p in pairs)
+    if not ok:
+        raise ValueError(f"{op}: a float32 raster needs value_range, one (lo, hi) or one per band ({channels}), got {value_range!r}")
+    ranges = [(float(lo), float(hi)) for lo, hi in pairs]
+    for lo, hi in ranges:
+        if not (math.isfinite(lo) and math.isfinite(hi) and math.isfinite(hi - lo) and lo < hi):
+            raise ValueError(f"{op}: value_range ({lo}, {hi}) must be finite with lo < hi")
+    return bins, ranges
+
+
+class RasterHist:
+    """The per-band histogram of the valid samples of any number of rasters: a device accumulator int64 [C, bins + 2] that
+    ``raster_hist`` adds to (gdl_raster_hist).  ``bins`` and ``ranges`` are its binning: 256 / 65536 / 65536 bins of one value
+    each for uint8 / uint16 / int16 (``ranges`` None), or ``bins`` equal bins over each band's (lo, hi) for float32.  The
+    accumulator is allocated by the first raster added."""
+
+    def __init__(self, dtype: torch.dtype, channels: int, bins: int, ranges=None) -> None:
+        self.dtype, self.channels, self.bins, self.ranges = dtype, int(channels), int(bins), ranges
+        self.acc = None
+
+    def admit(self, src: Tensor, bins: int, ranges) -> Tensor:
+        """The accumulator for ``src`` with that binning (refused where it is not this one's), allocated on first use."""
+        if (src.dtype, int(src.shape[0]), bins, ranges) != (self.dtype, self.channels, self.bins, self.ranges):
+            raise ValueError(f"raster_hist: the accumulator holds {self.channels} bands of {self.dtype} in {self.bins} bins over "
+                             f"{self.ranges}, got {int(src.shape[0])} of {src.dtype} in {bins} over {ranges}")
+        _need_cuda(src)
+        if self.acc is None:
+            self.acc = torch.zeros((self.channels, self.bins + 2), device=src.device, dtype=torch.int64)
+        if self.acc.device != src.device:
+            raise ValueError(f"raster_hist: the accumulator is on {self.acc.device}, the raster on {src.device}")
+        return self.acc
+
+    def _filled(self) -> Tensor:
+        if self.acc is None:
+            raise ValueError("RasterHist: no raster has been added yet")
+        return self.acc
+
+    @property
+    def counts(self) -> Tensor:
+        """int64 [C, bins] on the device (a view of the accumulator)."""
+        return self._filled()[:, :self.bins]
+
+    @property
+    def under(self) -> Tensor:
+        """int64 [C]: the float32 samples below their band's range (0 for the integer dtypes)."""
+        return self._filled()[:, self.bins]
+
+    @property
+    def over(self) -> Tensor:
+        return self._filled()[:, self.bins + 1]
+
+    @property
+    def total(self) -> Tensor:
+        """int64 [C] on the device: the samples in the bins (under and over left out)."""
+        return self.counts.sum(dim=1)
+
+    def bin_edges(self) -> tuple[list[float], list[float]]:
+        """(origin, step) per band: the value of bin b is origin + b * step (the bin's lower edge for float32)."""
+        if self.ranges is None:
+            return [_HIST_LAYOUT[self.dtype][1]] * self.channels, [1.0] * self.channels
+        return [lo for lo, _ in self.ranges], [(hi - lo) / self.bins for lo, hi in self.ranges]
+
+    def quantiles(self, qs) -> Tensor:
+        """float64 [C, Q] on the device: per band the ``qs``-quantiles (each in [0, 1], at most 64) of the valid samples, numpy's
+        ``method="lower"`` read off the histogram (gdl_raster_hist_quantiles; exact for the integer dtypes, the lower edge of the
+        sample's bin for float32); NaN for a band without a valid sample.  Nothing is copied to the host."""
+        qs = [qs] if _number(qs) else list(qs)
+        if not 1 <= len(qs) <= _lib.RASTER_TONE_MAX_Q or not all(_number(q) and 0.0 <= q <= 1.0 for q in qs):
+            raise ValueError(f"RasterHist.quantiles: 1..{_lib.RASTER_TONE_MAX_Q} numbers in [0, 1] expected, got {qs!r}")
+        acc = self._filled()
+        origin, step = self.bin_edges()
+        out = torch.empty((self.channels, len(qs)), device=acc.device, dtype=torch.float64)
+        doubles = C.c_double * self.channels
+        _lib.checked().gdl_raster_hist_quantiles(_p(acc), self.channels, self.bins, (C.c_double * len(qs))(*qs), len(qs),
+                                                 doubles(*origin), doubles(*step), _p(out), _stream())
+        return out
+
+    def percentile_bounds(self, lo_pct: float = 2.0, hi_pct: float = 98.0) -> Tensor:
+        """float64 [C, 2] on the device, contiguous: the two percentiles of every band, what ``raster_stretch`` takes as bounds."""
+        if not (_number(lo_pct) and _number(hi_pct) and 0.0 <= lo_pct <= hi_pct <= 100.0):
+            raise ValueError(f"RasterHist.percentile_bounds: 0 <= lo_pct <= hi_pct <= 100 expected, got {lo_pct!r}, {hi_pct!r}")
+        return self.quantiles([lo_pct / 100.0, hi_pct / 100.0])
+
+
+def raster_hist(src: Tensor, nodata=None, acc: RasterHist | None = None, *, bins: int | None = None, value_range=None) -> RasterHist:
+    """The histogram of the samples of ``src`` [C, H, W] (uint8/uint16/int16/float32, on the device) that are not their band's
+    ``nodata`` (None, one number or one per band; NaN for float32: the NaN samples), added per band to ``acc`` (a ``RasterHist``
+    of the same dtype, band count and binning; a new one where None), which is returned (gdl_raster_hist).  The integer dtypes
+    have one bin per value; float32 needs ``bins`` (1..65536) and ``value_range``, one (lo, hi) or one per band: samples below
+    and above are counted in ``.under`` / ``.over``, a NaN that is not nodata nowhere.  Exact integer counts, the same bits from
+    run to run.  The rule is stated in include/gdlhip_raster_tone.h; the reference has no counterpart."""
+    op = "raster_hist"
+    Cc, H, W = _raster_check(op, src)
+    if acc is not None and not isinstance(acc, RasterHist):
+        raise ValueError(f"{op}: acc must be a RasterHist, got {type(acc).__name__}")
+    nbins, ranges = _hist_binning(op, src.dtype, Cc, bins, value_range)
+    values, present = raster_nodata(op, nodata, src.dtype, Cc)
+    acc = RasterHist(src.dtype, Cc, nbins, ranges) if acc is None else acc
+    words = acc.admit(src, nbins, ranges)
+    doubles = C.c_double * Cc
+    lo, hi = (None, None) if ranges is None else (doubles(*[r[0] for r in ranges]), doubles(*[r[1] for r in ranges]))
+    _lib.checked().gdl_raster_hist(_p(src), _RAW_KIND[src.dtype], Cc, H, W, values, present, nbins, lo, hi, _p(words), _stream())
+    return acc
+
+
+def raster_stretch(src: Tensor, bounds, out_range=(0, 255), nodata=None, dst_nodata: float = 0,
+                   out_dtype: torch.dtype = torch.uint8, return_valid: bool = False):
+    """``src`` [C, H, W] (uint8/uint16/int16/float32, on the device) stretched band by band: the band's ``bounds`` (lo, hi) go to
+    ``out_range`` = (out_lo, out_hi), linearly in float64 and clipped, as uint8 (rounded half up) or float32 [C, H, W]
+    (gdl_raster_stretch; the rule is stated in include/gdlhip_raster_tone.h).  ``bounds``: a float64 [C, 2] tensor on the device
+    (``RasterHist.percentile_bounds``: nothing goes through the host) or a host sequence of C (lo, hi) pairs, which is uploaded.
+    Where hi <= lo the samples above lo take out_hi and the others out_lo.  A nodata sample (``nodata`` as in ``raster_stats``),
+    a NaN sample and every sample of a band whose bounds are NaN take ``dst_nodata``; with ``return_valid`` the uint8 [C, H, W]
+    plane that is 0 there comes back too.  There is no gamma."""
+    op = "raster_stretch"
+    Cc, H, W = _raster_check(op, src)
+    if out_dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"{op}: out_dtype must be torch.uint8 or torch.float32, got {out_dtype}")
+    if not (isinstance(out_range, (list, tuple)) and len(out_range) == 2 and all(_number(v) and math.isfinite(v) for v in out_range)):
+        raise ValueError(f"{op}: out_range must be two finite numbers (out_lo, out_hi), got {out_range!r}")
+    if out_dtype == torch.uint8 and not all(0 <= v <= 255 for v in out_range):
+        raise ValueError(f"{op}: out_range {tuple(out_range)!r} must lie in 0..255 for a uint8 destination")
+    fill = _dst_nodata_check(op, dst_nodata, out_dtype)
+    values, present = raster_nodata(op, nodata, src.dtype, Cc)
+    if isinstance(bounds, Tensor):
+        if bounds.dtype != torch.float64 or tuple(bounds.shape) != (Cc, 2) or not bounds.is_contiguous():
+            raise ValueError(f"{op}: bounds must be a contiguous float64 [C, 2] = [{Cc}, 2] tensor, got {bounds.dtype} {tuple(bounds.shape)}")
+    else:
+        pairs = list(bounds) if isinstance(bounds, (list, tuple)) else None
+        if pairs is None or len(pairs) != Cc or not all(isinstance(p, (list, tuple)) and len(p) == 2 and all(_number(v) for v in p)
+                                                          for p in pairs):
+            raise ValueError(f"{op}: bounds must be a float64 [C, 2] tensor or {Cc} (lo, hi) pairs, got {bounds!r}")
+        bounds = torch.tensor([[float(lo), float(hi)] for lo, hi in pairs], dtype=torch.float64)
+    _need_cuda(src)
+    bounds = bounds.to(src.device)
+    dst = torch.empty((Cc, H, W), device=src.device, dtype=out_dtype)
+    valid = torch.empty((Cc, H, W), device=src.device, dtype=torch.uint8) if return_valid else None
+    _lib.checked().gdl_raster_stretch(_p(src), _RAW_KIND[src.dtype], Cc, H, W, values, present, _p(bounds), float(out_range[0]),
+                                      float(out_range[1]), fill, _p(dst), _RAW_KIND[out_dtype], _p(valid), _stream())
+    return (dst, valid) if return_valid else dst

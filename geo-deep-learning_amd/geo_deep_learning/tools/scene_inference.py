@@ -36,6 +36,11 @@ Agreement (``agreement=True`` on ``predict_rings`` / ``predict_features``, or ``
 raster on the device (``ops.scene_burn``, the step GDAL rasterize takes) and compared with the mask: how many pixels the
 simplification moved to another class, how many lie where simplified arcs crossed, and the per-class counts behind an IoU.
 
+Stretch (``stretch=``): a uint16 / int16 / float32 scene is brought into the 8-bit range the model was trained on before it is
+cut: every band stretched linearly to the model's ``image_min..image_max`` and clipped, by the raster's own percentiles
+(``ops.raster_hist`` and its quantiles) or by given bounds (``ops.raster_stretch``), on the device.  The validity plane is taken
+from the original samples first; everything after the upload sees a uint8 raster.
+
 Determinism: the canvas is accumulated by a gather in tile order without atomics, so the mask and the probabilities do not
 depend on ``batch_size`` and are the same bits from run to run.  The reference has no counterpart (its inference stops at the
 tile, tools/script_model.py)."""
@@ -125,12 +130,19 @@ class SceneInference:
     plane the ``nodata_label`` pixels are no region: they are never changed and no pixel takes their label.  ``probs`` are the
     blended probabilities either way, so where the sieve changed a pixel their arg-max is no longer the mask.
     ``predict_rings`` goes on from the mask to the polygon rings of its regions, and with ``simplify=`` to their Douglas-Peucker
-    simplification per shared arc (``ops.scene_rings`` / ``ops.scene_rings_simplify``)."""
+    simplification per shared arc (``ops.scene_rings`` / ``ops.scene_rings_simplify``).
+    ``stretch``: ``None`` (the raster as given: the calls and the bits of before), a ``(lo_pct, hi_pct)`` pair of percentiles of the
+    uploaded raster itself, or fixed per-band bounds, C ``(lo, hi)`` pairs or a float64 [C, 2] tensor (those of the training set,
+    say).  The raster is replaced by its uint8 stretch from those bounds to the model's ``image_min..image_max`` (both must lie
+    in 0..255), a sample equal to its band's ``nodata`` becoming ``fill``, which must then be a byte.  The percentiles leave out
+    the samples equal to ``nodata`` and nothing more: a ``valid=`` plane does not enter them.  A float32 raster takes fixed
+    bounds only (its histogram would need a value range)."""
 
     def __init__(self, script_model: ScriptModel, tile: tuple[int, int] = (512, 512), overlap: float = 0.5,
                  stride: tuple[int, int] | None = None, window: str = "hann", batch_size: int = 64, threshold: float = 0.5,
                  fill: int = 0, *, lowres: bool = True, tta=None, nodata=None, nodata_rule: str = "all", nodata_label: int = 255,
-                 min_valid: int = 1, sieve: int | None = None, sieve_connectivity: int = 4, sieve_iterations: int = 1) -> None:
+                 min_valid: int = 1, sieve: int | None = None, sieve_connectivity: int = 4, sieve_iterations: int = 1,
+                 stretch=None) -> None:
         if not isinstance(script_model, ScriptModel):
             raise TypeError(f"SceneInference: a ScriptModel is expected, got {type(script_model).__name__}")
         self.model = script_model
@@ -161,8 +173,39 @@ class SceneInference:
         if isinstance(sieve_iterations, bool) or not isinstance(sieve_iterations, int) or sieve_iterations < 1:
             raise ValueError(f"SceneInference: sieve_iterations must be an int of at least 1, got {sieve_iterations!r}")
         self.sieve, self.sieve_connectivity, self.sieve_iterations = sieve, sieve_connectivity, sieve_iterations
+        self.stretch = None if stretch is None else self._stretch_spec(stretch)
         dev = script_model.device
         self.wy, self.wx = gscene.window(self.tile[0], window).to(dev), gscene.window(self.tile[1], window).to(dev)
+
+    def _stretch_spec(self, stretch):
+        """("percentiles", (lo, hi)) or ("bounds", C pairs or a float64 [C, 2] tensor), checked against the model and ``fill``."""
+        m, bands = self.model, self.model.mean.numel()
+        if not all(isinstance(v, (int, float)) and 0 <= v <= 255 for v in (m.image_min, m.image_max)):
+            raise ValueError(f"SceneInference: stretch needs the model's image_min / image_max in 0..255, got {m.image_min!r}, {m.image_max!r}")
+        if not ops.is_byte(self.fill):
+            raise ValueError(f"SceneInference: with stretch the cut reads a uint8 raster, so fill must be an int in 0..255, got {self.fill!r}")
+        if isinstance(stretch, torch.Tensor):
+            if stretch.dtype != torch.float64 or tuple(stretch.shape) != (bands, 2):
+                raise ValueError(f"SceneInference: stretch bounds must be float64 [{bands}, 2], got {stretch.dtype} {tuple(stretch.shape)}")
+            return "bounds", stretch.contiguous()
+        number = lambda v: not isinstance(v, bool) and isinstance(v, (int, float))      # noqa: E731
+        if isinstance(stretch, (list, tuple)) and len(stretch) == 2 and all(number(v) for v in stretch):
+            if not 0.0 <= stretch[0] <= stretch[1] <= 100.0:
+                raise ValueError(f"SceneInference: stretch percentiles must be 0 <= lo <= hi <= 100, got {stretch!r}")
+            return "percentiles", (float(stretch[0]), float(stretch[1]))
+        if isinstance(stretch, (list, tuple)) and len(stretch) == bands and all(
+                isinstance(p, (list, tuple)) and len(p) == 2 and all(number(v) for v in p) for p in stretch):
+            return "bounds", [(float(lo), float(hi)) for lo, hi in stretch]
+        raise ValueError(f"SceneInference: stretch must be None, a (lo_pct, hi_pct) pair, or {bands} (lo, hi) pairs / a float64 "
+                         f"[{bands}, 2] tensor, got {stretch!r}")
+
+    def _stretched(self, raster: torch.Tensor) -> torch.Tensor:
+        """The uploaded raster as its uint8 stretch to the model's input range (``stretch=``)."""
+        m = self.model
+        kind, spec = self.stretch
+        if kind == "percentiles":
+            spec = ops.raster_hist(raster, self.nodata).percentile_bounds(*spec)
+        return ops.raster_stretch(raster, spec, (m.image_min, m.image_max), self.nodata, self.fill, torch.uint8)
 
     def _blend(self, out, origins: torch.Tensor, canvas: torch.Tensor, box: tuple[int, int, int, int],
                xforms: torch.Tensor | None = None) -> None:
@@ -193,11 +236,15 @@ class SceneInference:
             ops.scene_nodata_values(self.nodata, raster.dtype, raster.shape[0], "SceneInference")
         if valid is not None and (valid.dtype not in (torch.uint8, torch.bool) or tuple(valid.shape) != (H, W)):
             raise ValueError(f"SceneInference: valid must be a uint8 / bool [H, W] = [{H}, {W}] plane, got {valid.dtype} {tuple(valid.shape)}")
+        if self.stretch is not None and self.stretch[0] == "percentiles" and raster.dtype == torch.float32:
+            raise ValueError("SceneInference: a float32 raster needs fixed stretch bounds, not percentiles")
         raster = raster.to(m.device).contiguous()      # a host raster is uploaded once
         plane = None if valid is None else valid.to(m.device).contiguous()
         if self.nodata is not None:
             own = ops.scene_valid(raster, self.nodata, self.nodata_rule)
             plane = own if plane is None else ((own != 0) & (plane != 0)).view(torch.uint8)
+        if self.stretch is not None:      # after the plane: that is of the original samples
+            raster = self._stretched(raster)
         return raster, plane
 
     def _plan(self, H: int, W: int, plane: torch.Tensor | None) -> tuple[torch.Tensor, torch.Tensor]:

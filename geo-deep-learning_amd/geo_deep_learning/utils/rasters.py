@@ -5,6 +5,11 @@ The work is defined on arrays, geotransforms in and tensors out: ``align_to_grid
 out (``ops.raster_stats``).  ``align_to_reference`` and ``compute_dataset_stats_from_list`` keep the reference's path-level
 signatures; they are file I/O around the two and import rasterio when they are called.
 
+Radiometry, which the reference leaves to the caller (its inference takes ``image_min`` / ``image_max`` as given):
+``compute_dataset_percentiles`` gives the per-band percentiles of a list of tiles and ``stretch_to_uint8`` brings a uint16 / int16 /
+float32 raster into the 8-bit range a model was trained on, by its own percentiles or by given bounds (``ops.raster_hist`` /
+``ops.raster_stretch``, include/gdlhip_raster_tone.h).
+
 Departures from the reference, all stated in INTEGRATION.md: no change of CRS (both grids are north-up and in one CRS); a NaN
 nodata value means "a NaN sample" (the reference's ``band != nan`` excludes nothing); the resampling and its validity rule are
 those of include/gdlhip_raster.h, not GDAL's.
@@ -90,6 +95,65 @@ def compute_dataset_stats(tiles: Iterable[Tensor], nodata=None) -> tuple[list[fl
     return stats.finish()
 
 
+def _percent_pair(who: str, percentiles) -> tuple[float, float]:
+    ok = isinstance(percentiles, (list, tuple)) and len(percentiles) == 2 and all(
+        not isinstance(p, bool) and isinstance(p, (int, float)) for p in percentiles)
+    if not ok or not 0.0 <= percentiles[0] <= percentiles[1] <= 100.0:
+        raise ValueError(f"{who}: percentiles must be (lo, hi) with 0 <= lo <= hi <= 100, got {percentiles!r}")
+    return float(percentiles[0]), float(percentiles[1])
+
+
+def _dataset_hist(tiles, nodata, hist_kw):
+    from gdlhip import ops
+
+    hist = None
+    for tile in tiles:
+        if isinstance(tile, Tensor) and not tile.is_cuda:
+            tile = tile.cuda()
+        hist = ops.raster_hist(tile.contiguous() if isinstance(tile, Tensor) else tile, nodata, hist, **hist_kw)
+    if hist is None:
+        msg = "No input tiles provided for percentiles."
+        raise ValueError(msg)
+    return hist
+
+
+def compute_dataset_percentiles(tiles: Iterable[Tensor], percentiles: tuple[float, float] = (2.0, 98.0), nodata=None,
+                                **hist_kw) -> list[list[float]]:
+    """Global per-band [lo, hi] percentiles over ``tiles``, an iterable of [C, H, W] tensors of one dtype and band count on the
+    device or the host (those are moved), the samples equal to their band's ``nodata`` left out: numpy's
+    ``percentile(valid, p, method="lower")`` over all tiles together, from one histogram on the device that every tile adds to.
+    Exact for uint8 / uint16 / int16; float32 tiles need ``bins=`` and ``value_range=`` (``ops.raster_hist``) and give the lower
+    edge of the percentile's bin.  A band without a valid sample gives NaN."""
+    lo, hi = _percent_pair("compute_dataset_percentiles", percentiles)
+    return _dataset_hist(tiles, nodata, hist_kw).percentile_bounds(lo, hi).cpu().tolist()
+
+
+def stretch_to_uint8(src: Tensor, bounds=None, percentiles: tuple[float, float] = (2.0, 98.0), nodata=None,
+                     out_range: tuple[float, float] = (1, 255), dst_nodata: int = 0, return_bounds: bool = False, **hist_kw):
+    """``src`` ([C, H, W] or [H, W]; uint8/uint16/int16/float32) as uint8, every band stretched linearly from its ``bounds``
+    (lo, hi) to ``out_range`` and clipped, nodata samples set to ``dst_nodata`` (``ops.raster_stretch``).  ``bounds``: C (lo, hi)
+    pairs or a float64 [C, 2] device tensor, for example the training set's ``compute_dataset_percentiles``; None: the raster's
+    own ``percentiles`` with nodata left out -- histogram, quantiles and stretch run on the device one after the other, and
+    nothing comes back to the host in between (float32 then needs ``bins=`` and ``value_range=``).  The default ``out_range``
+    keeps 0 free for ``dst_nodata``.  With ``return_bounds`` the bounds used come back too (the raster's own: a float64 [C, 2] device tensor)."""
+    from gdlhip import ops
+
+    lo, hi = _percent_pair("stretch_to_uint8", percentiles)
+    if not isinstance(src, Tensor) or src.dim() not in (2, 3):
+        raise ValueError("stretch_to_uint8: src must be a [C, H, W] or [H, W] tensor.")
+    bands = src if src.dim() == 3 else src[None]
+    if bounds is not None and hist_kw:
+        raise ValueError(f"stretch_to_uint8: {sorted(hist_kw)} are for the raster's own percentiles, not for given bounds")
+    if not bands.is_cuda:
+        bands = bands.cuda()
+    bands = bands.contiguous()
+    if bounds is None:
+        bounds = ops.raster_hist(bands, nodata, **hist_kw).percentile_bounds(lo, hi)
+    out = ops.raster_stretch(bands, bounds, out_range, nodata, dst_nodata, torch.uint8)
+    out = out if src.dim() == 3 else out[0]
+    return (out, bounds) if return_bounds else out
+
+
 def _rasterio(instead: str):
     try:
         import rasterio
@@ -144,3 +208,21 @@ def compute_dataset_stats_from_list(tile_paths: Sequence[str]) -> tuple[list[flo
             img, nodata = _torch_dtype(src.read()), list(src.nodatavals)
         stats = ops.raster_stats(torch.from_numpy(img).cuda(), nodata, stats)
     return stats.finish()
+
+
+def compute_dataset_percentiles_from_list(tile_paths: Sequence[str], percentiles: tuple[float, float] = (2.0, 98.0),
+                                          **hist_kw) -> list[list[float]]:
+    """``compute_dataset_percentiles`` over the rasters at ``tile_paths``, each with the nodata values of its own metadata."""
+    lo, hi = _percent_pair("compute_dataset_percentiles_from_list", percentiles)
+    if not tile_paths:
+        msg = "No input tiles provided for percentiles."
+        raise ValueError(msg)
+    rasterio = _rasterio("compute_dataset_percentiles")
+    from gdlhip import ops
+
+    hist = None
+    for path in tile_paths:
+        with rasterio.open(path) as src:
+            img, nodata = _torch_dtype(src.read()), list(src.nodatavals)
+        hist = ops.raster_hist(torch.from_numpy(img).cuda(), nodata, hist, **hist_kw)
+    return hist.percentile_bounds(lo, hi).cpu().tolist()
