@@ -12,6 +12,7 @@
 //   O^T[d,  q] = V^T · P^T       A = V^T rows (LDS), B = P^T = the S^T accumulator itself
 // The k-index order of the second MFMA is permuted to match the accumulator layout of the first
 // (legal for a reduction), so P never leaves registers and is only converted f32 -> bf16.
+// Also here: gdl_v_transpose (the V^T operand above) and gdl_softmax_rows, the two helpers of the unfused attention path.
 #include "gdl_common.h"
 
 namespace {
@@ -184,6 +185,62 @@ __global__ __launch_bounds__(256) void flash_fwd_kernel(const FArgs f) {
   }
 }
 
+// ------------------------------------------------------------------ helpers of the unfused path: V^T, row softmax
+// V rows (token n, head h at v + b*v_sB + n*v_sN + h*hd) -> vt [B,H,hd,Npad] (keys >= N zero).
+// 32x32 LDS tile transpose.
+template <typename T>
+__global__ __launch_bounds__(256) void v_transpose_kernel(const T* __restrict__ v, int N, int H, int hd,
+                                                          int64_t v_sB, int64_t v_sN, T* __restrict__ vt, int Npad) {
+  __shared__ T tile[32][33];
+  const int bh = blockIdx.z, b = bh / H, h = bh % H;
+  const int n0 = blockIdx.x * 32, d0 = blockIdx.y * 32;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+  const int64_t rowstride = v_sN;
+  const T* src = v + (int64_t)b * v_sB + (int64_t)h * hd;
+  for (int j = ty; j < 32; j += 8) {
+    const int n = n0 + j, d = d0 + tx;
+    tile[j][tx] = (n < N && d < hd) ? src[(int64_t)n * rowstride + d] : (T)0;
+  }
+  __syncthreads();
+  T* dst = vt + ((int64_t)bh * hd) * Npad;
+  for (int j = ty; j < 32; j += 8) {
+    const int d = d0 + j, n = n0 + tx;
+    if (d < hd && n < Npad) dst[(int64_t)d * Npad + n] = tile[tx][j];
+  }
+}
+
+// ------------------------------------------------------------------ row softmax
+// one wave per row; row cached in registers when it fits (n_cols <= 64*MAXV)
+template <typename T, int MAXV>
+__global__ __launch_bounds__(256) void softmax_rows_kernel(const void* __restrict__ in, void* out, int64_t rows,
+                                                           int n_valid, int n_cols) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int64_t base = row * n_cols;
+  float v[MAXV];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int c = i * 64 + lane;
+    v[i] = c < n_valid ? ElemIO<T>::load(in, base + c) : -INFINITY;
+    mx = fmaxf(mx, v[i]);
+  }
+  mx = wave_max(mx);
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    v[i] = (i * 64 + lane) < n_valid ? expf(v[i] - mx) : 0.f;
+    s += v[i];
+  }
+  const float inv = 1.f / wave_sum(s);
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int c = i * 64 + lane;
+    if (c < n_cols) ElemIO<T>::store(out, base + c, v[i] * inv);
+  }
+}
+
 }  // namespace
 
 extern "C" int gdl_flash_attn_fwd(const void* q, int64_t q_sB, int64_t q_sN, const void* k, int64_t k_sB, int64_t k_sN,
@@ -204,5 +261,35 @@ extern "C" int gdl_flash_attn_fwd(const void* q, int64_t q_sB, int64_t q_sN, con
   dim3 grid((Nq + 127) / 128, B * H);
   hipLaunchKernelGGL(flash_fwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, f);
   GDL_CHECK_LAUNCH("gdl_flash_attn_fwd");
+  return GDL_OK;
+}
+
+extern "C" int gdl_v_transpose(const void* v, int dtype, int B, int N, int H, int hd, int64_t v_sB, int64_t v_sN,
+                               void* vt, int Npad, gdl_stream_t stream) {
+  GDL_CHECK_ARG(v && vt && Npad >= N, "gdl_v_transpose: bad args");
+  dim3 grid((Npad + 31) / 32, (hd + 31) / 32, B * H);
+  if (dtype == GDL_BF16)
+    hipLaunchKernelGGL(v_transpose_kernel<uint16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t*)v, N, H, hd, v_sB, v_sN, (uint16_t*)vt, Npad);
+  else
+    hipLaunchKernelGGL(v_transpose_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float*)v, N, H, hd, v_sB, v_sN, (float*)vt, Npad);
+  GDL_CHECK_LAUNCH("gdl_v_transpose");
+  return GDL_OK;
+}
+
+extern "C" int gdl_softmax_rows(const void* in, void* out, int dtype, int64_t rows, int n_valid, int n_cols,
+                                gdl_stream_t stream) {
+  GDL_CHECK_ARG(in && out && n_valid > 0 && n_valid <= n_cols, "gdl_softmax_rows: bad args");
+  GDL_CHECK_ARG(n_cols <= 64 * 96, "gdl_softmax_rows: n_cols=%d too large (max 6144)", n_cols);
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned grid = (unsigned)((rows + 3) / 4);
+#define SM(T, V) hipLaunchKernelGGL((softmax_rows_kernel<T, V>), dim3(grid), dim3(256), 0, s, in, out, rows, n_valid, n_cols)
+  const int v = (n_cols + 63) / 64;
+  if (dtype == GDL_BF16) {
+    if (v <= 4) SM(bf16_tag, 4); else if (v <= 24) SM(bf16_tag, 24); else SM(bf16_tag, 96);
+  } else {
+    if (v <= 4) SM(float, 4); else if (v <= 24) SM(float, 24); else SM(float, 96);
+  }
+#undef SM
+  GDL_CHECK_LAUNCH("gdl_softmax_rows");
   return GDL_OK;
 }

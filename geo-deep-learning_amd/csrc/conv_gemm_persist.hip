@@ -167,16 +167,6 @@ __global__ __launch_bounds__(512) void conv_gemm_persist_kernel(const KArgs) {
   }
 }
 
-int num_cus() {
-  static int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    return cus;
-  }();
-  return n;
-}
-
 }  // namespace
 
 namespace gdlconv {
@@ -193,7 +183,7 @@ int conv_gemm_persist_launch(const KArgs& k, hipStream_t stream) {
   kk.tiles_n = (k.a.N + 255) / 256;
   kk.n_group = conv_n_group(k.a, 256, 256, 32);
   const int ntiles = kk.tiles_m * kk.tiles_n;
-  const int cus = num_cus();
+  const int cus = gdl_num_cus();
   dim3 grid(ntiles < cus ? ntiles : cus), block(512);
   GDL_SET_MAX_LDS_ONCE(conv_gemm_persist_kernel, PS_LDS);
   hipLaunchKernelGGL(conv_gemm_persist_kernel, grid, block, PS_LDS, stream, kk);

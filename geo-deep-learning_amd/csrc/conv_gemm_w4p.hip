@@ -444,16 +444,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   all(all, ic<0>{});
 }
 
-int num_cus() {
-  static int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    return cus;
-  }();
-  return n;
-}
-
 int64_t span_bytes(const gdl_conv_args& a) {
   return (((int64_t)a.B - 1) * a.out_sB + ((int64_t)a.Ho - 1) * a.out_sH + ((int64_t)a.Wo - 1) * a.out_sW + a.N) * 2;
 }
@@ -493,7 +483,7 @@ int conv_gemm_w4p_launch(const KArgs& k, hipStream_t stream) {
   kk.n_group = conv_n_group(a, 256, 256, 32);
   kk.out_span = (unsigned)span_bytes(a);
   const int ntiles = kk.tiles_m * kk.tiles_n;
-  const int cus = num_cus();
+  const int cus = gdl_num_cus();
   dim3 grid(ntiles < cus ? ntiles : cus), block(256);
 #define GDL_W4P_LAUNCH(SR, ST)                                                                      \
   do {                                                                                              \

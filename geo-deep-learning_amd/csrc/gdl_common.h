@@ -12,6 +12,8 @@ typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 void gdl_set_error(const char* fmt, ...);
+// CUs of the current device, queried once per process (256, the MI355X's, where the query fails): persistent grids size themselves by it
+int gdl_num_cus();
 
 #define GDL_CHECK_ARG(cond, ...)              \
   do {                                        \

@@ -1,5 +1,5 @@
 // The per-element expressions of the inference path, each defined once for the kernels that must agree on them bit for bit:
-// misc.hip (gdl_normalize_range, gdl_upsample_probs), scene.hip (gdl_scene_cut, gdl_scene_blend_lowres, gdl_scene_finish) and
+// embed.hip (gdl_normalize_range), predict.hip (gdl_class_probs, gdl_upsample_probs, the argmax kernels), scene.hip (gdl_scene_cut, gdl_scene_blend_lowres, gdl_scene_finish) and
 // scene_regions.hip (gdl_scene_regions_stats).
 #pragma once
 #include "gdl_common.h"

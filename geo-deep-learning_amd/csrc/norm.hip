@@ -1,5 +1,6 @@
 // LayerNorm / BatchNorm kernels (HBM-bound; wave-shuffle reductions, 16-byte accesses).
 #include "gdl_common.h"
+#include "head_final.h"
 
 namespace {
 
@@ -465,7 +466,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dx(const void* __restrict__ x, con
 // ever stored: both backward passes re-form them from the saved convolution output x and dlogits, with the expressions (and the
 // bf16 roundings) of the kernels they replace --
 //   z  = bf16((x - mean) * (rstd gamma) + beta, relu)          bn_apply_kernel
-//   dz = bf16(fma chain over k of dlogit[k] * W[k][c])          head_1x1_bwd_feat8_kernel (misc.hip)
+//   dz = bf16(fma chain over k of dlogit[k] * W[k][c])          head_1x1_bwd_feat8_kernel (head.hip)
 // C == 256: thread t owns the eight channels 8 (t % 32) of pixel row t / 32 (the mapping of bn_bwd_partial8<256> and of
 // head_1x1_bwd_w_partial8), so the K x 8 head weights and the per-channel constants live in registers.
 template <int K>
@@ -1252,7 +1253,6 @@ extern "C" int gdl_bn_bwd_dx(const void* x, const void* dy, void* dx, int dtype,
 // weights w [K][256] 16-byte aligned.  Single-process statistics.  The A/B hooks of the kernels these replace (gdl_debug_set_bn_wide,
 // gdl_debug_set_head_mfma) do not reach here: there is one form of each pass, selected by the caller (GDL_FUSE_BN_TAIL in gdlhip/nn.py).
 // K goes through a switch of its own: gdl_common.h's K_SWITCH instantiates up to 16 classes, these kernels hold K x 8 weights per lane.
-int head_bwd_w_final_launch(const float* ws, int nsplit, int C, int K, float* dw, float* db, hipStream_t s);   // misc.hip
 
 extern "C" int gdl_bn_head_bwd_ok(int dtype, int64_t P, int C, int K) {
   return dtype == GDL_BF16 && C == 256 && K >= 1 && K <= 8 && P >= 4096;

@@ -3,6 +3,7 @@
 // pointers already offset to the chunk (<= 65536 elements each), all f32, dense.  shadow (0 = none) = a bf16 copy of the
 // parameter in the same element order (the GEMM operand the next forward reads): the update writes it too, so the step has
 // no per-parameter cast launches (28 per DOFA + UperNet step).
+// Also here: the single-tensor entry points of the C ABI (gdl_sumsq, gdl_clip_coef, gdl_adam_step).
 #include "gdl_common.h"
 
 namespace {
@@ -186,6 +187,40 @@ __global__ __launch_bounds__(256) void multi_repack_kernel(const int64_t* __rest
   }
 }
 
+// ------------------------------------------------------------------ single-tensor forms (gdl_sumsq, gdl_clip_coef, gdl_adam_step)
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ out) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s += x[i] * x[i];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(out, (red[0] + red[1]) + (red[2] + red[3]));
+}
+
+__global__ void clip_coef_kernel(const float* __restrict__ sumsq, float max_norm, float* __restrict__ coef) {
+  const float norm = sqrtf(sumsq[0]);
+  const float c = max_norm / (norm + 1e-6f);   // torch.nn.utils.clip_grad_norm_
+  coef[0] = c < 1.f ? c : 1.f;
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, int64_t n, float lr, float b1, float b2,
+                                                   float eps, float wd, float bc1, float bc2,
+                                                   const float* __restrict__ clip_coef) {
+  const float cc = clip_coef ? clip_coef[0] : 1.f;
+  const float step = lr / bc1, rs = 1.f / sqrtf(bc2);
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    float gi = g[i] * cc;
+    const float pi = p[i];
+    if (wd != 0.f) gi += wd * pi;
+    const float mi = b1 * m[i] + (1.f - b1) * gi;
+    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi; v[i] = vi;
+    p[i] = pi - step * mi / (sqrtf(vi) * rs + eps);
+  }
+}
+
 }  // namespace
 
 extern "C" int gdl_multi_repack(const int64_t* table, int rows, int64_t total_tiles, gdl_stream_t stream) {
@@ -269,5 +304,32 @@ extern "C" int gdl_multi_sgd_dev(const int64_t* table, int nchunks, const float*
   if (nchunks == 0) return GDL_OK;
   hipLaunchKernelGGL(multi_sgd_dev_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, table, state, clip_coef);
   GDL_CHECK_LAUNCH("gdl_multi_sgd_dev");
+  return GDL_OK;
+}
+
+extern "C" int gdl_sumsq(const float* x, int64_t n, float* out_accum, gdl_stream_t stream) {
+  GDL_CHECK_ARG(x && out_accum, "gdl_sumsq: null pointer");
+  if (n <= 0) return GDL_OK;
+  int64_t g = (n + 4095) / 4096; if (g > 1024) g = 1024;
+  hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, x, n, out_accum);
+  GDL_CHECK_LAUNCH("gdl_sumsq");
+  return GDL_OK;
+}
+
+extern "C" int gdl_clip_coef(const float* sumsq, float max_norm, float* coef, gdl_stream_t stream) {
+  GDL_CHECK_ARG(sumsq && coef, "gdl_clip_coef: null pointer");
+  hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, sumsq, max_norm, coef);
+  GDL_CHECK_LAUNCH("gdl_clip_coef");
+  return GDL_OK;
+}
+
+extern "C" int gdl_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                             float beta2, float eps, float weight_decay, float bc1, float bc2,
+                             const float* clip_coef, gdl_stream_t stream) {
+  GDL_CHECK_ARG(p && g && m && v, "gdl_adam_step: null pointer");
+  if (n <= 0) return GDL_OK;
+  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, 1024)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2,
+                     eps, weight_decay, bc1, bc2, clip_coef);
+  GDL_CHECK_LAUNCH("gdl_adam_step");
   return GDL_OK;
 }

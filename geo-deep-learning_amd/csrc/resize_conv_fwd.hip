@@ -1216,15 +1216,10 @@ extern "C" void gdl_debug_set_tapsum_mfma(int mode) { g_tapsum_mfma = mode; }
 static int g_tapsum_persist = 1;
 extern "C" void gdl_debug_set_tapsum_persist(int on) { g_tapsum_persist = on; }  // A/B hook: 0 = one workgroup per patch (round 3)
 static std::atomic<int> g_tapsum_cus{0};       // the device's CU count once a launch has asked for it
-static int tapsum_num_cus() {
-  static int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    g_tapsum_cus.store(cus);
-    return cus;
-  }();
-  return n;
+static int tapsum_num_cus() {      // (the plan query below must not enter the HIP runtime: it reads what a launch left here)
+  const int cus = gdl_num_cus();
+  g_tapsum_cus.store(cus);
+  return cus;
 }
 static int g_tapsum_roll = 1;
 constexpr int kRollDepth4 = 3;    // factor 4: steps the row fetches of version 3 run ahead (ring of RollSrc<2, depth>::NSLOT = 3 + depth slots, three workgroups per CU)

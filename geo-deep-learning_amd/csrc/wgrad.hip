@@ -867,15 +867,6 @@ std::atomic<int> g_wgrad_old_splits{0};    // A/B hook: the round-3 split-K rule
 // the row-segment kernel runs all (n, c) tiles of a pixel range on one XCD (round 5, profiles/r05h_*: 256 -> 256 at 144^2
 // 783 -> 745 us, at 128^2 681 -> 607 us, no layer slower; bit-identical).  0 = launch order (GDL_WGRAD_ROWS_XCD=0)
 std::atomic<int> g_wgrad_rows_xcd{1};
-int wgrad_num_cus() {
-  static int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    return cus;
-  }();
-  return n;
-}
 std::atomic<int> g_wgrad_force_small{0};   // A/B hook: bit 0 = never use the 256^2 kernel, bit 1 = never use the row-segment kernel, bit 3 = N, C >= 256 layers on the 256^2 kernel
 
 // 256^2 tiles for wide bf16 layers whose operands fit 32-bit buffer offsets
@@ -935,7 +926,7 @@ int choose_splits(const gdl_wgrad_args& a, int64_t P, int bkp) {
     // - 1 of them: two full rounds plus a nearly empty third (lateral 768 -> 768 at 36^2: 9 tiles x 57 splits = 513 workgroups,
     // 120 us for 49 GF; now 28 splits = 252 workgroups, 89 us).  Per candidate: rounds x (K-steps of a split x cycles per
     // K-step + prologue and f32 partial-tile store) + the reduction pass over `splits` partial matrices at ~3 TB/s.
-    const int64_t slots = (int64_t)wgrad_num_cus() * (t == 256 ? 1 : 2);
+    const int64_t slots = (int64_t)gdl_num_cus() * (t == 256 ? 1 : 2);
     const double step_cyc = t == 256 ? 3000.0 : 1700.0, fixed_cyc = t == 256 ? 25000.0 : 11000.0;
     const int64_t ksteps = (P + bkp - 1) / bkp;
     const double out_bytes = (double)a.N * a.R * a.S * a.C * 4.0 * (a.nz > 1 ? a.nz : 1);

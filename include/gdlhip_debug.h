@@ -79,7 +79,7 @@ void gdl_debug_set_tapsum_roll(int on);
 /* ---- BatchNorm, classifier head, losses ---- */
 /* 0 = the 8-byte / 256-channel mapping of the BatchNorm backward for every shape (norm.hip) */
 void gdl_debug_set_bn_wide(int on);
-/* 0 = the wave-per-pixel classifier-head kernels instead of the MFMA ones (misc.hip) */
+/* 0 = the wave-per-pixel classifier-head kernels instead of the MFMA ones (head.hip) */
 void gdl_debug_set_head_mfma(int on);
 /* 0 = the gather kernel for every class count in the low-resolution Dice-family backward (loss_dice.hip) */
 void gdl_debug_set_dice_lowres_tiled(int on);

@@ -727,6 +727,22 @@ def test_head_and_logit_upsample(dtype, K):
     close(db, br.grad, dtype, "head db")
 
 
+@pytest.mark.parametrize("hw,out", [((7, 9), (16, 20)), ((16, 20), (7, 9))])
+def test_logit_upsample_runtime_class_count(hw, out):
+    """More than 16 classes: gdl_upsample_logits and gdl_upsample_logits_bwd take the class count at run time (instantiation 0 of
+    their kernels).  17 classes, an upsample and a downsample (the backward's candidate range holds more than two positions
+    there), against torch's bilinear resize and its gradient."""
+    B, K = 2, 17
+    low = rnd(B, K, *hw).requires_grad_(True)
+    ref = F.interpolate(low, size=out, mode="bilinear", align_corners=False)
+    got = ops.upsample_logits(low.detach().permute(0, 2, 3, 1).contiguous().to(DEV), out)
+    close(got, ref, torch.float32, "upsample logits, K = 17")
+    g = rnd(B, K, *out, seed=4)
+    ref.backward(g)
+    dlow = ops.upsample_logits_bwd(g.to(DEV), hw)
+    close(dlow.permute(0, 3, 1, 2), low.grad, torch.float32, "upsample logits backward, K = 17")
+
+
 @pytest.mark.parametrize("scale", [False, True])
 @pytest.mark.parametrize("C", [256, 128, 768, 512, 1024])
 @pytest.mark.parametrize("K,B,H,W", [(5, 2, 36, 36), (1, 1, 35, 31), (12, 1, 40, 40), (16, 3, 21, 17), (5, 4, 144, 144)])

@@ -1,6 +1,6 @@
 """Exact tests of the HBM-bound row and column kernels between the GEMMs of a transformer step: the column sums, LayerScale
 backward, LayerNorm backward, softmax backward, depthwise 3x3 + GELU backward and col2im of csrc/transformer_bwd.hip, the
-depthwise 3x3 forward (csrc/dwconv.hip, csrc/dwconv_walk.h), the LayerNorm forward (csrc/norm.hip) and add_rows (csrc/misc.hip).
+depthwise 3x3 forward (csrc/dwconv.hip, csrc/dwconv_walk.h), the LayerNorm forward (csrc/norm.hip) and add_rows (csrc/elementwise.hip).
 
 Operands are small seeded integers or dyadic rationals.  They are exact in bf16 and f32, every product is exact and every partial
 sum -- in any lane, wave, block partial or the final reduction -- stays below 2^24, so each output has one correct bit pattern
